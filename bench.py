@@ -9,7 +9,12 @@ ADP-shaped synthetic crystals of 194 atoms (periodic 5 A radius graph, ~2.8k edg
 rank per step (weak scaling: every rank owns its own crystals; one 10 MB gradient all-reduce per step).
 Inputs are resident in HBM before the timed region.
 
-Extra objects on the line:
+A plain run (no ``--full``) sets up, runs the pre-roll and the W warm-up steps, times the K steps and prints the line
+(headline, config, derived path figures, the multi-rank fields where N > 1).  ``--dump-outputs DIR`` writes what the
+last timed step computed (see dump_outputs) after the timed region.  ``--full`` adds every other figure below; the
+``--no-*`` switches then leave single ones out.
+
+Extra objects on the line (``--full`` only):
   roofline      the dominant kernel (the fp32-MFMA GEMM variant with the largest share of the step) priced live with HIP events on the
                 launch stream over the timed steps (cartnet_profile_gemm): executed 2*M*N*K FLOPs / measured time vs
                 157.3 TFLOP/s
@@ -148,6 +153,32 @@ def _csrc_digest() -> str:
                 h.update(name.encode())
                 h.update(f.read())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname: str, results: dict, model, opt) -> dict:
+    """``--dump-outputs``: what the last timed step handed its caller -- ``pred`` and ``target`` (the model's return
+    value), ``loss``, and the state the optimiser step left: ``params`` (FlatAdam's flat parameter vector) and
+    ``buffers`` (the model's floating-point buffers, BatchNorm running statistics among them, in named_buffers order) --
+    as float32 ``DIR/<name>.npy``.  ~10 MB at the headline size; should the whole exceed DUMP_BYTES_MAX, every array is
+    cut to the same fraction by a fixed seeded sample of its flattened elements (kept in order).  Returns the shapes."""
+    import numpy as np
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays = dict(results, params=opt.flat_param, buffers=torch.cat(bufs) if bufs else torch.zeros(0))
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    total = sum(4 * v.numel() for v in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    shapes = {}
+    for name, v in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            keep = v.numel() * (DUMP_BYTES_MAX - 65536) // total           # (room for the .npy headers)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), v.numpy())
+        shapes[name] = list(v.shape)
+    return shapes
 
 
 TIMED_EVERY = 4      # launches of the dominant GEMM variant between two timed ones inside the timed region
@@ -303,7 +334,19 @@ def main():
     ap.add_argument("--no-subconfigs", action="store_true",
                     help="skip the jarvis_bf16 / icomformer / ragged passes (BASELINE configs[2], [4] and the ragged batch)")
     ap.add_argument("--sub-steps", type=int, default=20, help="timed steps of each of those passes (after 5 warm-up steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: cold figure, GEMM kernel timer and roofline, "
+                         "telemetry, sustained stretch, calibration, the bf16x3 / bf16 / recipe / eval passes, the "
+                         "sub-configs and the CPU baseline (the --no-* switches leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run times the headline and nothing else (the pre-roll, warm-up and spin-up steps stay: they are what
+        # the headline figure needs, see the comments in main)
+        args.no_cold = args.no_kernel_timer = args.no_telemetry = args.no_calibration = True
+        args.no_x3_pass = args.no_recipe_pass = args.no_subconfigs = args.no_cpu_baseline = True
+        args.sustain_seconds = 0.0
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -362,8 +405,10 @@ def main():
     # more than one rank (or CARTNET_DIST_FORCE): the gradient all-reduce goes out in buckets under backward (GradSync)
     gsync = cdist.GradSync(opt.flat_grad, measure=True) if (cdist._active() and not icf) else None
 
-    def step(b):
+    def step(b, keep=None):
         pred, true = model(b)
+        if keep is not None:            # --dump-outputs: the timed loop keeps its last step's results
+            keep["pred"], keep["target"] = pred, true
         if args.bn_group_size > 0:
             loss = grouped_loss(pred, true, b, args.bn_group_size)[0]
         else:
@@ -442,7 +487,7 @@ def main():
         if warm_summary:
             only = warm_summary[max(warm_summary, key=lambda k: warm_summary[k]["ms"])]["variant"]
     from cartnet_amd import telemetry as tele
-    telemetry = {"before_timed": tele.compact(tele.read(local))} if rank == 0 else None
+    telemetry = {"before_timed": tele.compact(tele.read(local))} if (rank == 0 and args.full) else None
 
     def new_sampler():          # one period for every pass; None with --no-telemetry or off rank 0
         return tele.Sampler(local).start() if (rank == 0 and not args.no_telemetry) else None
@@ -463,9 +508,10 @@ def main():
     cdist.barrier()
     torch.cuda.synchronize()
     ops.profile_gemm(timer, only=only, every=timed_every)
+    keep = {} if args.dump_outputs else None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(batches[args.warmup + args.spinup + i])
+        loss = step(batches[args.warmup + args.spinup + i], keep)
     t_enq = time.perf_counter() - t0          # host time to enqueue all steps (GPU-bound when << dt)
     torch.cuda.synchronize()
     dt_rank = time.perf_counter() - t0        # this rank's own K steps (before it waits for the others)
@@ -480,6 +526,8 @@ def main():
     rank_lo, rank_hi = cdist.min_max_over_ranks(dt_rank, dev)
     if not torch.isfinite(loss):
         raise SystemExit("non-finite loss")
+    if keep is not None and rank == 0:      # before anything below steps the model again
+        dump_outputs(args.dump_outputs, dict(keep, loss=loss), model, opt)
 
     # Sustained stretch (outside the timed region, same step, same batches re-armed): long enough for the clock and
     # the power management to settle under the fp32 matrix load; windows of 100 steps are timed with one host sync each.
@@ -804,7 +852,7 @@ def main():
         # every step run before the timed region opened: the cold W + K, the rest of the pre-roll, W warm-up steps, the spin-up
         "untimed_steps_total": max(args.preroll_steps, cold_steps) + args.warmup + args.spinup,
         "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16" if args.precision == 2 else "f32", "data": "synthetic",
+        "vs_baseline": None, "dtype": "bf16" if args.precision == 2 else "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": (f"BASELINE configs[4]: iComformer D=256 (4 attention layers + edge-update layer, Cholesky "
                                 f"head) fp32 train step, " if icf else
                                 f"BASELINE configs[1]: CartNet L=4 D=256 R=64 fp32 train step, ") +
@@ -956,7 +1004,7 @@ def main():
                     if v["ms"] / 3 >= 0.05}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(which=args.model)
-        elif world > 1:
+        elif world > 1 and args.full:
             # (a SCALE record explains itself)
             out["cpu_baseline"] = None
             out["cpu_baseline_note"] = "the CPU oracle is timed on rank 0 of the N = 1 line only"

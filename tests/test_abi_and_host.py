@@ -365,7 +365,8 @@ def test_traffic_json_is_what_the_committed_pmc_passes_give():
     x3 = mod.analyse(need[2], need[3], verbose=False)
     assert out["per_step"]["hbm_bytes"] == ref["per_step"]["hbm_bytes"]
     assert x3["per_step"]["hbm_bytes"] == ref["per_step_x3"]["hbm_bytes"]
-    assert out["variants"]["fp32"]["tn256"] == ref["variants"]["fp32"]["tn256"]
-    assert x3["variants"]["x3"]["nn256"] == ref["variants"]["x3"]["nn256"]
+    # every variant of both steps (the fp32 step's dominant kernel has been the persistent one, nn256p, since round 6)
+    assert out["variants"]["fp32"] == ref["variants"]["fp32"] and "nn256p" in ref["variants"]["fp32"]
+    assert x3["variants"]["x3"] == ref["variants"]["x3"] and "nn256" in ref["variants"]["x3"]
     # the gfx950 correction is in: fetched bytes are the counter (KB) x 1024 x 2
     assert ref["per_step"]["fetch_bytes"] > ref["per_step"]["write_bytes"] > 0

@@ -22,7 +22,7 @@ def test_bench_line_with_four_ranks_on_one_card(tmp_path):
     prints ONE JSON line for the whole job: n_gpus 4, weak scaling, `sustained` present for world > 1 too."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CARTNET_DIST_FORCE")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--share-gpu", "--graphs", "4", "--steps", "3",
-           "--warmup", "2", "--sustain-seconds", "0.5", "--no-x3-pass", "--no-recipe-pass"]
+           "--warmup", "2", "--full", "--sustain-seconds", "0.5", "--no-x3-pass", "--no-recipe-pass"]
     out = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

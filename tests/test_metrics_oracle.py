@@ -14,7 +14,16 @@ def test_oracle_matches_reference_metrics():
     z = _load()
     for name in ("close", "far"):
         pred, true = z[f"{name}_pred"], z[f"{name}_true"]
-        assert torch.allclose(om.get_error_volume(pred, true), z[f"{name}_volume_error"], rtol=1e-5, atol=1e-7)
+        # |v1 - v2| / v1 amplifies the rounding of the fp32 determinants, which differs between LAPACK builds and CPUs:
+        # first-order bound of the fp32 evaluation's error, eps32 * (cond(pred) + cond(true)) * v2 / v1 (the reference's
+        # own fp32 run stays within 0.56 of it).  The oracle's fp32 result must be that close to the fp64 one, and agree
+        # with the reference's fp32 run to 1e-5 beyond it.
+        v1, v2 = om.get_volume(pred.double()), om.get_volume(true.double())
+        bound = float(np.finfo(np.float32).eps) * (torch.linalg.cond(pred.double()) + torch.linalg.cond(true.double())) * v2 / v1
+        ev = om.get_error_volume(pred, true).double()
+        assert torch.all((ev - z[f"{name}_volume_error64"]).abs() <= bound)
+        ref = z[f"{name}_volume_error"].double()
+        assert torch.all((ev - ref).abs() <= 1e-5 * ref.abs() + 1e-7 + bound)
         assert torch.allclose(om.get_similarity_index(pred, true), z[f"{name}_similarity_index"], rtol=1e-4, atol=1e-3)
         assert torch.allclose(om.compute_3d_iou(pred, true), z[f"{name}_iou"], rtol=0, atol=1e-4)
         # fp64 evaluation of the same formulas reproduces the reference's fp64 run

@@ -5,7 +5,8 @@
 OTHER=${1:-_prev}; [ $# -gt 0 ] && shift; [ "$1" == "--" ] && shift
 for round in 1 2; do
   for t in . "$OTHER"; do
-    (cd $t && timeout -k 10 300 python bench.py --no-subconfigs --steps 30 --warmup 10 --no-x3-pass --no-recipe-pass \
+    FULL=$(grep -q -- '"--full"' $t/bench.py && echo --full)     # a tree from before --full measures everything anyway
+    (cd $t && timeout -k 10 300 python bench.py $FULL --no-subconfigs --steps 30 --warmup 10 --no-x3-pass --no-recipe-pass \
       --no-cpu-baseline --sustain-seconds 0 --no-cold --preroll-steps 100 --no-calibration "$@" 2>/dev/null |
       python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$t', d['ms_per_step'], d['value'], 'dominant', r['avg_launch_us'], r['frac'])")
   done

@@ -1,6 +1,6 @@
 """Wave-cycle breakdown per kernel from one rocprofv3 PMC pass:
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT \\
-            SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer
+            SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer
 (MI355X_MICROARCH.md, "rocprofv3 PMC slots": WAIT_ANY = wave parked on s_waitcnt / barrier, WAIT_INST_ANY = issue stall,
 ACTIVE_INST_ANY = issuing; the three are disjoint and add up to WAVE_CYCLES.)
 Usage: python tools/pmc_stalls.py <counter_collection.csv> [top_n]"""

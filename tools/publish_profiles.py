@@ -57,11 +57,11 @@ tv = traffic["variants"]["fp32"].get(vkey.split("[")[0], {})
 tbytes = tv.get("hbm_bytes_per_launch_edge_rows", tv.get("hbm_bytes_per_launch"))
 md = f"""# Round {int(tag[1:3])} — rocprofv3 `--kernel-trace --stats` of the default bench command (1x MI355X)
 
-Command (on the GPU box, `tools/collect_profiles.sh`): `cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d <out> -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-recipe-pass --sustain-seconds 0`
+Command (on the GPU box, `tools/collect_profiles.sh`): `cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d <out> -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-recipe-pass --sustain-seconds 0`
 
 Files: `{tag}_bench_n1_kernel_stats.csv` (raw per-kernel stats), `{tag}_bench_n1_under_rocprof.json` (the bench line printed under the profiler),
-`{tag}_bench_n1.json` (un-profiled default run incl. `cpu_baseline` and `sustained`), `{tag}_pmc_fetch_size.csv` / `{tag}_pmc_write_size.csv` (separate `--pmc FETCH_SIZE` /
-`--pmc WRITE_SIZE` passes of `bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer --no-x3-pass`: fp32-MFMA steps only) and `traffic.json` (HBM bytes per launch per kernel derived from them by
+`{tag}_bench_n1.json` (un-profiled `--full` run incl. `cpu_baseline` and `sustained`), `{tag}_pmc_fetch_size.csv` / `{tag}_pmc_write_size.csv` (separate `--pmc FETCH_SIZE` /
+`--pmc WRITE_SIZE` passes of `bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer --no-x3-pass`: fp32-MFMA steps only) and `traffic.json` (HBM bytes per launch per kernel derived from them by
 `tools/pmc_traffic.py`: FETCH_SIZE doubled per the gfx950 note of MI355X_MICROARCH.md, WRITE_SIZE as is).
 
 The profiled process runs, in this order: 13 fp32-MFMA training steps on two streams (3 warm-up + 10 timed), 3 single-stream fp32 steps (the `roofline.isolated` pass),

@@ -26,9 +26,6 @@ EXTRA_FLAGS = {"radius_graph.hip": ["-ffp-contract=off"], "gemm_f32.hip": ["-Wno
 # inline-asm buffer instruction is read before it is written (the hazard recogniser does not look inside the string).
 NO_SPILL = {"gemm_f32p.hip", "gemm_f32p2.hip", "gemm_f32p3.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
-if os.environ.get("CARTNET_BUILD_EXPERIMENTAL"):       # experiments kept as a record (csrc/experimental/), never shipped
-    SOURCES.append("experimental/gemm_f32q.hip")
-    FLAGS.append("-DCN_EXPERIMENTAL_Q")
 FLAGS += os.environ.get("CARTNET_HIPCC_EXTRA", "").split()      # e.g. -DCN_SETPRIO=0 for an A/B library (tools/experiments/ab_bench.sh)
 
 

@@ -5,13 +5,12 @@
 #include <vector>
 
 namespace cn_gemm {
-thread_local bool g_half_launched = false;
 // Which DMA-fed fp32 kernel takes a prepacked activation x weight product: the 256-wide one (gemm_f32.h, two workgroups
 // per CU), or the 128-wide one (gemm_f32w128.h, three per CU) for the launches with the node-term gather epilogue (layer
 // GEMM 1) -- the one variant where a third resident workgroup pays: 402 vs 425 us sustained at the benchmark shape, the
 // training step 15.40 vs 15.57 ms (same box, interleaved).  Every other variant is equal or slower on the narrow tile
 // (SiLU on the A operand: -15 %, its prologue runs once per column tile).
-bool use_f32nn128(const CartnetGemmArgs& a) {
+static bool use_f32nn128(const CartnetGemmArgs& a) {
   if (a.tile_policy == 128) return true;
   if (a.tile_policy == 256) return false;
   if (a.gather_i[0] != nullptr && !a.a_act) return true;
@@ -29,9 +28,9 @@ bool use_f32nn128(const CartnetGemmArgs& a) {
   const long long tiles = (long long)((a.M + 127) / 128) * (a.N / 256) * a.ngroups;
   return tiles < 200;
 }
-extern template bool launch_bn<256>(const CartnetGemmArgs&, const GemmFlags&, hipStream_t);
-extern template bool launch_bn<128>(const CartnetGemmArgs&, const GemmFlags&, hipStream_t);
-extern template bool launch_bn<64>(const CartnetGemmArgs&, const GemmFlags&, hipStream_t);
+extern template void launch_bn<256>(const CartnetGemmArgs&, const GemmFlags&, bool, hipStream_t);
+extern template void launch_bn<128>(const CartnetGemmArgs&, const GemmFlags&, bool, hipStream_t);
+extern template void launch_bn<64>(const CartnetGemmArgs&, const GemmFlags&, bool, hipStream_t);
 }
 
 namespace {
@@ -171,60 +170,34 @@ static bool epilogue_rows_aligned(const CartnetGemmArgs& a) {
 }
 
 // K-segments that are adjacent column blocks of one matrix, with the image of the concatenated weight operand at hand:
-// one product over the concatenated K on the DMA-fed kernels.
-static bool segments_fold(const CartnetGemmArgs& a) {
-  if (!(a.nsegs > 1 && a.b_split_folded && a.N == cn_gemm::X3_BN && !a.a_kstrided && a.b_kstrided && a.splitk == 1 &&
-        a.ngroups == 1 && a.M > 0))
+// one product over the concatenated K (folded only where the DMA-fed kernels take it: B[0] alone does not describe the
+// folded operand).
+static bool segments_adjacent(const CartnetGemmArgs& a) {
+  if (!(a.nsegs > 1 && a.b_split_folded && a.N == cn_gemm::X3_BN && a.ngroups == 1 && a.K % cn_gemm::BK == 0 &&
+        (long long)a.K * a.nsegs <= a.lda))
     return false;
-  bool fold = epilogue_rows_aligned(a) && a.lda % 4 == 0 && a.ldb % 4 == 0 && a.K % cn_gemm::BK == 0 &&
-              (long long)a.K * a.nsegs <= a.lda && (double)a.M * a.lda * 4.0 < 4294967296.0;
-  for (int s = 0; s < a.nsegs && fold; ++s)
-    fold = a.A[s] && a.B[s] && aligned16(a.A[s]) && aligned16(a.B[s]) &&
-           reinterpret_cast<const char*>(a.A[s]) ==
-               reinterpret_cast<const char*>(a.A[0]) + (size_t)s * a.K * (a.a_half ? 2 : 4);
-  return fold;
+  for (int s = 0; s < a.nsegs; ++s)
+    if (!a.A[s] || !a.B[s] ||
+        reinterpret_cast<const char*>(a.A[s]) != reinterpret_cast<const char*>(a.A[0]) + (size_t)s * a.K * (a.a_half ? 2 : 4))
+      return false;
+  return true;
 }
 
-// precision 0, an activation x weight product whose weight image is at hand and whose shape the DMA-fed fp32 kernels take
-static bool f32_image_path(const CartnetGemmArgs& a) {
-  if (a.precision != 0 || a.a_kstrided || !a.b_kstrided || a.splitk != 1 || a.M <= 0 || a.K <= 0 || a.N % 256 != 0)
-    return false;
-  if (a.nsegs > 1) return segments_fold(a);
-  bool ok = epilogue_rows_aligned(a) && a.lda % 4 == 0 && a.ldb % 4 == 0 && a.K % cn_gemm::BK == 0 &&
+// An activation x weight product the DMA-fed 256-wide kernels take (gemm_f32.h, gemm_x3.h and their relatives): the
+// weight image of every group, whole K-steps, full column tiles, 16-byte aligned rows, 32-bit row offsets.
+static bool dma_fed(const CartnetGemmArgs& a, const cn_gemm::GemmFlags& fl) {
+  bool ok = !a.a_kstrided && a.b_kstrided && !a.b_act && a.splitk == 1 && a.nsegs == 1 && a.M > 0 && a.K > 0 &&
+            a.K % cn_gemm::BK == 0 && a.N % 256 == 0 && fl.vecA && fl.vecB && fl.wide &&
             (double)a.M * a.lda * 4.0 < 4294967296.0;
-  for (int gI = 0; gI < a.ngroups && ok; ++gI)
-    ok = a.b_split[gI] && a.A[gI] && a.B[gI] && aligned16(a.A[gI]) && aligned16(a.B[gI]);
+  for (int gI = 0; gI < a.ngroups && ok; ++gI) ok = a.b_split[gI] != nullptr;
   return ok;
 }
 
-static int choose_bn(const CartnetGemmArgs& a);
-
-// CartnetGemmArgs.gst_*: the launch reaches a kernel that carries the gate statistics epilogue -- precision 0:
-// cn_gemm_f32p_kernel<false, false, 530, 32> (edge-sized launches) or cn_gemm_f32nn128_kernel<false, 1 / 2>; precision 1 (bf16x3): cn_gemm_x3nn16_kernel<false, 1 / 2>.  (The same predicates the
-// dispatch below and launch_variant apply, in their order; the two DMA-fed families take the same shapes.)
-static bool gate_stats_launch_ok(const CartnetGemmArgs& a) {
-  if (!(a.gst_g && a.gst_mean_rstd && a.gst_gamma && a.gst_beta && a.gst_ld >= a.N && a.gst_ld % 4 == 0)) return false;
-  if (!(aligned16(a.gst_g) && aligned16(a.gst_mean_rstd) && aligned16(a.gst_gamma) && aligned16(a.gst_beta))) return false;
-  if (!((a.precision == 0 || a.precision == 1) && a.ngroups == 1 && !a.a_act && !a.b_act && !a.out_act && !a.dact[0] &&
-        !a.gather_i[0] && !a.cpre[0] && !a.bias[0] && a.colsum[0] && a.colsq[0] && !a.a_act_out[0] && a.N == 256))
-    return false;
-  CartnetGemmArgs q = a;
-  q.precision = 0;                       // (the image-path conditions do not depend on the operand format)
-  if (!f32_image_path(q) || choose_bn(a) != 256 || cn_gemm::any_half(a)) return false;
-  CartnetGemmArgs f = a;
-  if (segments_fold(a)) { f.K *= f.nsegs; f.nsegs = 1; }
-#ifdef CN_EXPERIMENTAL_Q
-  if (a.precision == 0 && cn_gemm::use_f32nnq(f)) return false;     // (launch_variant asks the quad kernel first: no GST code there)
-#endif
-  // (launch_variant asks the persistent kernel first: it has the form -- gemm_f32p.h, KIND 530)
-  return f.nsegs == 1 && (a.precision == 1 || cn_gemm::use_f32p(f) || cn_gemm::use_f32nn128(f));
-}
-
-extern "C" int cartnet_gemm_gate_stats_ok(const CartnetGemmArgs* args) { return args && gate_stats_launch_ok(*args) ? 1 : 0; }
-
-// Column-tile width of a launch (see the comment in cartnet_gemm_impl): 256 / 128 / 64 by N, narrower for launches
-// with few tiles.  Shared with the launch timer so that its variant names the kernel family that really runs.
-static int choose_bn(const CartnetGemmArgs& a) {
+// Few row tiles (atom-sized M, small batches): 128 x 256 tiles would leave most of the 256 CUs idle and the launch would
+// last one tile's latency (16+ K-steps of a full tile); narrower column tiles (the general kernel's 128- and 64-wide forms,
+// exact fp32) spread the same work over 2-4x as many workgroups.  Not at precision 2 (the bf16 kernels exist for 256-wide
+// tiles only and their tiles are 6x shorter to begin with: measured a loss), and later at precision 1.
+static int choose_bn(const CartnetGemmArgs& a, bool f32_image) {
   int bn = a.N > 128 ? 256 : (a.N > 64 ? 128 : 64);
   // (transposed-A launches: only the K-segment form -- iComformer's 256 x 256 x 512 chain-rule product dWe ran as TWO
   //  workgroups of the 256-wide general kernel, 110-150 us on the weight-gradient stream, five times per step; weight
@@ -236,15 +209,146 @@ static int choose_bn(const CartnetGemmArgs& a) {
     const long long few = a.precision == 0 ? 200 : 96;
     // fp32 with a weight image: from 64 tiles up the 128-wide DMA-fed kernel (use_f32nn128: 2 x tiles workgroups) beats the
     // register-staged narrow kernels -- the folded dX product of the node terms 85 -> 68 us sustained
-    if (tiles < few && !(tiles >= 64 && f32_image_path(a))) bn = (2 * tiles >= few) ? 128 : 64;
+    if (tiles < few && !(tiles >= 64 && f32_image)) bn = (2 * tiles >= few) ? 128 : 64;
   }
   return bn;
+}
+
+namespace {
+
+// The kernel family that takes a launch.
+enum class Family {
+  general,      // the general tile kernel (gemm_kernel.h) at 256 / 128 / 64 columns
+  general_x3,   // ... its predicate-free launches on the first-generation bf16x3 kernel (precision 1, no weight image)
+  f32p,         // persistent fp32 kernel (gemm_f32p.h)
+  f32nn,        // DMA-fed fp32, 256-wide (gemm_f32.h)
+  f32nn_actout, // ... writing silu(A) on its way into LDS (gemm_f32ao.h)
+  f32nn128,     // DMA-fed fp32, 128-wide (gemm_f32w128.h)
+  f32tn,        // fp32 weight gradient, whole or split-K (+ cn_gemm_tn_tail_kernel)
+  x3nn16,       // pre-split bf16x3 on the 16x16x32 MFMA shape (gemm_x3s.h, precision 1)
+  x3nn,         // pre-split bf16 (gemm_x3.h, precision 2)
+  x3nn_actout,  // ... writing silu(A) (gemm_x3ao.h, precision 1 / 2)
+  x3tn,         // bf16x3 / bf16 weight gradient, whole or split-K (+ cn_gemm_tn_tail_kernel)
+  hnn,          // half storage (gemm_h.h, precision 2)
+  htn,
+};
+enum class Reject { none, layout, half };
+
+// Every dispatch decision of one cartnet_gemm launch, taken once.
+struct GemmPlan {
+  CartnetGemmArgs a;        // the launch as it runs: K-segments folded, a_act_out cleared where the pre-pass writes it
+  cn_gemm::GemmFlags fl;
+  int bn;                   // column-tile width of the general and DMA-fed kernels
+  bool prepass;             // silu(A) -> a_act_out by cn_act_rows_kernel ahead of the product
+  Family family;
+  cn_gemm::HLaunch h;       // hnn / htn: the compiled operand combination
+  bool gate_stats;          // the family has the gate-statistics epilogue (f32p KIND 530, f32nn128 / x3nn16 <false, 1 / 2>)
+  int variant;              // the launch timer's key (cartnet_profile_gemm*)
+  Reject reject;            // no compiled kernel takes the launch
+};
+
+}  // namespace
+
+static GemmPlan plan_gemm(const CartnetGemmArgs& in) {
+  using cn_gemm::BK;
+  GemmPlan p{};
+  cn_gemm::GemmFlags& fl = p.fl;
+  const int nptr = in.ngroups > 1 ? in.ngroups : in.nsegs;
+  bool vecA = (in.lda % 4 == 0), vecB = (in.ldb % 4 == 0);
+  for (int i = 0; i < nptr; ++i) vecA = vecA && aligned16(in.A[i]), vecB = vecB && aligned16(in.B[i]);
+  fl.vecA = vecA ? 1 : 0;
+  fl.vecB = vecB ? 1 : 0;
+  fl.wide = epilogue_rows_aligned(in) ? 1 : 0;
+  fl.x3 = in.precision;
+  CartnetGemmArgs f = in;
+  if (segments_adjacent(in)) {
+    f.K *= f.nsegs;
+    f.nsegs = 1;
+    f.b_split[0] = f.b_split_folded;
+  }
+  const bool image = dma_fed(f, fl);
+  p.bn = choose_bn(in, in.precision == 0 && image);
+  const bool dma = p.bn == 256 && image;
+  p.a = dma ? f : in;
+  CartnetGemmArgs& a = p.a;
+  fl.tile_m0 = fl.split0 = fl.k_lo = 0;
+  fl.k_hi = a.K;
+  fl.kchunk = std::max(BK, cn_ceil_div(cn_ceil_div(a.K, a.splitk), BK) * BK);
+  // the DMA-fed 256-wide kernels write the activated operand on its way into LDS (gemm_f32ao.h, gemm_x3ao.h); any other
+  // launch (narrow tiles of a small batch, no weight image) gets it from an elementwise pass first
+  if (a.a_act_out[0]) {
+    bool fused = dma;
+    for (int gI = 0; gI < a.ngroups; ++gI) fused = fused && aligned16(a.a_act_out[gI]);
+    p.prepass = !fused;
+    if (p.prepass)
+      for (auto& o : a.a_act_out) o = nullptr;
+  }
+  const int combo = (a.a_kstrided ? 1 : 0) | (a.b_kstrided ? 2 : 0) | (a.a_act ? 4 : 0) | (a.b_act ? 8 : 0);
+  const bool half = cn_gemm::any_half(a);
+  if (combo != 0 && combo != 4 && combo != 2 && combo != 6 && combo != 3 && combo != 11) {
+    p.reject = Reject::layout;
+  } else if (dma && half) {
+    p.family = Family::hnn;
+    p.h = cn_gemm::find_hnn(a);
+  } else if (dma && a.precision == 0) {
+    p.family = cn_gemm::use_f32p(a)       ? Family::f32p
+               : a.a_act_out[0]           ? Family::f32nn_actout
+               : cn_gemm::use_f32nn128(a) ? Family::f32nn128
+                                          : Family::f32nn;
+  } else if (dma) {
+    // (precision 1: the six piece products on the 16x16x32 MFMA shape, gemm_x3s.h; round 3: -1...-4 % per launch)
+    p.family = a.a_act_out[0] ? Family::x3nn_actout : a.precision == 1 ? Family::x3nn16 : Family::x3nn;
+  } else if (a.a_kstrided && p.bn == 256) {
+    // weight gradients: the DMA-fed kernels take every row tile over the whole K-steps; a K tail (< 16 rows) is one more
+    // slab (split-K only).  Half storage: one kernel over all of K (it masks a ragged last K-step itself), S slabs.
+    const bool shape = a.M % 4 == 0 && fl.vecA && fl.vecB && a.nsegs == 1 && a.N % 256 == 0 && a.M > 0;
+    if (half) {
+      p.family = Family::htn;
+      p.h = shape && a.K >= 1 && (a.splitk > 1 || fl.wide) ? cn_gemm::find_htn(a) : nullptr;
+    } else if (shape && a.K >= BK && (a.splitk > 1 || (a.K % BK == 0 && fl.wide))) {
+      p.family = a.precision ? Family::x3tn : Family::f32tn;
+    }
+  } else if (half) {
+    p.reject = Reject::half;
+  } else if (a.precision == 1 && p.bn == 256 && a.b_kstrided && !a.a_kstrided) {
+    // precision 1 without a weight image: the first kernel that splits both operands in flight (precision 2 has no such
+    // form: the general kernel on fp32 operands)
+    p.family = Family::general_x3;
+  }
+  if ((p.family == Family::hnn || p.family == Family::htn) && !p.h) p.reject = Reject::half;
+  p.gate_stats = p.family == Family::f32p || p.family == Family::f32nn128 || p.family == Family::x3nn16;
+  // bits 0..3: the operand layouts and activations; bits 4..7: the tile width / 64 of the kernel that runs; bit 8: the
+  // streamed dimension (rows of an activation x weight product, reduction length of a weight gradient) is edge-sized;
+  // bit 9: silu(A) is written too; bits 10..17: the other inner dimension / 16 (K of an NN product, M of a weight
+  // gradient), capped; bit 18: the persistent kernel
+  const int width = p.family == Family::f32nn128 ? 128 : p.bn;
+  const long long streamed = a.a_kstrided ? a.K : a.M;
+  const int inner = a.a_kstrided ? a.M : a.K;
+  p.variant = combo | ((width / 64) << 4) | (streamed >= 32768 ? 256 : 0) | (in.a_act_out[0] ? 512 : 0) |
+              ((inner > 4080 ? 255 : inner / 16) << 10) | (p.family == Family::f32p ? (1 << 18) : 0);
+  return p;
+}
+
+// CartnetGemmArgs.gst_*: the statistics' operands and an epilogue with nothing else (checked before planning: a query
+// may come with arguments cartnet_gemm would refuse) ...
+static bool gate_stats_args(const CartnetGemmArgs& a) {
+  if (!(a.gst_g && a.gst_mean_rstd && a.gst_gamma && a.gst_beta && a.gst_ld >= a.N && a.gst_ld % 4 == 0)) return false;
+  if (!(aligned16(a.gst_g) && aligned16(a.gst_mean_rstd) && aligned16(a.gst_gamma) && aligned16(a.gst_beta))) return false;
+  return a.ngroups == 1 && a.nsegs >= 1 && a.nsegs <= CARTNET_MAX_GROUPS && !a.a_act && !a.b_act && !a.out_act &&
+         !a.dact[0] && !a.gather_i[0] && !a.cpre[0] && !a.bias[0] && a.colsum[0] && a.colsq[0] && !a.a_act_out[0] &&
+         a.N == 256;
+}
+// ... and a planned kernel that carries the epilogue
+static bool gate_stats_planned(const GemmPlan& p) { return p.reject == Reject::none && p.gate_stats; }
+
+extern "C" int cartnet_gemm_gate_stats_ok(const CartnetGemmArgs* args) {
+  return args && gate_stats_args(*args) && gate_stats_planned(plan_gemm(*args)) ? 1 : 0;
 }
 
 // ---- opt-in launch timing (bench.py): HIP events on the launch stream around every cartnet_gemm call ------------
 namespace {
 struct GemmRecord {
-  int variant;       // bit0 a_kstrided, bit1 b_kstrided, bit2 a_act, bit3 b_act, bits 4.. tile width / 64
+  int variant;       // GemmPlan.variant
   double flops;
   hipEvent_t e0, e1;
 };
@@ -254,8 +358,6 @@ int g_prof_every = 1;     // of the launches that qualify, every n-th is timed (
 long long g_prof_seen = 0;
 std::vector<GemmRecord> g_prof;
 }  // namespace
-
-static int cartnet_gemm_impl(const CartnetGemmArgs* args, void* stream);
 
 extern "C" int cartnet_profile_gemm(int32_t enable) {
   if (enable && !g_prof_on) {
@@ -302,42 +404,49 @@ extern "C" int cartnet_profile_gemm_read(CartnetGemmProfile* out, int32_t max_en
   return n;
 }
 
-extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
-  if (!g_prof_on || !args) return cartnet_gemm_impl(args, stream);
-  GemmRecord r;
-  int bn = choose_bn(*args) / 64;
-  // the variant names the kernel that runs: the 128-wide DMA-fed kernel reports tile width 128, the kernels that also
-  // write silu(A) set bit 9
-  const bool actout = args->a_act_out[0] != nullptr;
-  if (bn == 4 && !actout && f32_image_path(*args) && cn_gemm::use_f32nn128(*args) &&
-      !(args->nsegs == 1 && cn_gemm::use_f32p(*args)))
-    bn = 2;
-  // bit 8: the streamed dimension (rows of an activation x weight product, reduction length of a weight gradient) is
-  // edge-sized; bits 10..: the other inner dimension / 16 (K of an NN product, M of a weight gradient), capped
-  const long long streamed = args->a_kstrided ? args->K : args->M;
-  const int inner = args->a_kstrided ? args->M : args->K;
-  // bit 18: the persistent kernel takes the launch (gemm_f32p.hip; the same predicates launch_variant applies)
-  const bool persistent = bn == 4 && args->nsegs == 1 && args->splitk == 1 && epilogue_rows_aligned(*args) &&
-                          f32_image_path(*args) && cn_gemm::use_f32p(*args);
-  r.variant = (args->a_kstrided ? 1 : 0) | (args->b_kstrided ? 2 : 0) | (args->a_act ? 4 : 0) | (args->b_act ? 8 : 0) |
-              (bn << 4) | (streamed >= 32768 ? 256 : 0) | (actout ? 512 : 0) | ((inner > 4080 ? 255 : inner / 16) << 10) |
-              (persistent ? (1 << 18) : 0);
-  if (g_prof_only >= 0 && r.variant != g_prof_only) return cartnet_gemm_impl(args, stream);
-  if (g_prof_every > 1 && (g_prof_seen++ % g_prof_every) != 0) return cartnet_gemm_impl(args, stream);
-  const int nptr = args->ngroups > 1 ? args->ngroups : args->nsegs;
-  r.flops = 2.0 * args->M * args->N * (double)args->K * nptr;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return cartnet_gemm_impl(args, stream);
-  (void)hipEventRecord(r.e0, st);
-  const int rc = cartnet_gemm_impl(args, stream);
-  (void)hipEventRecord(r.e1, st);
-  g_prof.push_back(r);
-  return rc;
+// Enqueues a planned launch: the pre-pass, if any, then the family's launcher.
+static int run_plan(const GemmPlan& p, const CartnetGemmArgs& in, hipStream_t st) {
+  const CartnetGemmArgs& a = p.a;
+  if (p.prepass) {
+    ActJobs jobs;
+    for (int gI = 0; gI < CARTNET_MAX_GROUPS; ++gI) {
+      jobs.in[gI] = gI < a.ngroups ? a.A[gI] : nullptr;
+      jobs.out[gI] = gI < a.ngroups ? in.a_act_out[gI] : nullptr;
+    }
+    const long long total = (long long)a.M * a.K;
+    if (total > 0) {
+      const int blocks = (int)(total / 256 + 1 > 16384 ? 16384 : total / 256 + 1);
+      hipLaunchKernelGGL(cn_act_rows_kernel, dim3(blocks, a.ngroups), dim3(256), 0, st, jobs, a.M, a.K, a.lda);
+    }
+  }
+  // the DMA-fed activation x weight kernels: one workgroup per 128 x 256 tile (two per tile on the 128-wide kernel)
+  const dim3 grid(cn_ceil_div(a.M, cn_gemm::BM) * (a.N / 256), 1, a.ngroups);
+  switch (p.family) {
+    case Family::general: case Family::general_x3: {
+      const bool x3 = p.family == Family::general_x3;
+      if (p.bn == 256) cn_gemm::launch_bn<256>(a, p.fl, x3, st);
+      else if (p.bn == 128) cn_gemm::launch_bn<128>(a, p.fl, x3, st);
+      else cn_gemm::launch_bn<64>(a, p.fl, x3, st);
+      break;
+    }
+    case Family::f32p: cn_gemm::launch_f32p(a, st); break;
+    case Family::f32nn: cn_gemm::launch_f32nn(a.a_act, a, p.fl, grid, st); break;
+    case Family::f32nn_actout: cn_gemm::launch_f32nn_actout(a, p.fl, grid, st); break;
+    case Family::f32nn128: cn_gemm::launch_f32nn128(a.a_act, a, p.fl, dim3(2 * grid.x, 1, a.ngroups), st); break;
+    case Family::x3nn16: cn_gemm::launch_x3nn16(a.a_act, a, p.fl, grid, st); break;
+    case Family::x3nn: cn_gemm::launch_x3nn(a.a_act, a, p.fl, grid, st); break;
+    case Family::x3nn_actout: cn_gemm::launch_x3nn_actout(a, p.fl, grid, st); break;
+    case Family::f32tn: case Family::x3tn: cn_gemm::launch_tn(a, p.fl, st); break;
+    case Family::hnn: p.h(a, p.fl, grid, st); break;
+    case Family::htn: p.h(a, p.fl, dim3(grid.x, a.splitk, a.ngroups), st); break;
+  }
+  CN_LAUNCH_CHECK("cartnet_gemm");
+  return 0;
 }
 
-static int cartnet_gemm_impl(const CartnetGemmArgs* args, void* stream) {
+extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
   CN_CHECK(args != nullptr, "cartnet_gemm: null args");
-  CartnetGemmArgs a = *args;
+  const CartnetGemmArgs& a = *args;
   CN_CHECK(a.M >= 0 && a.N >= 0 && a.K >= 0, "cartnet_gemm: negative shape M=%d N=%d K=%d", a.M, a.N, a.K);
   CN_CHECK(a.ngroups >= 1 && a.ngroups <= CARTNET_MAX_GROUPS, "cartnet_gemm: ngroups=%d out of range", a.ngroups);
   CN_CHECK(a.nsegs >= 1 && a.nsegs <= CARTNET_MAX_GROUPS, "cartnet_gemm: nsegs=%d out of range", a.nsegs);
@@ -346,12 +455,7 @@ static int cartnet_gemm_impl(const CartnetGemmArgs* args, void* stream) {
   CN_CHECK(a.splitk == 1 || a.K >= 2 * cn_gemm::BK, "cartnet_gemm: split-K needs K >= %d", 2 * cn_gemm::BK);
   if (a.M == 0 || a.N == 0) return 0;
   const int nptr = a.ngroups > 1 ? a.ngroups : a.nsegs;
-  bool vecA = (a.lda % 4 == 0), vecB = (a.ldb % 4 == 0);
-  for (int i = 0; i < nptr; ++i) {
-    CN_CHECK(a.A[i] && a.B[i], "cartnet_gemm: null operand %d", i);
-    vecA = vecA && aligned16(a.A[i]);
-    vecB = vecB && aligned16(a.B[i]);
-  }
+  for (int i = 0; i < nptr; ++i) CN_CHECK(a.A[i] && a.B[i], "cartnet_gemm: null operand %d", i);
   for (int gI = 0; gI < a.ngroups; ++gI) {
     CN_CHECK(a.C[gI] != nullptr, "cartnet_gemm: null output %d", gI);
     CN_CHECK((a.gather_i[gI] == nullptr) == (a.gather_j[gI] == nullptr), "cartnet_gemm: gather_i/gather_j must pair");
@@ -368,16 +472,6 @@ static int cartnet_gemm_impl(const CartnetGemmArgs* args, void* stream) {
                    !a.out_act,
                "cartnet_gemm: split-K writes raw partial slabs, no epilogue allowed");
   }
-  CN_CHECK(!a.gst_g || gate_stats_launch_ok(a),
-           "cartnet_gemm: gst_g is set but this launch does not reach the kernel with the gate-statistics epilogue "
-           "(precision 0 / 1, N = 256, weight image, one group, colsum + colsq (+ resid) and nothing else, >= 64 / 96 row tiles: "
-           "ask cartnet_gemm_gate_stats_ok first)");
-  cn_gemm::GemmFlags fl;
-  fl.tile_m0 = 0;
-  fl.split0 = 0;
-  fl.k_lo = 0;
-  fl.k_hi = a.K;
-  fl.wide = epilogue_rows_aligned(a) ? 1 : 0;
   CN_CHECK(a.precision >= 0 && a.precision <= 2, "cartnet_gemm: precision=%d (0 = fp32 MFMA, 1 = bf16x3 split, 2 = bf16)",
            a.precision);
   CN_CHECK(a.dact_kind == 0 || (a.dact_kind == 1 && !cn_gemm::any_half(a)),
@@ -386,69 +480,40 @@ static int cartnet_gemm_impl(const CartnetGemmArgs* args, void* stream) {
            "cartnet_gemm: tile_policy=%d (0 = automatic, 1 = narrow tiles for grouped N = 256 products too, 3 = the persistent "
            "kernel wherever it has the form, 128 / 256 = force)",
            a.tile_policy);
-  // Few row tiles (atom-sized M, small batches): 128 x 256 tiles would leave most of the 256 CUs idle and the launch
-  // would last one tile's latency (16+ K-steps of a full tile); narrower column tiles (the general kernel's 128- and
-  // 64-wide forms, exact fp32) spread the same work over 2-4x as many workgroups.  Not at precision 2 (the bf16 kernels
-  // exist for 256-wide tiles only and their tiles are 6x shorter to begin with: measured a loss), and later at
-  // precision 1.
-  int bn = choose_bn(a);
-  if (bn == 256 && segments_fold(a)) {
-    // K-segments that are adjacent column blocks of one matrix: one product over the concatenated K.  Folded only when
-    // the DMA-fed kernel is certain to take the launch (B[0] alone does not describe the folded operand).
-    a.K *= a.nsegs;
-    a.nsegs = 1;
-    a.b_split[0] = a.b_split_folded;
-  }
-  fl.x3 = a.precision;
-  fl.vecA = vecA ? 1 : 0;
-  fl.vecB = vecB ? 1 : 0;
-  int kchunk = (a.K + a.splitk - 1) / a.splitk;
-  kchunk = ((kchunk + cn_gemm::BK - 1) / cn_gemm::BK) * cn_gemm::BK;
-  if (kchunk == 0) kchunk = cn_gemm::BK;
-  fl.kchunk = kchunk;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const GemmPlan p = plan_gemm(a);
+  CN_CHECK(!a.gst_g || (gate_stats_args(a) && gate_stats_planned(p)),
+           "cartnet_gemm: gst_g is set but this launch does not reach the kernel with the gate-statistics epilogue "
+           "(precision 0 / 1, N = 256, weight image, one group, colsum + colsq (+ resid) and nothing else, >= 64 / 96 row tiles: "
+           "ask cartnet_gemm_gate_stats_ok first)");
   if (a.a_act_out[0]) {
-    CN_CHECK(a.a_act && !a.a_kstrided && a.nsegs == 1, "cartnet_gemm: a_act_out needs a_act = 1, a k-contiguous A and no K-segments");
+    CN_CHECK(a.a_act && !a.a_kstrided && p.a.nsegs == 1, "cartnet_gemm: a_act_out needs a_act = 1, a k-contiguous A and no K-segments");
     for (int gI = 0; gI < a.ngroups; ++gI) CN_CHECK(a.a_act_out[gI] != nullptr, "cartnet_gemm: a_act_out[%d] missing", gI);
-    // the DMA-fed 256-wide kernels write the activated operand on its way into LDS (gemm_f32ao.h, gemm_x3ao.h); any
-    // other launch (narrow tiles of a small batch, no weight image) gets it from an elementwise pass first
-    bool fused = bn == 256 && !a.b_act && a.b_kstrided && a.splitk == 1 && fl.wide && vecA && vecB &&
-                 a.N % 256 == 0 && a.K > 0 && a.K % cn_gemm::BK == 0 && (double)a.M * a.lda * 4.0 < 4294967296.0;
-    for (int gI = 0; gI < a.ngroups; ++gI) fused = fused && a.b_split[gI] && aligned16(a.a_act_out[gI]);
-    if (!fused) {
-      ActJobs jobs;
-      for (int gI = 0; gI < CARTNET_MAX_GROUPS; ++gI) {
-        jobs.in[gI] = gI < a.ngroups ? a.A[gI] : nullptr;
-        jobs.out[gI] = gI < a.ngroups ? a.a_act_out[gI] : nullptr;
-        a.a_act_out[gI] = nullptr;
-      }
-      const long long total = (long long)a.M * a.K;
-      if (total > 0) {
-        const int blocks = (int)(total / 256 + 1 > 16384 ? 16384 : total / 256 + 1);
-        hipLaunchKernelGGL(cn_act_rows_kernel, dim3(blocks, a.ngroups), dim3(256), 0, st, jobs, a.M, a.K, a.lda);
-      }
-    }
   }
-  const bool half = cn_gemm::any_half(a);
-  if (half) {
-    CN_CHECK(a.precision == 2 && bn == 256 && a.K > 0,
+  if (cn_gemm::any_half(a)) {
+    CN_CHECK(a.precision == 2 && p.bn == 256 && a.K > 0,
              "cartnet_gemm: a_half / b_half / c_half / dact_half need precision 2 and a 256-wide launch");
-    CN_CHECK(!a.a_act_out[0] && !(a.a_kstrided && (a.c_half || a.dact_half)) && !(!a.a_kstrided && a.b_half),
+    CN_CHECK(!p.a.a_act_out[0] && !(a.a_kstrided && (a.c_half || a.dact_half)) && !(!a.a_kstrided && a.b_half),
              "cartnet_gemm: half storage: a_act_out, a bf16 weight-gradient output and a bf16 weight operand are not supported");
-    cn_gemm::g_half_launched = false;
   }
-  bool ok;
-  if (bn == 256) ok = cn_gemm::launch_bn<256>(a, fl, st);
-  else if (bn == 128) ok = cn_gemm::launch_bn<128>(a, fl, st);
-  else ok = cn_gemm::launch_bn<64>(a, fl, st);
-  CN_CHECK(ok, "cartnet_gemm: unsupported layout/activation combination (a_ks=%d b_ks=%d a_act=%d b_act=%d)",
+  CN_CHECK(p.reject != Reject::layout, "cartnet_gemm: unsupported layout/activation combination (a_ks=%d b_ks=%d a_act=%d b_act=%d)",
            a.a_kstrided, a.b_kstrided, a.a_act, a.b_act);
-  CN_CHECK(!half || cn_gemm::g_half_launched,
+  CN_CHECK(p.reject != Reject::half,
            "cartnet_gemm: no half-storage kernel for this launch (needs the pre-split weight image of an activation x "
            "weight product, or a weight gradient with M %% 4 == 0; 16-byte aligned rows; a compiled operand combination: "
            "csrc/gemm_h.hip)");
-  CN_LAUNCH_CHECK("cartnet_gemm");
-  return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!g_prof_on) return run_plan(p, a, st);
+  if (g_prof_only >= 0 && p.variant != g_prof_only) return run_plan(p, a, st);
+  if (g_prof_every > 1 && (g_prof_seen++ % g_prof_every) != 0) return run_plan(p, a, st);
+  GemmRecord r;
+  r.variant = p.variant;
+  r.flops = 2.0 * a.M * a.N * (double)a.K * nptr;
+  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return run_plan(p, a, st);
+  (void)hipEventRecord(r.e0, st);
+  const int rc = run_plan(p, a, st);
+  (void)hipEventRecord(r.e1, st);
+  g_prof.push_back(r);
+  return rc;
 }
 
 extern "C" int cartnet_splitk_reduce(const float* const* slabs, float* const* outs, int32_t njobs, int32_t splitk,

@@ -2,5 +2,5 @@
 #include "gemm_kernel.h"
 
 namespace cn_gemm {
-template bool launch_bn<64>(const CartnetGemmArgs&, const GemmFlags&, hipStream_t);
+template void launch_bn<64>(const CartnetGemmArgs&, const GemmFlags&, bool, hipStream_t);
 }

@@ -59,37 +59,19 @@ PLaunch p_find(bool a_act, bool act_out, int kind, int ns) {
   if (a_act == AA && act_out == AO && kind == KD && ns == NSV) return &p_launch<AA, AO, KD, NSV>;
   CN_P_FORMS_A(CN_P)
   CN_P_FORMS_B(CN_P)
-#ifndef CN_P_NO_C         /* A/B builds: the third unit's forms stay on the second-generation kernels */
   CN_P_FORMS_C(CN_P)
-#endif
 #undef CN_P
   return nullptr;
 }
 }  // namespace
 
-// A launch the persistent kernel takes.  The caller (launch_variant) has already established the DMA-fed path: precision 0,
-// weight images for every group, 16-byte aligned rows, one K-segment, no split-K, full 256-column tiles.
+// A launch the persistent kernel takes.  The caller (plan_gemm in gemm.hip) has already established the DMA-fed path:
+// precision 0, weight images for every group, 16-byte aligned rows, one K-segment, no split-K, full 256-column tiles.
 bool use_f32p(const CartnetGemmArgs& a) {
   // tile_policy: 3 forces this kernel (any size it has the form for), 128 / 256 exclude it; 0 (and 1: the iComformer path's
-  // grouped products) take it from 4 tiles per CU up.  CN_F32P_DEFAULT (A/B builds): 0 never, 1 policy 0 only, 2 both.
-  // Same-box A B A B (profiles/r06_exp_f32p_step_ab.txt): CartNet's step 13.68-13.73 -> 13.46-13.47 ms, iComformer's
-  // 27.31-27.34 -> 26.75-27.04 ms.
-#ifndef CN_F32P_DEFAULT
-#define CN_F32P_DEFAULT 2
-#endif
-#ifdef CN_P_WHY    /* diagnostic build: which edge-sized launches stay on the second-generation kernels, and why */
-  if (a.M >= 100000 && a.tile_policy != 128 && a.tile_policy != 256) {
-    const int subs = (a.N / F32_BN) * a.ngroups;
-    const bool form = p_find(a.a_act != 0, a.a_act_out[0] != nullptr, p_kind(a), a.K / BK) != nullptr;
-    const bool taken = (a.K == 256 || a.K == 512 || a.K == 768) && a.N % F32_BN == 0 && 32 % (subs ? subs : 1) == 0 && form;
-    fprintf(stderr, "f32p %s: M=%d N=%d K=%d groups=%d policy=%d a_act=%d act_out=%d kind=%d gather=%d gst=%d resid=%d dact=%d form=%d\n",
-            taken ? "TAKEN" : "LEFT", a.M, a.N, a.K, a.ngroups, a.tile_policy, a.a_act, a.a_act_out[0] != nullptr, p_kind(a),
-            a.gather_i[0] != nullptr, a.gst_g != nullptr, a.resid[0] != nullptr, a.dact[0] != nullptr, (int)form);
-  }
-#endif
+  // grouped products) take it from 4 tiles per CU up.  Same-box A B A B (profiles/r06_exp_f32p_step_ab.txt): CartNet's
+  // step 13.68-13.73 -> 13.46-13.47 ms, iComformer's 27.31-27.34 -> 26.75-27.04 ms.
   if (a.tile_policy == 128 || a.tile_policy == 256) return false;
-  if (a.tile_policy == 0 && CN_F32P_DEFAULT < 1) return false;
-  if (a.tile_policy == 1 && CN_F32P_DEFAULT < 2) return false;
   if (a.K != 256 && a.K != 512 && a.K != 768) return false;
   if (a.N % F32_BN != 0 || a.ngroups * a.N > P_BIAS_FLOATS || a.M < 2) return false;
   if (32 % ((a.N / F32_BN) * a.ngroups) != 0) return false;   // a workgroup keeps one (group, column tile): 32 slots per XCD
@@ -99,9 +81,6 @@ bool use_f32p(const CartnetGemmArgs& a) {
   if (a.gst_g && (!a.gst_env || a.ngroups != 1 || a.bias[0] || a.dact[0] || a.cpre[0] || a.out_act || a.a_act || !a.colsum[0] ||
                   !a.colsq[0] || (double)((double)a.M + 384.0) * a.gst_ld * 4.0 >= 4294967296.0))
     return false;
-#ifdef CN_P_NO_GATHER     /* A/B builds: the gather launches stay on the second-generation kernels */
-  if (a.gather_i[0]) return false;
-#endif
   if (a.gather_i[0] && (a.gather_rows <= 0 || !a.tgt || !a.src || (double)a.gather_rows * a.ldg * 4.0 >= 4294967296.0))
     return false;                                              // (the gather form's 32-bit offsets into the node-term tables)
   // every byte offset is 32 bits, every buffer descriptor's record count too

@@ -418,8 +418,7 @@ __device__ __forceinline__ void acc_block_to_scr(const f32x4 (&acc)[TM][TN], int
       for (int r = 0; r < 4; ++r) scr[(16 * ta + 4 * lq + r) * ld + 16 * tb + li] = acc[2 * a + ta][2 * b + tb][r];
 }
 
-// S: the wave grid (Shape<BN> for the 512-thread kernels, ShapeQ for the 256-thread one of gemm_f32q.h); NT: threads per
-// workgroup.
+// S: the wave grid (Shape<BN> for the 512-thread kernels); NT: threads per workgroup.
 template <class S, int BN, int NT, int KIND, class ACC>
 __device__ __forceinline__ void epilogue_wide_s(const CartnetGemmArgs& p, ACC& acc,
                                                 int g, int row0, int col0, int tile_m, int wm, int wn, int lane, int tid,
@@ -988,7 +987,8 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_kernel(const CartnetGemmA
 #undef CN_EPI
 }
 
-// gemm_x3.hip
+// The launchers of the DMA-fed kernel families (gemm.hip: plan_gemm picks one per launch)
+// gemm_x3.hip: precision 2 (bf16, pre-split weight image) activation x weight; precision 1 / 2 weight gradients
 void launch_x3nn(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
 void launch_x3tn(bool b_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
 // gemm_f32.hip
@@ -996,12 +996,6 @@ void launch_f32nn(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim
 void launch_f32tn(bool b_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
 // gemm_f32w128.hip: 128-wide DMA-fed fp32 kernel, chosen by use_f32nn128 (gemm.hip)
 void launch_f32nn128(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
-bool use_f32nn128(const CartnetGemmArgs& a);
-#ifdef CN_EXPERIMENTAL_Q
-// experimental/gemm_f32q.hip (not in the product build): 128 x 128 tiles on 256-thread workgroups, four per CU
-void launch_f32nnq(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
-bool use_f32nnq(const CartnetGemmArgs& a);
-#endif
 // gemm_f32p.hip: the persistent kernel (one workgroup per CU, two accumulator sets; K = 256 / 512)
 bool use_f32p(const CartnetGemmArgs& a);
 void launch_f32p(const CartnetGemmArgs& a, hipStream_t st);
@@ -1012,11 +1006,15 @@ void launch_f32nn_actout(const CartnetGemmArgs& a, const GemmFlags& fl, dim3 gri
 void launch_x3nn16(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
 // gemm_x3ao.hip: the same for the pre-split bf16x3 / bf16 kernel
 void launch_x3nn_actout(const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
-// gemm_h.hip: precision 2 with operands / output stored as bf16 (CartnetGemmArgs.*_half); false = combination not compiled
-bool launch_hnn(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
-bool launch_htn(bool b_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st);
+// gemm_h.hip: precision 2 with operands / output stored as bf16 (CartnetGemmArgs.*_half): the launcher of the compiled
+// operand combination of an activation x weight product / a weight gradient, nullptr where none is compiled
+typedef void (*HLaunch)(const CartnetGemmArgs&, const GemmFlags&, dim3, hipStream_t);
+HLaunch find_hnn(const CartnetGemmArgs& a);
+HLaunch find_htn(const CartnetGemmArgs& a);
 inline bool any_half(const CartnetGemmArgs& a) { return a.a_half || a.b_half || a.c_half || a.dact_half; }
-extern thread_local bool g_half_launched;     // set by launch_variant when a half-storage kernel took the launch
+// gemm_bn256.hip: a weight gradient on the DMA-fed kernels (launch_f32tn / launch_x3tn): one launch over all of K, or
+// split-K slabs over the whole K-steps with the < 16-row K tail as the last slab (cn_gemm_tn_tail_kernel)
+void launch_tn(const CartnetGemmArgs& a, GemmFlags fl, hipStream_t st);
 
 // K tail of a split-K weight gradient on the DMA-fed kernels (the < 16 rows behind the last whole K-step) as the LAST slab:
 // out[m, n] = sum_k A[k, m] (silu?)(B[k, n]), a few thousand FMAs per output row.  As a launch of the checked MFMA kernel
@@ -1046,8 +1044,11 @@ __global__ __launch_bounds__(256) void cn_gemm_tn_tail_kernel(const CartnetGemmA
   }
 }
 
+// The general tile kernel: the predicate-free kernel over the whole row tiles (and a ragged last one when A is
+// k-contiguous), the checked kernel over the rest.  x3 (precision 1, 256-wide activation x weight products without a
+// pre-split weight image): the predicate-free launches run the first-generation bf16x3 kernel, both operands split in flight.
 template <bool A_KS, bool B_KS, int BN, bool A_ACT, bool B_ACT>
-void launch_variant(const CartnetGemmArgs& a, GemmFlags fl, hipStream_t st) {
+void launch_variant(const CartnetGemmArgs& a, GemmFlags fl, bool x3, hipStream_t st) {
   const int tiles_n = cn_ceil_div(a.N, BN);
   const int full_m = a.M / BM, rag_m = (a.M % BM) ? 1 : 0;
   auto launch = [&](auto fast_tag, int m0, int nm, int s0, int ns, int k_lo, int k_hi, int kchunk) {
@@ -1058,107 +1059,17 @@ void launch_variant(const CartnetGemmArgs& a, GemmFlags fl, hipStream_t st) {
     fl.k_lo = k_lo;
     fl.k_hi = k_hi;
     fl.kchunk = kchunk;
-    // bf16x3 kernels exist for the 256-wide tile and the operand layouts of the model's big GEMMs
-    // (weight-gradient GEMMs, A_KS, stay on the fp32 MFMA: their k-strided operands need a transposing LDS fill that
-    //  measured 2.4x slower than the fp32 kernel)
-    constexpr bool X3_OK = FAST && BN == 256 && B_KS && !A_KS;
-    if constexpr (X3_OK) {
-      if (fl.x3) {
-        // second-generation kernel (gemm_x3.h) when the weight operand comes pre-split and the epilogue is vectorisable
-        bool presplit = fl.wide && a.splitk == 1 && m0 == 0 && a.nsegs == 1 && (double)a.M * a.lda * 4.0 < 4294967296.0;
-        const int nptr = a.ngroups > 1 ? a.ngroups : a.nsegs;
-        for (int i = 0; i < nptr; ++i) presplit = presplit && a.b_split[i] != nullptr;
-        if (presplit && fl.x3 == 2 && any_half(a)) {
-          g_half_launched = launch_hnn(A_ACT, a, fl, dim3(nm * tiles_n, ns, a.ngroups), st);
-          return;
-        }
-        if (presplit) {
-          if (A_ACT && a.a_act_out[0]) launch_x3nn_actout(a, fl, dim3(nm * tiles_n, ns, a.ngroups), st);
-          else launch_x3nn(A_ACT, a, fl, dim3(nm * tiles_n, ns, a.ngroups), st);
-          return;
-        }
-        if (fl.x3 == 1 && !any_half(a)) {   // first-generation kernel (both operands split in flight); precision 2 has no such form
-          hipLaunchKernelGGL((cn_gemm_kernel<A_KS, B_KS, BN, A_ACT, B_ACT, true, 1>), dim3(nm * tiles_n, ns, a.ngroups),
-                             dim3(NTHREADS), 0, st, a, fl);
-          return;
-        }
-      }
-    }
-    // fp32 MFMA with a pre-packed weight operand: second-generation kernel (gemm_f32.h)
     if constexpr (FAST && BN == 256 && B_KS && !A_KS) {
-      if (!fl.x3) {
-        bool prepacked = fl.wide && a.splitk == 1 && m0 == 0 && a.nsegs == 1 && (double)a.M * a.lda * 4.0 < 4294967296.0;
-        const int nptr = a.ngroups > 1 ? a.ngroups : a.nsegs;
-        for (int i = 0; i < nptr; ++i) prepacked = prepacked && a.b_split[i] != nullptr;
-#ifdef CN_P_WHY
-        if (!prepacked && a.M >= 100000)
-          fprintf(stderr, "f32p NOIMG: M=%d N=%d K=%d groups=%d segs=%d wide=%d splitk=%d m0=%d img0=%d\n", a.M, a.N, a.K, a.ngroups,
-                  a.nsegs, (int)fl.wide, a.splitk, m0, a.b_split[0] != nullptr);
-#endif
-        if (prepacked) {
-          if (use_f32p(a)) launch_f32p(a, st);
-          else if (A_ACT && a.a_act_out[0]) launch_f32nn_actout(a, fl, dim3(nm * tiles_n, ns, a.ngroups), st);
-#ifdef CN_EXPERIMENTAL_Q
-          else if (use_f32nnq(a)) launch_f32nnq(A_ACT, a, fl, dim3(nm * tiles_n * 2, ns, a.ngroups), st);
-#endif
-          else if (use_f32nn128(a)) launch_f32nn128(A_ACT, a, fl, dim3(nm * tiles_n * 2, ns, a.ngroups), st);
-          else launch_f32nn(A_ACT, a, fl, dim3(nm * tiles_n, ns, a.ngroups), st);
-          return;
-        }
+      if (x3) {
+        hipLaunchKernelGGL((cn_gemm_kernel<A_KS, B_KS, BN, A_ACT, B_ACT, true, 1>), dim3(nm * tiles_n, ns, a.ngroups),
+                           dim3(NTHREADS), 0, st, a, fl);
+        return;
       }
     }
-    if (any_half(a)) return;      // bf16 operands: only the half-storage kernels may read them (cartnet_gemm reports it)
     hipLaunchKernelGGL((cn_gemm_kernel<A_KS, B_KS, BN, A_ACT, B_ACT, FAST, 0>), dim3(nm * tiles_n, ns, a.ngroups),
                        dim3(NTHREADS), 0, st, a, fl);
   };
   auto round_up = [](int v) { return ((v + BK - 1) / BK) * BK; };
-  // weight gradients at precision 1 / 2: the transposing-read kernel takes every row tile (also a ragged last one)
-  // over the whole K-steps; a K tail (< 16 rows) is one more slab from the checked fp32 kernel
-  if constexpr (A_KS && B_KS && BN == 256 && !A_ACT) {
-    // precision 0: the all-DMA fp32 kernel (gemm_f32.h); a ragged last row tile needs M % 4 == 0 (its lanes clamp)
-    // (SiLU on the B operand: the five-stage instance that activates its DMA'd tiles in place in LDS, gemm_f32.h -- 10 %
-    //  slower than a plain operand; on the fragments it was 15 % and the register-staged kernel 2-3x)
-    if (fl.x3 == 2 && any_half(a)) {
-      // half-storage weight gradient: one kernel over all of K (it masks a ragged last K-step itself), S slabs
-      if (a.M % 4 == 0 && fl.vecA && fl.vecB && a.nsegs == 1 && a.N % BN == 0 && a.M > 0 && a.K >= 1 &&
-          (a.splitk > 1 || fl.wide)) {
-        fl.tile_m0 = 0; fl.split0 = 0; fl.k_lo = 0; fl.k_hi = a.K;
-        fl.kchunk = round_up(cn_ceil_div(a.K, a.splitk));
-        g_half_launched = launch_htn(B_ACT, a, fl, dim3(cn_ceil_div(a.M, BM) * tiles_n, a.splitk, a.ngroups), st);
-      }
-      return;
-    }
-#ifdef CN_TN_BACT_STAGED    /* A/B builds: SiLU-on-B weight gradients at precision 0 on the register-staged kernel */
-    const bool tn_ok = a.M % 4 == 0 && (fl.x3 || !B_ACT);
-#else
-    const bool tn_ok = a.M % 4 == 0;
-#endif
-    auto launch_tn = [&](dim3 grid) {
-      if (fl.x3) launch_x3tn(B_ACT, a, fl, grid, st);
-      else launch_f32tn(B_ACT, a, fl, grid, st);
-    };
-    if (tn_ok && fl.vecA && fl.vecB && a.nsegs == 1 && a.N % BN == 0 && a.M > 0 && a.K >= BK) {
-      const int K16x = (a.K / BK) * BK, tailx = a.K - K16x;
-      const int tiles_mx = cn_ceil_div(a.M, BM);
-      if (a.splitk == 1 && tailx == 0 && fl.wide) {
-        fl.tile_m0 = 0; fl.split0 = 0; fl.k_lo = 0; fl.k_hi = a.K; fl.kchunk = K16x;
-        launch_tn(dim3(tiles_mx * tiles_n, 1, a.ngroups));
-        return;
-      }
-      if (a.splitk > 1) {
-        const int nfastx = tailx ? a.splitk - 1 : a.splitk;
-        fl.tile_m0 = 0; fl.split0 = 0; fl.k_lo = 0; fl.k_hi = K16x;
-        fl.kchunk = round_up(cn_ceil_div(K16x, nfastx));
-        launch_tn(dim3(tiles_mx * tiles_n, nfastx, a.ngroups));
-        if (tailx) {
-          const long long items = (long long)a.M * (a.N / 4);
-          const int blocks = (int)(items / 256 + 1 > 2048 ? 2048 : items / 256 + 1);
-          hipLaunchKernelGGL((cn_gemm_tn_tail_kernel<B_ACT>), dim3(blocks, a.ngroups), dim3(256), 0, st, a, K16x, nfastx);
-        }
-        return;
-      }
-    }
-  }
   // the predicate-free kernel covers ragged row tiles too when A is k-contiguous (row clamp in Stager::load)
   const bool fast_ok = fl.vecA && fl.vecB && (a.N % BN == 0) && (full_m > 0 || !A_KS) && a.M > 0;
   const int fast_m = A_KS ? full_m : full_m + rag_m;      // row tiles the predicate-free kernel takes
@@ -1187,18 +1098,17 @@ void launch_variant(const CartnetGemmArgs& a, GemmFlags fl, hipStream_t st) {
   if (tail) launch(std::false_type{}, 0, full_m + rag_m, nfast, 1, K16, a.K, BK);
 }
 
-// Operand layouts / fused activations the CartNet path uses.  Returns false for an unsupported combination.
+// Operand layouts / fused activations the CartNet path uses (gemm.hip: plan_gemm refuses every other combination).
 template <int BN>
-bool launch_bn(const CartnetGemmArgs& a, const GemmFlags& fl, hipStream_t st) {
+void launch_bn(const CartnetGemmArgs& a, const GemmFlags& fl, bool x3, hipStream_t st) {
   const int combo = (a.a_kstrided ? 1 : 0) | (a.b_kstrided ? 2 : 0) | (a.a_act ? 4 : 0) | (a.b_act ? 8 : 0);
   switch (combo) {
-    case 0: launch_variant<false, false, BN, false, false>(a, fl, st); return true;   // Y = X W^T
-    case 4: launch_variant<false, false, BN, true, false>(a, fl, st); return true;    // Y = silu(X) W^T
-    case 2: launch_variant<false, true, BN, false, false>(a, fl, st); return true;    // dX = dY W ; Y = X Wt
-    case 6: launch_variant<false, true, BN, true, false>(a, fl, st); return true;     // Y = silu(X) Wt
-    case 3: launch_variant<true, true, BN, false, false>(a, fl, st); return true;     // dW = dY^T X
-    case 11: launch_variant<true, true, BN, false, true>(a, fl, st); return true;     // dW = dY^T silu(X)
-    default: return false;
+    case 0: launch_variant<false, false, BN, false, false>(a, fl, x3, st); break;   // Y = X W^T
+    case 4: launch_variant<false, false, BN, true, false>(a, fl, x3, st); break;    // Y = silu(X) W^T
+    case 2: launch_variant<false, true, BN, false, false>(a, fl, x3, st); break;    // dX = dY W ; Y = X Wt
+    case 6: launch_variant<false, true, BN, true, false>(a, fl, x3, st); break;     // Y = silu(X) Wt
+    case 3: launch_variant<true, true, BN, false, false>(a, fl, x3, st); break;     // dW = dY^T X
+    case 11: launch_variant<true, true, BN, false, true>(a, fl, x3, st); break;     // dW = dY^T silu(X)
   }
 }
 

@@ -3,12 +3,8 @@
 
 namespace cn_gemm {
 
+// precision 2: plain bf16 operands, one MFMA product (precision 1 runs gemm_x3s.h's kernel: launch_x3nn16)
 void launch_x3nn(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, dim3 grid, hipStream_t st) {
-  const bool one = fl.x3 == 2;   // precision 2: plain bf16 operands, one MFMA product
-  if (!one) {      // precision 1: the six piece products on the 16x16x32 MFMA shape (gemm_x3s.h; round 3: -1...-4 % per launch)
-    launch_x3nn16(a_act, a, fl, grid, st);
-    return;
-  }
   if (a_act) hipLaunchKernelGGL((cn_gemm_x3nn_kernel<true, true>), grid, dim3(NTHREADS), 0, st, a, fl);
   else hipLaunchKernelGGL((cn_gemm_x3nn_kernel<false, true>), grid, dim3(NTHREADS), 0, st, a, fl);
 }

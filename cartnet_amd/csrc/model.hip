@@ -873,10 +873,10 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
         a.colsum[0] = w.gpa; a.colsq[0] = w.gpb;
         CN_CHECK(cartnet_gemm_gate_stats_ok(&a) == 1,
                  "cartnet_model_backward: the dE product of layer %d does not take the gate-statistics kernel (model.hip: "
-                 "gate_sums_fused is out of step with gemm.hip: gate_stats_launch_ok)", l);
+                 "gate_sums_fused is out of step with gemm.hip: plan_gemm)", l);
       }
       if (half && D != 256) {
-        // the two K-segments only fold into one product at N = 256 (gemm.hip: segments_fold), and no kernel reads bf16
+        // the two K-segments only fold into one product at N = 256 (gemm.hip: segments_adjacent), and no kernel reads bf16
         // K-segments: two single-segment products instead, the second adding onto the first in place (every output
         // element is read and written by the same thread); the layer-0 epilogue goes on the second
         CartnetGemmArgs a1 = gemm_args(E, D, D, 2 * D, 3 * D, D);

@@ -382,9 +382,6 @@ def load() -> C.CDLL:
         if C.sizeof(cls) != sz:
             raise CartnetHipError(f"{LIB_PATH}: sizeof({cls.__name__}) is {sz} in the library, {C.sizeof(cls)} in "
                                   "cartnet_amd/lib.py -- rebuild the library (python -m cartnet_amd.build)")
-    # experiment builds only (CARTNET_BUILD_EXPERIMENTAL=1, csrc/experimental/): CARTNET_Q selects the quad kernel
-    if os.environ.get("CARTNET_Q") and hasattr(lib, "cartnet_gemm_experimental_q"):
-        lib.cartnet_gemm_experimental_q(int(os.environ["CARTNET_Q"]))
     _lib = lib
     return lib
 

@@ -340,3 +340,25 @@ def test_gate_statistics_form(ops, M, with_resid):
     for k, r in ((1, (v * w).sum(0)), (2, (v * w * ghat).sum(0))):
         scale = (v * w).abs().sum(0).max() if k == 1 else (v * w * ghat).abs().sum(0).max()
         assert (got[3][k] - r).abs().max() <= 5e-6 * scale and (got[3][k] - got[128][k]).abs().max() <= 5e-6 * scale
+
+
+def test_the_launch_timer_names_the_kernel_that_runs_a_folded_product(ops):
+    """Two adjacent K-segments with the image of the concatenated weight fold into one K = 512 product; the launch timer's
+    variant describes that launch as it runs: the persistent kernel where the library picks it (tile_policy 0, 1,024 row
+    tiles), the 256- / 128-wide DMA-fed kernels where tile_policy forces them -- each with the folded K."""
+    M = 128 * 1024
+    A = rnd(M, 2 * D, seed=81)
+    Wseg = [rnd(D, D, seed=82 + g, scale=0.06) for g in range(2)]
+    folded = torch.cat(ops.pack_b(Wseg))
+    out = torch.empty(M, D, device=dev())
+    names = {}
+    for pol in (0, 256, 128):
+        torch.cuda.synchronize()
+        ops.profile_gemm(True)
+        try:
+            ops.gemm([A[:, :D], A[:, D:]], Wseg, out, b_kstrided=True, segments=True, b_split_folded=folded, tile_policy=pol)
+            torch.cuda.synchronize()
+            names[pol] = {k: v["launches"] for k, v in ops.profile_gemm_read().items()}
+        finally:
+            ops.profile_gemm(False)
+    assert names == {0: {"nn256p[E-rows,K=512]": 1}, 256: {"nn256[E-rows,K=512]": 1}, 128: {"nn128[E-rows,K=512]": 1}}

@@ -40,6 +40,26 @@ __device__ __forceinline__ float cn_dsilu(float x) {
   return s * (1.0f + x * (1.0f - s));
 }
 
+// softplus(x) = max(x, 0) + log1p(exp(-|x|)), threshold 20 as torch.nn.functional.softplus, on the hardware exp / rcp.
+// The one definition for every site (cartnet_eltwise op 0, cartnet_softplus_update_fwd, the GEMM out_act epilogues with
+// dact_kind 1), so a value is the same bit for bit whichever of them produced it.  log1p(t) = 2 atanh(s) with
+// s = t / (2 + t) in [0, 1/3]: 2s (1 + s^2/3 + ... + s^10/11) leaves out less than 1.5e-7 of the sum for every t <= 1,
+// and no log(1 + t) is taken -- rounding 1 + t to fp32 loses log2(1/t) bits of t (that form was 1.2e-4 off near x = -7.6).
+// Accuracy pinned by tests/test_gpu_accuracy.py: within 2e-6 + 1e-7 |x| of fp64, relative, per element (the |x| term is
+// __expf's rounding of its argument x log2(e) to fp32).  libm's log1pf(expf(x)) made the element-wise passes compute-bound.
+__device__ __forceinline__ float cn_softplus(float x) {
+  if (x > 20.f) return x;
+  const float t = __expf(-fabsf(x));
+  const float s = t * __builtin_amdgcn_rcpf(2.0f + t);
+  const float z = s * s;
+  float p = fmaf(z, 1.f / 11.f, 1.f / 9.f);
+  p = fmaf(p, z, 1.f / 7.f);
+  p = fmaf(p, z, 1.f / 5.f);
+  p = fmaf(p, z, 1.f / 3.f);
+  const float r = s + s;
+  return fmaxf(x, 0.f) + fmaf(r * z, p, r);
+}
+
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // Per-block partial column sums, kept in fp64 (see cartnet_hip.h "partial sums").  Four waves each hold the sums

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void cn_gemm_f32p_kernel(const Cartnet
       const unsigned voff = lv_c + ((unsigned)c.row0 + (unsigned)(a * 32 + 8 * q + j)) * ldc4;
       if constexpr (CPRE) st1_stream(v[j], voff, p_srd, std::integral_constant<int, b * 128>{});
       float o = v[j];
-      if constexpr (OUTACT) o = (KIND & 256) ? fast_softplus(o) : fast_silu(o);
+      if constexpr (OUTACT) o = (KIND & 256) ? cn_softplus(o) : fast_silu(o);
       st1(o, voff, c_srd, std::integral_constant<int, b * 128>{});
     }
   };

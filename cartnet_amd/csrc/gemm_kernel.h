@@ -42,14 +42,6 @@ __device__ __forceinline__ float fast_dsilu(float x) {
   const float s = fast_sigmoid(x);
   return s * (1.0f + x * (1.0f - s));
 }
-// softplus(x) = max(x, 0) + log1p(exp(-|x|)) on the hardware exp / log (comformer_ops.hip's softplus_f: the same expression,
-// so a value is the same whether an epilogue or the element-wise kernel produced it); threshold 20 as torch's.
-__device__ __forceinline__ float fast_softplus(float x) {
-  if (x > 20.f) return x;
-  const float t = __expf(-fabsf(x));
-  const float l = t < 4.8828125e-4f ? t - 0.5f * t * t : __logf(1.0f + t);
-  return fmaxf(x, 0.f) + l;
-}
 
 // One operand tile (ROWS x BK) per K-step: global -> registers -> LDS.
 template <int ROWS, bool KS, bool ACT>
@@ -337,7 +329,7 @@ __device__ __forceinline__ void epilogue(const CartnetGemmArgs& p, f32x16 (&acc)
           cq[b] += (double)v * (double)v;
         }
         if (CPRE) cpre[(size_t)grow * p.ldc + gcol] = v;
-        if (OUTACT) v = (kind & 256) ? fast_softplus(v) : fast_silu(v);
+        if (OUTACT) v = (kind & 256) ? cn_softplus(v) : fast_silu(v);
         C[(size_t)grow * p.ldc + gcol] = v;
       }
     }
@@ -630,7 +622,7 @@ __device__ __forceinline__ void epilogue_wide_s(const CartnetGemmArgs& p, ACC& a
         if (CPRE) stv4_stream(cpre + (size_t)grow[i] * p.ldc + gcol, v);
         if (OUTACT) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = DSP ? fast_softplus(v[q]) : fast_silu(v[q]);
+          for (int q = 0; q < 4; ++q) v[q] = DSP ? cn_softplus(v[q]) : fast_silu(v[q]);
         }
         stv4(C + (size_t)grow[i] * p.ldc + gcol, v);
       }

@@ -11,6 +11,9 @@
     Asserted: both precisions stay under BOUND_U and bf16x3 is never worse than 2x the fp32 MFMA on the same operands.
 (b) fast_sigmoid / fast_silu / fast_dsilu (v_exp_f32 + bare v_rcp_f32, csrc/gemm_kernel.h:39) and the gate kernels'
     cn_sigmoid at edge values -- +-88 (exp overflow threshold), +-1e4, +-inf, NaN -- against torch's own SiLU / sigmoid.
+    cn_softplus (csrc/common.h) element by element through every site that runs it -- cartnet_eltwise op 0,
+    cartnet_softplus_update_fwd and the GEMM out_act epilogue of the general, DMA-fed and persistent kernels -- on the edge
+    values, ulp neighbourhoods and a dense sweep; softplus' (a * sigmoid(b), threshold 20) at the edge values.
 The MSE-loss training step against the oracle's autograd (reference train/train.py:173-178) is in test_gpu_model.py.
 """
 import math
@@ -231,3 +234,182 @@ def test_gate_sigmoid_edge_values(ops):
     assert ok, pair
     ok, pair = same_special(aggr, (want.double() * deg).float().expand(N, D), atol=1e-30, rtol=4e-6)
     assert ok, pair
+
+
+# ------------------------------------------------------------------------------------------------ softplus
+SP_COLS = 256
+SP_ROWS = 12416          # 97 row tiles of 128: enough for the bf16x3 kernels to take a precision-1 launch (96)
+SERIES_T = -math.log(2.0 ** 11)      # where an earlier form switched from log(1 + t) to the series t - t^2/2
+
+
+def ulp_neighbours(c, n=64):
+    """Every fp32 value within +-n ulp of c (c != 0)."""
+    bits = torch.tensor([c], dtype=torch.float32).view(torch.int32)
+    return (bits + torch.arange(-n, n + 1, dtype=torch.int32)).view(torch.float32)
+
+
+def softplus_sweep():
+    """[SP_ROWS, SP_COLS] fp32: the finite EDGE values, every fp32 value within 64 ulp of +-20 (the threshold) and of the
+    old series threshold, the underflow tail [-104, -30] and a dense sweep of [-30, 30] (over 2^20 values) filling the rest."""
+    fin = torch.tensor([x for x in EDGE if math.isfinite(x)])
+    near = torch.cat([ulp_neighbours(c) for c in (20.0, -20.0, SERIES_T)])
+    tail = torch.linspace(-104.0, -30.0, 1 << 16, dtype=torch.float64).float()
+    head = torch.cat([fin, near, tail])
+    dense = torch.linspace(-30.0, 30.0, SP_ROWS * SP_COLS - head.numel(), dtype=torch.float64).float()
+    assert dense.numel() >= 1 << 20
+    return torch.cat([head, dense]).view(SP_ROWS, SP_COLS)
+
+
+def softplus_rtol(x):
+    """Per-element relative bound of the fast softplus, rtol(x) = 2e-6 + 1e-7 |x|.
+
+    t = exp(-|x|) is v_exp_f32(fl(-|x| log2 e)): the rounded argument is off by up to |x| log2(e) 2^-24 in the exponent,
+    i.e. exp by a relative |x| 2^-24 = 6e-8 |x|, on top of the instruction's own ~1 ulp.  log1p(t) passes a relative
+    error of t on with a factor t / ((1 + t) log1p(t)) <= 1, and for x > 0 the sum x + log1p(t) only shrinks it.  What
+    remains is a few roundings of the log1p evaluation and of the final sum (each 2^-24 = 6e-8), which 2e-6 covers with
+    room; 1e-7 |x| covers the argument with a factor 1.7.  Past x = 20 the result is x itself (torch's threshold); below
+    x = -69 the result is under 1e-30 and only the absolute term of the comparison applies."""
+    return 2e-6 + 1e-7 * x.double().abs().nan_to_num(nan=0.0, posinf=0.0)      # (+-inf, NaN: compared exactly)
+
+
+def softplus_check(site, got, x):
+    """got = softplus(x) per element within softplus_rtol, NaN / +-inf as torch.nn.functional.softplus (fp64)."""
+    want = torch.nn.functional.softplus(x.double().cpu())
+    g = got.double().cpu()
+    fin = torch.isfinite(want) & (want.abs() > 1e-30)       # (below 1e-30 only the absolute term applies)
+    rel = ((g - want).abs() / want.abs())[fin]
+    i = int(rel.argmax())
+    print(f"SOFTPLUS {site:28s} max rel err {float(rel[i]):.3e} at x = {float(x.cpu().double()[fin][i]):.7g}")
+    ok, pair = same_special(got, want, atol=1e-30, rtol=softplus_rtol(x.cpu()))
+    assert ok, (site, pair)
+
+
+def softplus_nonfinite():
+    """Every EDGE value in one row (the columns past them 0): a bias vector for the GEMM epilogue, whose pre-activation is
+    then A B + bias = the value itself with A = 0 -- +-inf and NaN cannot pass through an identity product."""
+    return torch.tensor(EDGE + [0.0] * (SP_COLS - len(EDGE)))
+
+
+GEMM_SP_FORMS = [("general", 0), ("general", 1), ("dma", 0), ("dma", 1), ("persistent", 0)]
+
+
+def gemm_softplus(ops, A, bias, form, precision):
+    """out = softplus(A I + bias) with the pre-activation kept (cpre), through the kernel family `form` takes:
+    general -- no weight image (the general tile kernel; at precision 1 its bf16x3 form); dma -- weight image with
+    tile_policy 256 (the DMA-fed 256-wide kernels: f32nn / x3nn16); persistent -- weight image with tile_policy 3, K = 256
+    (gemm_f32p.h, precision 0 only: the bf16x3 path has no persistent kernel)."""
+    eye = torch.eye(SP_COLS, device=dev())
+    out = torch.full(tuple(A.shape), float("nan"), device=dev())
+    pre = torch.full(tuple(A.shape), float("nan"), device=dev())
+    kw = dict(b_kstrided=True, bias=bias.to(dev()), cpre=pre, out_act=True, dact_kind=1, precision=precision)
+    if form != "general":
+        kw["b_split"] = (ops.pack_b if precision == 0 else ops.split_b)([eye])[0]
+        kw["tile_policy"] = 256 if form == "dma" else 3
+    ops.gemm(A.to(dev()), eye, out, **kw)
+    return out, pre
+
+
+def test_softplus_eltwise_and_update_sweep(ops):
+    """cartnet_eltwise op 0 and cartnet_softplus_update_fwd (o = 0, mean 0, rstd 1, gamma 1, beta 0: u = x exactly) on the
+    sweep and on the non-finite EDGE values: element-wise against fp64, and the two sites bit for bit."""
+    X = softplus_sweep()
+    for V in (X, softplus_nonfinite().expand(8, SP_COLS).contiguous()):
+        Vd = V.to(dev())
+        y0 = torch.full_like(Vd, float("nan"))
+        ops.eltwise(0, Vd, None, y0)
+        softplus_check("eltwise op 0", y0, V)
+        D = SP_COLS
+        mr = torch.cat([torch.zeros(D), torch.ones(D)]).to(dev())
+        y1 = torch.full_like(Vd, float("nan"))
+        ops.softplus_update_fwd(torch.zeros_like(Vd), Vd, mr, torch.ones(D, device=dev()), torch.zeros(D, device=dev()), y1)
+        softplus_check("softplus_update_fwd", y1, V)
+        assert torch.equal(y0.isnan(), y1.isnan()) and torch.equal(y0.nan_to_num(7.0), y1.nan_to_num(7.0))
+
+
+@pytest.mark.parametrize("form,precision", GEMM_SP_FORMS)
+def test_softplus_gemm_epilogue_sweep(ops, form, precision):
+    """CartnetGemmArgs.out_act with dact_kind = 1 on the sweep: C = softplus(A I + 0) with cpre = A I + 0 (an identity
+    operand: at precision 0 the pre-activation is the sweep value itself), and on the non-finite EDGE values through the
+    bias.  Element-wise against fp64 of the kept pre-activation, and bit for bit what cartnet_eltwise op 0 makes of it."""
+    X = softplus_sweep()
+    out, pre = gemm_softplus(ops, X, torch.zeros(SP_COLS), form, precision)
+    dev_rel = ((pre.cpu().double() - X.double()).abs() / X.double().abs().clamp(min=1e-30)).max()
+    print(f"SOFTPLUS gemm {form} p{precision}: pre-activation vs the sweep value, max rel {float(dev_rel):.3e}")
+    if precision == 0:
+        assert torch.equal(pre.cpu(), X), form
+    else:        # bf16x3: the module's bound for a split product that keeps two of its three pieces (2^-14 relative)
+        assert float(dev_rel) <= 2.0 ** -14, form
+    softplus_check(f"gemm {form} p{precision}", out, pre)
+    chk = torch.empty_like(out)
+    ops.eltwise(0, pre, None, chk)
+    assert torch.equal(out, chk), f"{form} p{precision}: epilogue differs from cartnet_eltwise op 0"
+    v = softplus_nonfinite()
+    out, pre = gemm_softplus(ops, torch.zeros(SP_ROWS, SP_COLS), v, form, precision)
+    assert torch.equal(pre.cpu().nan_to_num(7.0), v.expand(SP_ROWS, SP_COLS).nan_to_num(7.0))
+    softplus_check(f"gemm {form} p{precision} edge", out, pre)
+    ops.eltwise(0, pre, None, chk)
+    assert torch.equal(out.isnan(), chk.isnan()) and torch.equal(out.nan_to_num(7.0), chk.nan_to_num(7.0))
+
+
+# softplus' = a * sigmoid(b) with torch's threshold 20 (b > 20: a): EDGE and the +-20 neighbourhoods in b, a = 1 and a = -3
+def dsoftplus_operands():
+    b = torch.cat([torch.tensor(EDGE), ulp_neighbours(20.0, 50), ulp_neighbours(-20.0, 50)])
+    b = torch.cat([b, torch.full((SP_COLS - b.numel(),), 0.5)])
+    B = b.expand(64, SP_COLS).contiguous()
+    A = torch.ones(64, SP_COLS)
+    A[32:] = -3.0
+    return A, B
+
+
+def dsoftplus_check(site, got, A, B):
+    b = B.double()
+    want = A.double() * torch.where(b > 20, torch.ones_like(b), torch.sigmoid(b))
+    # sigmoid(b) = rcp(1 + exp(-b)): the same argument rounding of the hardware exp as in softplus_rtol, relative
+    # |b| 2^-24 of exp(-b) and at most that of the sigmoid; the rest is a few ulp
+    ok, pair = same_special(got, want, atol=1e-30, rtol=softplus_rtol(B))
+    assert ok, (site, pair)
+
+
+def test_dsoftplus_eltwise_and_bwd_sums_edge_values(ops):
+    """cartnet_eltwise op 1 and cartnet_softplus_bwd_sums (out = a * sigmoid(b), threshold 20) at the edge values."""
+    A, B = dsoftplus_operands()
+    Ad, Bd = A.to(dev()), B.to(dev())
+    y0, y1 = torch.full_like(Ad, float("nan")), torch.full_like(Ad, float("nan"))
+    ops.eltwise(1, Ad, Bd, y0)
+    dsoftplus_check("eltwise op 1", y0, A, B)
+    s = torch.empty(SP_COLS, device=dev())
+    ops.softplus_bwd_sums(Ad, Bd, y1, s)
+    dsoftplus_check("softplus_bwd_sums", y1, A, B)
+    assert torch.equal(y0.nan_to_num(7.0), y1.nan_to_num(7.0))
+
+
+@pytest.mark.parametrize("form,precision", [("general", 0), ("general", 1), ("dma", 0), ("dma", 1)])
+def test_dsoftplus_gemm_epilogue_edge_values(ops, form, precision):
+    """dact with dact_kind = 1: C = (A I) * sigmoid(pre), A I = a exactly, the edge values in `pre`."""
+    A, B = dsoftplus_operands()
+    M = SP_ROWS if precision == 1 else 256          # precision 1: enough row tiles for the bf16x3 kernels
+    A, B = A.repeat(M // 64, 1), B.repeat(M // 64, 1)
+    eye = torch.eye(SP_COLS, device=dev())
+    C = torch.full((M, SP_COLS), float("nan"), device=dev())
+    kw = dict(b_kstrided=True, dact=B.to(dev()), dact_kind=1, precision=precision)
+    if form == "dma":
+        kw["b_split"] = (ops.pack_b if precision == 0 else ops.split_b)([eye])[0]
+        kw["tile_policy"] = 256
+    ops.gemm(A.to(dev()), eye, C, **kw)
+    dsoftplus_check(f"gemm dact {form} p{precision}", C, A, B)
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_dsoftplus_update_bwd_apply_edge_values(ops, training):
+    """cartnet_softplus_update_bwd_apply with o = 0, mean 0, rstd 1, gamma 1, beta 0 (u = x, ohat = 0) and the edge values
+    in x: dx = dy * softplus'(u) (+ dx_add), d_o = gamma rstd (du - sums_a / N) -- here sums = 0, so d_o = du."""
+    A, B = dsoftplus_operands()
+    N, D = A.shape
+    Ad, Bd = A.to(dev()), B.to(dev())
+    mr = torch.cat([torch.zeros(D), torch.ones(D)]).to(dev())
+    one, zero = torch.ones(D, device=dev()), torch.zeros(D, device=dev())
+    d_o, dx = torch.full_like(Ad, float("nan")), torch.full_like(Ad, float("nan"))
+    ops.softplus_update_bwd_apply(torch.zeros_like(Ad), Bd, Ad, mr, one, zero, torch.zeros(2 * D, device=dev()), training,
+                                  d_o, None, dx)
+    dsoftplus_check("softplus_update_bwd_apply dx", dx, A, B)
+    dsoftplus_check("softplus_update_bwd_apply d_o", d_o, A, B)

@@ -60,6 +60,41 @@ class Data:
         return f"{self.__class__.__name__}({', '.join(parts)})"
 
 
+def remove_hydrogens(data: Data) -> Data:
+    """The crystal without its hydrogen atoms: the reference's ``DatasetADP.get`` with ``hydrogens=False``
+    (dataset/datasetADP.py:49-72), as a new ``Data`` (the input is not modified).
+
+      * ``x`` / ``pos`` (and ``natoms``) of the atoms with ``x != 1``;
+      * an edge stays if its source and its target stay, in the original order, so ``edge_index[1]`` is still sorted;
+        ``edge_index`` is renumbered to each atom's rank among the survivors; ``cart_dir`` / ``cart_dist`` follow;
+      * ``y``, ``cell``, ``temperature`` as they are (per-atom targets exist for non-hydrogen atoms only);
+      * ``non_H_mask`` (if the crystal carries one) all ones.
+
+    A crystal that keeps no edge gets ``edge_index`` of shape [2, 0] int64; the reference builds it from an empty
+    Python list there, ``torch.tensor([]).t()``: a float tensor of shape [0].  ``DeviceShard.without_hydrogens`` does
+    the same to a whole resident shard on the GPU."""
+    keep = data.x != 1
+    if hasattr(data, "non_H_mask") and not torch.equal(data.non_H_mask.to(torch.bool), keep):
+        raise ValueError("non_H_mask disagrees with x != 1: the per-atom targets would not match the atoms that remain")
+    new_id = torch.cumsum(keep.to(torch.int64), 0) - 1                   # rank among the survivors
+    src, tgt = data.edge_index[0], data.edge_index[1]
+    keep_e = keep[src] & keep[tgt]
+    out = data.__class__()
+    for k, v in data.__dict__.items():
+        setattr(out, k, v)
+    out.x = data.x[keep]
+    if hasattr(data, "pos"):
+        out.pos = data.pos[keep]
+    if hasattr(data, "natoms"):
+        out.natoms = torch.tensor([int(out.x.shape[0])], dtype=data.natoms.dtype)
+    out.edge_index = torch.stack((new_id[src[keep_e]], new_id[tgt[keep_e]])).to(torch.int64).reshape(2, -1)
+    out.cart_dir = data.cart_dir[keep_e]
+    out.cart_dist = data.cart_dist[keep_e]
+    if hasattr(data, "non_H_mask"):
+        out.non_H_mask = torch.ones(out.x.shape[0], dtype=torch.bool)
+    return out
+
+
 class Batch(Data):
     """A collated batch of graphs.  ``num_graphs`` is kept on the host so no device sync is needed."""
 

@@ -331,6 +331,12 @@ PROTOTYPES = {
     "cartnet_adp_metrics": (C.c_int, [c_f32p, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p, c_stream]),
     "cartnet_collate": (C.c_int, [C.POINTER(Shard), c_i64p, c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int64, C.c_int64,
                                   C.c_int64, c_f32p, C.c_float, C.c_float, C.POINTER(Collated), c_stream]),
+    "cartnet_shard_drop_h_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "cartnet_shard_drop_h_count": (C.c_int, [C.POINTER(Shard), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                             c_i64p, c_i64p, c_stream]),
+    "cartnet_shard_drop_h_fill": (C.c_int, [C.POINTER(Shard), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                            c_i64p, C.c_int64, C.c_int64, c_i32p, c_f32p, c_u8p, c_i64p, c_i32p, c_i32p,
+                                            c_f32p, c_f32p, c_stream]),
     "cartnet_profile_gemm": (C.c_int, [C.c_int32]),
     "cartnet_profile_gemm_only": (C.c_int, [C.c_int32]),
     "cartnet_profile_gemm_every": (C.c_int, [C.c_int32]),

@@ -176,7 +176,11 @@ class DeviceShard:
             if k in sizes and int(a.shape[0]) != int(sizes[k]):
                 raise ValueError(f"{k}: {a.shape[0]} rows, expected {int(sizes[k])}")
             self.t[k] = torch.from_numpy(np.array(a)).to(dev)       # np.array: memmaps are read-only
-        self.y_width = int(arrays["y"].shape[1]) if arrays["y"].ndim == 2 else 1
+        self._describe()
+
+    def _describe(self) -> None:
+        """The C descriptor of the device tensors in ``self.t``."""
+        self.y_width = int(self.t["y"].shape[1]) if self.t["y"].dim() == 2 else 1
         self.per_atom_target = self.y_width == 9
         d = _l.Shard()
         for k in ("atom_ptr", "edge_ptr", "y_ptr", "z", "pos", "non_h_mask", "edge_src", "edge_tgt", "cart_dist",
@@ -196,6 +200,53 @@ class DeviceShard:
 
     def nbytes(self) -> int:
         return sum(v.numel() * v.element_size() for v in self.t.values())
+
+    def without_hydrogens(self) -> "DeviceShard":
+        """The same crystals without their hydrogen atoms, as a new resident shard (this one is untouched): what the
+        reference's ``DatasetADP(hydrogens=False)`` does per crystal and per access on the host
+        (dataset/datasetADP.py:49-72; ``cartnet_amd.data.remove_hydrogens`` states the rule in torch), done once for the
+        whole shard by a stable compaction on the GPU (csrc/shard_ops.hip).  ``y``, ``y_ptr``, ``cell`` and
+        ``temperature`` are shared with this shard.  Raises ``ValueError`` if a stored ``non_h_mask`` disagrees with
+        ``z != 1``: the rows of a per-atom ``y`` would no longer line up with the kept atoms."""
+        dev, t, G = self.device, self.t, self.num_graphs
+        N, E = int(self.atom_ptr[-1]), int(self.edge_ptr[-1])
+        with torch.cuda.device(dev):
+            ws_bytes = int(self._lib.cartnet_shard_drop_h_workspace_bytes(N, E))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            atom_ptr = torch.empty(G + 1, dtype=torch.int64, device=dev)
+            edge_ptr = torch.empty(G + 1, dtype=torch.int64, device=dev)
+            totals = torch.empty(3, dtype=torch.int64, device=dev)
+            _l.check(self._lib.cartnet_shard_drop_h_count(_l.C.byref(self._desc), G, N, E, ws.data_ptr(), ws_bytes,
+                                                          atom_ptr.data_ptr(), totals.data_ptr(), _l.stream_ptr()),
+                     "cartnet_shard_drop_h_count")
+            n_out, e_out, status = totals.tolist()              # the one device-to-host copy: sizes of the new arrays
+            if status == 1:
+                raise ValueError("the shard's non_h_mask disagrees with z != 1: its per-atom targets would not match the "
+                                 "atoms that remain")
+            if status != 0:
+                raise ValueError("the shard has an edge whose end lies outside its crystal")
+            new: Dict[str, torch.Tensor] = {"atom_ptr": atom_ptr, "edge_ptr": edge_ptr,
+                                            "z": torch.empty(n_out, dtype=torch.int32, device=dev),
+                                            "edge_src": torch.empty(e_out, dtype=torch.int32, device=dev),
+                                            "edge_tgt": torch.empty(e_out, dtype=torch.int32, device=dev),
+                                            "cart_dist": torch.empty(e_out, dtype=torch.float32, device=dev),
+                                            "cart_dir": torch.empty((e_out, 3), dtype=torch.float32, device=dev)}
+            if "pos" in t:
+                new["pos"] = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+            if "non_h_mask" in t:
+                new["non_h_mask"] = torch.empty(n_out, dtype=torch.uint8, device=dev)
+            _l.check(self._lib.cartnet_shard_drop_h_fill(
+                _l.C.byref(self._desc), G, N, E, ws.data_ptr(), ws_bytes, atom_ptr.data_ptr(), n_out, e_out,
+                new["z"].data_ptr(), _l.ptr(new.get("pos")), _l.ptr(new.get("non_h_mask")), edge_ptr.data_ptr(),
+                new["edge_src"].data_ptr(), new["edge_tgt"].data_ptr(), new["cart_dist"].data_ptr(),
+                new["cart_dir"].data_ptr(), _l.stream_ptr()), "cartnet_shard_drop_h_fill")
+            ptrs = torch.stack((atom_ptr, edge_ptr)).cpu().numpy()      # ShardLoader balances ranks by these
+        out = object.__new__(DeviceShard)
+        out.device, out.num_graphs, out._lib = dev, G, self._lib
+        out.atom_ptr, out.edge_ptr, out.y_ptr = ptrs[0].copy(), ptrs[1].copy(), self.y_ptr
+        out.t = {k: new[k] if k in new else v for k, v in t.items()}
+        out._describe()
+        return out
 
     def collate(self, sel: Sequence[int], rot: Optional[torch.Tensor] = None, temp_mean: float = 0.0,
                 temp_std: float = 1.0) -> Batch:

@@ -388,6 +388,33 @@ int cartnet_collate(const CartnetShard* shard, const int64_t* sel, const int64_t
                     const int64_t* out_edge_ptr, const int64_t* out_y_ptr, int32_t B, int64_t N, int64_t E, int64_t M,
                     const float* rot, float temp_mean, float temp_std, const CartnetCollated* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * The hydrogen-free copy of a whole shard (reference: dataset/datasetADP.py:49-72, DatasetADP.get with
+ * hydrogens = False -- per crystal and per access on the host: x / pos of the atoms with x != 1, the edges whose two
+ * ends survive, renumbered through a Python dict, cart_dir / cart_dist under the same mask, non_H_mask all ones; y,
+ * cell and temperature as they are).  Here it is one stable compaction of the shard's flat arrays, run once per
+ * dataset (cartnet_amd/csrc/shard_ops.hip): atoms and edges keep their order, so edge_tgt stays ascending per crystal.
+ * G crystals, N = atom_ptr[G] atoms, E = edge_ptr[G] edges; every array 16-byte aligned.  Two calls, as
+ * cartnet_radius_graph_count / _fill:
+ *   count: workspace of cartnet_shard_drop_h_workspace_bytes(N, E) bytes, kept for fill.  Writes atom_ptr_out [G+1]
+ *          and totals [3] int64 (device): kept atoms, kept edges, status -- 0 ok; 1 the shard's non_h_mask disagrees
+ *          with z != 1 somewhere (the rows of a per-atom y would no longer match the kept atoms); 2 an edge end lies
+ *          outside its crystal.  The caller reads totals (the one device-to-host copy), allocates, and calls
+ *   fill:  z_out [N_out], pos_out [N_out,3] (NULL when the shard has no pos), non_h_mask_out [N_out] = 1 (or NULL),
+ *          edge_ptr_out [G+1], edge_src_out / edge_tgt_out [E_out] (rank of the end among its crystal's kept atoms),
+ *          cart_dist_out [E_out], cart_dir_out [E_out,3].  y_ptr, y, cell, temperature are not touched: share them.
+ * Prefix sums are reduce-then-scan (tile sums, one scan of the sums, a fill pass that adds the tile's carry): no
+ * workgroup waits for another, no atomics, identical bytes on every run.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t cartnet_shard_drop_h_workspace_bytes(int64_t N, int64_t E);
+int cartnet_shard_drop_h_count(const CartnetShard* shard, int32_t G, int64_t N, int64_t E, void* workspace,
+                               size_t workspace_bytes, int64_t* atom_ptr_out, int64_t* totals, void* stream);
+int cartnet_shard_drop_h_fill(const CartnetShard* shard, int32_t G, int64_t N, int64_t E, const void* workspace,
+                              size_t workspace_bytes, const int64_t* atom_ptr_out, int64_t N_out, int64_t E_out,
+                              int32_t* z_out, float* pos_out, uint8_t* non_h_mask_out, int64_t* edge_ptr_out,
+                              int32_t* edge_src_out, int32_t* edge_tgt_out, float* cart_dist_out, float* cart_dir_out,
+                              void* stream);
+
 /* Opt-in timing of cartnet_gemm launches (the only PROCESS-global state in the library; used by bench.py, off by default
  * and not for concurrent use from several threads):
  * while enabled, every cartnet_gemm call -- also those issued inside cartnet_model_forward/backward -- is bracketed

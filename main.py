@@ -22,7 +22,7 @@ import torch
 
 from cartnet_amd import distributed as cdist
 from cartnet_amd.config import cfg, set_cfg
-from cartnet_amd.data import DataLoader
+from cartnet_amd.data import DataLoader, remove_hydrogens
 from cartnet_amd.master import create_model
 from cartnet_amd.optim import FlatAdam, one_cycle_lr, one_cycle_momentum
 from cartnet_amd.synthetic import augment_data, make_crystal
@@ -126,12 +126,17 @@ def create_loaders(args, rank: int, world: int):
     tr = [graphs[i] for i in perm[:n_tr]]
     va = [graphs[i] for i in perm[n_tr:n_tr + n_va]] or tr[:1]
     te = [graphs[i] for i in perm[n_tr + n_va:]] or tr[:1]
+    no_h = adp and not cfg.use_H            # loader/loader.py:29-32: DatasetADP(hydrogens=cfg.use_H), whatever the model
     if args.resident_dataset:                                             # cartnet_amd/shard.py
         from cartnet_amd.shard import DeviceShard, ShardLoader
         shards = [DeviceShard.from_data_list(part, cfg.device) for part in (tr, va, te)]
+        if no_h:
+            shards = [s.without_hydrogens() for s in shards]
         return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
                             augment=cfg.augment),
                 ShardLoader(shards[1], cfg.batch), ShardLoader(shards[2], 1 if adp else cfg.batch)]
+    if no_h:
+        tr, va, te = ([remove_hydrogens(d) for d in part] for part in (tr, va, te))
     gen = torch.Generator().manual_seed(cfg.seed + 1000 * rank)
     aug = (lambda d: augment_data(d, gen)) if cfg.augment else None
     return [DataLoader(tr, cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world, transform=aug),

@@ -7,7 +7,9 @@ packed shard, every batch collated and SO(3)-augmented on the device, one traini
     [batch 64 as 16 groups of 4]       (--grouped: reference-recipe BatchNorm / loss semantics in one pass per step)
 
 Two epochs per recipe: the first warms the allocator up, the second (>= 5 s) is the record.  Prints one JSON object; profiles/r02_config4_share.json is a copy of it.
-usage: python tools/bench_config4.py [--crystals 20284] [--precision 0] [--grouped]"""
+--no-hydrogens compacts the shard to its hydrogen-free copy first (DeviceShard.without_hydrogens: the reference's
+CartNet_no_H ablation, main.py --disable_H), so its graphs/s can be read beside the full graph's.
+usage: python tools/bench_config4.py [--crystals 20284] [--precision 0] [--grouped] [--no-hydrogens]"""
 import argparse
 import json
 import os
@@ -31,6 +33,7 @@ ap.add_argument("--precision", type=int, default=0)
 ap.add_argument("--chunk", type=int, default=256, help="crystals per radius-graph launch")
 ap.add_argument("--grouped", action="store_true", help="also run batch 64 with BatchNorm / loss per group of 4")
 ap.add_argument("--only-batch64", action="store_true", help="skip the literal micro-batch recipe (full-epoch runs)")
+ap.add_argument("--no-hydrogens", action="store_true", help="train on the hydrogen-free copy of the shard")
 args = ap.parse_args()
 cfg.radius = 5.0
 dev = torch.device("cuda:0")
@@ -53,12 +56,23 @@ atom_ptr = arrays["atom_ptr"]
 del geo
 shard = DeviceShard(arrays, dev)
 print(f"graph built in {t_graph:.1f} s, shard resident", file=sys.stderr, flush=True)
+n_atoms, n_edges, t_no_h = int(atom_ptr[-1]), int(arrays["edge_ptr"][-1]), None
+if args.no_hydrogens:
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    shard = shard.without_hydrogens()
+    torch.cuda.synchronize()
+    t_no_h = time.perf_counter() - t0
+    n_atoms, n_edges = int(shard.atom_ptr[-1]), int(shard.edge_ptr[-1])
 what = "the whole epoch of BASELINE configs[3] on ONE GPU" if n >= 162270 else "one rank's share of BASELINE configs[3]"
-out = {"workload": f"{what}: {n} synthetic ADP crystals of 64..324 atoms "
-                   f"({int(atom_ptr[-1])} atoms, {int(arrays['edge_ptr'][-1])} edges), SO(3) augmentation on, CartNet L=4 "
+no_h = " without their hydrogens" if args.no_hydrogens else ""
+out = {"workload": f"{what}: {n} synthetic ADP crystals of 64..324 atoms{no_h} "
+                   f"({n_atoms} atoms, {n_edges} edges), SO(3) augmentation on, CartNet L=4 "
                    f"D=256 fp32 storage, gemm_precision={args.precision}, 1x MI355X",
        "host_geometry_seconds": round(t_geo, 2), "gpu_radius_graph_seconds": round(t_graph, 2),
        "shard_bytes_in_hbm": shard.nbytes(), "recipes": []}
+if t_no_h is not None:
+    out["without_hydrogens_seconds"] = round(t_no_h, 4)
 
 recipes = [("batch 64 x accumulation 1", 64, 1, 0)]
 if not args.only_batch64:

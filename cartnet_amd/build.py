@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcartnet_hip.so")
-SOURCES = ["abi.hip", "gemm.hip", "gemm_bn256.hip", "gemm_bn128.hip", "gemm_bn64.hip", "gemm_x3.hip", "gemm_x3s.hip", "gemm_f32.hip", "gemm_f32w128.hip", "gemm_f32ao.hip", "gemm_f32p.hip", "gemm_f32p2.hip", "gemm_f32p3.hip", "gemm_f32gate.hip", "gemm_x3ao.hip", "gemm_h.hip", "graph_ops.hip", "edge_ops.hip", "node_ops.hip", "optim.hip", "model.hip", "icomformer.hip", "comformer_ops.hip", "equi_ops.hip", "radius_graph.hip", "metrics.hip", "collate.hip", "shard_ops.hip", "coop_layer.hip"]
+SOURCES = ["abi.hip", "gemm.hip", "gemm_bn256.hip", "gemm_bn128.hip", "gemm_bn64.hip", "gemm_x3.hip", "gemm_x3s.hip", "gemm_f32.hip", "gemm_f32w128.hip", "gemm_f32ao.hip", "gemm_f32p.hip", "gemm_f32p2.hip", "gemm_f32p3.hip", "gemm_f32gate.hip", "gemm_x3ao.hip", "gemm_h.hip", "graph_ops.hip", "edge_ops.hip", "node_ops.hip", "optim.hip", "model.hip", "icomformer.hip", "comformer_ops.hip", "equi_ops.hip", "radius_graph.hip", "metrics.hip", "collate.hip", "shard_ops.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-source additions (the reason is at the top of the source file)
 # gemm_f32.hip: cn_gemm_f32tn_kernel declares 4 waves per SIMD to cap its registers at 128 (so that a main-stream GEMM
@@ -26,7 +26,7 @@ EXTRA_FLAGS = {"radius_graph.hip": ["-ffp-contract=off"], "gemm_f32.hip": ["-Wno
 # inline-asm buffer instruction is read before it is written (the hazard recogniser does not look inside the string).
 NO_SPILL = {"gemm_f32p.hip", "gemm_f32p2.hip", "gemm_f32p3.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
-FLAGS += os.environ.get("CARTNET_HIPCC_EXTRA", "").split()      # e.g. -DCN_SETPRIO=0 for an A/B library (tools/experiments/ab_bench.sh)
+FLAGS += os.environ.get("CARTNET_HIPCC_EXTRA", "").split()      # e.g. -DCN_HOST_PROFILE for a diagnostic build of the whole library
 
 
 def _digest(paths) -> str:
@@ -68,7 +68,7 @@ def _includes(src: str) -> list:
 def build(force: bool = False, verbose: bool = True) -> str:
     """Compile what changed: every object carries the digest of its source + the headers it includes + the flags
     (csrc/<name>.o.sha), so editing one kernel recompiles one translation unit; the link runs when any object did."""
-    srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    srcs = [os.path.join(CSRC, s) for s in SOURCES]      # a missing source fails in _digest: nothing is optional
     stamp = os.path.join(CSRC, ".build_stamp")
     dig = _digest(srcs + _deps())
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == dig:

@@ -78,9 +78,6 @@ class ComformerConv_edge(nn.Module):
         self.bn_att, self.bn = nn.BatchNorm1d(c), nn.BatchNorm1d(c)
 
 
-import os as _os
-_KEEP_ACT = _os.environ.get("CARTNET_ICF_ACT_OUT", "0") != "0"      # off: measured twice (r2, r3), no gain -- see _Attention.forward
-_SIDE_BRANCHES = _os.environ.get("CARTNET_ICF_SIDE_BRANCH", "1") != "0"    # A/B switch, see _side_branch
 _GEMM_PRECISION = [0]     # CartnetGemmArgs.precision of the running forward / backward (set from model.gemm_precision)
 
 
@@ -264,7 +261,7 @@ class _side_branch:
 
     def __init__(self, inputs):
         self.inputs = [t for t in inputs if t is not None]
-        self.side = _SIDE["stream"] if (_SIDE["on"] and _SIDE_BRANCHES) else None
+        self.side = _SIDE["stream"] if _SIDE["on"] else None
         self.ctx = None
 
     def __enter__(self):
@@ -330,15 +327,12 @@ class _Attention:
                  gather_i=[term_i[:, :C], term_i[:, C:]], gather_j=[term_j[:, :C], term_j[:, C:]], tgt=idx_i, src=idx_j)
         keyb = _e((R, 2 * C), dev)      # key' in the first half (second half unused: groups share a leading dim)
         gs = _e((R, 2 * C), dev)        # [alpha | msg]
-        # Optional (CARTNET_ICF_ACT_OUT=1): keep silu(pr) (written by this GEMM on its way into LDS, a_act_out) so that the
-        # second Linears' weight gradients read a plain operand and run on the all-DMA kernel.  Measured in rounds 2 and 3:
-        # no gain (36.5-36.7 vs 36.2-36.4 ms) -- the cheaper product sits on the weight-gradient stream, which has slack,
-        # while the costlier forward GEMM sits on the critical chain.
-        act = _e((R, 2 * C), dev) if (_KEEP_ACT and _GEMM_PRECISION[0] == 0 and C % 256 == 0) else None
+        # silu(pr) is not kept for the second Linears' weight gradients (a_act_out, which would let them read a plain operand
+        # on the all-DMA kernel).  Measured in rounds 2 and 3: no gain (36.5-36.7 vs 36.2-36.4 ms) -- the cheaper product sits
+        # on the weight-gradient stream, which has slack, while the costlier forward GEMM sits on the critical chain.
         _gemm([pr[:, :C], pr[:, C:]], [P[pre + ".key_update.2.weight"], P[pre + ".lin_msg_update.2.weight"]],
                  [keyb[:, :C], gs[:, C:]], a_act=True,
-                 bias=[P[pre + ".key_update.2.bias"], P[pre + ".lin_msg_update.2.bias"]],
-                 **({"a_act_out": [act[:, :C], act[:, C:]]} if act is not None else {}))
+                 bias=[P[pre + ".key_update.2.bias"], P[pre + ".lin_msg_update.2.bias"]])
         npart = ops.segment_nparts(S)
         ps, pq = _parts(npart * C, dev), _parts(npart * C, dev)
         scale = 1.0 / math.sqrt(C)
@@ -350,7 +344,7 @@ class _Attention:
         gp = ops.gate_nparts(S)
         ops.gate_scatter_fwd(gs, None, None, seg_layout, mr1, P[pre + ".bn_att.weight"], P[pre + ".bn_att.bias"], None,
                              aggr, _parts(gp * C, dev), _parts(gp * C, dev))
-        sv.update(pr=pr, keyb=keyb, gs=gs, mr1=mr1, aggr=aggr, act=act)
+        sv.update(pr=pr, keyb=keyb, gs=gs, mr1=mr1, aggr=aggr)
         return aggr
 
     @staticmethod
@@ -376,13 +370,8 @@ class _Attention:
         G[pre + ".key_update.2.bias"] = _e((C,), dev)
         ops.colsum(gs[:, :C], G[pre + ".key_update.2.bias"])
         G[pre + ".key_update.2.weight"], G[pre + ".lin_msg_update.2.weight"] = _e((C, C), dev), _e((C, C), dev)
-        act = sv.get("act")
-        if act is not None:
-            _wgrad([gs[:, :C], gs[:, C:]], [act[:, :C], act[:, C:]],
-                   [G[pre + ".key_update.2.weight"], G[pre + ".lin_msg_update.2.weight"]])
-        else:
-            _wgrad([gs[:, :C], gs[:, C:]], [pr[:, :C], pr[:, C:]],
-                   [G[pre + ".key_update.2.weight"], G[pre + ".lin_msg_update.2.weight"]], b_act=True)
+        _wgrad([gs[:, :C], gs[:, C:]], [pr[:, :C], pr[:, C:]],
+               [G[pre + ".key_update.2.weight"], G[pre + ".lin_msg_update.2.weight"]], b_act=True)
         tiles = ops.gemm_tiles_m(R)
         csk, csm = _parts(tiles * C, dev), _parts(tiles * C, dev)
         dpr = _e((R, 2 * C), dev)       # not in place over pr: the weight-gradient stream may still be reading silu(pr)

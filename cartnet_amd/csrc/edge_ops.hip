@@ -12,10 +12,7 @@ namespace {
 
 constexpr int NODES_PER_BLOCK = 4;   // one wave per node
 constexpr int MAX_PARTS = 1024;
-#ifndef CN_GATE_BATCH
-#define CN_GATE_BATCH 8
-#endif
-constexpr int GATE_BATCH = CN_GATE_BATCH;     // edges whose row loads are in flight together per wave (8: 5.28 TB/s forward, 4: 4.98)
+constexpr int GATE_BATCH = 8;     // edges whose row loads are in flight together per wave (8: 5.28 TB/s forward, 4: 4.98)
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
@@ -117,13 +114,11 @@ __global__ __launch_bounds__(256) void cn_gate_scatter_fwd_kernel(
 #pragma unroll
           for (int u = 0; u < GATE_BATCH; ++u) {
             const int kk = min(k + u, k1 - 1);
-#ifndef CN_NO_GATE_LOAD_NT      /* last use of gs before backward: non-temporal (round 5: -0.03...-0.08 ms per step, same-box A B C x 3) */
+            // last use of gs before backward: non-temporal (round 5: -0.03...-0.08 ms per step, same-box A B C x 3)
             if constexpr (!GH) {
               g[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gs + (size_t)kk * ld + c));
               sv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gs + (size_t)kk * ld + D + c));
-            } else
-#endif
-            {
+            } else {
               g[u] = ldrow<GH>(gs, (size_t)kk * ld + c);
               sv[u] = ldrow<GH>(gs, (size_t)kk * ld + D + c);
             }
@@ -254,10 +249,7 @@ __global__ __launch_bounds__(256) void cn_gate_scatter_bwd_kernel(
 // One wave per (segment, 256-column slab).  The row loads of a batch are independent (SEG_BATCH x 1 KiB in flight per
 // wave; a dependent load-add chain left the kernel latency-bound at 2.5 TB/s); the adds keep position order.  Segment
 // bounds and permutation entries are wave-uniform, so they travel through the scalar unit.
-#ifndef CN_SEG_BATCH
-#define CN_SEG_BATCH 8
-#endif
-constexpr int SEG_BATCH = CN_SEG_BATCH;
+constexpr int SEG_BATCH = 8;
 
 template <bool RH>
 __global__ __launch_bounds__(256) void cn_segment_sum_kernel(const float* __restrict__ rows, int ld,
@@ -686,8 +678,8 @@ extern "C" int cartnet_gate_scatter_bwd_apply_h(void* gs_bf16, const float* de_o
                                      sums, E, training, N, D, parts_dg, parts_ds, groups, stream);
 }
 
-static int segment_sum_impl(bool half, const float* rows, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N,
-                            int32_t W, float* out, int32_t ldo, void* stream) {
+extern "C" int cartnet_segment_sum(const float* rows, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N,
+                                   int32_t W, float* out, int32_t ldo, void* stream) {
   CN_CHECK(N >= 0 && W >= 4 && W % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && ld >= W && ldo >= W,
            "cartnet_segment_sum: W=%d ld=%d ldo=%d must be multiples of 4", W, ld, ldo);
   if (N == 0) return 0;
@@ -695,12 +687,8 @@ static int segment_sum_impl(bool half, const float* rows, int32_t ld, const int3
   long long items = (long long)N * ((W + 255) / 256);
   long long blocks = (items + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK;   // one item per wave up to 64k blocks
   if (blocks > 65536) blocks = 65536;
-  if (half)
-    hipLaunchKernelGGL(cn_segment_sum_kernel<true>, dim3((int)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       rows, ld, ptr, perm, N, W, out, ldo, /*reverse=*/perm ? 1 : 0);
-  else
-    hipLaunchKernelGGL(cn_segment_sum_kernel<false>, dim3((int)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       rows, ld, ptr, perm, N, W, out, ldo, /*reverse=*/perm ? 1 : 0);
+  hipLaunchKernelGGL(cn_segment_sum_kernel<false>, dim3((int)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     rows, ld, ptr, perm, N, W, out, ldo, /*reverse=*/perm ? 1 : 0);
   CN_LAUNCH_CHECK("cartnet_segment_sum");
   return 0;
 }
@@ -719,18 +707,12 @@ static int segment_sum_pair_impl(bool half, const float* rows, int32_t ld, const
   // One run of N / 8 consecutive atoms per XCD (kernel comment) when every block then has exactly one trip; else the plain
   // dealing.  Alone on the chip, 64 crystals x 194 atoms (tools/experiments/exp_segpair_xcd.py): 682 -> 465 MB fetched,
   // 102.6 -> 79.4 us per launch; runs of 128 / 256 / 512 atoms: 577 / 524 / 498 MB, 86.9 / 84.0 / 81.0 us.
-  // (CN_SEG_XCD_NODES: 0 = plain dealing, > 0 = runs of that many atoms; A/B builds)
   int xcd_blocks = 0;
-#ifndef CN_SEG_XCD_NODES
-#define CN_SEG_XCD_NODES -1
-#endif
-  if (CN_SEG_XCD_NODES != 0) {
-    const long long per_node = 2LL * ((W + 255) / 256);
-    const long long nodes = CN_SEG_XCD_NODES > 0 ? (long long)CN_SEG_XCD_NODES : ((long long)N + 7) / 8;
-    const long long run = (nodes * per_node + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK;      // blocks per run
-    const long long padded = (blocks + 8 * run - 1) / (8 * run) * (8 * run);
-    if (padded <= 65536 && blocks >= 8 * run) { xcd_blocks = (int)run; blocks = padded; }
-  }
+  const long long per_node = 2LL * ((W + 255) / 256);
+  const long long nodes = ((long long)N + 7) / 8;
+  const long long run = (nodes * per_node + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK;      // blocks per run
+  const long long padded = (blocks + 8 * run - 1) / (8 * run) * (8 * run);
+  if (padded <= 65536 && blocks >= 8 * run) { xcd_blocks = (int)run; blocks = padded; }
   if (blocks > 65536) blocks = 65536;
   if (half)
     hipLaunchKernelGGL(cn_segment_sum_pair_kernel<true>, dim3((int)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
@@ -752,15 +734,6 @@ extern "C" int cartnet_segment_sum_pair_h(const void* rows_bf16, int32_t ld, con
                                           int32_t ldo, int32_t ochunk, void* stream) {
   return segment_sum_pair_impl(true, static_cast<const float*>(rows_bf16), ld, rowptr, colptr, perm, N, W, out_t, out_s, ldo,
                                ochunk, stream);
-}
-
-extern "C" int cartnet_segment_sum(const float* rows, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N,
-                                   int32_t W, float* out, int32_t ldo, void* stream) {
-  return segment_sum_impl(false, rows, ld, ptr, perm, N, W, out, ldo, stream);
-}
-extern "C" int cartnet_segment_sum_h(const void* rows_bf16, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N,
-                                     int32_t W, float* out, int32_t ldo, void* stream) {
-  return segment_sum_impl(true, static_cast<const float*>(rows_bf16), ld, ptr, perm, N, W, out, ldo, stream);
 }
 
 template <bool COMPACT>

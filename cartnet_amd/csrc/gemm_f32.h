@@ -24,8 +24,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_f32nn_kernel(const Cartne
   __shared__ __attribute__((aligned(16))) float smem[2 * F32_BUF_BYTES / 4];
   char* lds = reinterpret_cast<char*>(smem);
 
-  CN_PHASE(0);
-  CN_PHASE_ID();
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -163,8 +161,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_f32nn_kernel(const Cartne
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    CN_STAMP_BEGIN();
-    CN_PHASE(1);
     int u = 0;
     for (; u + 4 < nsteps; u += 2) {        // both steps satisfy u + 3 < nsteps
       step_full(std::integral_constant<int, 0>{}, u, r1);
@@ -174,8 +170,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_f32nn_kernel(const Cartne
       step(std::integral_constant<int, 0>{}, u, r1);
       if (u + 1 < nsteps) step(std::integral_constant<int, 1>{}, u + 1, r0);
     }
-    CN_STAMP_END();
-    CN_PHASE(2);
   }
   // epilogue (shared with gemm_kernel.h)
   const int kind = (p.gather_i[g] ? 1 : 0) | (p.resid[g] ? 2 : 0) | (p.dact[g] ? 4 : 0) |
@@ -194,11 +188,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_f32nn_kernel(const Cartne
     default: CN_EPIW(-1); break;
   }
 #undef CN_EPIW
-#ifdef CN_PHASE_STAMP
-  CN_PHASE(3);                                             // last store issued
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  CN_PHASE(4);                                             // ... and acknowledged
-#endif
 }
 
 }  // namespace cn_gemm
@@ -223,10 +212,7 @@ constexpr int F32T_B_BYTES = BK * F32_BN * 4;      // 16 KB
 constexpr int F32T_STAGE = F32T_A_BYTES + F32T_B_BYTES;
 // Four stages = 96 KB of LDS: at most ONE of these workgroups per CU, on purpose (model.hip, split_k: the launches share
 // every CU with the kernels of the main stream for the whole of backward; 52 KB stay free for one of theirs).
-#ifndef CN_TN_STAGES
-#define CN_TN_STAGES 4
-#endif
-constexpr int F32T_NSTAGE = CN_TN_STAGES;
+constexpr int F32T_NSTAGE = 4;
 
 #ifdef CN_TN_STAMP
 // Diagnostic build (tools/exp_tn_stamps.py): per workgroup [main-loop shader cycles, 100 MHz ticks, K-steps, 0] and per wave
@@ -441,7 +427,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_f32tn_kernel(const Cartne
       mma16(0);
     };
     int u = 0;
-#ifndef CN_TN_ROLLED
     for (; u + 2 * NST - 1 <= nsteps; u += NST) {          // every (u + c) + PF < nsteps
       iter_c(u, std::integral_constant<int, 0>{});
       iter_c(u + 1, std::integral_constant<int, 1>{});
@@ -450,7 +435,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_f32tn_kernel(const Cartne
       if constexpr (NST > 4) iter_c(u + 4, std::integral_constant<int, 4>{});
       if constexpr (NST > 5) iter_c(u + 5, std::integral_constant<int, 5>{});
     }
-#endif
     for (; u + 1 < nsteps; ++u) {
       __builtin_amdgcn_sched_barrier(0);
 #ifdef CN_TN_STAMP

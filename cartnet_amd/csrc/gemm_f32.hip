@@ -85,20 +85,6 @@ extern "C" int cartnet_gemm_pack_b(const float* const* src, void* const* dst, co
   return 0;
 }
 
-#ifdef CN_CLOCK_STAMP
-// diagnostic build: copies this translation unit's stamp buffer out (4096 pairs of 64-bit counters)
-extern "C" int cartnet_debug_clock_f32(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_gemm::cn_clock_dbg), sizeof(unsigned long long) * 2 * 4096);
-}
-#endif
-
-#ifdef CN_PHASE_STAMP
-// diagnostic build: the per-workgroup phase stamps of the last launches (8192 x 8 64-bit words)
-extern "C" int cartnet_debug_phase_f32(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_gemm::cn_phase_dbg), sizeof(unsigned long long) * 8 * 8192);
-}
-#endif
-
 #ifdef CN_TN_STAMP
 // diagnostic build: the weight-gradient kernel's stamps of the last launch
 extern "C" int cartnet_debug_tn_stamps(unsigned long long* wg, unsigned long long* waves) {

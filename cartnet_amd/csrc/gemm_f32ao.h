@@ -15,11 +15,7 @@
 // through and not kept (sc0 sc1 nt), the 363 MB per launch stop evicting the output `gs` that the gate kernel reads next
 // -- same-box A B A B A B, 60 steps each: 14.01-14.06 vs 14.19-14.20 ms per step (nt alone / sc1 alone: half of that;
 // the same bits on the weight-gradient kernel's operand loads, non-temporal A loads here: nothing / +0.1 ms).
-#ifdef CN_NO_STREAM_STORES
-#define CN_AO_STORE_POLICY ""
-#else
 #define CN_AO_STORE_POLICY "sc0 sc1 nt"
-#endif
 
 namespace cn_gemm {
 

@@ -214,11 +214,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void cn_gemm_f32p_kernel(const Cartnet
   auto make_ctx = [&](int i) {
     Ctx c;
     const int k = wslot + per_xcd_slots * min(i, n_my - 1);   // past the end: the last tile again (prefetches stay in bounds)
-#ifdef CN_P_XCD_INTERLEAVED      /* A/B builds: XCD x owns the row tiles x, x + 8, ... */
-    c.row0 = (k * 8 + xcd) * BM;
-#else
     c.row0 = (xcd_base + k) * BM;
-#endif
     c.a_voff = ((unsigned)min(c.row0 + arow, p.M - 1) * (unsigned)p.lda + akq * 4) * 4u;
     return c;
   };
@@ -528,9 +524,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void cn_gemm_f32p_kernel(const Cartnet
         acc[SET][a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kg][a][j], bf[kg][b][j], FIRST ? zero : acc[SET][a][b], 0, 0, 0);
   };
 
-#ifdef CN_P_PRIO          /* experiment: static priority for the younger wave of each SIMD */
-  if (wid >= 4) __builtin_amdgcn_s_setprio(CN_P_PRIO);
-#endif
   Ctx prev, cur, next;
   int pend_row0 = tiles_m * BM;          // statistics waiting in `red` for their store (tile before `prev`; none yet)
 
@@ -559,9 +552,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void cn_gemm_f32p_kernel(const Cartnet
     f32x4 own;
 
     if constexpr (COMPUTE) {
-#ifdef CN_P_FLIP
-      __builtin_amdgcn_s_setprio(CN_P_FLIP);
-#endif
 #if !(defined(CN_P_X) && (CN_P_X & 4))
       frags(U & (NA - 1), U & 3, 1);
 #endif
@@ -619,9 +609,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void cn_gemm_f32p_kernel(const Cartnet
     if constexpr (COMPUTE) {
       mma4(SetC{}, std::false_type{}, 0, 3);
       __builtin_amdgcn_sched_barrier(0);
-#ifdef CN_P_FLIP
-      __builtin_amdgcn_s_setprio(0);
-#endif
 #if !(defined(CN_P_X) && (CN_P_X & 4))
       frags((U + 1) & (NA - 1), (U + 1) & 3, 0);
 #endif

@@ -245,98 +245,12 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_hnn_kernel(const CartnetG
   // (scalar base + one lane-offset VGPR; the builtin keeps a 64-bit address pair per piece in VGPRs, which this
   // kernel cannot afford at 128 registers).
   const unsigned lds_b = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds + X3_A_BYTES + wid * 1024;
-  auto b_issue = [&](int v, int buf) {
-    const char* src = b_base(v) + wid * 1024;
-    const unsigned dst = lds_b + buf * X3_BUF_BYTES;
-#pragma unroll
-    for (int j = 0; j < (ONE ? 1 : 3); ++j)   // piece j of every wave belongs to plane j (h, m, l)
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                   :: "s"(dst + j * 8192), "v"(b_voff), "s"(src + j * 8192) : "memory", "m0");
-  };
   auto b_issue_slot = [&](int v, int slot) {     // ring slot of x3_one_deep_loop
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                  :: "s"(lds_b + x3_one_slot(slot)), "v"(b_voff), "s"(b_base(v) + wid * 1024) : "memory", "m0");
   };
-  bf16x8 ah[2], am[2], al[2], bh, bm, bl;
-  auto frag_a = [&](int buf) {
-    const char* cA = lds + buf * X3_BUF_BYTES;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const char* q = cA + x3_offset(wm * S::WM + a * 32 + li, lh);
-      ah[a] = *reinterpret_cast<const bf16x8*>(q);
-      if constexpr (!ONE) {
-        am[a] = *reinterpret_cast<const bf16x8*>(q + X3_A_PLANE);
-        al[a] = *reinterpret_cast<const bf16x8*>(q + 2 * X3_A_PLANE);
-      }
-    }
-  };
-  auto frag_b = [&](int buf, int b) {
-    const char* q = lds + buf * X3_BUF_BYTES + X3_A_BYTES + x3_offset(wn * S::WN + b * 32 + li, lh);
-    bh = *reinterpret_cast<const bf16x8*>(q);
-    if constexpr (!ONE) {
-      bm = *reinterpret_cast<const bf16x8*>(q + X3_B_PLANE);
-      bl = *reinterpret_cast<const bf16x8*>(q + 2 * X3_B_PLANE);
-    }
-  };
-  auto mma = [&](int b) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {   // small terms first
-      if constexpr (ONE) {
-        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh, acc[a][b], 0, 0, 0);
-        continue;
-      }
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[a], bh, acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bl, acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[a], bm, acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[a], bh, acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bm, acc[a][b], 0, 0, 0);
-      acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[a], bh, acc[a][b], 0, 0, 0);
-    }
-  };
-  // one K-step; r holds the A tile of step u+1 on entry and receives the load of step u+3
-  auto step = [&](auto cur_c, int u, RA& r) {
-    constexpr int CUR = decltype(cur_c)::value;
-    frag_a(CUR);
-    __builtin_amdgcn_sched_barrier(0);
-    if (u + 1 < nsteps) {
-      a_store(r, CUR ^ 1);
-      __builtin_amdgcn_sched_barrier(0);
-      b_issue(u + 1, CUR ^ 1);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (u + 3 < nsteps) a_issue(r, u + 3);
-    __builtin_amdgcn_sched_barrier(0);
-    frag_b(CUR, 0);
-    mma(0);
-    frag_b(CUR, 1);
-    mma(1);
-    __builtin_amdgcn_sched_barrier(0);
-    if (u + 3 < nsteps) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-
-  if constexpr (CN_ONE_DEEP) {
-    x3_one_deep_loop<RA>(nsteps, lds, x3_offset(wm * S::WM + li, lh), x3_offset(wn * S::WN + li, lh), acc, a_issue, a_store,
-                         b_issue_slot);
-  } else if (nsteps > 0) {
-    RA r0, r1;
-    a_issue(r0, 0);
-    b_issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0) :: "memory");
-    a_store(r0, 0);
-    if (nsteps > 1) a_issue(r1, 1);
-    if (nsteps > 2) a_issue(r0, 2);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(r0), "+v"(r1) :: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    int u = 0;
-    for (; u < nsteps; u += 2) {
-      step(std::integral_constant<int, 0>{}, u, r1);
-      if (u + 1 < nsteps) step(std::integral_constant<int, 1>{}, u + 1, r0);
-    }
-  }
+  x3_one_deep_loop<RA>(nsteps, lds, x3_offset(wm * S::WM + li, lh), x3_offset(wn * S::WN + li, lh), acc, a_issue, a_store,
+                       b_issue_slot);
   h_epilogue<C_H, D_H>(p, acc, g, row0, col0, tile_m, wm, wn, lane, tid, smem);
 }
 

@@ -131,42 +131,6 @@ struct Stager {
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// Diagnostic build only (-DCN_CLOCK_STAMP, tools/experiments/exp_clock_x3.py): one (shader clock ticks, 100 MHz ticks) pair per
-// workgroup around the main loop, into a buffer nothing else reads; the product build has no stamp.
-#ifdef CN_CLOCK_STAMP
-static __device__ unsigned long long cn_clock_dbg[2 * 4096];
-#define CN_STAMP_BEGIN() const unsigned long long cn_t0 = __builtin_amdgcn_s_memtime(), cn_w0 = __builtin_amdgcn_s_memrealtime()
-#define CN_STAMP_END()                                                                   \
-  if (threadIdx.x == 0) {                                                                \
-    cn_clock_dbg[2 * (blockIdx.x & 4095)] = __builtin_amdgcn_s_memtime() - cn_t0;        \
-    cn_clock_dbg[2 * (blockIdx.x & 4095) + 1] = __builtin_amdgcn_s_memrealtime() - cn_w0; \
-  }
-#else
-#define CN_STAMP_BEGIN()
-#define CN_STAMP_END()
-#endif
-// Second diagnostic (-DCN_PHASE_STAMP, tools/experiments/exp_phases.py): per workgroup of the fp32 activation x weight kernel the
-// 100 MHz time at entry, main-loop start, main-loop end, last store issued and all stores acknowledged, with the
-// hardware id of the CU it ran on -- the life of every workgroup on every CU of one launch.
-#ifdef CN_PHASE_STAMP
-static __device__ unsigned long long cn_phase_dbg[8192 * 8];
-#define CN_PHASE(slot)                                                                                         \
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0) {   /* wave 0, a scalar branch */                 \
-    const unsigned cn_lin = blockIdx.x + gridDim.x * blockIdx.z;                                               \
-    if (cn_lin < 8192) cn_phase_dbg[cn_lin * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();                   \
-  }
-#define CN_PHASE_ID()                                                                                          \
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0) {                                                 \
-    const unsigned cn_hw = __builtin_amdgcn_s_getreg((4 | (0 << 6) | (31 << 11)));   /* HW_REG_HW_ID, 32 bits */  \
-    const unsigned cn_xcc = __builtin_amdgcn_s_getreg((20 | (0 << 6) | (31 << 11))); /* HW_REG_XCC_ID */         \
-    const unsigned cn_lin = blockIdx.x + gridDim.x * blockIdx.z;                                               \
-    if (cn_lin < 8192) cn_phase_dbg[cn_lin * 8 + 5] = ((unsigned long long)cn_xcc << 32) | cn_hw;              \
-  }
-#else
-#define CN_PHASE(slot)
-#define CN_PHASE_ID()
-#endif
-
 struct Split3 {
   bf16x4 h, m, l;
 };
@@ -381,11 +345,7 @@ __device__ __forceinline__ void stv4(float* p, f32x4 v) { *reinterpret_cast<f32x
 // gemm_f32ao.h).  (s_nop: a store of more than 8 bytes reads its data registers up to two cycles after issue and the
 // hazard recogniser does not look inside inline asm.)
 __device__ __forceinline__ void stv4_stream(float* p, f32x4 v) {
-#ifdef CN_NO_STREAM_STORES
-  stv4(p, v);
-#else
   asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
-#endif
 }
 
 // Accumulator layouts the wide epilogue takes: 32x32 MFMA tiles (f32x16 per tile: column = lane & 31, rows
@@ -515,20 +475,6 @@ __device__ __forceinline__ void epilogue_wide_s(const CartnetGemmArgs& p, ACC& a
 #pragma unroll
     for (int b = 0; b < S::TN; ++b) {
       const int gcol = col0 + wn * S::WN + b * 32 + c4 * 4;
-#ifdef CN_EPI_RAW      /* diagnostic: same stores, same addresses, no transpose and no operands (WRONG values) */
-      if constexpr (!MF16) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (grow[i] < p.M)
-            stv4(C + (size_t)grow[i] * p.ldc + gcol,
-                 f32x4{acc[a][b][4 * i], acc[a][b][4 * i + 1], acc[a][b][4 * i + 2], acc[a][b][4 * i + 3]});
-#ifdef CN_PHASE_STAMP
-        if (a == 0 && b == 0) { CN_PHASE(6); }
-        if (a == 0 && b == S::TN - 1) { CN_PHASE(7); }
-#endif
-        continue;
-      }
-#endif
       acc_block_to_scr(acc, a, b, scr, lane, SCR_LD);
       __builtin_amdgcn_wave_barrier();
       // The two epilogues with ONE operand row per output row and nothing else (residual: dE; `silu'`: dpre) load the
@@ -558,10 +504,6 @@ __device__ __forceinline__ void epilogue_wide_s(const CartnetGemmArgs& p, ACC& a
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm volatile("" :: "v"(vv[i]), "v"(ptr[i]));
         __builtin_amdgcn_wave_barrier();
-#ifdef CN_PHASE_STAMP
-        if (a == 0 && b == 0) { CN_PHASE(6); }
-        if (a == 0 && b == S::TN - 1) { CN_PHASE(7); }
-#endif
         continue;
       }
       // (bf16x3 kernel only, where the epilogue is longer than the partner's main loop and therefore on the critical
@@ -627,10 +569,6 @@ __device__ __forceinline__ void epilogue_wide_s(const CartnetGemmArgs& p, ACC& a
         stv4(C + (size_t)grow[i] * p.ldc + gcol, v);
       }
       __builtin_amdgcn_wave_barrier();
-#ifdef CN_PHASE_STAMP
-      if (a == 0 && b == 0) { CN_PHASE(6); }
-      if (a == 0 && b == S::TN - 1) { CN_PHASE(7); }
-#endif
     }
   }
   if (SUM1 || SUM2 || GST) {

@@ -63,9 +63,6 @@ __device__ __forceinline__ void x3_epilogue(const CartnetGemmArgs& p, ACC& acc, 
 // Same LDS footprint, same products in the same order per accumulator (bit-identical results).  Memory operations retire
 // in issue order; per step the order is B(u+4), A(u+6), so at the end of step u -- when B(u+2) and A(u+3) must be in --
 // the ones that may still fly are A(u+4), B(u+3), A(u+5), B(u+4), A(u+6), each counted only if it exists.
-#ifndef CN_ONE_DEEP
-#define CN_ONE_DEEP 1
-#endif
 __device__ __forceinline__ void x3_wait_all_but(int n) {
   switch (n) {
     case 5: asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory"); break;
@@ -398,11 +395,9 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn_kernel(const Cartnet
 #undef CN_MMA
 #undef CN_SB
 
-  if constexpr (ONE && CN_ONE_DEEP) {
-    CN_STAMP_BEGIN();
+  if constexpr (ONE) {
     x3_one_deep_loop<f32x4>(nsteps, lds, x3_offset(wm * S::WM + li, lh), x3_offset(wn * S::WN + li, lh), acc, a_issue, a_store,
                             b_issue_slot);
-    CN_STAMP_END();
   } else if (nsteps > 0) {
     // all of the pipeline head's loads in ONE memory round trip (K-step 0 into a third register set, 1 and 2 into the ring)
     f32x4 r0, r1, rt;
@@ -415,7 +410,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn_kernel(const Cartnet
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    CN_STAMP_BEGIN();
     int u = 0;
     if constexpr (!ONE) {
       for (; u + 4 < nsteps; u += 2) {        // both steps satisfy u + 3 < nsteps
@@ -427,7 +421,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn_kernel(const Cartnet
       step(std::integral_constant<int, 0>{}, u, r1);
       if (u + 1 < nsteps) step(std::integral_constant<int, 1>{}, u + 1, r0);
     }
-    CN_STAMP_END();
   }
   x3_epilogue<0>(p, acc, g, row0, col0, tile_m, wm, wn, lane, tid, smem);
 }

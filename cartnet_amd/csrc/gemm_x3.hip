@@ -98,10 +98,3 @@ extern "C" int cartnet_gemm_split_b(const float* const* src, void* const* dst, c
   }
   return 0;
 }
-
-#ifdef CN_CLOCK_STAMP
-// diagnostic build: copies this translation unit's stamp buffer out (4096 pairs of 64-bit counters)
-extern "C" int cartnet_debug_clock_x3(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_gemm::cn_clock_dbg), sizeof(unsigned long long) * 2 * 4096);
-}
-#endif

@@ -30,8 +30,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn16_kernel(const Cartn
   __shared__ __attribute__((aligned(16))) float smem[2 * X3_BUF_BYTES / 4];
   char* lds = reinterpret_cast<char*>(smem);
 
-  CN_PHASE(0);
-  CN_PHASE_ID();
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -167,15 +165,10 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn16_kernel(const Cartn
   // 3 = after groups 1, 4, 7 3,676 / 1.74 / 834.  Without the DMA at all the step takes 3,387 cycles: the issue of a
   // piece is the loop's largest non-matrix cost.  Cycles saved come back partly as a lower clock (the loop is
   // power-bound): placement 1 is worth ~1 % of the launch.
-#ifndef CN_DMA_POS
-#define CN_DMA_POS 1
-#endif
-  // after MFMA group n (0..11) of the step: DMA piece j if the placement says so, then the A load once all three are out
-#define CN_AFTER(n)                                                                                      \
-  if (CN_DMA_POS == 1 && (n) <= 2) b_piece(u + 1, CUR ^ 1, (n));                                           \
-  if (CN_DMA_POS == 2 && (n) >= 4 && (n) <= 6) b_piece(u + 1, CUR ^ 1, (n) - 4);                           \
-  if (CN_DMA_POS == 3 && ((n) == 1 || (n) == 4 || (n) == 7)) b_piece(u + 1, CUR ^ 1, ((n) - 1) / 3);       \
-  if ((CN_DMA_POS <= 1 && (n) == 2) || (CN_DMA_POS == 2 && (n) == 6) || (CN_DMA_POS == 3 && (n) == 7)) a_issue(r, u + 3)
+  // after MFMA group n (0..11) of the step: DMA piece n after each of the first three, then the A load once all three are out
+#define CN_AFTER(n)                                     \
+  if ((n) <= 2) b_piece(u + 1, CUR ^ 1, (n));           \
+  if ((n) == 2) a_issue(r, u + 3)
 #define CN_SB() __builtin_amdgcn_sched_barrier(0)
 #define CN_G(A0, A1, A2, A3, B, b)                                                          \
   acc[0][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A0, B, acc[0][b], 0, 0, 0);          \
@@ -193,8 +186,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn16_kernel(const Cartn
     bf16x8 p0 = rd(ae + a_hl), p1 = rd(ao + a_hl + 512), p2 = rd(ae + a_hl + 1024), p3 = rd(ao + a_hl + 1536);
     bf16x8 b0 = rd(be + b_lh), b1 = rd(bo + b_lh + 512);
     CN_SB();
-    if (CN_DMA_POS == 0) b_issue(u + 1, CUR ^ 1);
-    CN_SB();
+    CN_SB();   // (placement 0 issued the whole tile between these two)
     if (A_ACT) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) r[c] = fast_silu(r[c]);
@@ -300,8 +292,6 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn16_kernel(const Cartn
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    CN_STAMP_BEGIN();
-    CN_PHASE(1);
     int u = 0;
     for (; u + 4 < nsteps; u += 2) {        // both steps satisfy u + 3 < nsteps
       step_full(std::integral_constant<int, 0>{}, u, r1);
@@ -311,17 +301,10 @@ __global__ __launch_bounds__(NTHREADS, 4) void cn_gemm_x3nn16_kernel(const Cartn
       step(std::integral_constant<int, 0>{}, u, r1);
       if (u + 1 < nsteps) step(std::integral_constant<int, 1>{}, u + 1, r0);
     }
-    CN_STAMP_END();
-    CN_PHASE(2);
   }
   if constexpr (GSTK == 1) epilogue_wide<X3_BN, 130>(p, acc, g, row0, col0, tile_m, wm, wn, lane, tid, smem, 130);
   else if constexpr (GSTK == 2) epilogue_wide<X3_BN, 128>(p, acc, g, row0, col0, tile_m, wm, wn, lane, tid, smem, 128);
   else x3_epilogue<0>(p, acc, g, row0, col0, tile_m, wm, wn, lane, tid, smem);
-#ifdef CN_PHASE_STAMP
-  CN_PHASE(3);                                             // last store issued
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  CN_PHASE(4);                                             // ... and acknowledged
-#endif
 }
 
 }  // namespace cn_gemm

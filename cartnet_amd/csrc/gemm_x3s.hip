@@ -12,17 +12,3 @@ void launch_x3nn16(bool a_act, const CartnetGemmArgs& a, const GemmFlags& fl, di
 }
 
 }  // namespace cn_gemm
-
-#ifdef CN_CLOCK_STAMP
-// diagnostic build: copies this translation unit's stamp buffer out (4096 pairs of 64-bit counters)
-extern "C" int cartnet_debug_clock_x3s(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_gemm::cn_clock_dbg), sizeof(unsigned long long) * 2 * 4096);
-}
-#endif
-
-#ifdef CN_PHASE_STAMP
-// diagnostic build: the per-workgroup phase stamps of the last launches (8192 x 8 64-bit words)
-extern "C" int cartnet_debug_phase_x3s(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_gemm::cn_phase_dbg), sizeof(unsigned long long) * 8 * 8192);
-}
-#endif

@@ -122,12 +122,7 @@ thread_local Jobs g_jobs;
 // statistics pass only reads them, and the gate kernels of both directions recompute the product (cartnet_att_gate_fwd,
 // cartnet_att_gate_bwd_apply with key = NULL).  Needs the one-chunk kernels (C <= 256).
 inline bool icf_alpha_free(int C) {
-#ifdef CN_ICF_KEEP_ALPHA
-  (void)C;
-  return false;
-#else
   return C <= 256;
-#endif
 }
 
 struct IWork {
@@ -529,15 +524,10 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
     const bool img = w.use_img && n >= 2048;      // a handful of rows (lattice lengths): the plain NT form
     a.A[0] = r; a.C[0] = pre; a.bias[0] = bias;
     if (img) { a.b_kstrided = 1; a.B[0] = T_; a.b_split[0] = F_; } else { a.B[0] = W_; }
-#ifndef CN_ICF_NO_RBF_FUSE
     // pre and softplus(pre) from the product's epilogue (CartnetGemmArgs.dact_kind = 1 with cpre + out_act): the element-wise
     // pass read pre and wrote out, 0.25 ms per step over the E + 3E rows
     a.C[0] = out; a.cpre[0] = pre; a.out_act = 1; a.dact_kind = 1;
     return cartnet_gemm(&a, st);
-#else
-    RUN(cartnet_gemm(&a, st));
-    return cartnet_eltwise(0, pre, nullptr, out, n, C, C, 0, C, 1.0f, st);
-#endif
   };
   RUN(rbf_branch(w.edge_feat, b.E, m.rbf_centers, m.gamma_rbf, P.rbf_w, w.rbfT, w.rbfF, P.rbf_b, w.r_e, w.pre_e, w.e0));
   RUN(rbf_branch(w.nl, (long long)Bg * 3, m.rbf_centers, m.gamma_rbf, P.rbf_w, w.rbfT, w.rbfF, P.rbf_b, w.r_nl, w.pre_nl, w.NLt));
@@ -708,16 +698,8 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   // (round 5: the bias gradients that are column sums of a tensor an element-wise pass of this file writes come out of
   //  that pass -- d_o here, dkey / dq in cartnet_rowmul_bwd_sums, the RBF branches' dpre -- and those of a tensor a GEMM
   //  writes out of its epilogue; they were 34 cartnet_colsum_partial passes per step, 1.5 ms of the main stream's work)
-#ifdef CN_ICF_NO_BIAS_FUSE
-  const bool bias_fuse = false;
-#else
   const bool bias_fuse = C <= 256;
-#endif
-#ifdef CN_ICF_NO_RBF_FUSE
-  const bool rbf_fuse = false;
-#else
   const bool rbf_fuse = bias_fuse;
-#endif
   auto softplus_bwd = [&](int l, const CartnetIcfConv& q, const CartnetIcfConv& g, const float* dy, int rows,
                           const float* x_in, float* concate_b) -> int {
     RUN(cartnet_softplus_update_bwd_stats(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, rows, C, w.pa, w.pb, st));
@@ -758,11 +740,7 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
       RUN(cartnet_colsum_finalize2(parts, outs, gr, 2, fused_sums ? cartnet_segment_nparts(t.S) : t.gparts, C, st));
     }
     const float scale = 1.0f / sqrtf((float)C);
-#ifdef CN_ICF_NO_GATE_ROWMUL
-    const bool gate_rowmul = false;
-#else
     const bool gate_rowmul = bias_fuse;
-#endif
     CN_CHECK(gate_rowmul || !icf_alpha_free(C), "cartnet_icomformer_backward: the alpha-free forward needs the fused gate backward");
     if (gate_rowmul) {
       // gate backward + query x key backward + the three bias gradients in one pass: gs = [dkey | dmsg], dq

@@ -58,9 +58,6 @@ struct Work {
 // fp32 MFMA or bf16x3, D = 256 -- the two K-segments of dE fold into one product --, at least 64 / 96 row tiles), one
 // BatchNorm group and per-rank statistics.  Training-mode passes only (the callers check `training`).
 inline bool gate_sums_fused(const CartnetModel& m, int G, int tiles_e, long long E) {
-#ifdef CN_NO_GATE_FUSE      /* A/B builds only (tools/build_variant.sh): the statistics pass of rounds 1-4 */
-  return false;
-#endif
   if (!(m.gemm_precision <= 1 && G == 1 && m.half_storage == 0 && m.bn_allreduce == nullptr && E > 0)) return false;
   // ONE predicate for "the dE product takes the kernel with the epilogue" (ADVICE r5): the launch cartnet_model_backward
   // will build (same shapes, strides and flags; placeholder pointers with the alignment the workspace guarantees) is put
@@ -163,10 +160,8 @@ Work carve(const CartnetModel& m, int N, long long E, int Bg, int M, bool need_b
   if (need_bwd && m.gemm_precision == 0 && D % 256 == 0) {
     // (Round 6: with SiLU applied in place to the weight-gradient kernel's DMA'd tile -- cn_gemm_f32tn_kernel<true, 5> --
     //  dropping the layers' kept silu(pre) saves 1.45 GB of writes per step and costs 0.09 ms: the product 346 -> 380 us,
-    //  the second Linears 405 -> 378; 13.23-13.25 kept vs 13.32-13.35 ms dropped, same box.  Kept; -DCN_DROP_LAYER_ACT drops.)
-#ifndef CN_DROP_LAYER_ACT
+    //  the second Linears 405 -> 378; 13.23-13.25 kept vs 13.32-13.35 ms dropped, same box.  Kept.)
     for (int l = 0; l < L; ++l) w.act[l] = c.take<float>(En * 2 * D);
-#endif
     w.he_act = c.take<float>(En * 2 * D);
   }
   if (need_bwd && gate_sums_fused(m, w.G, w.tiles_e, E)) {
@@ -297,10 +292,6 @@ inline int cartnet_gate_scatter_bwd_apply_f(void* gs, const float* de, const flo
                                             const CartnetGroups* g, void* st) {
   return cartnet_gate_scatter_bwd_apply(static_cast<float*>(gs), de, da, env, rowptr, mr, ga, be, sums, E, training, N, D, pdg,
                                         pds, g, st);
-}
-inline int cartnet_segment_sum_f(const void* rows, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N, int32_t W,
-                                 float* out, int32_t ldo, void* st) {
-  return cartnet_segment_sum(static_cast<const float*>(rows), ld, ptr, perm, N, W, out, ldo, st);
 }
 
 // column `elems` of a row-major matrix whose elements are fp32 or (half storage) bf16
@@ -901,14 +892,8 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
     };
     // node-side halves: reduce dpre over each atom's incoming (target) and outgoing (source) edges
     auto segsums = [&](void* s_) -> int {
-#ifndef CN_NO_SEG_PAIR
       if (!half) return cartnet_segment_sum_pair(dpre, 2 * D, w.rowptr, w.colptr, w.perm, N, 2 * D, dPn, dPn + 2 * D, 4 * D, 256, s_);
       return cartnet_segment_sum_pair_h(dpre, 2 * D, w.rowptr, w.colptr, w.perm, N, 2 * D, dPn, dPn + 2 * D, 4 * D, 256, s_);
-#else                       /* (A/B builds: the two launches of rounds 1-4) */
-      RUN((half ? cartnet_segment_sum_h : cartnet_segment_sum_f)(dpre, 2 * D, w.rowptr, nullptr, N, 2 * D, dPn, 4 * D, s_));
-      return (half ? cartnet_segment_sum_h : cartnet_segment_sum_f)(dpre, 2 * D, w.colptr, w.perm, N, 2 * D, dPn + 2 * D,
-                                                                    4 * D, s_);
-#endif
     };
     auto side_wn = [&]() -> int {   // bias gradients of the first Linears = column sums of the by-target half of dPn; node blocks
       double* parts[2] = {w.pc[par], w.pd[par]};      // the second Linears' bias sums were finalised above (same stream)

@@ -31,11 +31,9 @@ struct Carver {
 // matrix pipe as well as two (0.97 of it alone, profiles/r03_exp_phases.md) and leaves the other half of every CU's
 // registers to the chain that the step's length depends on.  cn_gemm_f32tn_kernel enforces it with its LDS footprint
 // (four stages = 96 KB: a second one does not fit, gemm_f32.h), which is also one more K-step of prefetch.
-#ifndef CN_WGRAD_TARGET
-#define CN_WGRAD_TARGET 256
-#endif
+constexpr int WGRAD_TARGET = 256;
 inline int split_k(long long K, int tiles) {
-  long long s = (CN_WGRAD_TARGET + tiles - 1) / tiles;
+  long long s = (WGRAD_TARGET + tiles - 1) / tiles;
   if (s > K / 256) s = K / 256;
   if (s < 1) s = 1;
   return (int)s;

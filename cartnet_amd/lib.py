@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CARTNET_LIB (tools only): a diagnostic / A-B build of the same ABI next to the product library (tools/build_variant.sh)
 LIB_PATH = os.environ.get("CARTNET_LIB") or os.path.join(_HERE, "libcartnet_hip.so")
 MAX_GROUPS = 4
-ABI_VERSION = 12         # cartnet_abi_version() of the library this binding mirrors (include/cartnet_hip.h)
+ABI_VERSION = 13         # cartnet_abi_version() of the library this binding mirrors (include/cartnet_hip.h)
 
 _lib: Optional[C.CDLL] = None
 
@@ -253,8 +253,6 @@ PROTOTYPES = {
                                                  c_groups, c_stream]),
     "cartnet_segment_sum": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32,
                                       c_stream]),
-    "cartnet_segment_sum_h": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32,
-                                        c_stream]),
     "cartnet_segment_sum_pair": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p,
                                            C.c_int32, C.c_int32, c_stream]),
     "cartnet_segment_sum_pair_h": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p,
@@ -268,10 +266,6 @@ PROTOTYPES = {
                                                    c_groups, c_stream]),
     "cartnet_node_update_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, c_f32p,
                                           c_groups, c_stream]),
-    # prototype (csrc/coop_layer.hip): one cooperative launch for one layer's forward at configs[2] sizes
-    "cartnet_coop_layer_workspace_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "cartnet_coop_layer_fwd": (C.c_int, [C.c_void_p] * 15 + [C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 8 +
-                               [C.c_uint32, C.c_void_p, c_stream]),
     "cartnet_node_update_bwd_stats": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, c_f32p,
                                                 c_f32p, c_groups, c_stream]),
     "cartnet_node_update_bwd_apply": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32,

@@ -4,7 +4,6 @@ with a flush on the last iteration, optimiser + scheduler step at the boundary. 
 the loops return plain numbers (graphs/s is what this build reports)."""
 from __future__ import annotations
 
-import os
 import time
 from typing import Callable, Optional
 
@@ -12,9 +11,6 @@ import torch
 
 from .config import cfg
 from . import distributed as cdist
-
-
-_FUSED_LOSS = os.environ.get("CARTNET_FUSED_LOSS", "1") != "0"      # A/B switch (README)
 
 
 class _FusedLoss(torch.autograd.Function):
@@ -123,7 +119,7 @@ def _two_node_backward(loss: torch.Tensor, one: torch.Tensor) -> bool:
 def compute_loss(pred: torch.Tensor, true: torch.Tensor):
     """(MAE, MSE) with mean reduction over all elements (train/metrics.py:26-27).  Device tensors go through the fused
     kernels; host tensors (the CPU tests of the loops' bookkeeping) through torch."""
-    if _FUSED_LOSS and pred.is_cuda and pred.dtype == torch.float32 and true.dtype == torch.float32 and pred.shape == true.shape \
+    if pred.is_cuda and pred.dtype == torch.float32 and true.dtype == torch.float32 and pred.shape == true.shape \
             and pred.numel() > 0:
         return _FusedLoss.apply(pred, true)
     diff = pred - true

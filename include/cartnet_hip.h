@@ -35,7 +35,7 @@ int cartnet_abi_version(void);
 /* sizeof of every struct below, in header order (CartnetGemmArgs, CartnetShard, CartnetCollated, CartnetGemmProfile,
  * CartnetGroups, CartnetLayerParams, CartnetLayerBuffers, CartnetParams, CartnetModel, CartnetBatch,
  * CartnetGateGemmArgs, CartnetIcfConv, CartnetIcfParams, CartnetIcfModel); returns the number of structs.  A binding checks its mirrors against these when it loads the
- * library, and cartnet_abi_version() against the version it was written for (12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
+ * library, and cartnet_abi_version() against the version it was written for (13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
  * aux_stream in cartnet_model_forward, CartnetGateGemmArgs in the size table; cartnet_gemm_tile_policy() is gone). */
 int cartnet_abi_struct_sizes(size_t* out, int32_t capacity);
 
@@ -639,9 +639,6 @@ int cartnet_gate_scatter_bwd_apply_h(void* gs_bf16, const float* de_out, const f
  * Backward of the two index_selects PyG performs per layer (x_i by target: perm = NULL; x_j by source: CSC). */
 int cartnet_segment_sum(const float* rows, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N,
                         int32_t W, float* out, int32_t ldo, void* stream);
-/* rows kept as bf16 (ld in elements), fp32 sums */
-int cartnet_segment_sum_h(const void* rows_bf16, int32_t ld, const int32_t* ptr, const int32_t* perm, int32_t N,
-                          int32_t W, float* out, int32_t ldo, void* stream);
 /* Both index_select backwards of a layer in one launch: out_t[t, :] = the by-target sum (rowptr, rows in place), out_s[t, :]
  * = the by-source sum (colptr + perm), same values and summation orders as two cartnet_segment_sum calls.  The work items
  * of a node's two sums are adjacent, so the rows of a crystal are read twice within microseconds and the second read
@@ -921,24 +918,6 @@ int cartnet_icomformer_backward(const CartnetIcfModel* model, const CartnetBatch
  * grad_scale multiplies g first (1/world_size after the RCCL gradient all-reduce). */
 int cartnet_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                       float beta1, float beta2, float eps, int32_t step, float grad_scale, void* stream);
-
-/* ------------------------------------------------------------------------------------------------------
- * PROTOTYPE (not on the model's path): the forward of ONE CartNet layer
- * (/root/reference/models/cartnet.py:204-274: propagate -> message -> aggregate -> update, training-mode BatchNorm,
- * envelope on) as ONE cooperative launch for the small batches of BASELINE configs[2] -- 256 workgroups, five phases,
- * four grid barriers (csrc/coop_layer.hip).  Precision 2 arithmetic (bf16 operands, fp32 accumulate and storage), D = 256,
- * E <= 16,384, every atom with at least one incoming edge; running statistics are not updated.
- * wn / w1e / w2: bf16 [4D][D] (gate_i | aggr_i | gate_j | aggr_j rows of MLP_*.0.weight), [2D][D] (its edge columns),
- * [2D][D] (MLP_gate.2 | MLP_aggr.2); b1 / b2 [2D]; Pn [N,4D], pre / gs [E,2D], e_out [E,D], aggr / x_out [N,D];
- * work: cartnet_coop_layer_workspace_floats(N, E) floats; bar: 3 x 8 x 32 zeroed words, epoch = launches on it so far;
- * status: one word, set to 1 if a barrier gave up (results are then invalid).
- * ---------------------------------------------------------------------------------------------------- */
-size_t cartnet_coop_layer_workspace_floats(int32_t N, int32_t E);
-int cartnet_coop_layer_fwd(const float* x, const float* e, const int32_t* tgt, const int32_t* src, const int32_t* rowptr,
-                           const float* env, const void* wn_bf16, const void* w1e_bf16, const void* w2_bf16, const float* b1,
-                           const float* b2, const float* bn1_w, const float* bn1_b, const float* bn2_w, const float* bn2_b,
-                           int32_t N, int32_t E, float eps, float* Pn, float* pre, float* gs, float* e_out, float* aggr,
-                           float* x_out, float* work, uint32_t* bar, uint32_t epoch, uint32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

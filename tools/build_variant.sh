@@ -11,9 +11,9 @@ CSRC=$ROOT/cartnet_amd/csrc
 python -c "from cartnet_amd import build; build.build(verbose=False)"
 TMP=$(mktemp -d)
 OBJS=""
-for o in $CSRC/*.o; do
-  b=$(basename $o .o)
-  use=$o
+for s in $(python -c "from cartnet_amd import build; print(' '.join(build.SOURCES))"); do      # not csrc/*.o: a stale object of a removed source must not be linked
+  b=$(basename $s .hip)
+  use=$CSRC/$b.o
   for f in "$@"; do
     if [ "$(basename $f .hip)" == "$b" ]; then
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -fno-gpu-rdc -Wno-unused-function -Wno-inline-asm $EXTRA -c $CSRC/$b.hip -o $TMP/$b.o &

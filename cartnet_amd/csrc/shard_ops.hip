@@ -23,12 +23,9 @@
 // writes the offsets of the crystals that start there (empty ones at the end of the shard, and entry G).
 // Memory-bound: 8 B read per edge in count (+ two cached 8-byte rank gathers), 24 B read + 24 B per kept edge in fill.
 #include "common.h"
+#include "shard_tiles.h"
 
 namespace {
-
-constexpr int SO_THREADS = 256;
-constexpr int SO_ITEMS = 4;
-constexpr int SO_TILE = SO_THREADS * SO_ITEMS;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -64,23 +61,6 @@ __device__ __forceinline__ void so_block_sum_store(int v, int* lds, int32_t* out
   int total;
   so_block_scan(v, lds, total);
   if (threadIdx.x == 0) *out = total;
-}
-
-// largest g in [lo, hi) with ptr[g] <= i; requires ptr[lo] <= i and (hi == G + 1 or i < ptr[hi])
-__device__ __forceinline__ int so_find(const int64_t* __restrict__ ptr, int lo, int hi, int64_t i) {
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// crystal of item i0 = the first item of this thread, searched among the crystals the tile [t0, t0 + 1024) touches
-__device__ __forceinline__ int so_first_crystal(const int64_t* __restrict__ ptr, int G, int64_t n, int64_t t0, int64_t i0) {
-  const int64_t t1 = t0 + SO_TILE - 1 < n ? t0 + SO_TILE - 1 : n;
-  const int g_lo = so_find(ptr, 0, G + 1, t0);
-  const int g_hi = so_find(ptr, g_lo, G + 1, t1);
-  return so_find(ptr, g_lo, g_hi + 1, i0);
 }
 
 // the offsets of the crystals that start at item i (crystal g and the empty ones right before it) are `rank`

@@ -12,6 +12,7 @@ target image, so this module restates the collation contract for exactly the att
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable, List, Sequence
 
 import torch
@@ -92,6 +93,138 @@ def remove_hydrogens(data: Data) -> Data:
     out.cart_dist = data.cart_dist[keep_e]
     if hasattr(data, "non_H_mask"):
         out.non_H_mask = torch.ones(out.x.shape[0], dtype=torch.bool)
+    return out
+
+
+# enumeration of the reference's expand_lattice (dataset/utils.py:400-408): i, j, k in -2..2 with k fastest, (0,0,0) skipped
+_LATTICE_COEFFS = torch.tensor([(i, j, k) for i in range(-2, 3) for j in range(-2, 3) for k in range(-2, 3)
+                                if (i, j, k) != (0, 0, 0)], dtype=torch.int64)
+
+
+def _lattice_candidates(cell: torch.Tensor) -> torch.Tensor:
+    """The 124 vectors i c0 + j c1 + k c2, evaluated as the reference does: ((i c0) + (j c1)) + (k c2)."""
+    c = _LATTICE_COEFFS.to(cell.dtype)
+    return (c[:, 0:1] * cell[0] + c[:, 1:2] * cell[1]) + c[:, 2:3] * cell[2]
+
+
+def _select_lattice(cand: torch.Tensor, half_pi: float):
+    """Ranks (positions in the (norm, enumeration index) order) and signs of the three vectors the reference's
+    ``optmize_lattice`` picks (dataset/utils.py:425-449, before the handedness step), or None for a degenerate cell."""
+    order = torch.sort(torch.norm(cand, dim=1), stable=True).indices      # ties: the lower enumeration index first
+    v = cand[order]
+    v1 = v[0]
+
+    def sign(w):                                                          # vector_angle(v1, w) > pi / 2
+        cos = torch.dot(v1, w) / (torch.norm(v1) * torch.norm(w))
+        return -1 if bool(torch.abs(torch.acos(cos)) > half_pi) else 1
+    r2 = next((r for r in range(1, v.shape[0])
+               if not bool(torch.norm(torch.linalg.cross(v1, v[r])) <= 1e-3)), None)
+    if r2 is None:
+        return None
+    s2 = sign(v[r2])
+    n12 = torch.linalg.cross(v1, s2 * v[r2])
+    # the reference restarts one element early (closest_vectors[i:], i = r2 - 1): that element was rejected as collinear
+    # with v1 or is v1 itself, and v2 lies in its own plane with v1, so both are rejected again and the search in effect
+    # starts after v2
+    r3 = next((r for r in range(r2 + 1, v.shape[0]) if not bool(torch.abs(torch.dot(n12, v[r])) <= 1e-3)), None)
+    if r3 is None:
+        return None
+    return order, (0, r2, r3), (1, s2, sign(v[r3]))
+
+
+def lattice_basis(cell: torch.Tensor) -> torch.Tensor:
+    """[3,3] int64: row r holds the signed integer coefficients, in the rows of ``cell`` [3,3] fp32, of the r-th vector of
+    the canonical reduced lattice (the reference's ``optmize_lattice``, dataset/utils.py:420-449, handedness included).
+
+    Candidates are ordered by (Euclidean norm, enumeration index).  The reference's ``argsort`` is not stable, so its
+    order inside a +v / -v pair is an accident of the sort; for a generic cell the final lattice is the same, because a
+    flipped v1 flips v2 and v3 with it (their sign is taken against v1) and the handedness step undoes the overall sign.
+    Raises ``ValueError`` for a cell with no admissible second or third vector."""
+    cell = cell.to(torch.float32).reshape(3, 3)
+    cand = _lattice_candidates(cell)
+    # the reference compares an fp32 angle with the Python float pi / 2: the comparison runs in fp32, where acos(0) equals
+    # fp32(pi / 2), so exactly orthogonal vectors are not negated
+    sel = _select_lattice(cand, float(torch.tensor(math.pi / 2, dtype=torch.float32)))
+    if sel is None:
+        raise ValueError("degenerate cell: no three linearly independent lattice vectors among the candidates")
+    order, ranks, signs = sel
+    idx = order[list(ranks)]
+    basis = _LATTICE_COEFFS[idx] * torch.tensor(signs).unsqueeze(1)
+    v = cand[idx] * torch.tensor(signs, dtype=cand.dtype).unsqueeze(1)
+    if bool(torch.dot(torch.linalg.cross(v[0], v[1]), v[2]) < 0):        # find_right_hand_system, dataset/utils.py:414-418
+        basis = -basis
+    return basis
+
+
+def lattice_frame(vectors: torch.Tensor):
+    """(new_cell, R) of three lattice vectors [3,3] (rows), the reference's ``rotate_crystal_to_lattice``
+    (dataset/utils.py:366-398): the rows of R are x = v1 / |v1|, y = the normalised part of v2 orthogonal to x and
+    z = x cross y; ``new_cell = vectors @ R^T`` is lower-triangular with a positive diagonal."""
+    x = vectors[0] / torch.linalg.norm(vectors[0])
+    p = vectors[1] - torch.dot(vectors[1], x) * x
+    y = p / torch.linalg.norm(p)
+    R = torch.stack([x, y, torch.linalg.cross(x, y)])
+    return vectors @ R.T, R
+
+
+def optimize_lattice(cell: torch.Tensor):
+    """``(new_cell, R)`` of a cell [3,3] fp32 (rows are lattice vectors): the reference's ``optmize_lattice``
+    (dataset/utils.py:420-452) on the CPU.  ``new_cell`` describes the same lattice by its three shortest independent
+    vectors (see ``lattice_basis``), rotated by ``R`` into the frame of ``lattice_frame``."""
+    cell = cell.to(torch.float32).reshape(3, 3)
+    cand = _lattice_candidates(cell)
+    b = lattice_basis(cell)
+    idx = ((b[:, 0] + 2) * 25 + (b[:, 1] + 2) * 5 + (b[:, 2] + 2))
+    idx = idx - (idx > 62).to(idx.dtype)                                  # (0,0,0) is not enumerated
+    return lattice_frame(cand[idx])
+
+
+def lattice_margins(cell: torch.Tensor):
+    """How far the selection of ``lattice_basis`` is from a tie, in fp64: ``(gap, cos)``.  ``gap`` is the smallest
+    relative difference between the norms of consecutive candidates, up to the one after the third chosen vector, that
+    are not each other's negative; ``cos`` is the smaller |cos| of the angle between the first chosen vector and the
+    other two.  Where both exceed fp32 rounding by a wide margin, every fp32 evaluation of the rule picks the same basis.
+    (0, 0) for a degenerate cell."""
+    cand = _lattice_candidates(cell.to(torch.float64).reshape(3, 3))
+    sel = _select_lattice(cand, math.pi / 2)
+    if sel is None:
+        return 0.0, 0.0
+    order, ranks, _ = sel
+    norms = torch.norm(cand, dim=1)[order]
+    coeff = _LATTICE_COEFFS[order]
+    gap = float("inf")
+    for r in range(min(ranks[2] + 1, norms.shape[0] - 1)):
+        if bool((coeff[r] == -coeff[r + 1]).all()):
+            continue
+        gap = min(gap, float((norms[r + 1] - norms[r]) / norms[r + 1]))
+    v = cand[order[list(ranks)]]
+    cos = min(abs(float(torch.dot(v[0], v[j]) / (norms[0] * torch.norm(v[j])))) for j in (1, 2))
+    return gap, cos
+
+
+def optimize_cell(data: Data, name=None) -> Data:
+    """The crystal in the frame of its canonical reduced lattice: the reference's ``DatasetADP.get`` with
+    ``optimize_cell=True`` (dataset/datasetADP.py:75-80), as a new ``Data`` (the input is not modified).
+
+      * ``cell`` <- the reduced lattice of ``optimize_lattice`` ([1,3,3]), ``cell_og`` <- the cell as it was;
+      * ``cart_dir`` <- ``cart_dir @ R`` and, for per-atom 3x3 targets, ``y`` <- ``R^T y R``.
+
+    The lattice is multiplied by ``R^T`` and the directions by ``R``: that is what the reference does, reproduced as it is
+    (DESIGN.md section 3).  ``DeviceShard.with_optimized_cell`` does the same to a whole resident shard on the GPU.
+    Raises ``ValueError`` naming the crystal (``name``, else its ``refcode`` if it has one) for a degenerate cell."""
+    try:
+        new_cell, R = optimize_lattice(data.cell.reshape(3, 3))
+    except ValueError as e:
+        who = name if name is not None else getattr(data, "refcode", "?")
+        raise ValueError(f"crystal {who}: {e}") from None
+    out = data.__class__()
+    for k, v in data.__dict__.items():
+        setattr(out, k, v)
+    out.cell_og = data.cell
+    out.cell = new_cell.unsqueeze(0)
+    out.cart_dir = data.cart_dir @ R
+    if data.y.dim() == 3 and tuple(data.y.shape[1:]) == (3, 3):
+        out.y = R.transpose(-1, -2) @ data.y @ R
     return out
 
 

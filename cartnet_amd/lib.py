@@ -331,6 +331,10 @@ PROTOTYPES = {
     "cartnet_shard_drop_h_fill": (C.c_int, [C.POINTER(Shard), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
                                             c_i64p, C.c_int64, C.c_int64, c_i32p, c_f32p, c_u8p, c_i64p, c_i32p, c_i32p,
                                             c_f32p, c_f32p, c_stream]),
+    "cartnet_shard_optimize_cell_select": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p, C.c_void_p, c_i32p, c_i64p,
+                                                     c_stream]),
+    "cartnet_shard_optimize_cell_rotate": (C.c_int, [C.POINTER(Shard), C.c_int32, C.c_int64, C.c_int64, c_f32p, c_f32p,
+                                                     c_f32p, c_stream]),
     "cartnet_profile_gemm": (C.c_int, [C.c_int32]),
     "cartnet_profile_gemm_only": (C.c_int, [C.c_int32]),
     "cartnet_profile_gemm_every": (C.c_int, [C.c_int32]),

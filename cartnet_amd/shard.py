@@ -248,6 +248,45 @@ class DeviceShard:
         out._describe()
         return out
 
+    def with_optimized_cell(self) -> "DeviceShard":
+        """The same crystals, each in the frame of its canonical reduced lattice, as a new resident shard (this one is
+        untouched): what the reference's ``DatasetADP(optimize_cell=True)`` does per crystal and per access on the host
+        for iComformer (dataset/datasetADP.py:75-80, dataset/utils.py:366-452; ``cartnet_amd.data.optimize_cell`` states
+        the rule in torch), done once for the whole shard on the GPU (csrc/lattice_ops.hip).  The new shard owns ``cell``,
+        ``cart_dir`` and, for per-atom 3x3 targets, ``y``; every other array is shared.  It also carries ``rotation``
+        [G,9] fp32 (R per crystal) and ``basis`` [G,9] int8 (the signed integer coefficients of the three chosen vectors in
+        the rows of the old cell).  Composes with ``without_hydrogens()`` in either order.  Raises ``ValueError`` naming
+        the first crystal whose cell is degenerate (no three independent vectors among the candidates)."""
+        dev, t, G = self.device, self.t, self.num_graphs
+        if "cell" not in t:
+            raise ValueError("the shard carries no cell")
+        E, M = int(self.edge_ptr[-1]), int(self.y_ptr[-1])
+        with torch.cuda.device(dev):
+            new: Dict[str, torch.Tensor] = {"cell": torch.empty((G, 9), dtype=torch.float32, device=dev),
+                                            "rotation": torch.empty((G, 9), dtype=torch.float32, device=dev),
+                                            "basis": torch.empty((G, 9), dtype=torch.int8, device=dev),
+                                            "cart_dir": torch.empty((E, 3), dtype=torch.float32, device=dev)}
+            if self.per_atom_target:
+                new["y"] = torch.empty((M, 9), dtype=torch.float32, device=dev)
+            status = torch.empty(G, dtype=torch.int32, device=dev)
+            first_bad = torch.empty(1, dtype=torch.int64, device=dev)
+            _l.check(self._lib.cartnet_shard_optimize_cell_select(
+                t["cell"].data_ptr(), G, new["cell"].data_ptr(), new["rotation"].data_ptr(), new["basis"].data_ptr(),
+                status.data_ptr(), first_bad.data_ptr(), _l.stream_ptr()), "cartnet_shard_optimize_cell_select")
+            _l.check(self._lib.cartnet_shard_optimize_cell_rotate(
+                _l.C.byref(self._desc), G, E, M, new["rotation"].data_ptr(), new["cart_dir"].data_ptr(),
+                _l.ptr(new.get("y")), _l.stream_ptr()), "cartnet_shard_optimize_cell_rotate")
+            bad = int(first_bad.item())                         # the one device-to-host copy
+        if bad >= 0:
+            raise ValueError(f"crystal {bad}: degenerate cell: no three linearly independent lattice vectors among the "
+                             "candidates")
+        out = object.__new__(DeviceShard)
+        out.device, out.num_graphs, out._lib = dev, G, self._lib
+        out.atom_ptr, out.edge_ptr, out.y_ptr = self.atom_ptr, self.edge_ptr, self.y_ptr
+        out.t = {**t, **new}
+        out._describe()
+        return out
+
     def collate(self, sel: Sequence[int], rot: Optional[torch.Tensor] = None, temp_mean: float = 0.0,
                 temp_std: float = 1.0) -> Batch:
         """Batch of crystals ``sel`` (in that order) with PyG's collation rules (cartnet_amd/data.py), on the GPU.

@@ -159,10 +159,11 @@ def make_geometry(g: int, n_atoms: Optional[int] = 194, n_range=(64, 324), adp: 
 
 
 def make_crystal(g: int, n_atoms: Optional[int] = 194, radius: float = 5.0, n_range=(64, 324),
-                 adp: bool = True, base_seed: int = 1234) -> Data:
-    """One synthetic crystal graph with the attribute set CartNet reads (SURVEY.md §8a batch table)."""
+                 adp: bool = True, base_seed: int = 1234, max_neighbors: Optional[int] = None) -> Data:
+    """One synthetic crystal graph with the attribute set CartNet reads (SURVEY.md §8a batch table).  ``max_neighbors``:
+    the reference's neighbour cap on the radius graph (``compute_knn``, dataset/utils.py:456-486); None = uncapped."""
     geo = make_geometry(g, n_atoms, n_range, adp, base_seed)
-    edge_index, cart_dist, cart_dir = radius_graph_pbc_single(geo.pos, geo.cell[0], radius)
+    edge_index, cart_dist, cart_dir = radius_graph_pbc_single(geo.pos, geo.cell[0], radius, max_neighbors=max_neighbors)
     d = Data(x=geo.x, pos=geo.pos, cell=geo.cell, edge_index=edge_index, cart_dist=cart_dist, cart_dir=cart_dir,
              natoms=geo.natoms)
     d.y = geo.y

@@ -415,6 +415,27 @@ int cartnet_shard_drop_h_fill(const CartnetShard* shard, int32_t G, int64_t N, i
                               int32_t* edge_src_out, int32_t* edge_tgt_out, float* cart_dist_out, float* cart_dir_out,
                               void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Every crystal of a shard in the frame of its canonical reduced lattice (reference: dataset/datasetADP.py:75-80,
+ * DatasetADP.get with optimize_cell = True, which loader/loader.py:24-32 sets for iComformer on ADP -- per crystal and
+ * per access on the host: optmize_lattice, dataset/utils.py:366-452, picks the three shortest independent vectors among
+ * the 124 candidates i c0 + j c1 + k c2 (i, j, k in -2..2) in (norm, enumeration) order, fixes their signs against the
+ * first one and their handedness, and rotates them so that the result is lower-triangular; then cart_dir <- cart_dir R
+ * and y <- R^T y R).  Here it runs once per dataset on the resident shard (cartnet_amd/csrc/lattice_ops.hip;
+ * cartnet_amd.data.optimize_cell is the per-crystal host form).  Two calls, no host synchronisation in either:
+ *   select: cell [G,9] -> cell_out [G,9] (= [v1;v2;v3] R^T), rotation [G,9] (R, row-major), basis [G,9] int8 (row r: the
+ *           signed integer coefficients of v_r in the rows of the old cell), status [G] int32 (scratch: 1 = the crystal has
+ *           no admissible second or third vector; its cell is passed through with R = I) and *first_bad (device): the
+ *           first crystal with a non-zero status, or -1 -- the one word the caller reads back.
+ *   rotate: cart_dir_out [E,3] = cart_dir R[g(e)]; y_out [M,9] = R^T y R per target row (NULL: targets are not 3x3 and
+ *           stay as they are).  E = edge_ptr[G], M = y_ptr[G]; cart_dir, y and the outputs 16-byte aligned.
+ * No atomics, no workgroup waits for another, identical bytes on every run.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_shard_optimize_cell_select(const float* cell, int32_t G, float* cell_out, float* rotation, int8_t* basis,
+                                       int32_t* status, int64_t* first_bad, void* stream);
+int cartnet_shard_optimize_cell_rotate(const CartnetShard* shard, int32_t G, int64_t E, int64_t M, const float* rotation,
+                                       float* cart_dir_out, float* y_out, void* stream);
+
 /* Opt-in timing of cartnet_gemm launches (the only PROCESS-global state in the library; used by bench.py, off by default
  * and not for concurrent use from several threads):
  * while enabled, every cartnet_gemm call -- also those issued inside cartnet_model_forward/backward -- is bracketed

@@ -22,7 +22,7 @@ import torch
 
 from cartnet_amd import distributed as cdist
 from cartnet_amd.config import cfg, set_cfg
-from cartnet_amd.data import DataLoader, remove_hydrogens
+from cartnet_amd.data import DataLoader, optimize_cell, remove_hydrogens
 from cartnet_amd.master import create_model
 from cartnet_amd.optim import FlatAdam, one_cycle_lr, one_cycle_momentum
 from cartnet_amd.synthetic import augment_data, make_crystal
@@ -120,23 +120,33 @@ def fill_cfg(args) -> None:
 def create_loaders(args, rank: int, world: int):
     """Synthetic stand-in for loader/loader.py:create_loader: seed-123 80/10/10 split (loader.py:130-141)."""
     adp = cfg.dataset.name == "ADP"
-    graphs = [make_crystal(g, None, cfg.radius, tuple(args.atoms), adp=adp) for g in range(args.synthetic)]
+    # every model but CartNet trains on the capped graphs (main.py:176, loader/loader.py:26,108: compute_knn)
+    cap = cfg.max_neighbours if cfg.max_neighbours > 0 else None
+    graphs = [make_crystal(g, None, cfg.radius, tuple(args.atoms), adp=adp, max_neighbors=cap)
+              for g in range(args.synthetic)]
     perm = torch.randperm(len(graphs), generator=torch.Generator().manual_seed(123)).tolist()
     n_tr, n_va = int(0.8 * len(graphs)), int(0.1 * len(graphs))
     tr = [graphs[i] for i in perm[:n_tr]]
     va = [graphs[i] for i in perm[n_tr:n_tr + n_va]] or tr[:1]
     te = [graphs[i] for i in perm[n_tr + n_va:]] or tr[:1]
     no_h = adp and not cfg.use_H            # loader/loader.py:29-32: DatasetADP(hydrogens=cfg.use_H), whatever the model
+    # loader/loader.py:24-32: iComformer on ADP reads DatasetADP(optimize_cell=True); as in DatasetADP.get the order is
+    # cap on the full crystal, hydrogen removal, canonical lattice frame
+    canonical = adp and cfg.model == "icomformer"
     if args.resident_dataset:                                             # SURVEY.md 8f-3: cartnet_amd/shard.py
         from cartnet_amd.shard import DeviceShard, ShardLoader
         shards = [DeviceShard.from_data_list(part, cfg.device) for part in (tr, va, te)]
         if no_h:
             shards = [s.without_hydrogens() for s in shards]
+        if canonical:
+            shards = [s.with_optimized_cell() for s in shards]
         return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
                             augment=cfg.augment),
                 ShardLoader(shards[1], cfg.batch), ShardLoader(shards[2], 1 if adp else cfg.batch)]
     if no_h:
         tr, va, te = ([remove_hydrogens(d) for d in part] for part in (tr, va, te))
+    if canonical:
+        tr, va, te = ([optimize_cell(d) for d in part] for part in (tr, va, te))
     gen = torch.Generator().manual_seed(cfg.seed + 1000 * rank)
     aug = (lambda d: augment_data(d, gen)) if cfg.augment else None
     return [DataLoader(tr, cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world, transform=aug),

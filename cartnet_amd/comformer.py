@@ -924,6 +924,7 @@ class _IcfNativeFunction(torch.autograd.Function):
                 raise ValueError(f"parameter {n} must be a contiguous fp32 CUDA tensor")
         md = _l.IcfModel()
         md.C, md.n_types, md.gemm_precision = C_, N_ATOM_TYPES, int(model.gemm_precision)
+        md.bn_group_size = int(model.bn_group_size)
         md.gamma_rbf, md.gamma_angle = float(model.rbf[0].gamma), float(model.rbf_angle[0].gamma)
         md.bn_eps, md.bn_momentum = BN_EPS, BN_MOMENTUM
         md.rbf_centers, md.rbf_angle_centers = B["rbf.0.centers"].data_ptr(), B["rbf_angle.0.centers"].data_ptr()
@@ -1010,6 +1011,11 @@ class iComformer(nn.Module):
         # True (default): ONE C-ABI call per direction (csrc/icomformer.hip).  False: the same kernels sequenced from
         # Python (`_IComformerFunction`, what eComformer uses) -- kept as the cross-check of the C++ sequence
         self.native_sequence = True
+        # > 0: consecutive crystals of a batch form BatchNorm groups of this size in training mode (CartnetIcfModel.
+        # bn_group_size): the reference's recipe --batch 4 --batch_accumulation 16 (scripts/train_icomformer_adp.sh:3) as
+        # ONE pass over 64 crystals with the statistics, the running-statistics updates and (train.grouped_loss) the loss
+        # taken per micro-batch.  The C++ sequence only.
+        self.bn_group_size = 0
 
     def _aux_stream_ptr(self, dev):
         if not getattr(self, "overlap_weight_gradients", True):
@@ -1019,6 +1025,8 @@ class iComformer(nn.Module):
         return self._aux.cuda_stream
 
     def forward(self, data):
+        if int(self.bn_group_size) > 0 and not self.native_sequence:
+            raise ValueError("bn_group_size > 0 needs native_sequence = True: the Python-sequenced path has one BatchNorm group")
         params = [p for _, p in self.named_parameters()]
         if not params[0].is_cuda:
             raise RuntimeError("cartnet_amd.iComformer runs only on an AMD GPU (HIP kernels); there is no CPU fallback")

@@ -19,6 +19,35 @@ inline int seg_parts(int S) {
   return b;
 }
 
+// BatchNorm groups (CartnetGroups, common.h: cn_group_range) in the segment kernels below.  GR = false is the single-group
+// kernel as it always was: group 0, workgroup blockIdx.x of a one-dimensional grid, segments [0, S) -- compile-time
+// constants, so those instantiations keep their instructions.  GR = true: grid (parts, G), group g owns the segments
+// [seg_gptr[g], seg_gptr[g + 1]), reads its statistics at mean_rstd + g * 2C (sums + g * 2C) and writes the partial row
+// g * parts + bx; a group's row count is ptr[s1] - ptr[s0].
+template <bool GR>
+__device__ __forceinline__ void cn_seg_group(const int* __restrict__ seg_gptr, int S, bool reverse, int& g, int& bx, int& s0,
+                                             int& s1) {
+  if constexpr (GR) {
+    cn_group_range(seg_gptr, S, reverse, g, bx, s0, s1);
+  } else {
+    g = 0; bx = (int)blockIdx.x; s0 = 0; s1 = S;
+  }
+}
+
+// the workgroup's index inside its group, in the type the single-group kernels have always computed with (blockIdx.x itself)
+template <bool GR>
+__device__ __forceinline__ auto cn_seg_bx(int bx) {
+  if constexpr (GR) return bx;
+  else return blockIdx.x;
+}
+
+// the workgroup's row of the partial sums
+template <bool GR>
+__device__ __forceinline__ int cn_seg_prow(int g, int bx) {
+  if constexpr (GR) return g * (int)gridDim.x + bx;
+  else return (int)blockIdx.x;
+}
+
 // out[r, k] = exp(-gamma (v[r] - centers[k])^2)      (models/utils.py:125-129)
 __global__ void cn_rbf_expand_kernel(const float* __restrict__ v, long long n, const float* __restrict__ centers,
                                      int bins, float gamma, float* __restrict__ out, int ldo) {
@@ -110,19 +139,25 @@ __global__ void cn_eltwise_kernel(int op, const float* a, const float* b, float*
 }
 
 // alpha[r] = key[r] * q[s] * scale for the rows r of segment s (+ fp64 column statistics of alpha).
+template <bool GR>
 __global__ __launch_bounds__(256) void cn_rowmul_fwd_kernel(const float* __restrict__ key, int ldk,
                                                             const float* __restrict__ q, int ldq,
                                                             const int* __restrict__ ptr, int S, int C, float scale,
                                                             float* __restrict__ alpha, int lda,
                                                             double* __restrict__ parts_sum,
-                                                            double* __restrict__ parts_sq) {
+                                                            double* __restrict__ parts_sq,
+                                                            const int* __restrict__ seg_gptr) {
   __shared__ double red[NODES_PER_BLOCK * 256];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int gi, bx, s0, s1;
+  cn_seg_group<GR>(seg_gptr, S, false, gi, bx, s0, s1);
+  const auto bxx = cn_seg_bx<GR>(bx);
+  const int prow = cn_seg_prow<GR>(gi, bx);
   for (int c0 = 0; c0 < C; c0 += 256) {
     const int c = c0 + lane * 4;
     const bool active = c < C;
     f64x4 ps = {0, 0, 0, 0}, pq = {0, 0, 0, 0};
-    for (int s = blockIdx.x * NODES_PER_BLOCK + wid; s < S; s += gridDim.x * NODES_PER_BLOCK) {
+    for (int s = s0 + bxx * NODES_PER_BLOCK + wid; s < s1; s += gridDim.x * NODES_PER_BLOCK) {
       if (!active) continue;
       const f32x4 qv = ld4(q + (size_t)s * ldq + c) * scale;
       for (int r = ptr[s]; r < ptr[s + 1]; ++r) {
@@ -135,8 +170,8 @@ __global__ __launch_bounds__(256) void cn_rowmul_fwd_kernel(const float* __restr
         }
       }
     }
-    cn_block_store_parts(ps, red, parts_sum, C, c, active, wid, lane);
-    cn_block_store_parts(pq, red, parts_sq, C, c, active, wid, lane);
+    cn_block_store_parts_row(ps, red, parts_sum, C, c, active, wid, lane, prow);
+    cn_block_store_parts_row(pq, red, parts_sq, C, c, active, wid, lane, prow);
   }
 }
 
@@ -187,21 +222,27 @@ __global__ __launch_bounds__(256) void cn_rowmul_bwd_kernel(float* dalpha, int l
 // cartnet_rowmul_fwd wrote alpha (R x D) and cartnet_gate_scatter_fwd read it back; here the statistics pass
 // (cartnet_rowmul_fwd with alpha = NULL) only reads, and this kernel reads the key rows where that one read alpha.
 constexpr int ATT_BATCH = 8;
-template <bool BC>
+template <bool BC, bool GR>
 __global__ __launch_bounds__(256) void cn_att_gate_fwd_kernel(const float* __restrict__ gs, const float* __restrict__ q, int ldq,
                                                               const int* __restrict__ ptr,
                                                               const float* __restrict__ mean_rstd,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float qscale, int S, int D,
-                                                              float* __restrict__ aggr, float* __restrict__ bc) {
+                                                              float* __restrict__ aggr, float* __restrict__ bc,
+                                                              const int* __restrict__ seg_gptr) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int ld = 2 * D;
   const int chunks = (D + 255) / 256;
-  const long long items = (long long)S * chunks;
-  for (long long it0 = (long long)blockIdx.x * NODES_PER_BLOCK + wid; it0 < items;
+  int gi, bx, s0, s1;
+  cn_seg_group<GR>(seg_gptr, S, true, gi, bx, s0, s1);      // (groups and their workgroups descending as well)
+  const auto bxx = cn_seg_bx<GR>(bx);
+  if constexpr (GR) mean_rstd += (size_t)gi * 2 * D;
+  const long long items = (long long)(s1 - s0) * chunks;
+  for (long long it0 = (long long)bxx * NODES_PER_BLOCK + wid; it0 < items;
        it0 += (long long)gridDim.x * NODES_PER_BLOCK) {
     const long long it = items - 1 - it0;      // descending: the statistics pass in front ran ascending
-    const int t = (int)(it / chunks);
+    int t = (int)(it / chunks);
+    if constexpr (GR) t += s0;
     const int c = (int)(it % chunks) * 256 + lane * 4;
     if (c >= D) continue;
     const f32x4 mean = ld4(mean_rstd + c), rstd = ld4(mean_rstd + D + c), gam = ld4(gamma + c), shift = ld4(beta + c);
@@ -252,17 +293,29 @@ __global__ __launch_bounds__(256) void cn_att_gate_fwd_kernel(const float* __res
 // Descending sweep: the statistics pass in front (or the products that wrote daggr) ran ascending.
 // KEY_IN_GS: gs[:, :D] holds the key rows themselves (alpha = key * q[s] * scale is recomputed here as the forward gate
 // kernel cn_att_gate_fwd_kernel recomputed it: alpha is never written), `key` is unused.
-template <bool KEY_IN_GS>
+template <bool KEY_IN_GS, bool GR>
 __global__ __launch_bounds__(256) void cn_att_gate_bwd_kernel(
     float* gs, const float* __restrict__ key, int ldk, const float* __restrict__ q, int ldq,
     const float* __restrict__ daggr, const int* __restrict__ ptr, const float* __restrict__ mean_rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums, float inv_count,
     float scale, int S, int D, float* __restrict__ dq, int lddq, double* __restrict__ parts_dkey,
-    double* __restrict__ parts_dmsg, double* __restrict__ parts_dq) {
+    double* __restrict__ parts_dmsg, double* __restrict__ parts_dq, const int* __restrict__ seg_gptr) {
   __shared__ double red[NODES_PER_BLOCK * 256];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int ld = 2 * D;
-  const int stride = gridDim.x * NODES_PER_BLOCK, nsweeps = (S + stride - 1) / stride;
+  int gi, bx, s0, s1;
+  cn_seg_group<GR>(seg_gptr, S, true, gi, bx, s0, s1);
+  const auto bxx = cn_seg_bx<GR>(bx);
+  if constexpr (GR) {
+    mean_rstd += (size_t)gi * 2 * D;
+    sums += (size_t)gi * 2 * D;
+    if (inv_count != 0.f) {      // training-mode BatchNorm backward: means over THIS group's rows
+      const int rg = ptr[s1] - ptr[s0];
+      inv_count = rg > 0 ? 1.0f / (float)rg : 0.f;
+    }
+  }
+  const int prow = cn_seg_prow<GR>(gi, bx);
+  const int stride = gridDim.x * NODES_PER_BLOCK, nsweeps = (s1 - s0 + stride - 1) / stride;
   for (int c0 = 0; c0 < D; c0 += 256) {
     const int c = c0 + lane * 4;
     const bool active = c < D;
@@ -278,8 +331,8 @@ __global__ __launch_bounds__(256) void cn_att_gate_bwd_kernel(
     }
     f64x4 tk = {0, 0, 0, 0}, tm = {0, 0, 0, 0}, tq = {0, 0, 0, 0};
     for (int j = nsweeps - 1; j >= 0; --j) {
-      const int t = blockIdx.x * NODES_PER_BLOCK + wid + j * stride;
-      if (t >= S || !active) continue;
+      const int t = s0 + bxx * NODES_PER_BLOCK + wid + j * stride;
+      if (t >= s1 || !active) continue;
       const int k0 = ptr[t], k1 = ptr[t + 1];
       const f32x4 dm = ld4(daggr + (size_t)t * D + c);
       const f32x4 qv = ld4(q + (size_t)t * ldq + c) * scale;
@@ -317,20 +370,29 @@ __global__ __launch_bounds__(256) void cn_att_gate_bwd_kernel(
       cn_acc4(tm, pm);
       cn_acc4(tq, accq);
     }
-    cn_block_store_parts(tk, red, parts_dkey, D, c, active, wid, lane);
-    cn_block_store_parts(tm, red, parts_dmsg, D, c, active, wid, lane);
-    cn_block_store_parts(tq, red, parts_dq, D, c, active, wid, lane);
+    cn_block_store_parts_row(tk, red, parts_dkey, D, c, active, wid, lane, prow);
+    cn_block_store_parts_row(tm, red, parts_dmsg, D, c, active, wid, lane, prow);
+    cn_block_store_parts_row(tq, red, parts_dq, D, c, active, wid, lane, prow);
   }
 }
 
 // y = softplus(x + bn(o))   (ComformerConv.forward, comformer_conv.py:88)
+// GR: grid (parts, G), group g = blockIdx.y owns the rows [row_gptr[g], row_gptr[g + 1]) and the statistics row g
+template <bool GR>
 __global__ void cn_softplus_update_fwd_kernel(const float* __restrict__ o, const float* __restrict__ x,
                                               const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
                                               const float* __restrict__ beta, long long N, int D,
-                                              float* __restrict__ y) {
-  const long long total4 = N * D / 4;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += (long long)gridDim.x * blockDim.x) {
+                                              float* __restrict__ y, const int* __restrict__ row_gptr) {
+  long long base4 = 0, total4 = N * D / 4;
+  if constexpr (GR) {
+    const int n0 = row_gptr[blockIdx.y], n1 = row_gptr[blockIdx.y + 1];
+    mean_rstd += (size_t)blockIdx.y * 2 * D;
+    base4 = (long long)n0 * D / 4;
+    total4 = (long long)(n1 - n0) * D / 4;
+  }
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < total4;
+       j += (long long)gridDim.x * blockDim.x) {
+    const long long i = base4 + j;
     const int c = (int)((i * 4) % D);
     const f32x4 a = ld4(o + i * 4), xi = ld4(x + i * 4);
     const f32x4 mean = ld4(mean_rstd + c), rstd = ld4(mean_rstd + D + c), gam = ld4(gamma + c), bet = ld4(beta + c);
@@ -343,14 +405,26 @@ __global__ void cn_softplus_update_fwd_kernel(const float* __restrict__ o, const
 
 // MODE 0: du = dy * sigmoid(u), u = x + bn(o); partial sums of du and du * ohat.
 // MODE 1: do = gamma * rstd * (du - sum_a/N - ohat * sum_b/N); dx = du (+ dx_add); with parts_a: column partials of do.
-template <int MODE>
+template <int MODE, bool GR>
 __global__ __launch_bounds__(256) void cn_softplus_update_bwd_kernel(
     const float* __restrict__ o, const float* __restrict__ x, const float* __restrict__ dy,
     const float* __restrict__ mean_rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ sums, float inv_count, int N, int D, double* __restrict__ parts_a,
-    double* __restrict__ parts_b, float* __restrict__ d_o, const float* dx_add, float* dx) {
+    double* __restrict__ parts_b, float* __restrict__ d_o, const float* dx_add, float* dx,
+    const int* __restrict__ row_gptr) {
   __shared__ double red[NODES_PER_BLOCK * 256];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int gi, bx, n0, n1;
+  cn_seg_group<GR>(row_gptr, N, false, gi, bx, n0, n1);
+  const auto bxx = cn_seg_bx<GR>(bx);
+  if constexpr (GR) {
+    mean_rstd += (size_t)gi * 2 * D;
+    if (MODE == 1) {
+      sums += (size_t)gi * 2 * D;
+      if (inv_count != 0.f) inv_count = n1 > n0 ? 1.0f / (float)(n1 - n0) : 0.f;      // means over THIS group's rows
+    }
+  }
+  const int prow = cn_seg_prow<GR>(gi, bx);
   for (int c0 = 0; c0 < D; c0 += 256) {
     const int c = c0 + lane * 4;
     const bool active = c < D;
@@ -367,7 +441,7 @@ __global__ __launch_bounds__(256) void cn_softplus_update_bwd_kernel(
       }
     }
     f64x4 pa = {0, 0, 0, 0}, pb = {0, 0, 0, 0};
-    for (int n = blockIdx.x * NODES_PER_BLOCK + wid; n < N; n += gridDim.x * NODES_PER_BLOCK) {
+    for (int n = n0 + bxx * NODES_PER_BLOCK + wid; n < n1; n += gridDim.x * NODES_PER_BLOCK) {
       if (!active) continue;
       const f32x4 a = ld4(o + (size_t)n * D + c), xi = ld4(x + (size_t)n * D + c), g = ld4(dy + (size_t)n * D + c);
       f32x4 vo, vx;
@@ -392,10 +466,10 @@ __global__ __launch_bounds__(256) void cn_softplus_update_bwd_kernel(
       }
     }
     if (MODE == 0) {
-      cn_block_store_parts(pa, red, parts_a, D, c, active, wid, lane);
-      cn_block_store_parts(pb, red, parts_b, D, c, active, wid, lane);
+      cn_block_store_parts_row(pa, red, parts_a, D, c, active, wid, lane, prow);
+      cn_block_store_parts_row(pb, red, parts_b, D, c, active, wid, lane, prow);
     } else if (parts_a) {     // MODE 1: the column partials of d_o (the bias gradient of the Linear that produced o)
-      cn_block_store_parts(pa, red, parts_a, D, c, active, wid, lane);
+      cn_block_store_parts_row(pa, red, parts_a, D, c, active, wid, lane, prow);
     }
   }
 }
@@ -442,23 +516,29 @@ __global__ __launch_bounds__(256) void cn_softplus_bwd_sums_kernel(const float* 
 
 // Column partial sums of d[r, c] * bc[r, c] and d[r, c] * bc[r, C + c] (bc [R, 2C]): the targets' share of the gate's
 // BatchNorm-backward sums from the per-target sums the forward gate kernel left (cartnet_gate_scatter_fwd_bc).
+template <bool GR>
 __global__ __launch_bounds__(256) void cn_coldot_bc_partial_kernel(const float* __restrict__ d, int ld,
                                                                    const float* __restrict__ bc, int R, int C,
-                                                                   double* __restrict__ parts_a, double* __restrict__ parts_b) {
+                                                                   double* __restrict__ parts_a, double* __restrict__ parts_b,
+                                                                   const int* __restrict__ row_gptr) {
   __shared__ double red[NODES_PER_BLOCK * 256];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int gi, bx, r0, r1;
+  cn_seg_group<GR>(row_gptr, R, false, gi, bx, r0, r1);
+  const auto bxx = cn_seg_bx<GR>(bx);
+  const int prow = cn_seg_prow<GR>(gi, bx);
   for (int c0 = 0; c0 < C; c0 += 256) {
     const int c = c0 + lane * 4;
     const bool active = c < C;
     f64x4 pa = {0, 0, 0, 0}, pb = {0, 0, 0, 0};
-    for (int r = blockIdx.x * NODES_PER_BLOCK + wid; r < R; r += gridDim.x * NODES_PER_BLOCK)
+    for (int r = r0 + bxx * NODES_PER_BLOCK + wid; r < r1; r += gridDim.x * NODES_PER_BLOCK)
       if (active) {
         const f32x4 v = ld4(d + (size_t)r * ld + c);
         cn_acc4(pa, v * ld4(bc + (size_t)r * 2 * C + c));
         cn_acc4(pb, v * ld4(bc + (size_t)r * 2 * C + C + c));
       }
-    cn_block_store_parts(pa, red, parts_a, C, c, active, wid, lane);
-    cn_block_store_parts(pb, red, parts_b, C, c, active, wid, lane);
+    cn_block_store_parts_row(pa, red, parts_a, C, c, active, wid, lane, prow);
+    cn_block_store_parts_row(pb, red, parts_b, C, c, active, wid, lane, prow);
   }
 }
 
@@ -521,16 +601,38 @@ extern "C" int cartnet_eltwise(int32_t op, const float* a, const float* b, float
   return 0;
 }
 
+// Grouped forms (CartnetGroups; cartnet_hip.h "iComformer: BatchNorm groups").  Every *_grouped entry point with
+// groups == NULL launches exactly what the entry point without the suffix launches.  The segment kernels that feed or read
+// bn_att (rows = "edges") take groups->edge_parts workgroups per group, the softplus update (bn over the segments
+// themselves) groups->node_parts.
+static int rowmul_fwd(const char* who, const float* key, int32_t ldk, const float* q, int32_t ldq, const int32_t* ptr, int32_t S,
+                      int32_t C, float scale, float* alpha, int32_t lda, double* parts_sum, double* parts_sq,
+                      const CartnetGroups* groups, void* stream) {
+  CN_CHECK(S >= 0 && C >= 4 && C % 4 == 0 && ldk % 4 == 0 && ldq % 4 == 0 && lda % 4 == 0,
+           "%s: C and leading dimensions must be multiples of 4", who);
+  CN_CHECK(key && q && ptr && parts_sum && parts_sq, "%s: null pointer", who);
+  CN_CHECK(cn_groups_ok(groups), "%s: bad groups", who);
+  if (groups)
+    hipLaunchKernelGGL(cn_rowmul_fwd_kernel<true>, dim3(groups->edge_parts, groups->G), dim3(256), 0, ST(stream), key, ldk, q,
+                       ldq, ptr, S, C, scale, alpha, lda, parts_sum, parts_sq, groups->node_gptr);
+  else
+    hipLaunchKernelGGL(cn_rowmul_fwd_kernel<false>, dim3(seg_parts(S)), dim3(256), 0, ST(stream), key, ldk, q, ldq, ptr, S, C,
+                       scale, alpha, lda, parts_sum, parts_sq, (const int*)nullptr);
+  CN_LAUNCH_CHECK(who);
+  return 0;
+}
+
 extern "C" int cartnet_rowmul_fwd(const float* key, int32_t ldk, const float* q, int32_t ldq, const int32_t* ptr,
                                   int32_t S, int32_t C, float scale, float* alpha, int32_t lda, double* parts_sum,
                                   double* parts_sq, void* stream) {
-  CN_CHECK(S >= 0 && C >= 4 && C % 4 == 0 && ldk % 4 == 0 && ldq % 4 == 0 && lda % 4 == 0,
-           "cartnet_rowmul_fwd: C and leading dimensions must be multiples of 4");
-  CN_CHECK(key && q && ptr && parts_sum && parts_sq, "cartnet_rowmul_fwd: null pointer");
-  hipLaunchKernelGGL(cn_rowmul_fwd_kernel, dim3(seg_parts(S)), dim3(256), 0, ST(stream), key, ldk, q, ldq, ptr, S, C,
-                     scale, alpha, lda, parts_sum, parts_sq);
-  CN_LAUNCH_CHECK("cartnet_rowmul_fwd");
-  return 0;
+  return rowmul_fwd("cartnet_rowmul_fwd", key, ldk, q, ldq, ptr, S, C, scale, alpha, lda, parts_sum, parts_sq, nullptr, stream);
+}
+
+extern "C" int cartnet_rowmul_fwd_grouped(const float* key, int32_t ldk, const float* q, int32_t ldq, const int32_t* ptr,
+                                          int32_t S, int32_t C, float scale, float* alpha, int32_t lda, double* parts_sum,
+                                          double* parts_sq, const CartnetGroups* groups, void* stream) {
+  return rowmul_fwd("cartnet_rowmul_fwd_grouped", key, ldk, q, ldq, ptr, S, C, scale, alpha, lda, parts_sum, parts_sq, groups,
+                    stream);
 }
 
 extern "C" int cartnet_rowmul_bwd(float* dalpha, int32_t lda, const float* key, int32_t ldk, const float* q,
@@ -562,22 +664,76 @@ extern "C" int cartnet_rowmul_bwd_sums(float* dalpha, int32_t lda, const float* 
   return 0;
 }
 
-extern "C" int cartnet_att_gate_fwd(const float* gs, const float* q, int32_t ldq, const int32_t* ptr, const float* mean_rstd,
-                                    const float* gamma, const float* beta, float scale, int32_t S, int32_t D, float* aggr,
-                                    float* bc, void* stream) {
-  CN_CHECK(S >= 0 && D >= 4 && D % 4 == 0 && ldq % 4 == 0 && ldq >= D, "cartnet_att_gate_fwd: D / ldq must be multiples of 4");
+static int att_gate_fwd(const char* who, const float* gs, const float* q, int32_t ldq, const int32_t* ptr, const float* mean_rstd,
+                        const float* gamma, const float* beta, float scale, int32_t S, int32_t D, float* aggr, float* bc,
+                        const CartnetGroups* groups, void* stream) {
+  CN_CHECK(S >= 0 && D >= 4 && D % 4 == 0 && ldq % 4 == 0 && ldq >= D, "%s: D / ldq must be multiples of 4", who);
   if (S == 0) return 0;
-  CN_CHECK(gs && q && ptr && mean_rstd && gamma && beta && aggr, "cartnet_att_gate_fwd: null pointer");
-  CN_CHECK(!bc || (reinterpret_cast<uintptr_t>(bc) & 15u) == 0, "cartnet_att_gate_fwd: bc must be 16-byte aligned");
+  CN_CHECK(gs && q && ptr && mean_rstd && gamma && beta && aggr, "%s: null pointer", who);
+  CN_CHECK(!bc || (reinterpret_cast<uintptr_t>(bc) & 15u) == 0, "%s: bc must be 16-byte aligned", who);
+  CN_CHECK(cn_groups_ok(groups), "%s: bad groups", who);
+  if (groups) {
+    const dim3 grid(groups->edge_parts, groups->G);
+    if (bc)
+      hipLaunchKernelGGL((cn_att_gate_fwd_kernel<true, true>), grid, dim3(256), 0, ST(stream), gs, q, ldq, ptr, mean_rstd, gamma,
+                         beta, scale, S, D, aggr, bc, groups->node_gptr);
+    else
+      hipLaunchKernelGGL((cn_att_gate_fwd_kernel<false, true>), grid, dim3(256), 0, ST(stream), gs, q, ldq, ptr, mean_rstd, gamma,
+                         beta, scale, S, D, aggr, bc, groups->node_gptr);
+    CN_LAUNCH_CHECK(who);
+    return 0;
+  }
   long long blocks = ((long long)S * ((D + 255) / 256) + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK;
   if (blocks > 4096) blocks = 4096;
   if (bc)
-    hipLaunchKernelGGL(cn_att_gate_fwd_kernel<true>, dim3((int)blocks), dim3(256), 0, ST(stream), gs, q, ldq, ptr, mean_rstd,
-                       gamma, beta, scale, S, D, aggr, bc);
+    hipLaunchKernelGGL((cn_att_gate_fwd_kernel<true, false>), dim3((int)blocks), dim3(256), 0, ST(stream), gs, q, ldq, ptr,
+                       mean_rstd, gamma, beta, scale, S, D, aggr, bc, (const int*)nullptr);
   else
-    hipLaunchKernelGGL(cn_att_gate_fwd_kernel<false>, dim3((int)blocks), dim3(256), 0, ST(stream), gs, q, ldq, ptr, mean_rstd,
-                       gamma, beta, scale, S, D, aggr, bc);
-  CN_LAUNCH_CHECK("cartnet_att_gate_fwd");
+    hipLaunchKernelGGL((cn_att_gate_fwd_kernel<false, false>), dim3((int)blocks), dim3(256), 0, ST(stream), gs, q, ldq, ptr,
+                       mean_rstd, gamma, beta, scale, S, D, aggr, bc, (const int*)nullptr);
+  CN_LAUNCH_CHECK(who);
+  return 0;
+}
+
+extern "C" int cartnet_att_gate_fwd(const float* gs, const float* q, int32_t ldq, const int32_t* ptr, const float* mean_rstd,
+                                    const float* gamma, const float* beta, float scale, int32_t S, int32_t D, float* aggr,
+                                    float* bc, void* stream) {
+  return att_gate_fwd("cartnet_att_gate_fwd", gs, q, ldq, ptr, mean_rstd, gamma, beta, scale, S, D, aggr, bc, nullptr, stream);
+}
+
+extern "C" int cartnet_att_gate_fwd_grouped(const float* gs, const float* q, int32_t ldq, const int32_t* ptr,
+                                            const float* mean_rstd, const float* gamma, const float* beta, float scale,
+                                            int32_t S, int32_t D, float* aggr, float* bc, const CartnetGroups* groups,
+                                            void* stream) {
+  return att_gate_fwd("cartnet_att_gate_fwd_grouped", gs, q, ldq, ptr, mean_rstd, gamma, beta, scale, S, D, aggr, bc, groups,
+                      stream);
+}
+
+static int att_gate_bwd_apply(const char* who, float* gs, const float* key, int32_t ldk, const float* q, int32_t ldq,
+                              const float* daggr, const int32_t* ptr, const float* mean_rstd, const float* gamma,
+                              const float* beta, const float* sums, int64_t count, int32_t training, float scale, int32_t S,
+                              int32_t D, float* dq, int32_t lddq, double* parts_dkey, double* parts_dmsg, double* parts_dq,
+                              const CartnetGroups* groups, void* stream) {
+  CN_CHECK(S >= 0 && D >= 4 && D % 4 == 0 && ldk % 4 == 0 && ldq % 4 == 0 && lddq % 4 == 0 && ldk >= D && ldq >= D && lddq >= D,
+           "%s: D and leading dimensions must be multiples of 4", who);
+  CN_CHECK(mean_rstd && gamma && beta && sums && parts_dkey && parts_dmsg && parts_dq &&
+               (S == 0 || (gs && q && daggr && ptr && dq)),
+           "%s: null pointer", who);
+  CN_CHECK(cn_groups_ok(groups) && (!groups || ptr), "%s: bad groups", who);
+  // (groups: a non-zero value only says "training"; the kernel takes every group's own row count from ptr)
+  const float inv = (training && count > 0) ? (float)(1.0 / (double)count) : 0.f;
+  const dim3 grid = groups ? dim3(groups->edge_parts, groups->G) : dim3(seg_parts(S));
+  const int* gp = groups ? groups->node_gptr : nullptr;
+#define CN_ATT_BWD(KIG, GR)                                                                                                  \
+  hipLaunchKernelGGL((cn_att_gate_bwd_kernel<KIG, GR>), grid, dim3(256), 0, ST(stream), gs, key, ldk, q, ldq, daggr, ptr,      \
+                     mean_rstd, gamma, beta, sums, inv, scale, S, D, dq, lddq, parts_dkey, parts_dmsg, parts_dq, gp)
+  if (key) {
+    if (groups) CN_ATT_BWD(false, true); else CN_ATT_BWD(false, false);
+  } else {
+    if (groups) CN_ATT_BWD(true, true); else CN_ATT_BWD(true, false);
+  }
+#undef CN_ATT_BWD
+  CN_LAUNCH_CHECK(who);
   return 0;
 }
 
@@ -586,32 +742,65 @@ extern "C" int cartnet_att_gate_bwd_apply(float* gs, const float* key, int32_t l
                                           const float* gamma, const float* beta, const float* sums, int64_t count,
                                           int32_t training, float scale, int32_t S, int32_t D, float* dq, int32_t lddq,
                                           double* parts_dkey, double* parts_dmsg, double* parts_dq, void* stream) {
-  CN_CHECK(S >= 0 && D >= 4 && D % 4 == 0 && ldk % 4 == 0 && ldq % 4 == 0 && lddq % 4 == 0 && ldk >= D && ldq >= D && lddq >= D,
-           "cartnet_att_gate_bwd_apply: D and leading dimensions must be multiples of 4");
-  CN_CHECK(mean_rstd && gamma && beta && sums && parts_dkey && parts_dmsg && parts_dq &&
-               (S == 0 || (gs && q && daggr && ptr && dq)),
-           "cartnet_att_gate_bwd_apply: null pointer");
-  const float inv = (training && count > 0) ? (float)(1.0 / (double)count) : 0.f;
-  if (key)
-    hipLaunchKernelGGL(cn_att_gate_bwd_kernel<false>, dim3(seg_parts(S)), dim3(256), 0, ST(stream), gs, key, ldk, q, ldq, daggr,
-                       ptr, mean_rstd, gamma, beta, sums, inv, scale, S, D, dq, lddq, parts_dkey, parts_dmsg, parts_dq);
-  else
-    hipLaunchKernelGGL(cn_att_gate_bwd_kernel<true>, dim3(seg_parts(S)), dim3(256), 0, ST(stream), gs, key, ldk, q, ldq, daggr,
-                       ptr, mean_rstd, gamma, beta, sums, inv, scale, S, D, dq, lddq, parts_dkey, parts_dmsg, parts_dq);
-  CN_LAUNCH_CHECK("cartnet_att_gate_bwd_apply");
+  return att_gate_bwd_apply("cartnet_att_gate_bwd_apply", gs, key, ldk, q, ldq, daggr, ptr, mean_rstd, gamma, beta, sums, count,
+                            training, scale, S, D, dq, lddq, parts_dkey, parts_dmsg, parts_dq, nullptr, stream);
+}
+
+extern "C" int cartnet_att_gate_bwd_apply_grouped(float* gs, const float* key, int32_t ldk, const float* q, int32_t ldq,
+                                                  const float* daggr, const int32_t* ptr, const float* mean_rstd,
+                                                  const float* gamma, const float* beta, const float* sums, int64_t count,
+                                                  int32_t training, float scale, int32_t S, int32_t D, float* dq,
+                                                  int32_t lddq, double* parts_dkey, double* parts_dmsg, double* parts_dq,
+                                                  const CartnetGroups* groups, void* stream) {
+  return att_gate_bwd_apply("cartnet_att_gate_bwd_apply_grouped", gs, key, ldk, q, ldq, daggr, ptr, mean_rstd, gamma, beta, sums,
+                            count, training, scale, S, D, dq, lddq, parts_dkey, parts_dmsg, parts_dq, groups, stream);
+}
+
+static int softplus_update_fwd(const char* who, const float* o, const float* x, const float* mean_rstd, const float* gamma,
+                               const float* beta, int64_t N, int32_t D, float* y, const CartnetGroups* groups, void* stream) {
+  CN_CHECK(N >= 0 && D >= 4 && D % 4 == 0, "%s: D=%d must be a multiple of 4", who, D);
+  if (N == 0) return 0;
+  CN_CHECK(o && x && mean_rstd && gamma && beta && y, "%s: null pointer", who);
+  CN_CHECK(cn_groups_ok(groups), "%s: bad groups", who);
+  if (groups) {
+    hipLaunchKernelGGL(cn_softplus_update_fwd_kernel<true>, dim3(groups->node_parts, groups->G), dim3(256), 0, ST(stream), o, x,
+                       mean_rstd, gamma, beta, (long long)N, D, y, groups->node_gptr);
+  } else {
+    long long blocks = (N * D / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(cn_softplus_update_fwd_kernel<false>, dim3((int)blocks), dim3(256), 0, ST(stream), o, x, mean_rstd, gamma,
+                       beta, (long long)N, D, y, (const int*)nullptr);
+  }
+  CN_LAUNCH_CHECK(who);
   return 0;
 }
 
 extern "C" int cartnet_softplus_update_fwd(const float* o, const float* x, const float* mean_rstd, const float* gamma,
                                            const float* beta, int64_t N, int32_t D, float* y, void* stream) {
-  CN_CHECK(N >= 0 && D >= 4 && D % 4 == 0, "cartnet_softplus_update_fwd: D=%d must be a multiple of 4", D);
-  if (N == 0) return 0;
-  CN_CHECK(o && x && mean_rstd && gamma && beta && y, "cartnet_softplus_update_fwd: null pointer");
-  long long blocks = (N * D / 4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(cn_softplus_update_fwd_kernel, dim3((int)blocks), dim3(256), 0, ST(stream), o, x, mean_rstd, gamma,
-                     beta, (long long)N, D, y);
-  CN_LAUNCH_CHECK("cartnet_softplus_update_fwd");
+  return softplus_update_fwd("cartnet_softplus_update_fwd", o, x, mean_rstd, gamma, beta, N, D, y, nullptr, stream);
+}
+
+extern "C" int cartnet_softplus_update_fwd_grouped(const float* o, const float* x, const float* mean_rstd, const float* gamma,
+                                                   const float* beta, int64_t N, int32_t D, float* y,
+                                                   const CartnetGroups* groups, void* stream) {
+  return softplus_update_fwd("cartnet_softplus_update_fwd_grouped", o, x, mean_rstd, gamma, beta, N, D, y, groups, stream);
+}
+
+static int softplus_update_bwd_stats(const char* who, const float* o, const float* x, const float* dy, const float* mean_rstd,
+                                     const float* gamma, const float* beta, int32_t N, int32_t D, double* parts_a,
+                                     double* parts_b, const CartnetGroups* groups, void* stream) {
+  CN_CHECK(N >= 0 && D >= 4 && D % 4 == 0, "%s: D=%d must be a multiple of 4", who, D);
+  CN_CHECK(mean_rstd && gamma && beta && parts_a && parts_b && (N == 0 || (o && x && dy)), "%s: null pointer", who);
+  CN_CHECK(cn_groups_ok(groups), "%s: bad groups", who);
+  if (groups)
+    hipLaunchKernelGGL((cn_softplus_update_bwd_kernel<0, true>), dim3(groups->node_parts, groups->G), dim3(256), 0, ST(stream), o,
+                       x, dy, mean_rstd, gamma, beta, (const float*)nullptr, 0.f, N, D, parts_a, parts_b, (float*)nullptr,
+                       (const float*)nullptr, (float*)nullptr, groups->node_gptr);
+  else
+    hipLaunchKernelGGL((cn_softplus_update_bwd_kernel<0, false>), dim3(seg_parts(N)), dim3(256), 0, ST(stream), o, x, dy,
+                       mean_rstd, gamma, beta, (const float*)nullptr, 0.f, N, D, parts_a, parts_b, (float*)nullptr,
+                       (const float*)nullptr, (float*)nullptr, (const int*)nullptr);
+  CN_LAUNCH_CHECK(who);
   return 0;
 }
 
@@ -619,26 +808,36 @@ extern "C" int cartnet_softplus_update_bwd_stats(const float* o, const float* x,
                                                  const float* mean_rstd, const float* gamma, const float* beta,
                                                  int32_t N, int32_t D, double* parts_a, double* parts_b,
                                                  void* stream) {
-  CN_CHECK(N >= 0 && D >= 4 && D % 4 == 0, "cartnet_softplus_update_bwd_stats: D=%d must be a multiple of 4", D);
-  CN_CHECK(mean_rstd && gamma && beta && parts_a && parts_b && (N == 0 || (o && x && dy)),
-           "cartnet_softplus_update_bwd_stats: null pointer");
-  hipLaunchKernelGGL(cn_softplus_update_bwd_kernel<0>, dim3(seg_parts(N)), dim3(256), 0, ST(stream), o, x, dy,
-                     mean_rstd, gamma, beta, (const float*)nullptr, 0.f, N, D, parts_a, parts_b, (float*)nullptr,
-                     (const float*)nullptr, (float*)nullptr);
-  CN_LAUNCH_CHECK("cartnet_softplus_update_bwd_stats");
-  return 0;
+  return softplus_update_bwd_stats("cartnet_softplus_update_bwd_stats", o, x, dy, mean_rstd, gamma, beta, N, D, parts_a, parts_b,
+                                   nullptr, stream);
+}
+
+extern "C" int cartnet_softplus_update_bwd_stats_grouped(const float* o, const float* x, const float* dy,
+                                                         const float* mean_rstd, const float* gamma, const float* beta,
+                                                         int32_t N, int32_t D, double* parts_a, double* parts_b,
+                                                         const CartnetGroups* groups, void* stream) {
+  return softplus_update_bwd_stats("cartnet_softplus_update_bwd_stats_grouped", o, x, dy, mean_rstd, gamma, beta, N, D, parts_a,
+                                   parts_b, groups, stream);
 }
 
 static int softplus_update_bwd_apply(const char* who, const float* o, const float* x, const float* dy,
                                      const float* mean_rstd, const float* gamma, const float* beta, const float* sums,
                                      int32_t training, int32_t N, int32_t D, float* d_o, const float* dx_add, float* dx,
-                                     double* parts_do, void* stream) {
+                                     double* parts_do, const CartnetGroups* groups, void* stream) {
   CN_CHECK(N >= 0 && D >= 4 && D % 4 == 0, "%s: D=%d must be a multiple of 4", who, D);
   if (N == 0 && !parts_do) return 0;
   CN_CHECK(mean_rstd && gamma && beta && sums && (N == 0 || (o && x && dy && d_o && dx)), "%s: null pointer", who);
+  CN_CHECK(cn_groups_ok(groups), "%s: bad groups", who);
+  // (groups: a non-zero value only says "training"; the kernel divides by every group's own row count)
   const float inv = (training && N > 0) ? (float)(1.0 / (double)N) : 0.f;
-  hipLaunchKernelGGL(cn_softplus_update_bwd_kernel<1>, dim3(seg_parts(N)), dim3(256), 0, ST(stream), o, x, dy,
-                     mean_rstd, gamma, beta, sums, inv, N, D, parts_do, (double*)nullptr, d_o, dx_add, dx);
+  if (groups)
+    hipLaunchKernelGGL((cn_softplus_update_bwd_kernel<1, true>), dim3(groups->node_parts, groups->G), dim3(256), 0, ST(stream), o,
+                       x, dy, mean_rstd, gamma, beta, sums, inv, N, D, parts_do, (double*)nullptr, d_o, dx_add, dx,
+                       groups->node_gptr);
+  else
+    hipLaunchKernelGGL((cn_softplus_update_bwd_kernel<1, false>), dim3(seg_parts(N)), dim3(256), 0, ST(stream), o, x, dy,
+                       mean_rstd, gamma, beta, sums, inv, N, D, parts_do, (double*)nullptr, d_o, dx_add, dx,
+                       (const int*)nullptr);
   CN_LAUNCH_CHECK(who);
   return 0;
 }
@@ -648,7 +847,7 @@ extern "C" int cartnet_softplus_update_bwd_apply(const float* o, const float* x,
                                                  const float* sums, int32_t training, int32_t N, int32_t D, float* d_o,
                                                  const float* dx_add, float* dx, void* stream) {
   return softplus_update_bwd_apply("cartnet_softplus_update_bwd_apply", o, x, dy, mean_rstd, gamma, beta, sums, training, N, D,
-                                   d_o, dx_add, dx, nullptr, stream);
+                                   d_o, dx_add, dx, nullptr, nullptr, stream);
 }
 
 // ... leaving the fp64 column partials of d_o too (cartnet_segment_nparts(N) rows of D -> cartnet_colsum_finalize)
@@ -659,7 +858,17 @@ extern "C" int cartnet_softplus_update_bwd_apply_sums(const float* o, const floa
                                                       void* stream) {
   CN_CHECK(parts_do, "cartnet_softplus_update_bwd_apply_sums: null pointer");
   return softplus_update_bwd_apply("cartnet_softplus_update_bwd_apply_sums", o, x, dy, mean_rstd, gamma, beta, sums, training,
-                                   N, D, d_o, dx_add, dx, parts_do, stream);
+                                   N, D, d_o, dx_add, dx, parts_do, nullptr, stream);
+}
+
+// both of the above with groups: parts_do may be NULL (apply) or [G * node_parts][D] (apply_sums)
+extern "C" int cartnet_softplus_update_bwd_apply_grouped(const float* o, const float* x, const float* dy,
+                                                         const float* mean_rstd, const float* gamma, const float* beta,
+                                                         const float* sums, int32_t training, int32_t N, int32_t D,
+                                                         float* d_o, const float* dx_add, float* dx, double* parts_do,
+                                                         const CartnetGroups* groups, void* stream) {
+  return softplus_update_bwd_apply("cartnet_softplus_update_bwd_apply_grouped", o, x, dy, mean_rstd, gamma, beta, sums, training,
+                                   N, D, d_o, dx_add, dx, parts_do, groups, stream);
 }
 
 // out = a * sigmoid(b) over [R, C] views + the fp64 column partials of out (cartnet_segment_nparts(R) rows of C)
@@ -676,14 +885,29 @@ extern "C" int cartnet_softplus_bwd_sums(const float* a, int32_t lda, const floa
 
 extern "C" int cartnet_segment_nparts(int32_t S) { return seg_parts(S); }
 
+static int coldot_bc_partial(const char* who, const float* d, int32_t ld, const float* bc, int32_t R, int32_t C, double* parts_a,
+                             double* parts_b, const CartnetGroups* groups, void* stream) {
+  CN_CHECK(R >= 0 && C >= 4 && C % 4 == 0 && ld % 4 == 0 && ld >= C, "%s: C/ld must be multiples of 4", who);
+  CN_CHECK(((d && bc) || R == 0) && parts_a && parts_b, "%s: null pointer", who);
+  CN_CHECK(cn_groups_ok(groups), "%s: bad groups", who);
+  if (groups)
+    hipLaunchKernelGGL(cn_coldot_bc_partial_kernel<true>, dim3(groups->edge_parts, groups->G), dim3(256), 0, ST(stream), d, ld,
+                       bc, R, C, parts_a, parts_b, groups->node_gptr);
+  else
+    hipLaunchKernelGGL(cn_coldot_bc_partial_kernel<false>, dim3(seg_parts(R)), dim3(256), 0, ST(stream), d, ld, bc, R, C, parts_a,
+                       parts_b, (const int*)nullptr);
+  CN_LAUNCH_CHECK(who);
+  return 0;
+}
+
 extern "C" int cartnet_coldot_bc_partial(const float* d, int32_t ld, const float* bc, int32_t R, int32_t C, double* parts_a,
                                          double* parts_b, void* stream) {
-  CN_CHECK(R >= 0 && C >= 4 && C % 4 == 0 && ld % 4 == 0 && ld >= C, "cartnet_coldot_bc_partial: C/ld must be multiples of 4");
-  CN_CHECK(((d && bc) || R == 0) && parts_a && parts_b, "cartnet_coldot_bc_partial: null pointer");
-  hipLaunchKernelGGL(cn_coldot_bc_partial_kernel, dim3(seg_parts(R)), dim3(256), 0, ST(stream), d, ld, bc, R, C, parts_a,
-                     parts_b);
-  CN_LAUNCH_CHECK("cartnet_coldot_bc_partial");
-  return 0;
+  return coldot_bc_partial("cartnet_coldot_bc_partial", d, ld, bc, R, C, parts_a, parts_b, nullptr, stream);
+}
+
+extern "C" int cartnet_coldot_bc_partial_grouped(const float* d, int32_t ld, const float* bc, int32_t R, int32_t C,
+                                                 double* parts_a, double* parts_b, const CartnetGroups* groups, void* stream) {
+  return coldot_bc_partial("cartnet_coldot_bc_partial_grouped", d, ld, bc, R, C, parts_a, parts_b, groups, stream);
 }
 
 extern "C" int cartnet_colsum_partial(const float* x, int32_t ld, int32_t R, int32_t C, double* parts, void* stream) {

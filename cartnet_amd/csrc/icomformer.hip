@@ -47,6 +47,13 @@ __global__ void cn_icf_index_kernel(const int* __restrict__ src32, const int64_t
   for (long long g = i0; g <= Bg; g += stride) gedge_ptr[g] = rowptr[(int)graph_ptr[g]];
 }
 
+// BatchNorm groups of the edge layer: its segments are the edges (group g owns [edge_gptr[g], edge_gptr[g + 1]), the first
+// descriptor's edge ranges) and its rows the (edge, lattice vector) pairs, three per edge: rows_gptr[g] = 3 edge_gptr[g]
+__global__ void cn_icf_group3_kernel(const int* __restrict__ edge_gptr, int G, int* __restrict__ rows_gptr) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g <= G) rows_gptr[g] = 3 * edge_gptr[g];
+}
+
 // out[i, t] += u[i] * v[t]  (C x C block with row stride ldo): the bias part of dW1e = dF We^T + db be^T; blockIdx.y picks
 // the (out, u) pair: key / msg in one launch
 __global__ void cn_icf_rank1_kernel(float* __restrict__ out0, float* __restrict__ out1, int ldo, const float* __restrict__ u0,
@@ -155,6 +162,12 @@ struct IWork {
   float *slabs;
   size_t slab_floats;
   int tiles_3e, tiles_e, tiles_n, nparts_n, gp_n, gp_e, sp_n, sp_e, sp_3e;
+  // BatchNorm groups (CartnetIcfModel.bn_group_size > 0 and more than one group in this batch; training mode only):
+  // grp for the conv layers (segments = atoms, rows = edges), grp_e for the edge layer (segments = edges, rows = 3E)
+  int G;
+  int *node_gptr, *edge_gptr, *edge3_gptr;
+  CartnetGroups grp, grp_e;
+  const CartnetGroups *groups, *groups_e;      // &grp / &grp_e, or nullptr for one group (set by the entry points)
 };
 
 size_t img_bytes(int prec, int K, int N) {
@@ -172,6 +185,21 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
   w.nparts_n = cartnet_node_nparts(N);
   w.gp_n = cartnet_gate_scatter_nparts(N); w.gp_e = cartnet_gate_scatter_nparts((int)E);
   w.sp_n = cartnet_segment_nparts(N); w.sp_e = cartnet_segment_nparts((int)E); w.sp_3e = cartnet_segment_nparts((int)(3 * E));
+  // groups as model.hip's carve deals them: ceil(segments / G / segments-per-workgroup) workgroups per group (the edge
+  // layer's 3-row segments: at most 256, G x 256 workgroups cover the chip several times over)
+  w.G = (m.bn_group_size > 0 && Bg > m.bn_group_size) ? (Bg + m.bn_group_size - 1) / m.bn_group_size : 1;
+  size_t grows = 0;      // partial rows of the grouped kernels
+  if (w.G > 1) {
+    auto parts = [&](size_t segs, int cap) {
+      const size_t per = (segs + (size_t)4 * w.G - 1) / ((size_t)4 * w.G);
+      return (int)(per < 1 ? 1 : (per > (size_t)cap ? cap : per));
+    };
+    w.grp.G = w.grp_e.G = w.G;
+    w.grp.edge_parts = parts(Nn, 1024); w.grp.node_parts = parts(Nn, 256);
+    w.grp_e.edge_parts = w.grp_e.node_parts = parts(En, 256);
+    grows = (size_t)w.G * std::max(w.grp.edge_parts, w.grp_e.edge_parts);
+  }
+  const size_t Gn = (size_t)w.G;
   w.src32 = c.take<int>(En); w.tgt32 = c.take<int>(En); w.rowptr = c.take<int>(Nn + 1); w.colptr = c.take<int>(Nn + 1);
   w.perm = c.take<int>(En); w.idx = c.take<int>(Nn); w.idx_edge = c.take<int>(E3); w.idx_gl = c.take<int>(E3);
   w.ptr3 = c.take<int>(En + 1); w.gedge_ptr = c.take<int>((size_t)Bg + 1);
@@ -199,8 +227,8 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
     // per-segment sums for the backward BatchNorm sums (conv layers; with the alpha-free forward the edge layer too: its
     // statistics pass would need alpha, and 363 MB written + 544 MB read there replace a 1.09 GB pass)
     w.bc[l] = (edge && !icf_alpha_free(C)) ? nullptr : c.take<float>(S * 2 * C);
-    w.mr1[l] = c.take<float>(2 * C); w.aggr[l] = c.take<float>(S * C); w.o[l] = c.take<float>(S * C);
-    w.mr2[l] = c.take<float>(2 * C);
+    w.mr1[l] = c.take<float>(Gn * 2 * C); w.aggr[l] = c.take<float>(S * C); w.o[l] = c.take<float>(S * C);
+    w.mr2[l] = c.take<float>(Gn * 2 * C);
     w.y[l] = (l == 3) ? nullptr : c.take<float>(S * C);     // layer 3 writes the caller's x_out
   }
   w.KY = c.take<float>(B3 * C); w.VY = c.take<float>(B3 * C); w.Ka = c.take<float>(En * 2 * C);
@@ -227,7 +255,7 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
   }
   // statistics scratch: fp64 partial rows.  The largest producers: GEMM epilogues over 3E rows (tiles_3e rows), the
   // gate / segment kernels (<= 1024 rows)
-  const size_t prow = (size_t)std::max(std::max(w.tiles_3e, 1024), w.nparts_n) * C;
+  const size_t prow = std::max((size_t)std::max(std::max(w.tiles_3e, 1024), w.nparts_n), grows) * C;
   w.pa = c.take<double>(prow); w.pb = c.take<double>(prow); w.pc = c.take<double>(prow); w.pd = c.take<double>(prow);
   w.cs = c.take<double>(prow); w.cq = c.take<double>(prow); w.cs_side = c.take<double>(prow);
   // backward
@@ -239,7 +267,7 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
     const size_t S = edge ? En : Nn, R = edge ? E3 : En;
     w.d_o[l] = c.take<float>(S * C); w.dres[l] = c.take<float>(S * C); w.daggr[l] = c.take<float>(S * C);
     w.dQKV[l] = c.take<float>(S * 3 * C); w.dpr[l] = c.take<float>(R * 2 * C);
-    w.sums1[l] = c.take<float>(2 * C); w.sums2[l] = c.take<float>(2 * C);
+    w.sums1[l] = c.take<float>(Gn * 2 * C); w.sums2[l] = c.take<float>(Gn * 2 * C);
     if (!edge) {
       w.de[l] = c.take<float>(En * C);
       w.dKP[l] = c.take<float>(Nn * 4 * C); w.dx[l] = c.take<float>(Nn * C);
@@ -259,6 +287,9 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
   slab(4, N, C, C); slab(1, N, C, C); slab(1, N, H, C); slab(2, Bg * 3, C, C); slab(1, Bg, C, C); slab(1, Bg * 3, C, C);
   w.slab_floats = sl;
   w.slabs = c.take<float>(sl > 0 ? sl : 1);
+  w.node_gptr = c.take<int>(Gn + 1); w.edge_gptr = c.take<int>(Gn + 1); w.edge3_gptr = c.take<int>(Gn + 1);
+  w.grp.node_gptr = w.node_gptr; w.grp.edge_gptr = w.edge_gptr;
+  w.grp_e.node_gptr = w.edge_gptr; w.grp_e.edge_gptr = w.edge3_gptr;
   if (total) *total = align_up(c.off);
   return w;
 }
@@ -404,6 +435,7 @@ struct Att {
   long long count;                // rows the bn_att statistics divide by
   int gparts, sparts;             // partial rows of the gate / segment kernels over S segments
   int grows;                      // upper bound of the rows of term_i / term_j
+  const CartnetGroups* groups;    // BatchNorm groups over the segments, or nullptr
 };
 
 int att_forward(const CartnetIcfModel& m, const CartnetIcfConv& P, const CartnetIcfBn& bn_att, const ConvW& cw, const Att& t,
@@ -431,19 +463,20 @@ int att_forward(const CartnetIcfModel& m, const CartnetIcfConv& P, const Cartnet
     RUN(cartnet_gemm(&a, st));
   }
   const float scale = 1.0f / sqrtf((float)C);
-  RUN(cartnet_rowmul_fwd(afree ? w.gs[l] : w.keyb[l], 2 * C, t.q, t.ldq, t.segptr, t.S, C, scale, afree ? nullptr : w.gs[l],
-                         2 * C, w.pa, w.pb, st));
+  // (t.groups: [G][edge_parts][C] partial rows, one statistics row and one running-statistics update per group)
+  RUN(cartnet_rowmul_fwd_grouped(afree ? w.gs[l] : w.keyb[l], 2 * C, t.q, t.ldq, t.segptr, t.S, C, scale,
+                                 afree ? nullptr : w.gs[l], 2 * C, w.pa, w.pb, t.groups, st));
   RUN(cartnet_bn_finalize(w.pa, w.pb, t.sparts, t.count, C, m.bn_eps, m.bn_momentum, training, bn_att.mean, bn_att.var,
-                          bn_att.nbt, w.mr1[l], nullptr, 1, 1, st));
+                          bn_att.nbt, w.mr1[l], t.groups, 1, 1, st));
   if (afree)
-    RUN(cartnet_att_gate_fwd(w.gs[l], t.q, t.ldq, t.segptr, w.mr1[l], P.bn_att_w, P.bn_att_b, scale, t.S, C, w.aggr[l],
-                             w.bc[l], st));     // (in eval mode too: the sums identity does not depend on the mode)
-  else if (training && w.bc[l])
+    RUN(cartnet_att_gate_fwd_grouped(w.gs[l], t.q, t.ldq, t.segptr, w.mr1[l], P.bn_att_w, P.bn_att_b, scale, t.S, C,
+                                     w.aggr[l], w.bc[l], t.groups, st));     // (in eval mode too: the sums identity does not depend on the mode)
+  else if (training && w.bc[l] && !t.groups)     // (the per-target sums of this kernel: one BatchNorm group only)
     RUN(cartnet_gate_scatter_fwd_bc(w.gs[l], nullptr, nullptr, t.segptr, w.mr1[l], P.bn_att_w, P.bn_att_b, t.S, C, nullptr,
                                     w.aggr[l], w.pc, w.pd, w.bc[l], st));
   else
     RUN(cartnet_gate_scatter_fwd(w.gs[l], nullptr, nullptr, t.segptr, w.mr1[l], P.bn_att_w, P.bn_att_b, t.S, C, nullptr,
-                                 w.aggr[l], w.pc, w.pd, nullptr, st));
+                                 w.aggr[l], w.pc, w.pd, t.groups, st));
   return 0;
 }
 }  // namespace
@@ -504,6 +537,15 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
 
   // ---- graph layout, embeddings, lattice features (comformer.py:116-124)
   RUN(cartnet_csr_build(b.edge_index, b.E, N, b.graph_ptr, Bg, w.src32, w.tgt32, w.rowptr, w.colptr, w.perm, status, st));
+  // BatchNorm groups: training mode only (eval mode normalises every row with the running statistics)
+  w.groups = (training && w.G > 1) ? &w.grp : nullptr;
+  w.groups_e = w.groups ? &w.grp_e : nullptr;
+  if (w.groups) {
+    RUN(cartnet_group_ptrs(b.graph_ptr, Bg, m.bn_group_size, w.rowptr, w.G, w.node_gptr, w.edge_gptr, st));
+    hipLaunchKernelGGL(cn_icf_group3_kernel, dim3((w.G + 256) / 256), dim3(256), 0, (hipStream_t)st, w.edge_gptr, w.G,
+                       w.edge3_gptr);
+    CN_LAUNCH_CHECK("cartnet_icomformer_forward (group rows of the edge layer)");
+  }
   RUN(cartnet_node_embed(b.z, b.batch, b.temperature, P.embedding, P.temp_w, P.temp_b, nullptr, N, C, m.n_types, Bg,
                          status, w.x0, st));
   RUN(cartnet_lattice_features(cell, b.batch, w.src32, b.cart_dist, b.cart_dir, b.E, Bg, w.edge_feat, w.nl, w.nc, st));
@@ -556,18 +598,21 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
       a.bias[0] = q.key0_b; a.bias[1] = q.msg0_b;
       RUN(cartnet_gemm(&a, st));
     }
-    Att t{E, N, w.rowptr, w.tgt32, w.src32, w.KPi[l], w.KPj[l], w.QKV[l], 3 * C, (long long)b.E, w.gp_n, w.sp_n, N};
+    Att t{E, N, w.rowptr, w.tgt32, w.src32, w.KPi[l], w.KPj[l], w.QKV[l], 3 * C, (long long)b.E, w.gp_n, w.sp_n, N, w.groups};
     RUN(att_forward(m, q, m.att_bn_att[l], cw, t, l, e, w, training, st));
     {  // o = lin_concate(aggr) with the BatchNorm statistics over atoms
       CartnetGemmArgs a = gargs(prec, N, C, C, C, C, C);
       fwd_form(a, cw, F_CAT, C, w.use_img);
       a.A[0] = w.aggr[l]; a.C[0] = w.o[l]; a.bias[0] = q.concate_b; fwd_operand(a, 0, cw, F_CAT, w.use_img);
-      a.colsum[0] = w.cs; a.colsq[0] = w.cq;
+      if (!w.groups) { a.colsum[0] = w.cs; a.colsq[0] = w.cq; }
       RUN(cartnet_gemm(&a, st));
     }
+    // BatchNorm groups: a 128-row tile of the product may straddle two groups, so the statistics come from a pass over
+    // every group's atoms (as CartNet's gate pre-activation, model.hip)
+    if (w.groups) RUN(cartnet_colstats_grouped_nodes(w.o[l], C, C, w.groups, w.cs, w.cq, st));
     RUN(cartnet_bn_finalize(w.cs, w.cq, w.tiles_n, N, C, m.bn_eps, m.bn_momentum, training, m.att_bn[l].mean,
-                            m.att_bn[l].var, m.att_bn[l].nbt, w.mr2[l], nullptr, 1, 0, st));
-    return cartnet_softplus_update_fwd(w.o[l], x, w.mr2[l], q.bn_w, q.bn_b, N, C, y, st);
+                            m.att_bn[l].var, m.att_bn[l].nbt, w.mr2[l], w.groups, 0, 0, st));
+    return cartnet_softplus_update_fwd_grouped(w.o[l], x, w.mr2[l], q.bn_w, q.bn_b, N, C, y, w.groups, st);
   };
 
   // ---- ComformerConv_edge (comformer_conv.py:156-193) on rows r = 3 e + lattice vector
@@ -605,19 +650,21 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
       a.A[0] = w.KY; a.A[1] = w.VY; a.B[0] = q.key0_w + C; a.B[1] = q.msg0_w + C; a.C[0] = w.KYb; a.C[1] = w.KYb + C;
       RUN(cartnet_gemm(&a, st));
     }
-    Att t{3 * E, E, w.ptr3, w.idx_edge, w.idx_gl, w.Ka, w.KYb, w.QKV[l], 3 * C, 3LL * b.E, w.gp_e, w.sp_e, E > 3 * Bg ? E : 3 * Bg};
+    Att t{3 * E, E, w.ptr3, w.idx_edge, w.idx_gl, w.Ka, w.KYb, w.QKV[l], 3 * C, 3LL * b.E, w.gp_e, w.sp_e, E > 3 * Bg ? E : 3 * Bg,
+          w.groups_e};
     RUN(att_forward(m, q, m.edge_bn_att, cw, t, l, w.NA, w, training, st));
     RUN(cartnet_eltwise(3, q.concate_b, nullptr, w.bias3, 1, C, C, 0, C, 3.0f, st));
     {
       CartnetGemmArgs a = gargs(prec, E, C, C, C, C, C);
       fwd_form(a, cw, F_CAT, C, w.use_img);
       a.A[0] = w.aggr[l]; a.C[0] = w.o[l]; a.bias[0] = w.bias3; fwd_operand(a, 0, cw, F_CAT, w.use_img);
-      a.colsum[0] = w.cs; a.colsq[0] = w.cq;
+      if (!w.groups_e) { a.colsum[0] = w.cs; a.colsq[0] = w.cq; }
       RUN(cartnet_gemm(&a, st));
     }
+    if (w.groups_e) RUN(cartnet_colstats_grouped_nodes(w.o[l], C, C, w.groups_e, w.cs, w.cq, st));     // over every group's edges
     RUN(cartnet_bn_finalize(w.cs, w.cq, w.tiles_e, b.E, C, m.bn_eps, m.bn_momentum, training, m.edge_bn.mean, m.edge_bn.var,
-                            m.edge_bn.nbt, w.mr2[l], nullptr, 1, 0, st));
-    return cartnet_softplus_update_fwd(w.o[l], e, w.mr2[l], q.bn_w, q.bn_b, E, C, y, st);
+                            m.edge_bn.nbt, w.mr2[l], w.groups_e, 0, 0, st));
+    return cartnet_softplus_update_fwd_grouped(w.o[l], e, w.mr2[l], q.bn_w, q.bn_b, E, C, y, w.groups_e, st);
   };
 
   RUN(conv(0, w.x0, w.e0, w.y[0]));
@@ -652,6 +699,8 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   size_t need = 0;
   IWork w = icarve(m, b.N, b.E, b.Bg, b.M, static_cast<char*>(workspace), &need);
   CN_CHECK(workspace_bytes >= need, "cartnet_icomformer_backward: workspace %zu < required %zu bytes", workspace_bytes, need);
+  w.groups = (training && w.G > 1) ? &w.grp : nullptr;      // node_gptr / edge_gptr / edge3_gptr were filled by the forward call
+  w.groups_e = w.groups ? &w.grp_e : nullptr;
   const int C = m.C, H = C / 2, N = b.N, Bg = b.Bg, prec = m.gemm_precision;
   const int E = (int)b.E;
   for (int l = 0; l < 5; ++l) {        // the views (the forms themselves were built by forward and are still in the workspace)
@@ -700,23 +749,29 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   //  writes out of its epilogue; they were 34 cartnet_colsum_partial passes per step, 1.5 ms of the main stream's work)
   const bool bias_fuse = C <= 256;
   const bool rbf_fuse = bias_fuse;
+  // (grp: the BatchNorm groups over these rows -- per-group sums [G][2C] for the apply pass, their total = the affine
+  //  gradients; lin_concate's bias gradient is the sum over all G x node_parts partial rows)
   auto softplus_bwd = [&](int l, const CartnetIcfConv& q, const CartnetIcfConv& g, const float* dy, int rows,
-                          const float* x_in, float* concate_b) -> int {
-    RUN(cartnet_softplus_update_bwd_stats(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, rows, C, w.pa, w.pb, st));
-    double* parts[2] = {w.pa, w.pb};
-    float* outs[2] = {w.sums2[l], w.sums2[l] + C};
-    float* gr[2] = {g.bn_b, g.bn_w};
-    RUN(cartnet_colsum_finalize2(parts, outs, gr, 2, cartnet_segment_nparts(rows), C, st));
+                          const float* x_in, float* concate_b, const CartnetGroups* grp) -> int {
+    RUN(cartnet_softplus_update_bwd_stats_grouped(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, rows, C, w.pa, w.pb, grp, st));
+    if (grp) {
+      RUN(cartnet_group_sums_finalize(w.pa, w.pb, C, grp, 0, w.sums2[l], g.bn_b, g.bn_w, st));
+    } else {
+      double* parts[2] = {w.pa, w.pb};
+      float* outs[2] = {w.sums2[l], w.sums2[l] + C};
+      float* gr[2] = {g.bn_b, g.bn_w};
+      RUN(cartnet_colsum_finalize2(parts, outs, gr, 2, cartnet_segment_nparts(rows), C, st));
+    }
     if (!bias_fuse) {
-      RUN(cartnet_softplus_update_bwd_apply(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, w.sums2[l], training, rows, C,
-                                            w.d_o[l], nullptr, w.dres[l], st));
+      RUN(cartnet_softplus_update_bwd_apply_grouped(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, w.sums2[l], training, rows, C,
+                                                    w.d_o[l], nullptr, w.dres[l], nullptr, grp, st));
       return colsum(w.d_o[l], C, rows, C, w.pa, concate_b, st);
     }
-    RUN(cartnet_softplus_update_bwd_apply_sums(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, w.sums2[l], training, rows, C,
-                                               w.d_o[l], nullptr, w.dres[l], w.pa, st));
+    RUN(cartnet_softplus_update_bwd_apply_grouped(w.o[l], x_in, dy, w.mr2[l], q.bn_w, q.bn_b, w.sums2[l], training, rows, C,
+                                                  w.d_o[l], nullptr, w.dres[l], w.pa, grp, st));
     double* bp[1] = {w.pa};
     float* bo[1] = {concate_b};
-    return cartnet_colsum_finalize(bp, bo, 1, cartnet_segment_nparts(rows), C, st);
+    return cartnet_colsum_finalize(bp, bo, 1, grp ? grp->G * grp->node_parts : cartnet_segment_nparts(rows), C, st);
   };
 
   // backward of the attention block: consumes gs[l]; leaves dpr[l] (gradient at the first Linears' pre-activation,
@@ -727,13 +782,18 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     float* gs = w.gs[l];
     // sum(dbn), sum(dbn ghat): no edge residual here, so with the per-target sums of the forward pass (conv layers) both
     // are sums over the TARGETS -- 25 MB instead of a 363 MB pass over gs
-    const bool fused_sums = w.bc[l] != nullptr && (training || icf_alpha_free(C));
+    // (BatchNorm groups without the alpha-free forward: cartnet_gate_scatter_fwd left no per-target sums)
+    const CartnetGroups* grp = t.groups;
+    const int grp_rows = grp ? grp->G * grp->edge_parts : 0;      // partial rows of the grouped segment kernels
+    const bool fused_sums = w.bc[l] != nullptr && (training || icf_alpha_free(C)) && (!grp || icf_alpha_free(C));
     if (fused_sums)
-      RUN(cartnet_coldot_bc_partial(daggr, C, w.bc[l], t.S, C, w.pa, w.pb, st));
+      RUN(cartnet_coldot_bc_partial_grouped(daggr, C, w.bc[l], t.S, C, w.pa, w.pb, grp, st));
     else
       RUN(cartnet_gate_scatter_bwd_stats(gs, nullptr, daggr, nullptr, t.segptr, w.mr1[l], q.bn_att_w, q.bn_att_b, t.S, C, w.pa,
-                                         w.pb, nullptr, st));
-    {
+                                         w.pb, grp, st));
+    if (grp) {     // per-group sums for the apply pass, their total = the BatchNorm affine gradients
+      RUN(cartnet_group_sums_finalize(w.pa, w.pb, C, grp, 1, w.sums1[l], g.bn_att_b, g.bn_att_w, st));
+    } else {
       double* parts[2] = {w.pa, w.pb};
       float* outs[2] = {w.sums1[l], w.sums1[l] + C};
       float* gr[2] = {g.bn_att_b, g.bn_att_w};
@@ -744,18 +804,19 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     CN_CHECK(gate_rowmul || !icf_alpha_free(C), "cartnet_icomformer_backward: the alpha-free forward needs the fused gate backward");
     if (gate_rowmul) {
       // gate backward + query x key backward + the three bias gradients in one pass: gs = [dkey | dmsg], dq
-      RUN(cartnet_att_gate_bwd_apply(gs, icf_alpha_free(C) ? nullptr : w.keyb[l], 2 * C, t.q, t.ldq, daggr, t.segptr, w.mr1[l], q.bn_att_w, q.bn_att_b,
-                                     w.sums1[l], t.count, training, scale, t.S, C, dq_out, 3 * C, w.pa, w.pd, w.pb, st));
+      RUN(cartnet_att_gate_bwd_apply_grouped(gs, icf_alpha_free(C) ? nullptr : w.keyb[l], 2 * C, t.q, t.ldq, daggr, t.segptr,
+                                             w.mr1[l], q.bn_att_w, q.bn_att_b, w.sums1[l], t.count, training, scale, t.S, C,
+                                             dq_out, 3 * C, w.pa, w.pd, w.pb, grp, st));
       double* parts[3] = {w.pa, w.pd, w.pb};
       float* outs[3] = {g.key2_b, g.msg2_b, g.query_b};
-      RUN(cartnet_colsum_finalize(parts, outs, 3, cartnet_segment_nparts(t.S), C, st));
+      RUN(cartnet_colsum_finalize(parts, outs, 3, grp ? grp_rows : cartnet_segment_nparts(t.S), C, st));
     } else {
       RUN(cartnet_gate_scatter_bwd_apply(gs, nullptr, daggr, nullptr, t.segptr, w.mr1[l], q.bn_att_w, q.bn_att_b, w.sums1[l],
-                                         t.count, training, t.S, C, w.pc, w.pd, nullptr, st));     // gs = [dalpha | dmsg]
+                                         t.count, training, t.S, C, w.pc, w.pd, grp, st));     // gs = [dalpha | dmsg]
       {
         double* parts[1] = {w.pd};
         float* outs[1] = {g.msg2_b};
-        RUN(cartnet_colsum_finalize(parts, outs, 1, t.gparts, C, st));
+        RUN(cartnet_colsum_finalize(parts, outs, 1, grp ? grp_rows : t.gparts, C, st));
       }
       if (bias_fuse) {    // gs = [dkey | dmsg]; key_update.2's and lin_query's bias gradients from the same pass
         RUN(cartnet_rowmul_bwd_sums(gs, 2 * C, w.keyb[l], 2 * C, t.q, t.ldq, t.segptr, t.S, C, scale, dq_out, 3 * C, w.pa, w.pb, st));
@@ -867,10 +928,10 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     const ConvW& cw = w.cw[l];
     const float* x_in = l == 0 ? w.x0 : w.y[l - 1];
     const float* e_in = l == 0 ? w.e0 : w.y[4];
-    RUN(softplus_bwd(l, q, g, dy, N, x_in, g.concate_b));
+    RUN(softplus_bwd(l, q, g, dy, N, x_in, g.concate_b, w.groups));
     RUN(wg({w.d_o[l]}, C, {w.aggr[l]}, C, {g.concate_w}, C, N, C, C));
     RUN(dgemm(w.d_o[l], C, q.concate_w, C, w.use_img ? cw.B[B_CAT] : nullptr, w.daggr[l], C, N, C, C, nullptr, 0, st));
-    Att t{E, N, w.rowptr, w.tgt32, w.src32, w.KPi[l], w.KPj[l], w.QKV[l], 3 * C, (long long)b.E, w.gp_n, w.sp_n, N};
+    Att t{E, N, w.rowptr, w.tgt32, w.src32, w.KPi[l], w.KPj[l], w.QKV[l], 3 * C, (long long)b.E, w.gp_n, w.sp_n, N, w.groups};
     RUN(att_backward(l, q, g, t, w.daggr[l], w.dQKV[l]));
     float* dpr = w.dpr[l];
     // lin_edge (folded into the row block): nothing on the chain of atom gradients reads de before the edge layer's
@@ -923,11 +984,12 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     const CartnetIcfConv& q = P.edge;
     const CartnetIcfConv& g = G.edge;
     const ConvW& cw = w.cw[l];
-    RUN(softplus_bwd(l, q, g, dy, E, w.e0, w.tmpb));
+    RUN(softplus_bwd(l, q, g, dy, E, w.e0, w.tmpb, w.groups_e));
     RUN(cartnet_eltwise(3, w.tmpb, nullptr, g.concate_b, 1, C, C, 0, C, 3.0f, st));     // the bias entered three times
     RUN(wg({w.d_o[l]}, C, {w.aggr[l]}, C, {g.concate_w}, C, b.E, C, C));
     RUN(dgemm(w.d_o[l], C, q.concate_w, C, w.use_img ? cw.B[B_CAT] : nullptr, w.daggr[l], C, b.E, C, C, nullptr, 0, st));
-    Att t{3 * E, E, w.ptr3, w.idx_edge, w.idx_gl, w.Ka, w.KYb, w.QKV[l], 3 * C, 3LL * b.E, w.gp_e, w.sp_e, E > 3 * Bg ? E : 3 * Bg};
+    Att t{3 * E, E, w.ptr3, w.idx_edge, w.idx_gl, w.Ka, w.KYb, w.QKV[l], 3 * C, 3LL * b.E, w.gp_e, w.sp_e, E > 3 * Bg ? E : 3 * Bg,
+          w.groups_e};
     RUN(att_backward(l, q, g, t, w.daggr[l], w.dQKV[l]));
     float* dpr = w.dpr[l];
     // angle branch (lin_edge folded, no bias): only the RBF backward at the very end reads dNA

@@ -752,6 +752,19 @@ extern "C" int cartnet_colstats_grouped(const float* x, int32_t ld, int32_t C, c
   return 0;
 }
 
+// The same statistics over the groups' NODE ranges ([G][node_parts][C]): iComformer's lin_concate output, one row per
+// segment of the attention block
+extern "C" int cartnet_colstats_grouped_nodes(const float* x, int32_t ld, int32_t C, const CartnetGroups* groups,
+                                              double* parts_sum, double* parts_sq, void* stream) {
+  CN_CHECK(groups && cn_groups_ok(groups), "cartnet_colstats_grouped_nodes: groups required");
+  CN_CHECK(C >= 4 && C % 4 == 0 && ld % 4 == 0 && ld >= C, "cartnet_colstats_grouped_nodes: C=%d ld=%d must be multiples of 4", C, ld);
+  CN_CHECK(x && parts_sum && parts_sq, "cartnet_colstats_grouped_nodes: null pointer");
+  hipLaunchKernelGGL(cn_colstats_grouped_kernel, dim3(groups->node_parts, groups->G), dim3(256), 0, ST(stream), x, ld, C,
+                     groups->node_gptr, parts_sum, parts_sq);
+  CN_LAUNCH_CHECK("cartnet_colstats_grouped_nodes");
+  return 0;
+}
+
 extern "C" int cartnet_group_sums_finalize(double* parts_a, double* parts_b, int32_t D, const CartnetGroups* groups,
                                            int32_t over_edges, float* sums, float* grad_a, float* grad_b,
                                            void* stream) {

@@ -149,7 +149,7 @@ class IcfParams(C.Structure):
 
 
 class IcfModel(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("C", "n_types", "gemm_precision", "reserved")] + \
+    _fields_ = [(n, C.c_int32) for n in ("C", "n_types", "gemm_precision", "bn_group_size")] + \
                [(n, C.c_float) for n in ("gamma_rbf", "gamma_angle", "bn_eps", "bn_momentum")] + \
                [("rbf_centers", C.c_void_p), ("rbf_angle_centers", C.c_void_p), ("p", IcfParams),
                 ("att_bn", IcfBn * 4), ("att_bn_att", IcfBn * 4), ("edge_bn", IcfBn), ("edge_bn_att", IcfBn)]
@@ -236,6 +236,24 @@ PROTOTYPES = {
     "cartnet_bn_sync_scale": (C.c_int, [c_f32p, C.c_int32, C.c_int64, c_f32p, c_stream]),
     "cartnet_group_ptrs": (C.c_int, [c_i64p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p, c_stream]),
     "cartnet_colstats_grouped": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_groups, c_f32p, c_f32p, c_stream]),
+    "cartnet_colstats_grouped_nodes": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_groups, c_f32p, c_f32p, c_stream]),
+    "cartnet_rowmul_fwd_grouped": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_float,
+                                             c_f32p, C.c_int32, c_f32p, c_f32p, c_groups, c_stream]),
+    "cartnet_att_gate_fwd_grouped": (C.c_int, [c_f32p, c_f32p, C.c_int32, c_i32p, c_f32p, c_f32p, c_f32p, C.c_float,
+                                               C.c_int32, C.c_int32, c_f32p, c_f32p, c_groups, c_stream]),
+    "cartnet_att_gate_bwd_apply_grouped": (C.c_int, [c_f32p, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_i32p, c_f32p,
+                                                     c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                                     C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p, c_groups,
+                                                     c_stream]),
+    "cartnet_coldot_bc_partial_grouped": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_f32p, c_f32p,
+                                                    c_groups, c_stream]),
+    "cartnet_softplus_update_fwd_grouped": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p,
+                                                      c_groups, c_stream]),
+    "cartnet_softplus_update_bwd_stats_grouped": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32,
+                                                            C.c_int32, c_f32p, c_f32p, c_groups, c_stream]),
+    "cartnet_softplus_update_bwd_apply_grouped": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                            C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p,
+                                                            c_f32p, c_groups, c_stream]),
     "cartnet_group_sums_finalize": (C.c_int, [c_f32p, c_f32p, C.c_int32, c_groups, C.c_int32, c_f32p, c_f32p, c_f32p,
                                               c_stream]),
     "cartnet_gate_scatter_nparts": (C.c_int, [C.c_int32]),

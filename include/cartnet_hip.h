@@ -579,6 +579,47 @@ int cartnet_bn_finalize(double* parts_sum, double* parts_sq, int32_t nparts, int
                         int64_t* num_batches_tracked, float* mean_rstd, const CartnetGroups* groups,
                         int32_t parts_over_edges, int32_t count_over_edges, void* stream);
 
+/* iComformer: BatchNorm groups (scripts/train_icomformer_adp.sh:3: --batch 4 --batch_accumulation 16, the same recipe as
+ * CartNet's).  The ten BatchNorm1d are the only coupling between the crystals of a batch (models/comformer_conv.py:67,68
+ * bn_att / bn of ComformerConv, :151,153 of ComformerConv_edge), so the statistics-carrying kernels of the attention block
+ * and of the softplus update take CartnetGroups like the kernels above.  The SEGMENTS of the block are dealt to the groups
+ * by groups->node_gptr (conv layers: atoms; edge layer: edges), a group's rows are ptr[node_gptr[g]] .. ptr[node_gptr[g+1]]
+ * (= groups->edge_gptr: what cartnet_bn_finalize counts with count_over_edges).  Grid (parts, G) with parts =
+ * groups->edge_parts for the kernels around bn_att (rowmul_fwd, att_gate_fwd, att_gate_bwd_apply, coldot_bc_partial) and
+ * groups->node_parts for the softplus update around bn; partial rows [G][parts][C]; mean_rstd and sums are [G][2C]; the
+ * training-mode means of the backward passes divide by the group's own row count (`count` / N only say "training").
+ * Column partials that are no BatchNorm sums (dkey, dmsg, dq, d_o) are summed over all G * parts rows by
+ * cartnet_colsum_finalize.  groups == NULL: exactly the call without the suffix.  No atomics, no workgroup waits for
+ * another, identical bytes on every run.  (cartnet_rowmul_bwd carries no statistic and needs no grouped form.) */
+int cartnet_rowmul_fwd_grouped(const float* key, int32_t ldk, const float* q, int32_t ldq, const int32_t* ptr, int32_t S,
+                               int32_t C, float scale, float* alpha, int32_t lda, double* parts_sum, double* parts_sq,
+                               const CartnetGroups* groups, void* stream);                  /* comformer_conv.py:95-96,176-177 */
+int cartnet_att_gate_fwd_grouped(const float* gs, const float* q, int32_t ldq, const int32_t* ptr, const float* mean_rstd,
+                                 const float* gamma, const float* beta, float scale, int32_t S, int32_t D, float* aggr,
+                                 float* bc, const CartnetGroups* groups, void* stream);     /* comformer_conv.py:96-99,177-180 */
+int cartnet_att_gate_bwd_apply_grouped(float* gs, const float* key, int32_t ldk, const float* q, int32_t ldq,
+                                       const float* daggr, const int32_t* ptr, const float* mean_rstd, const float* gamma,
+                                       const float* beta, const float* sums, int64_t count, int32_t training, float scale,
+                                       int32_t S, int32_t D, float* dq, int32_t lddq, double* parts_dkey, double* parts_dmsg,
+                                       double* parts_dq, const CartnetGroups* groups, void* stream);   /* ... backward */
+int cartnet_coldot_bc_partial_grouped(const float* d, int32_t ld, const float* bc, int32_t R, int32_t C, double* parts_a,
+                                      double* parts_b, const CartnetGroups* groups, void* stream);     /* bn_att backward sums */
+int cartnet_softplus_update_fwd_grouped(const float* o, const float* x, const float* mean_rstd, const float* gamma,
+                                        const float* beta, int64_t N, int32_t D, float* y, const CartnetGroups* groups,
+                                        void* stream);                                      /* comformer_conv.py:88,193 */
+int cartnet_softplus_update_bwd_stats_grouped(const float* o, const float* x, const float* dy, const float* mean_rstd,
+                                              const float* gamma, const float* beta, int32_t N, int32_t D, double* parts_a,
+                                              double* parts_b, const CartnetGroups* groups, void* stream);
+/* cartnet_softplus_update_bwd_apply (parts_do == NULL) and _apply_sums (parts_do [G * node_parts][D]) */
+int cartnet_softplus_update_bwd_apply_grouped(const float* o, const float* x, const float* dy, const float* mean_rstd,
+                                              const float* gamma, const float* beta, const float* sums, int32_t training,
+                                              int32_t N, int32_t D, float* d_o, const float* dx_add, float* dx,
+                                              double* parts_do, const CartnetGroups* groups, void* stream);
+/* cartnet_colstats_grouped over the groups' NODE ranges, partial rows [G][node_parts][C]: the statistics of lin_concate's
+ * output (comformer_conv.py:87-88,190-193), which a single-group run takes from the GEMM epilogue. */
+int cartnet_colstats_grouped_nodes(const float* x, int32_t ld, int32_t C, const CartnetGroups* groups, double* parts_sum,
+                                   double* parts_sq, void* stream);
+
 /* Sync-BatchNorm across data-parallel ranks (optional; the reference's BatchNorm1d layers at
  * models/cartnet.py:198-199,238,269 see one process's batch): the column sums behind every BatchNorm statistic are
  * summed over the ranks before the statistic is formed, so that N ranks with a shard each compute what one process
@@ -916,7 +957,11 @@ typedef struct CartnetIcfParams {
 } CartnetIcfParams;
 
 typedef struct CartnetIcfModel {
-  int32_t C, n_types, gemm_precision, reserved;
+  int32_t C, n_types, gemm_precision;
+  int32_t bn_group_size;                 /* > 0: consecutive crystals form BatchNorm groups of this size in training mode
+                                            (CartnetGroups; the edge layer runs on a second descriptor whose segments are
+                                            the edges and whose rows are the 3E (edge, lattice vector) pairs); <= 0: one
+                                            group.  Took the place of a reserved word every binding wrote 0 into.      */
   float gamma_rbf, gamma_angle;          /* RBFExpansion gammas (models/utils.py:118-119)                              */
   float bn_eps, bn_momentum;
   const float *rbf_centers, *rbf_angle_centers;     /* [C] each                                                       */

@@ -75,13 +75,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--fused_accumulation", action="store_true",
                    help="run the batch x batch_accumulation micro-batches of an optimiser step as ONE pass with BatchNorm "
                         "statistics and loss per micro-batch (CartnetGroups): the reference recipe's numbers at the "
-                        "large-batch rate")
+                        "large-batch rate; CartNet and iComformer (ignored for the other models)")
     p.add_argument("--bf16_storage", action="store_true",
                    help="with --gemm_precision 2: keep the layers' edge-sized intermediate tensors in HBM as bf16 (fp32 "
                         "accumulate, fp32 BatchNorm statistics)")
     p.add_argument("--sync_batchnorm", action="store_true",
                    help="data-parallel runs: BatchNorm statistics over the crystals of ALL ranks (one small all-reduce per "
-                        "BatchNorm and direction) instead of per rank; CartNet only, not with --fused_accumulation")
+                        "BatchNorm and direction) instead of per rank; CartNet only (iComformer has no sync-BatchNorm), not "
+                        "with --fused_accumulation")
     p.add_argument("--resident_dataset", action="store_true",
                    help="keep the splits as packed shards in HBM and build every batch (and its augmentation) on the GPU")
     return p
@@ -110,7 +111,7 @@ def fill_cfg(args) -> None:
     cfg.bn_group_size = 0
     cfg.half_storage = bool(args.bf16_storage) and cfg.model == "CartNet" and args.gemm_precision == 2
     cfg.sync_batchnorm = bool(args.sync_batchnorm) and cfg.model == "CartNet" and not args.fused_accumulation
-    if args.fused_accumulation and cfg.model == "CartNet" and cfg.batch_accumulation > 1:
+    if args.fused_accumulation and cfg.model in ("CartNet", "icomformer") and cfg.batch_accumulation > 1:
         # the loader hands out whole optimiser steps; the model normalises (and train_epoch averages the loss) per
         # micro-batch of the reference's size
         cfg.bn_group_size = cfg.batch

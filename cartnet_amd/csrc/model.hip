@@ -502,8 +502,8 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
     RUN(cartnet_csc_build(w.src32, w.rowptr, b.graph_ptr, b.Bg, N, b.E, w.colptr, w.perm, status, sw));
 
   const bool half = m.half_storage != 0 && m.gemm_precision == 2;
-  CN_CHECK(!m.half_storage || (m.gemm_precision == 2 && !w.groups && D % 256 == 0),
-           "cartnet_model_forward: half_storage needs gemm_precision 2, D %% 256 == 0 and no BatchNorm groups");
+  CN_CHECK(!m.half_storage || (m.gemm_precision == 2 && D % 256 == 0),
+           "cartnet_model_forward: half_storage needs gemm_precision 2 and D %% 256 == 0");
   // ---- encoder, edges (cartnet.py:159)
   RUN(cartnet_edge_features(b.cart_dist, b.cart_dir, m.rbf_means, m.rbf_betas, b.E, m.R, m.invariant, m.radius,
                             m.env_radius, w.feat, w.ldf, w.env, st));
@@ -621,8 +621,12 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
       RUN(cartnet_gemm(&a, st));
     }
     // BatchNorm groups: a 128-row GEMM tile may straddle two groups, so the gate statistics are taken per group by a
-    // pass of their own over the gate half of gs (181 MB at the benchmark batch, ~40 us) instead of in the epilogue
-    if (w.groups && training) RUN(cartnet_colstats_grouped(w.gs[l], 2 * D, D, w.groups, w.cs, w.cq, st));
+    // pass of their own over the gate half of gs (181 MB at the benchmark batch, ~40 us) instead of in the epilogue.
+    // Half storage: half the bytes, and the statistics of the bf16 values as stored -- what the gate kernel normalises
+    // (the epilogue of a single-group run takes them before rounding)
+    if (w.groups && training)
+      RUN(half ? cartnet_colstats_grouped_h(w.gs[l], 2 * D, D, w.groups, w.cs, w.cq, st)
+               : cartnet_colstats_grouped(w.gs[l], 2 * D, D, w.groups, w.cs, w.cq, st));
     RUN(bn_stats(w.cs, w.cq, w.tiles_e, b.E, m.buf[l].norm_mean, m.buf[l].norm_var, m.buf[l].norm_nbt, w.mr1[l], 1));
     if (training && w.bc[l])      // also leaves the per-target sums the backward pass builds its BatchNorm sums from
       RUN(cartnet_gate_scatter_fwd_bc(w.gs[l], e, m.use_envelope[l] ? w.env : nullptr, w.rowptr, w.mr1[l], q.norm_w, q.norm_b,
@@ -731,8 +735,8 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
   for (int i = 0; i < CARTNET_MAX_LAYERS + 2; ++i) side_done[i] = nullptr;
 
   const bool half = m.half_storage != 0 && m.gemm_precision == 2;
-  CN_CHECK(!m.half_storage || (m.gemm_precision == 2 && !w.groups && D % 256 == 0),
-           "cartnet_model_backward: half_storage needs gemm_precision 2, D %% 256 == 0 and no BatchNorm groups");
+  CN_CHECK(!m.half_storage || (m.gemm_precision == 2 && D % 256 == 0),
+           "cartnet_model_backward: half_storage needs gemm_precision 2 and D %% 256 == 0");
   // sync-BatchNorm: the sums of the BatchNorm backward over all ranks for the apply pass (pre-scaled so that the kernels'
   // division by the LOCAL row count yields sum_global / count_global); the affine gradients keep the local sums
   const bool sync_bn = training && m.bn_allreduce != nullptr;

@@ -218,9 +218,19 @@ __global__ void cn_group_ptrs_kernel(const int64_t* __restrict__ graph_ptr, int 
 }
 
 // Per-group column sums / sums of squares of x [rows, C] (row stride ld): group g = blockIdx.y owns rows
-// [row_gptr[g], row_gptr[g+1]); partial row (g * gridDim.x + blockIdx.x) of parts_sum / parts_sq.  Four independent
+// [row_gptr[g], row_gptr[g+1]); partial row (g * gridDim.x + blockIdx.x) of parts_sum / parts_sq.  ROWS independent
 // row loads in flight per wave, fp64 accumulation (BatchNorm variance as E[v^2] - mean^2 needs the digits).
-__global__ __launch_bounds__(256) void cn_colstats_grouped_kernel(const float* __restrict__ x, int ld, int C,
+// T = float, or __bf16 for rows kept as bf16 (half storage; ld counts elements, a lane's four columns are one 8-byte
+// load): the statistics of the values AS STORED -- bf16 -> fp32 is exact.  A bf16 row is half the bytes, so ROWS = 8 of
+// them keep the same bytes in flight per wave as four fp32 rows.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 ldrow4(const float* p) { return ld4(p); }
+__device__ __forceinline__ f32x4 ldrow4(const __bf16* p) {
+  return __builtin_convertvector(*reinterpret_cast<const bf16x4*>(p), f32x4);
+}
+
+template <typename T, int ROWS>
+__global__ __launch_bounds__(256) void cn_colstats_grouped_kernel(const T* __restrict__ x, int ld, int C,
                                                                   const int* __restrict__ row_gptr,
                                                                   double* __restrict__ parts_sum,
                                                                   double* __restrict__ parts_sq) {
@@ -234,15 +244,15 @@ __global__ __launch_bounds__(256) void cn_colstats_grouped_kernel(const float* _
     const bool active = c < C;
     f64x4 ps = {0, 0, 0, 0}, pq = {0, 0, 0, 0};
     if (active) {
-      for (int r = r0 + blockIdx.x * NODES_PER_BLOCK + wid; r < r1; r += 4 * stride) {
-        f32x4 v[4];
+      for (int r = r0 + blockIdx.x * NODES_PER_BLOCK + wid; r < r1; r += ROWS * stride) {
+        f32x4 v[ROWS];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < ROWS; ++u) {
           const int rr = r + u * stride;
-          v[u] = rr < r1 ? ld4(x + (size_t)rr * ld + c) : f32x4{0, 0, 0, 0};
+          v[u] = rr < r1 ? ldrow4(x + (size_t)rr * ld + c) : f32x4{0, 0, 0, 0};
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+        for (int u = 0; u < ROWS; ++u)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             ps[q] += (double)v[u][q];
@@ -746,9 +756,22 @@ extern "C" int cartnet_colstats_grouped(const float* x, int32_t ld, int32_t C, c
   CN_CHECK(groups && cn_groups_ok(groups), "cartnet_colstats_grouped: groups required");
   CN_CHECK(C >= 4 && C % 4 == 0 && ld % 4 == 0 && ld >= C, "cartnet_colstats_grouped: C=%d ld=%d must be multiples of 4", C, ld);
   CN_CHECK(x && parts_sum && parts_sq, "cartnet_colstats_grouped: null pointer");
-  hipLaunchKernelGGL(cn_colstats_grouped_kernel, dim3(groups->edge_parts, groups->G), dim3(256), 0, ST(stream), x, ld, C,
-                     groups->edge_gptr, parts_sum, parts_sq);
+  hipLaunchKernelGGL((cn_colstats_grouped_kernel<float, 4>), dim3(groups->edge_parts, groups->G), dim3(256), 0, ST(stream),
+                     x, ld, C, groups->edge_gptr, parts_sum, parts_sq);
   CN_LAUNCH_CHECK("cartnet_colstats_grouped");
+  return 0;
+}
+
+// The same over rows kept as bf16 (half storage: the gate half of gs)
+extern "C" int cartnet_colstats_grouped_h(const void* x_bf16, int32_t ld, int32_t C, const CartnetGroups* groups,
+                                          double* parts_sum, double* parts_sq, void* stream) {
+  CN_CHECK(groups && cn_groups_ok(groups), "cartnet_colstats_grouped_h: groups required");
+  CN_CHECK(C >= 4 && C % 4 == 0 && ld % 4 == 0 && ld >= C, "cartnet_colstats_grouped_h: C=%d ld=%d must be multiples of 4", C, ld);
+  CN_CHECK(x_bf16 && parts_sum && parts_sq, "cartnet_colstats_grouped_h: null pointer");
+  CN_CHECK((reinterpret_cast<uintptr_t>(x_bf16) & 7u) == 0, "cartnet_colstats_grouped_h: x must be 8-byte aligned");
+  hipLaunchKernelGGL((cn_colstats_grouped_kernel<__bf16, 8>), dim3(groups->edge_parts, groups->G), dim3(256), 0, ST(stream),
+                     static_cast<const __bf16*>(x_bf16), ld, C, groups->edge_gptr, parts_sum, parts_sq);
+  CN_LAUNCH_CHECK("cartnet_colstats_grouped_h");
   return 0;
 }
 
@@ -759,8 +782,8 @@ extern "C" int cartnet_colstats_grouped_nodes(const float* x, int32_t ld, int32_
   CN_CHECK(groups && cn_groups_ok(groups), "cartnet_colstats_grouped_nodes: groups required");
   CN_CHECK(C >= 4 && C % 4 == 0 && ld % 4 == 0 && ld >= C, "cartnet_colstats_grouped_nodes: C=%d ld=%d must be multiples of 4", C, ld);
   CN_CHECK(x && parts_sum && parts_sq, "cartnet_colstats_grouped_nodes: null pointer");
-  hipLaunchKernelGGL(cn_colstats_grouped_kernel, dim3(groups->node_parts, groups->G), dim3(256), 0, ST(stream), x, ld, C,
-                     groups->node_gptr, parts_sum, parts_sq);
+  hipLaunchKernelGGL((cn_colstats_grouped_kernel<float, 4>), dim3(groups->node_parts, groups->G), dim3(256), 0, ST(stream),
+                     x, ld, C, groups->node_gptr, parts_sum, parts_sq);
   CN_LAUNCH_CHECK("cartnet_colstats_grouped_nodes");
   return 0;
 }

@@ -236,6 +236,7 @@ PROTOTYPES = {
     "cartnet_bn_sync_scale": (C.c_int, [c_f32p, C.c_int32, C.c_int64, c_f32p, c_stream]),
     "cartnet_group_ptrs": (C.c_int, [c_i64p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p, c_stream]),
     "cartnet_colstats_grouped": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_groups, c_f32p, c_f32p, c_stream]),
+    "cartnet_colstats_grouped_h": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_groups, c_f32p, c_f32p, c_stream]),
     "cartnet_colstats_grouped_nodes": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_groups, c_f32p, c_f32p, c_stream]),
     "cartnet_rowmul_fwd_grouped": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_float,
                                              c_f32p, C.c_int32, c_f32p, c_f32p, c_groups, c_stream]),

@@ -397,14 +397,17 @@ class CartNet(nn.Module):
         self.overlap_weight_gradients = True   # run weight-gradient GEMMs on a second stream during backward
         # > 0: consecutive crystals of a batch form BatchNorm groups of this size -- the reference recipe's micro-batches
         # (batch 4 x accumulation 16, scripts/train_cartnet_adp.sh:4) travel through the network as ONE batch of 64 with
-        # per-micro-batch statistics; pair it with cartnet_amd.train.grouped_loss (include/cartnet_hip.h: CartnetGroups)
+        # per-micro-batch statistics; pair it with cartnet_amd.train.grouped_loss (include/cartnet_hip.h: CartnetGroups).
+        # Combines with half_storage (the recipe at bf16 storage); not with sync_batchnorm
         self.bn_group_size = 0
         # True: every BatchNorm's statistics (forward) and gradient sums (backward) are summed over the data-parallel ranks
         # (torch.distributed), so that N ranks with a shard each compute what one process would on the union batch
         # (SURVEY.md 8e "sync-BN", optional; default = per-rank statistics, the reference's single-process semantics)
         self.sync_batchnorm = False
         # gemm_precision 2 only: pre / gs / dpre [E, 2D] of every layer are kept in the workspace as bf16 ("bf16 storage /
-        # fp32 accumulate"): half the bytes of the tensors that dominate the step's HBM traffic
+        # fp32 accumulate"): half the bytes of the tensors that dominate the step's HBM traffic.
+        # With bn_group_size the per-group gate statistics are those of gs as stored, i.e. after rounding to bf16
+        # (cartnet_colstats_grouped_h); one group takes them in the GEMM epilogue before rounding
         self.half_storage = False
         self._aux_stream = None
         self._status_ring = None        # in-flight pinned copies of the batches' graph status words (_defer_graph_check)
@@ -442,8 +445,8 @@ class CartNet(nn.Module):
         md.bn_eps, md.bn_momentum = BN_EPS, BN_MOMENTUM
         md.gemm_precision = int(self.gemm_precision)
         md.bn_group_size = int(self.bn_group_size)
-        if self.half_storage and (int(self.gemm_precision) != 2 or self.bn_group_size > 0 or self.dim_in % 256 != 0):
-            raise ValueError("half_storage needs gemm_precision = 2, dim_in % 256 == 0 and no BatchNorm groups")
+        if self.half_storage and (int(self.gemm_precision) != 2 or self.dim_in % 256 != 0):
+            raise ValueError("half_storage needs gemm_precision = 2 and dim_in % 256 == 0")
         md.half_storage = int(bool(self.half_storage))
         B = self._buffers_dict()
         md.rbf_means, md.rbf_betas = B["encoder.rbf.means"].data_ptr(), B["encoder.rbf.betas"].data_ptr()

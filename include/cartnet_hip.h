@@ -564,6 +564,14 @@ int cartnet_group_ptrs(const int64_t* graph_ptr, int32_t Bg, int32_t group_size,
  * single-group run takes from the GEMM epilogue (a 128-row tile may straddle two groups). */
 int cartnet_colstats_grouped(const float* x, int32_t ld, int32_t C, const CartnetGroups* groups, double* parts_sum,
                              double* parts_sq, void* stream);
+/* The same over rows kept as bf16 (CartnetModel.half_storage with bn_group_size: the gate half of gs, the input of the
+ * BatchNorm at models/cartnet.py:238): x_bf16 points at bf16 elements (8-byte aligned), ld counts elements; same partial
+ * rows, fp64 accumulation in a fixed order, no atomics, an empty group writes zero rows.  These are the statistics of the
+ * values AS STORED, i.e. after rounding to bf16 -- the values cartnet_gate_scatter_fwd_h then normalises.  A single-group
+ * half-storage run takes them in the GEMM epilogue from acc + bias BEFORE rounding (csrc/gemm_h.h): the two means differ
+ * by the mean of the round-to-nearest errors of a column (|error| <= 2^-9 |value| each), far inside the bf16 budget. */
+int cartnet_colstats_grouped_h(const void* x_bf16, int32_t ld, int32_t C, const CartnetGroups* groups, double* parts_sum,
+                               double* parts_sq, void* stream);
 /* Backward statistics per group: sums[g][0:D] / sums[g][D:2D] = column sums of group g's rows of parts_a / parts_b
  * ([G][parts][D], parts = edge_parts if over_edges else node_parts); grad_a / grad_b (may be NULL) = the sums over all
  * groups (the BatchNorm affine gradients).  The partial rows are consumed (row 0 of every group is overwritten). */
@@ -849,8 +857,9 @@ typedef struct CartnetModel {
      kernel to kernel -- pre [E, 2D], gs / dgs [E, 2D], dpre [E, 2D] -- and the edge encoder's pre-activation [E, 2D]
      live in the workspace as bf16 (the MFMA operands
      are bf16 at this precision anyway; accumulation, BatchNorm statistics, the residual streams x / e and every
-     gradient of a parameter stay fp32).  SURVEY.md 8d config 3: "bf16 storage / fp32 accumulate".  Not with
-     bn_group_size (the per-group statistics pass reads gs as fp32). */
+     gradient of a parameter stay fp32).  SURVEY.md 8d config 3: "bf16 storage / fp32 accumulate".  Needs D % 256 == 0.
+     With bn_group_size the per-group gate statistics are taken from gs as stored (cartnet_colstats_grouped_h: after
+     rounding to bf16; one group takes them in the GEMM epilogue before rounding). */
   int32_t half_storage;
   /* optional, cartnet_model_backward only: see CartnetGradReadyFn.  Non-zero return = error. */
   CartnetGradReadyFn grad_ready;

@@ -75,10 +75,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--fused_accumulation", action="store_true",
                    help="run the batch x batch_accumulation micro-batches of an optimiser step as ONE pass with BatchNorm "
                         "statistics and loss per micro-batch (CartnetGroups): the reference recipe's numbers at the "
-                        "large-batch rate; CartNet and iComformer (ignored for the other models)")
+                        "large-batch rate; CartNet (also with --gemm_precision 2 --bf16_storage) and iComformer (ignored for "
+                        "the other models)")
     p.add_argument("--bf16_storage", action="store_true",
                    help="with --gemm_precision 2: keep the layers' edge-sized intermediate tensors in HBM as bf16 (fp32 "
-                        "accumulate, fp32 BatchNorm statistics)")
+                        "accumulate, fp64-summed BatchNorm statistics); combines with --fused_accumulation (the per-micro-batch "
+                        "gate statistics are then those of the bf16 values as stored)")
     p.add_argument("--sync_batchnorm", action="store_true",
                    help="data-parallel runs: BatchNorm statistics over the crystals of ALL ranks (one small all-reduce per "
                         "BatchNorm and direction) instead of per rank; CartNet only (iComformer has no sync-BatchNorm), not "

@@ -112,10 +112,16 @@ __global__ __launch_bounds__(256) void cn_rg_kernel(const float* __restrict__ po
         for (int u2i = lo2; u2i <= hi2; ++u2i)
           for (int u3i = lo3; u3i <= hi3; ++u3i) {
             const float u1 = (float)u1i, u2 = (float)u2i, u3 = (float)u3i;
-            // image offset = cell^T u, accumulated as (a1 u1 + a3 u3) + a2 u2 -- the order torch.bmm uses for this sum
-            const float ox = add(add(mul(a[0], u1), mul(a[6], u3)), mul(a[3], u2));
-            const float oy = add(add(mul(a[1], u1), mul(a[7], u3)), mul(a[4], u2));
-            const float oz = add(add(mul(a[2], u1), mul(a[8], u3)), mul(a[5], u2));
+            // image offset = cell^T u, accumulated in the order of the sum, (a1 u1 + a2 u2) + a3 u3, every product and
+            // sum rounded.  The reference takes it from torch.bmm (dataset/utils.py:182), whose rounding depends on the
+            // BLAS code path: this order is what it gives for the 27 images of a cell wider than the radius on every host
+            // measured, and for every image count on the EPYC hosts of the MI355X machines; MKL on a Xeon adds a3 u3
+            // before a2 u2 from 45 images on.  The two differ by one ulp of the offset in a few per cent of the images:
+            // far inside the tests' tolerance for atoms stored in their cell (|offset| <~ 2 radius), 1.3e-6 in a
+            // direction for an atom stored two cells away at 0.74 A from its neighbour.
+            const float ox = add(add(mul(a[0], u1), mul(a[3], u2)), mul(a[6], u3));
+            const float oy = add(add(mul(a[1], u1), mul(a[4], u2)), mul(a[7], u3));
+            const float oz = add(add(mul(a[2], u1), mul(a[5], u2)), mul(a[8], u3));
             const float dx = sub(px, add(qx, ox)), dy = sub(py, add(qy, oy)), dz = sub(pz, add(qz, oz));
             const float d2 = add(add(mul(dx, dx), mul(dy, dy)), mul(dz, dz));
             if ((d2 <= r2) && (d2 > eps2)) emit(dx, dy, dz, d2);
@@ -234,17 +240,23 @@ __global__ __launch_bounds__(256) void cn_cap_fill_kernel(const int64_t* __restr
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// The reference keeps a pair when d^2 <= radius * radius with the product taken in double (a Python float,
+// dataset/utils.py:202) and rounded to fp32 once, for the comparison with the fp32 d^2.  The fp32 product of the rounded
+// radius is one ulp larger for some radii (3.7: 13.6899996 against 13.6900005), so the radius crosses the ABI in double;
+// the repetition counts use the fp32 product radius |b_d|, as the reference's tensor arithmetic does (:140).
+static float cn_rg_threshold(double radius) { return (float)(radius * radius); }
+
 extern "C" int cartnet_radius_graph_count(const float* pos, const float* cell, const int64_t* graph_ptr,
-                                          const int64_t* batch, int32_t N, int32_t Bg, float radius, int32_t* reps,
+                                          const int64_t* batch, int32_t N, int32_t Bg, double radius, int32_t* reps,
                                           int32_t* deg, void* stream) {
-  CN_CHECK(N >= 0 && Bg >= 1 && radius > 0.f, "cartnet_radius_graph_count: bad sizes");
+  CN_CHECK(N >= 0 && Bg >= 1 && radius > 0.0, "cartnet_radius_graph_count: bad sizes");
   CN_CHECK(cell && graph_ptr && reps && (N == 0 || (pos && batch && deg)), "cartnet_radius_graph_count: null pointer");
   float* recip = reinterpret_cast<float*>(reps + 3 * (size_t)Bg);      // second part of the caller's [15 * Bg] buffer
-  hipLaunchKernelGGL(cn_rg_reps_kernel, dim3(cn_ceil_div(Bg, 64)), dim3(64), 0, ST(stream), cell, Bg, radius, reps, recip);
+  hipLaunchKernelGGL(cn_rg_reps_kernel, dim3(cn_ceil_div(Bg, 64)), dim3(64), 0, ST(stream), cell, Bg, (float)radius, reps, recip);
   CN_LAUNCH_CHECK("cartnet_radius_graph_count/reps");
   if (N == 0) return 0;
   hipLaunchKernelGGL(cn_rg_kernel<false>, dim3(cn_ceil_div(N, 4)), dim3(256), 0, ST(stream), pos, cell, graph_ptr, batch,
-                     reps, recip, N, radius * radius, 0.0001f, deg, (const int64_t*)nullptr, (int64_t*)nullptr, 0LL,
+                     reps, recip, N, cn_rg_threshold(radius), 0.0001f, deg, (const int64_t*)nullptr, (int64_t*)nullptr, 0LL,
                      (float*)nullptr, (float*)nullptr, (float*)nullptr);
   CN_LAUNCH_CHECK("cartnet_radius_graph_count");
   return 0;
@@ -252,15 +264,15 @@ extern "C" int cartnet_radius_graph_count(const float* pos, const float* cell, c
 
 extern "C" int cartnet_radius_graph_fill(const float* pos, const float* cell, const int64_t* graph_ptr,
                                          const int64_t* batch, const int32_t* reps, const int64_t* rowptr, int32_t N,
-                                         int32_t Bg, float radius, int64_t E, int64_t* edge_index, float* cart_dist,
+                                         int32_t Bg, double radius, int64_t E, int64_t* edge_index, float* cart_dist,
                                          float* cart_dir, float* cart_dist_sq, void* stream) {
-  CN_CHECK(N >= 0 && Bg >= 1 && radius > 0.f && E >= 0, "cartnet_radius_graph_fill: bad sizes");
+  CN_CHECK(N >= 0 && Bg >= 1 && radius > 0.0 && E >= 0, "cartnet_radius_graph_fill: bad sizes");
   if (N == 0 || E == 0) return 0;
   CN_CHECK(pos && cell && graph_ptr && batch && reps && rowptr && edge_index && cart_dist && cart_dir,
            "cartnet_radius_graph_fill: null pointer");
   const float* recip = reinterpret_cast<const float*>(reps + 3 * (size_t)Bg);
   hipLaunchKernelGGL(cn_rg_kernel<true>, dim3(cn_ceil_div(N, 4)), dim3(256), 0, ST(stream), pos, cell, graph_ptr, batch,
-                     reps, recip, N, radius * radius, 0.0001f, (int*)nullptr, rowptr, edge_index, (long long)E, cart_dist,
+                     reps, recip, N, cn_rg_threshold(radius), 0.0001f, (int*)nullptr, rowptr, edge_index, (long long)E, cart_dist,
                      cart_dir, cart_dist_sq);
   CN_LAUNCH_CHECK("cartnet_radius_graph_fill");
   return 0;

@@ -21,6 +21,8 @@ def radius_graph_pbc(pos: torch.Tensor, cell: torch.Tensor, ptr: torch.Tensor, r
                      max_neighbors: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """pos [N,3] fp32, cell [Bg,3,3] fp32 (rows = lattice vectors), ptr [Bg+1] int64 atom offsets -- all on the GPU.
     ``max_neighbors`` None or <= 0: no cap (what figshare_dataset.py:18 maps -1 to).
+    ``radius`` goes to the library as a double: the cutoff is fp32(radius * radius) with the product taken in double, as
+    dataset/utils.py:202 takes it (the fp32 product of the rounded radius is one ulp larger for e.g. 3.7 and 4.3).
     Returns (edge_index [2,E] int64 = (source, target), cart_dist [E], cart_dir [E,3])."""
     if not (pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2 and pos.shape[1] == 3):
         raise ValueError("pos must be a CUDA fp32 tensor [N,3]")

@@ -35,7 +35,7 @@ int cartnet_abi_version(void);
 /* sizeof of every struct below, in header order (CartnetGemmArgs, CartnetShard, CartnetCollated, CartnetGemmProfile,
  * CartnetGroups, CartnetLayerParams, CartnetLayerBuffers, CartnetParams, CartnetModel, CartnetBatch,
  * CartnetGateGemmArgs, CartnetIcfConv, CartnetIcfParams, CartnetIcfModel); returns the number of structs.  A binding checks its mirrors against these when it loads the
- * library, and cartnet_abi_version() against the version it was written for (13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
+ * library, and cartnet_abi_version() against the version it was written for (14: cartnet_radius_graph_count / _fill take the radius in double -- the cutoff is the fp32 rounding of the double product; 13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
  * aux_stream in cartnet_model_forward, CartnetGateGemmArgs in the size table; cartnet_gemm_tile_policy() is gone). */
 int cartnet_abi_struct_sizes(size_t* out, int32_t capacity);
 
@@ -278,6 +278,8 @@ int cartnet_coldot_bc_partial(const float* d, int32_t ld, const float* bc, int32
  * Periodic radius graph on the GPU (reference: dataset/utils.py:57-237 radius_graph_pbc as used by
  * dataset/figshare_dataset.py:65-68; pairs with d^2 <= 1e-4 dropped).  Edges come out in the
  * reference's order (target, source, periodic image), i.e. edge_index[1] ascending.
+ * radius is a double: a pair is kept when its fp32 d^2 <= (float)(radius * radius), the product taken in double as
+ * the reference takes it (dataset/utils.py:202); the fp32 product is one ulp larger for some radii (3.7, 4.3).
  *   count: reps = caller's scratch of 15 * Bg 4-byte words, kept for fill: int32 [Bg,3] periodic repetitions per
  *          lattice direction, then fp32 [Bg,12] reciprocal lattice vectors and radius |b_d| (the per-pair image box:
  *          only images that can lie within the radius are tested); deg[N] = in-degree of every atom.
@@ -293,9 +295,9 @@ int cartnet_coldot_bc_partial(const float* d, int32_t ld, const float* bc, int32
  *              [2,E_out], cart_dist, cart_dir.
  * ---------------------------------------------------------------------------------------------------- */
 int cartnet_radius_graph_count(const float* pos, const float* cell, const int64_t* graph_ptr, const int64_t* batch,
-                               int32_t N, int32_t Bg, float radius, int32_t* reps, int32_t* deg, void* stream);
+                               int32_t N, int32_t Bg, double radius, int32_t* reps, int32_t* deg, void* stream);
 int cartnet_radius_graph_fill(const float* pos, const float* cell, const int64_t* graph_ptr, const int64_t* batch,
-                              const int32_t* reps, const int64_t* rowptr, int32_t N, int32_t Bg, float radius,
+                              const int32_t* reps, const int64_t* rowptr, int32_t N, int32_t Bg, double radius,
                               int64_t E, int64_t* edge_index, float* cart_dist, float* cart_dir, float* cart_dist_sq,
                               void* stream);
 int cartnet_neighbor_cap_count(const int64_t* rowptr, const float* dist_sq, int32_t N, int32_t max_neighbors,

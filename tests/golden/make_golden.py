@@ -14,6 +14,10 @@ Fixtures (all fp32 unless suffixed _f64):
   config1     D=64, R=64, L=2, 4 crystals of 30..70 atoms (BASELINE.json configs[0] shape); weights from seed
   config2     D=256, R=64, L=4, 2 crystals of 194 atoms (configs[1] shape); weights from seed
   radius_graph  reference radius_graph_pbc output for 3 crystals (integers compared bit-exactly)
+  tiny_radius6 / tiny_radius4   tiny_adp's shape under ``--radius 6`` / ``--radius 4`` as models/master.py runs it: the
+              graph and every layer's envelope (cfg.radius) use the flag, the encoder's RBF keeps its default cutoff 5.0
+  radius_graph_radii  reference radius_graph_pbc on a hexagonal and a triclinic cell at radius 3.7 and 6.0 (uncapped and
+              cap 8), and on two pairs whose fp32 d^2 lies between fp32(radius^2) and fp32(radius)^2
   icomformer_tiny / icomformer_c32   the reference's iComformer (models/comformer.py) at C=16 / C=32
   train_epoch   the reference's own ``train_epoch`` (train/train.py:148-199) run for two epochs of five micro-batches
               with accumulation 3 (optimiser steps after micro-batches 3 and 5: the last-iteration flush), torch Adam as
@@ -32,8 +36,10 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))      # golden_utils: the cells and threshold pairs shared with the tests
 sys.path.insert(0, HERE)
 
+import golden_utils as gu  # noqa: E402
 from _ref_import import import_reference  # noqa: E402
 
 from cartnet_amd.data import Batch, Data  # noqa: E402
@@ -69,7 +75,7 @@ def clone_batch(batch, dtype=None):
 def run_reference(sd, batch, hp, training, dtype=torch.float32, want_grads=False, trace=False):
     """One forward (+ backward) of the reference CartNet.  Returns dict of outputs."""
     ref_cfg.invariant = hp["invariant"]
-    ref_cfg.radius = hp["radius"]
+    ref_cfg.radius = hp["env_radius"]            # models/cartnet.py:201: every layer's envelope reads the global
     torch.manual_seed(0)
     m = ref_cartnet.CartNet(dim_in=hp["dim_in"], dim_rbf=hp["dim_rbf"], num_layers=hp["num_layers"],
                             radius=hp["radius"], invariant=hp["invariant"], temperature=hp["temperature"],
@@ -105,6 +111,7 @@ def hp_dict(dim_in, dim_rbf, num_layers, **kw):
     hp = dict(dim_in=dim_in, dim_rbf=dim_rbf, num_layers=num_layers, radius=5.0, invariant=False, temperature=True,
               use_envelope=True, atom_types=True, cholesky=True)
     hp.update(kw)
+    hp.setdefault("env_radius", hp["radius"])    # cfg.radius (the layers' envelope); "radius" is the encoder's RBF cutoff
     return hp
 
 
@@ -211,9 +218,65 @@ def icomformer_fixture(name, dim, batch, seed, store_weights):
           f"{unused} -> {os.path.getsize(path) / 1024:.0f} KiB")
 
 
-def tiny_batch(adp=True):
-    items = [make_crystal(100, 7, adp=adp), make_crystal(101, 9, adp=adp)]
+def tiny_batch(adp=True, radius=5.0):
+    items = [make_crystal(100, 7, radius=radius, adp=adp), make_crystal(101, 9, radius=radius, adp=adp)]
     return Batch.from_data_list(items)
+
+
+def radius_batch(radius):
+    """tiny_batch built with another cutoff, and the condition that makes the fixture tell the two radii apart."""
+    b = tiny_batch(radius=radius)
+    d, E = b.cart_dist, b.edge_index.shape[1]
+    if radius > 5.0:
+        far = int((d >= 5.0).sum())
+        assert far >= 0.2 * E and bool((d < radius).all()), (far, E)      # RBF exactly 0, envelope positive
+        print(f"radius {radius}: {far} of {E} edges ({100 * far / E:.0f} %) have 5 <= d < {radius}")
+    else:
+        assert E >= 50 and bool((d < radius).all()), E                   # envelope narrower than the RBF
+        print(f"radius {radius}: {E} edges, none with d >= {radius}")
+    return b
+
+
+def _reference_graph(pos, cell, radius, cap):
+    """The reference's radius_graph_pbc on one crystal; asserts that the host builder restates it bit for bit."""
+    data = type("D", (), {})()
+    data.pos, data.cell, data.natoms = pos, cell.view(1, 3, 3), torch.tensor([pos.shape[0]])
+    data.pbc = torch.tensor([[True, True, True]])
+    ei, _, _, vec = ref_dutils.radius_graph_pbc(data, radius, cap)
+    dist = torch.norm(vec, p=2, dim=-1)                     # dataset/figshare_dataset.py:67
+    dirn = torch.nn.functional.normalize(vec, p=2, dim=-1)  # dataset/figshare_dataset.py:68
+    mine_ei, mine_dist, mine_dir = radius_graph_pbc_single(pos, cell, radius, max_neighbors=cap)
+    assert torch.equal(ei, mine_ei), "edge_index differs from the reference"
+    assert torch.equal(dist, mine_dist) and torch.equal(dirn, mine_dir), "edge geometry differs"
+    return ei, dist, dirn
+
+
+def radius_graph_radii_fixture():
+    arrays = {"radii": np.array([3.7, 6.0])}
+    for name, seed in (("hexagonal", 41), ("triclinic", 42)):
+        pos, cell = gu.crystal(name, 12, seed)
+        arrays[f"{name}_pos"], arrays[f"{name}_cell"] = to_np(pos), to_np(cell)
+        for r in (3.7, 6.0):
+            full = _reference_graph(pos, cell, r, None)
+            cap = _reference_graph(pos, cell, r, 8)
+            assert cap[0].shape[1] < full[0].shape[1]
+            for tag, (ei, dist, dirn) in (("", full), ("cap8_", cap)):
+                key = f"{name}_r{r}_{tag}"
+                arrays[key + "edge_index"], arrays[key + "dist"], arrays[key + "dir"] = to_np(ei), to_np(dist), to_np(dirn)
+            print(f"radius_graph_radii[{name}, {r}]: E={full[0].shape[1]}, cap 8 -> {cap[0].shape[1]}, identical to reference")
+    for i, (r, y) in enumerate(gu.THRESHOLD_PAIRS):
+        pos, cell = gu.threshold_pair(y)
+        d2 = (pos[1] ** 2).sum().numpy()                   # fp32: 9 + y^2, the sum the reference forms for this pair
+        assert d2 == np.float32(r) * np.float32(r) and d2 > np.float32(r * r), (r, d2)
+        up = float(np.nextafter(np.float32(r), np.float32(10)))
+        at, above = _reference_graph(pos, cell, r, None), _reference_graph(pos, cell, up, None)
+        assert at[0].shape[1] == 0 and above[0].shape[1] == 2
+        arrays[f"pair{i}_pos"], arrays[f"pair{i}_cell"] = to_np(pos), to_np(cell)
+        arrays[f"pair{i}_radius"], arrays[f"pair{i}_radius_up"] = np.float64(r), np.float64(up)
+        arrays[f"pair{i}_edge_index"] = to_np(at[0])
+        arrays[f"pair{i}_up_edge_index"], arrays[f"pair{i}_up_dist"], arrays[f"pair{i}_up_dir"] = (to_np(t) for t in above)
+        print(f"radius_graph_radii[pair {i}]: d2 = {d2!r}: 0 edges at {r}, 2 at {up!r}, identical to reference")
+    np.savez_compressed(os.path.join(HERE, "radius_graph_radii.npz"), **arrays)
 
 
 def radius_graph_fixture():
@@ -387,6 +450,7 @@ def main():
     b2 = lambda: Batch.from_data_list([make_crystal(400 + g, 194) for g in range(2)])
     jobs = {
         "radius_graph": radius_graph_fixture,
+        "radius_graph_radii": radius_graph_radii_fixture,
         "adp_metrics": metrics_fixture,
         "train_epoch": train_epoch_fixture,
         "tiny_adp": lambda: save_model_fixture("tiny_adp", hp_dict(16, 8, 2), tiny_batch(), seed=11,
@@ -406,6 +470,12 @@ def main():
                                                    hp_dict(16, 8, 2, atom_types=False, temperature=False),
                                                    tiny_batch(), seed=15, store_weights=True, full_grads=True,
                                                    trace=True),
+        # main.py --radius 6 / 4: models/master.py never hands the flag to CartNet, so the RBF cutoff stays 5.0 while
+        # the graph and the envelopes follow cfg.radius
+        "tiny_radius6": lambda: save_model_fixture("tiny_radius6", hp_dict(16, 8, 2, env_radius=6.0), radius_batch(6.0),
+                                                   seed=16, store_weights=True, full_grads=True, trace=True),
+        "tiny_radius4": lambda: save_model_fixture("tiny_radius4", hp_dict(16, 8, 2, env_radius=4.0), radius_batch(4.0),
+                                                   seed=17, store_weights=True, full_grads=True, trace=True),
         "config1": lambda: save_model_fixture("config1", hp_dict(64, 64, 2), b1(), seed=21, store_weights=False,
                                               full_grads=True, trace=False),
         "icomformer_tiny": lambda: icomformer_fixture("icomformer_tiny", 16, tiny_batch(), seed=31,

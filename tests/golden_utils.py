@@ -8,7 +8,39 @@ from cartnet_amd.data import Batch
 from cartnet_amd.model import make_state_dict
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-MODEL_FIXTURES = ["tiny_adp", "tiny_scalar", "tiny_invariant", "tiny_noatom", "tiny_nothing", "config1", "config2"]
+MODEL_FIXTURES = ["tiny_adp", "tiny_scalar", "tiny_invariant", "tiny_noatom", "tiny_nothing", "config1", "config2",
+                  "tiny_radius6", "tiny_radius4"]
+
+# Cells (a, b, c, alpha, beta, gamma) away from the nearly cubic ones of cartnet_amd.synthetic: the radius-graph tests and
+# the radius_graph_radii fixture share them.
+CELLS = {"hexagonal": (4.1, 4.1, 9.7, 90.0, 90.0, 120.0), "rhombohedral": (5.3, 5.3, 5.3, 50.0, 50.0, 50.0),
+         "triclinic": (3.4, 6.2, 8.8, 67.0, 104.0, 118.0), "small": (2.6, 2.9, 3.3, 85.0, 95.0, 100.0)}
+# (radius, y): cell 20 I, atoms at (0, 0, 0) and (3, y, 0).  The pair's fp32 d^2 equals fp32(radius) * fp32(radius) and lies
+# one ulp above fp32(radius * radius), the reference's threshold (dataset/utils.py:202 takes the product in double).
+THRESHOLD_PAIRS = [(3.7, 2.1656408309936523), (4.3, 3.0805845260620117)]
+
+
+def lattice(a, b, c, alpha, beta, gamma):
+    """fp32 [3,3] cell (rows = lattice vectors) in the standard setting: a1 along x, a2 in the xy plane."""
+    al, be, ga = (np.deg2rad(v) for v in (alpha, beta, gamma))
+    cy = (np.cos(al) - np.cos(be) * np.cos(ga)) / np.sin(ga)
+    m = np.array([[a, 0.0, 0.0], [b * np.cos(ga), b * np.sin(ga), 0.0],
+                  [c * np.cos(be), c * cy, c * np.sqrt(1.0 - np.cos(be) ** 2 - cy ** 2)]])
+    return torch.from_numpy(m).to(torch.float32)
+
+
+def crystal(name, n, seed, rotate=False):
+    """(pos [n,3], cell [3,3]) fp32: ``n`` atoms at uniform fractional coordinates in CELLS[name], optionally rotated."""
+    from cartnet_amd.synthetic import random_rotation
+    gen = torch.Generator().manual_seed(seed)
+    cell = lattice(*CELLS[name])
+    if rotate:
+        cell = cell @ random_rotation(gen)
+    return torch.rand(n, 3, generator=gen, dtype=torch.float32) @ cell, cell
+
+
+def threshold_pair(y):
+    return torch.tensor([[0.0, 0.0, 0.0], [3.0, y, 0.0]], dtype=torch.float32), 20.0 * torch.eye(3)
 
 
 def load(name):
@@ -38,6 +70,7 @@ def clone_batch(b):
 
 
 def oracle_kwargs(hp):
-    return dict(num_layers=hp["num_layers"], radius=hp["radius"], invariant=hp["invariant"],
+    return dict(num_layers=hp["num_layers"], radius=hp["radius"], envelope_radius=hp.get("env_radius", hp["radius"]),
+                invariant=hp["invariant"],
                 use_temperature=hp["temperature"], use_envelope=hp["use_envelope"], atom_types=hp["atom_types"],
                 cholesky=hp["cholesky"])

@@ -6,6 +6,7 @@ integers bit-exact.
 """
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -522,6 +523,43 @@ def test_edge_features_vs_oracle(ops, invariant):
         assert torch.equal(feat[:, R:R + 3].cpu(), dirv)
         assert torch.count_nonzero(feat[:, R + 3:]) == 0
     assert rel_err(env, orc.cosine_cutoff(dist.double(), 4.0)) < TOL
+
+
+@pytest.mark.parametrize("invariant", [False, True])
+def test_edge_features_with_envelope_radius_beyond_the_rbf_cutoff(ops, invariant):
+    """--radius 6 (the reference's contract: RBF cutoff 5.0, envelope radius 6.0, edges up to 6): RBF columns exactly 0
+    from 5.0 on, envelope exactly 0 from 6.0 on, both at the fp64 formulas elsewhere.  Pinned: 5.0 and 6.0 with their fp32
+    neighbours on either side."""
+    from oracle import cartnet_ref as orc
+    E, R, radius, env_radius = 1000, 64, 5.0, 6.0
+    g = torch.Generator().manual_seed(1)
+    dist = (0.01 + 6.29 * torch.rand(E, generator=g))
+    f32 = lambda v, to: float(np.nextafter(np.float32(v), np.float32(to)))
+    pinned = torch.tensor([5.0, f32(5.0, 0.0), f32(5.0, 10.0), 6.0, f32(6.0, 0.0), f32(6.0, 10.0)])
+    assert pinned.tolist() == [5.0, 4.999999523162842, 5.000000476837158, 6.0, 5.999999523162842, 6.000000476837158]
+    dist[:6] = pinned
+    assert int((dist >= 6.0).sum()) > 20 and int(((dist >= 5.0) & (dist < 6.0)).sum()) > 100
+    dirv = torch.nn.functional.normalize(torch.randn(E, 3, generator=g), dim=-1)
+    means, betas = orc.rbf_constants(radius, R)
+    ldf = 72
+    feat = torch.full((E, ldf), 7.0, device=dev())
+    env = torch.full((E,), 7.0, device=dev())
+    ops.edge_features(dist.to(dev()), dirv.to(dev()), means.to(dev()), betas.to(dev()), invariant, radius, env_radius,
+                      feat, env)
+    feat, env = feat.cpu(), env.cpu()
+    # bitwise zeros (+0.0: the byte pattern, not merely == 0)
+    assert torch.equal(feat[dist >= radius, :R].view(torch.int32), torch.zeros(int((dist >= radius).sum()), R, dtype=torch.int32))
+    assert torch.equal(env[dist >= env_radius].view(torch.int32), torch.zeros(int((dist >= env_radius).sum()), dtype=torch.int32))
+    assert bool((env[(dist < env_radius - 1e-2)] > 0).all())                  # positive on the edges the RBF does not see
+    assert bool((feat[dist < radius - 1e-2, :R].amax(1) > 0).all())
+    rbf = orc.exp_normal_smearing(dist.double(), means.double(), betas.double(), radius)
+    assert rel_err(feat[:, :R], rbf) < TOL
+    assert rel_err(env, orc.cosine_cutoff(dist.double(), env_radius)) < TOL
+    if invariant:
+        assert torch.count_nonzero(feat[:, R:]) == 0
+    else:
+        assert torch.equal(feat[:, R:R + 3], dirv)
+        assert torch.count_nonzero(feat[:, R + 3:]) == 0
 
 
 def _gate_reference(gs, e_in, env, tgt, N, mean, rstd, gamma, beta):

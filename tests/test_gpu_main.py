@@ -120,3 +120,24 @@ def test_inference_and_montecarlo_on_a_checkpoint(tmp_path, monkeypatch):
     assert all(os.path.exists(tmp_path / f"inf_montecarlo_{i}.pkl") for i in range(3))
     with pytest.raises(AssertionError, match="Weights not provided"):
         entry.main(common + ["--inference"])
+
+
+def test_main_with_radius_6_keeps_the_rbf_cutoff_at_5(tmp_path, monkeypatch):
+    """--radius 6 end to end, with the reference's contract: the graphs and every layer's envelope follow the flag, the
+    encoder's RBF keeps cutoff 5.0 (models/master.py never hands the flag to CartNet)."""
+    import main as entry
+    from cartnet_amd.config import cfg
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(cfg, "radius", cfg.radius)                   # main() writes the flag into the global: put it back
+    seen = {}
+    make_model, make_loaders = entry.create_model, entry.create_loaders
+    monkeypatch.setattr(entry, "create_model", lambda: seen.setdefault("model", make_model()))
+    monkeypatch.setattr(entry, "create_loaders", lambda *a: seen.setdefault("loaders", make_loaders(*a)))
+    res = entry.main(["--synthetic", "12", "--atoms", "10", "20", "--dim_in", "32", "--num_layers", "2", "--epochs", "2",
+                      "--batch", "3", "--radius", "6", "--name", "radius6"])
+    assert len(res["history"]) == 2
+    assert all(torch.isfinite(torch.tensor([h["train_mae"], h["val_mae"]])).all() for h in res["history"])
+    m = seen["model"]
+    assert m.encoder.rbf.cutoff_upper == 5.0 and all(l.envelope_radius == 6.0 for l in m.layers)
+    dist = torch.cat([b.cart_dist.cpu() for loader in seen["loaders"][1:] for b in loader])
+    assert bool((dist > 5.0).any()) and bool((dist <= 6.0).all())

@@ -27,13 +27,22 @@ PRECISIONS = [0, 1]      # 0: fp32 MFMA, 1: bf16x3 split-operand MFMA -- both mu
 
 
 def _model(hp, sd, precision=0):
+    """hp["radius"] is the encoder's RBF cutoff (a constructor argument); the layers' envelope radius is the global
+    cfg.radius at construction time (models/cartnet.py:201), hp["env_radius"] where a fixture sets the two apart.  The
+    global is put back: other tests build CartNet without setting it."""
     from cartnet_amd.config import cfg
     from cartnet_amd.model import CartNet
-    cfg.radius = hp["radius"]
+    old = cfg.radius, cfg.invariant
+    cfg.radius = hp.get("env_radius", hp["radius"])
     cfg.invariant = hp["invariant"]
-    m = CartNet(hp["dim_in"], hp["dim_rbf"], hp["num_layers"], radius=hp["radius"], invariant=hp["invariant"],
-                temperature=hp["temperature"], use_envelope=hp["use_envelope"], atom_types=hp["atom_types"],
-                cholesky=hp["cholesky"])
+    try:
+        m = CartNet(hp["dim_in"], hp["dim_rbf"], hp["num_layers"], radius=hp["radius"], invariant=hp["invariant"],
+                    temperature=hp["temperature"], use_envelope=hp["use_envelope"], atom_types=hp["atom_types"],
+                    cholesky=hp["cholesky"])
+    finally:
+        cfg.radius, cfg.invariant = old
+    assert m.encoder.rbf.cutoff_upper == hp["radius"]
+    assert all(l.envelope_radius == hp.get("env_radius", hp["radius"]) for l in m.layers)
     m.load_state_dict(sd, strict=True)
     m.validate_graph = True
     m.gemm_precision = precision
@@ -83,6 +92,61 @@ def test_per_layer_features_against_reference_golden():
         m(bb)
     assert rel_err(bb.x, torch.from_numpy(z[f"trace_x{L}"])) < PRED_TOL
     assert rel_err(bb.edge_attr, torch.from_numpy(z[f"trace_e{L}"])) < PRED_TOL
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("name", ["tiny_radius6", "tiny_radius4"])
+def test_per_layer_features_with_two_radii_against_reference_golden(name, precision):
+    """--radius 6 / 4 as the reference runs it (RBF cutoff 5.0, envelope radius = the flag): the last layer's node and
+    edge features against the reference's trace."""
+    z, hp, b, sd = gu.load(name)
+    L = hp["num_layers"]
+    m = _model(hp, sd, precision).train()
+    bb = gu.clone_batch(b).to("cuda:0")
+    with torch.no_grad():
+        m(bb)
+    assert rel_err(bb.x, torch.from_numpy(z[f"trace_x{L}"])) < PRED_TOL
+    assert rel_err(bb.edge_attr, torch.from_numpy(z[f"trace_e{L}"])) < PRED_TOL
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_two_radii_at_width_256_against_oracle(precision):
+    """--radius 6 at the width that takes the DMA-fed kernels: crystals built with radius 6 (edges with 5 <= d < 6: RBF
+    block exactly 0, envelope positive), cfg.radius = 6 for the envelopes, RBF cutoff 5.0.  Train and eval against the fp64
+    oracle; the same oracle with the envelope at 5.0 is far outside the budget, so crossed plumbing cannot pass."""
+    from cartnet_amd.data import Batch
+    from cartnet_amd.model import make_state_dict
+    from cartnet_amd.synthetic import make_crystal
+    from oracle import cartnet_ref as orc
+    hp = dict(dim_in=256, dim_rbf=64, num_layers=2, radius=5.0, env_radius=6.0, invariant=False, temperature=True,
+              use_envelope=True, atom_types=True, cholesky=True)
+    b = Batch.from_data_list([make_crystal(340 + i, n, radius=6.0) for i, n in enumerate((12, 20))])
+    assert int((b.cart_dist >= 5.0).sum()) >= 0.2 * b.cart_dist.numel() and bool((b.cart_dist < 6.0).all())
+    sd = make_state_dict(256, 64, 2, seed=13)
+    m = _model(hp, sd, precision)
+    assert m.encoder.rbf.cutoff_upper == 5.0 and m.layers[0].envelope_radius == 6.0
+    names = set(k for k, _ in m.named_parameters())
+    m.train()
+    pred, true = m(gu.clone_batch(b).to("cuda:0"))
+    (pred - true).abs().mean().backward()
+    ref, gref = _oracle_run(b, hp, sd, names)
+    assert rel_err(pred, ref) < PRED_TOL
+    _check_grads({k: p.grad for k, p in m.named_parameters()}, gref, "two radii")
+    b64 = gu.clone_batch(b)
+    for k, v in list(b64.__dict__.items()):
+        if torch.is_tensor(v) and v.is_floating_point():
+            setattr(b64, k, v.double())
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    crossed = orc.cartnet_forward(sd64, b64, training=True, **{**gu.oracle_kwargs(hp), "envelope_radius": 5.0})
+    assert rel_err(pred, crossed) > 1e-3
+    m.eval()
+    m.load_state_dict(sd)                                  # the training pass moved the running statistics
+    with torch.no_grad():
+        pred_eval, _ = m(gu.clone_batch(b).to("cuda:0"))
+    ref_eval = orc.cartnet_forward(sd64, b64, training=False, **gu.oracle_kwargs(hp))
+    assert rel_err(pred_eval, ref_eval) < PRED_TOL
+    crossed = orc.cartnet_forward(sd64, b64, training=False, **{**gu.oracle_kwargs(hp), "envelope_radius": 5.0})
+    assert rel_err(pred_eval, crossed) > 1e-3
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)

@@ -136,3 +136,123 @@ def test_degenerate_cells_do_not_hang_or_fault():
     ref_ei, ref_dist, _ = radius_graph_pbc_single(good.pos, good.cell[0], 5.0)
     assert torch.equal((ei[:, sel] - 15).cpu(), ref_ei)
     assert torch.allclose(dist[sel].cpu(), ref_dist, rtol=1e-6, atol=0)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Away from radius 5 and nearly cubic cells.  The reference is the host builder called per crystal (bit-identical to the
+# reference's dataset/utils.py on these cells, atom counts and radii: tests/golden/make_golden.py asserts it for the
+# radius_graph_radii fixture); the GPU is called on batches, so repetition counts differ per crystal within a launch.
+_OBLIQUE = [("hexagonal", False), ("rhombohedral", False), ("triclinic", False), ("triclinic", True), ("small", False)]
+_HOST_GRAPHS = {}
+
+
+def _crystal(name, n, rotate=False):
+    return gu.crystal(name, n, seed=1000 + 10 * n + sorted(gu.CELLS).index(name) + (5 if rotate else 0), rotate=rotate)
+
+
+def _host_graph(pos, cell, radius, cap=None):
+    """Host-builder graph of one crystal, computed once per (crystal, radius, cap) and shared between tests."""
+    from cartnet_amd.synthetic import radius_graph_pbc_single
+    key = (pos.numpy().tobytes(), cell.numpy().tobytes(), radius, cap)
+    if key not in _HOST_GRAPHS:
+        _HOST_GRAPHS[key] = radius_graph_pbc_single(pos, cell, radius, max_neighbors=cap)
+    return _HOST_GRAPHS[key]
+
+
+def _gpu_batch_against_host(crystals, radius, cap=None):
+    """One GPU call on the whole batch against the per-crystal host graphs; returns the GPU edge_index."""
+    from cartnet_amd.graph import radius_graph_pbc
+    ref_ei, ref_d, ref_v, off = [], [], [], 0
+    for pos, cell in crystals:
+        ei, d, v = _host_graph(pos, cell, radius, cap)
+        ref_ei.append(ei + off); ref_d.append(d); ref_v.append(v); off += pos.shape[0]
+    ptr = torch.tensor([0] + list(np.cumsum([p.shape[0] for p, _ in crystals])))
+    pos, cell = torch.cat([p for p, _ in crystals]).cuda(), torch.stack([c for _, c in crystals]).cuda()
+    ei, dist, dirs = radius_graph_pbc(pos, cell, ptr.cuda(), radius, max_neighbors=cap)
+    _check(ei, dist, dirs, torch.cat(ref_ei, 1), torch.cat(ref_d), torch.cat(ref_v))
+    return ei
+
+
+@pytest.mark.parametrize("radius", [2.0, 3.5, 6.0, 8.0])
+def test_oblique_cells_and_other_radii_match_cpu_builder(radius):
+    """Hexagonal, rhombohedral (50 degrees), triclinic, rotated triclinic and a cell smaller than the radius (repetition
+    counts of 3 and more), 1 / 3 / 70 atoms (70: more than one 64-lane source round), all crystals of a radius in one
+    batch.  The 2.6 x 2.9 x 3.3 cell keeps its 70 atoms up to radius 3.5 (~36k edges there)."""
+    crystals = [_crystal(name, n, rot) for name, rot in _OBLIQUE for n in (1, 3, 70)
+                if not (name == "small" and n == 70 and radius > 3.5)]
+    assert len(crystals) == (15 if radius <= 3.5 else 14)
+    ei = _gpu_batch_against_host(crystals, radius)
+    assert ei.shape[1] > 0 and bool((ei[1][1:] >= ei[1][:-1]).all())
+    if radius >= 6.0:         # the condition this case is for: some crystal needs three or more images along an axis
+        cell = gu.lattice(*gu.CELLS["small"])
+        height = torch.det(cell).abs() / torch.linalg.cross(cell[1], cell[2]).norm()
+        assert radius / float(height) > 2.0
+
+
+def test_atoms_stored_outside_the_unit_cell_match_cpu_builder():
+    """A third of the atoms moved by integer lattice translations in [-2, 2]^3.  The reference only tests the images in
+    [-R_d, R_d]; the kernel's per-pair image box is clamped to the same range and must emit exactly those edges.
+    Image offsets reach 20 A here, so this is also the case that sees the rounding ORDER of the offset sum: with
+    (a1 u1 + a3 u3) + a2 u2 in the kernel against (a1 u1 + a2 u2) + a3 u3 in this host's torch.bmm, two of 21,570
+    directions were off by 1.27e-6 (a pair 0.74 A apart, offset one ulp apart); with the same order the maximum is 1.2e-7."""
+    pos, cell = _crystal("triclinic", 70)
+    gen = torch.Generator().manual_seed(77)
+    shift = torch.randint(-2, 3, (70, 3), generator=gen).to(torch.float32)
+    shift[torch.randperm(70, generator=gen)[70 // 3:]] = 0.0
+    assert int((shift.abs().sum(1) > 0).sum()) >= 15
+    moved = pos + shift @ cell
+    ei = _gpu_batch_against_host([(moved, cell)], 6.0)
+    inside = _host_graph(pos, cell, 6.0)[0]
+    assert ei.shape[1] != inside.shape[1]        # the clamped range really drops (or adds) images for the moved atoms
+
+
+@pytest.mark.parametrize("radius", [3.5, 6.0])
+def test_neighbour_cap_on_oblique_cells_matches_cpu_builder(radius):
+    crystals = [_crystal("hexagonal", 70), _crystal("triclinic", 70)]
+    ei = _gpu_batch_against_host(crystals, radius, cap=12)
+    full = sum(_host_graph(p, c, radius)[0].shape[1] for p, c in crystals)
+    assert 12 * 140 <= ei.shape[1] < full
+
+
+@pytest.mark.parametrize("radius,y", gu.THRESHOLD_PAIRS)
+def test_cutoff_is_the_fp32_rounding_of_the_double_product(radius, y):
+    """The reference keeps d^2 <= radius * radius with the product taken in double (dataset/utils.py:202) and rounded to
+    fp32 for the comparison.  These pairs have an fp32 d^2 equal to fp32(radius) * fp32(radius), one ulp above that
+    threshold: no edge at the radius, both edges one fp32 step above it -- on the host builder and on the GPU."""
+    from cartnet_amd.graph import radius_graph_pbc
+    from cartnet_amd.synthetic import radius_graph_pbc_single
+    pos, cell = gu.threshold_pair(y)
+    d2 = (pos[1] ** 2).sum().numpy()
+    assert d2 == np.float32(radius) * np.float32(radius) and d2 > np.float32(radius * radius)   # between the thresholds
+    ptr = torch.tensor([0, 2]).cuda()
+    assert radius_graph_pbc_single(pos, cell, radius)[0].shape[1] == 0
+    ei, dist, dirs = radius_graph_pbc(pos.cuda(), cell.view(1, 3, 3).cuda(), ptr, radius)
+    print(f"radius {radius}: GPU edges {ei.shape[1]} (reference 0)")
+    assert ei.shape[1] == 0
+    up = float(np.nextafter(np.float32(radius), np.float32(10)))
+    ref = radius_graph_pbc_single(pos, cell, up)
+    assert ref[0].shape[1] == 2
+    _check(*radius_graph_pbc(pos.cuda(), cell.view(1, 3, 3).cuda(), ptr, up), *ref)
+
+
+def test_other_radii_match_reference_golden_fixture():
+    """tests/golden/radius_graph_radii.npz: the reference's own output (not the restatement) at radius 3.7 and 6.0 on a
+    hexagonal and a triclinic cell, uncapped and capped at 8, and on the two threshold pairs."""
+    from cartnet_amd.graph import radius_graph_pbc
+    z = np.load(gu.GOLDEN + "/radius_graph_radii.npz")
+    t = lambda k: torch.from_numpy(z[k])
+    for name in ("hexagonal", "triclinic"):
+        pos, cell = t(f"{name}_pos").cuda(), t(f"{name}_cell").view(1, 3, 3).cuda()
+        ptr = torch.tensor([0, pos.shape[0]]).cuda()
+        for r in z["radii"].tolist():
+            for tag, cap in (("", None), ("cap8_", 8)):
+                key = f"{name}_r{r}_{tag}"
+                _check(*radius_graph_pbc(pos, cell, ptr, r, max_neighbors=cap), t(key + "edge_index"), t(key + "dist"),
+                       t(key + "dir"))
+    for i in range(2):
+        pos, cell = t(f"pair{i}_pos").cuda(), t(f"pair{i}_cell").view(1, 3, 3).cuda()
+        ptr = torch.tensor([0, 2]).cuda()
+        assert z[f"pair{i}_edge_index"].shape[1] == 0
+        assert radius_graph_pbc(pos, cell, ptr, float(z[f"pair{i}_radius"]))[0].shape[1] == 0
+        _check(*radius_graph_pbc(pos, cell, ptr, float(z[f"pair{i}_radius_up"])), t(f"pair{i}_up_edge_index"),
+               t(f"pair{i}_up_dist"), t(f"pair{i}_up_dir"))

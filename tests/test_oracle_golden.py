@@ -103,6 +103,68 @@ def test_neighbour_cap_matches_reference_bit_exact():
     assert z["cubic_cap10_edge_index"].shape[1] == 18 and z["cubic_cap25_edge_index"].shape[1] == 26
 
 
+@pytest.mark.parametrize("name,env_radius", [("tiny_radius6", 6.0), ("tiny_radius4", 4.0)])
+def test_radius_fixtures_separate_the_rbf_cutoff_from_the_envelope_radius(name, env_radius):
+    """``--radius r`` as the reference runs it: models/master.py never hands the flag to CartNet, so the encoder's RBF keeps
+    cutoff 5.0 (models/cartnet.py:138) while the graph and every layer's envelope follow cfg.radius (:201).  The fixtures
+    must be able to tell the two apart: at 6 a good share of the edges lies beyond the RBF cutoff (RBF block exactly 0,
+    envelope positive), at 4 no edge reaches the envelope's zero; the per-layer trace matches, and an oracle with either
+    radius in the other's place is off by three orders more than the parity budget."""
+    z, hp, b, sd = gu.load(name)
+    assert hp["radius"] == 5.0 and hp["env_radius"] == env_radius
+    d, E = b.cart_dist, b.edge_index.shape[1]
+    assert bool((d < env_radius).all())
+    if env_radius > 5.0:
+        assert int((d >= 5.0).sum()) >= 0.2 * E
+    else:
+        assert E >= 50
+    kw = gu.oracle_kwargs(hp)
+    assert kw["radius"] == 5.0 and kw["envelope_radius"] == env_radius
+    trace = {}
+    orc.cartnet_forward(sd, b, training=True, trace=trace, **kw)
+    assert len(trace) == 2 * (hp["num_layers"] + 1)
+    for k, v in trace.items():
+        assert rel_err(v, torch.from_numpy(z["trace_" + k])) < 1e-5, k
+    if env_radius > 5.0:      # the RBF block of the far edges is exactly zero in the reference's encoder input
+        rbf = orc.exp_normal_smearing(d, sd["encoder.rbf.means"], sd["encoder.rbf.betas"], 5.0)
+        assert torch.count_nonzero(rbf[d >= 5.0]) == 0 and torch.count_nonzero(rbf[d < 4.9]) > 0
+    ref = torch.from_numpy(z["train_pred_f64"])
+    sd64, b64 = _f(sd, torch.float64), _b(b, torch.float64)
+    for wrong in (dict(envelope_radius=5.0), dict(radius=env_radius)):
+        pred = orc.cartnet_forward(sd64, b64, training=True, **{**kw, **wrong})
+        assert rel_err(pred, ref) > 1e-3, wrong
+
+
+def test_radius_graph_at_other_radii_and_cells_matches_reference_bit_exact():
+    """tests/golden/radius_graph_radii.npz: a hexagonal and a triclinic cell at radius 3.7 and 6.0, uncapped and capped at
+    8, and the two pairs whose fp32 d^2 lies between fp32(radius^2) (the reference's threshold, dataset/utils.py:202) and
+    fp32(radius)^2: no edge at the radius itself, both edges one fp32 step above it."""
+    from cartnet_amd.synthetic import radius_graph_pbc_single
+    z = np.load(gu.GOLDEN + "/radius_graph_radii.npz")
+    for name in ("hexagonal", "triclinic"):
+        pos, cell = torch.from_numpy(z[f"{name}_pos"]), torch.from_numpy(z[f"{name}_cell"])
+        assert torch.equal(cell, gu.lattice(*gu.CELLS[name]))
+        for r in z["radii"].tolist():
+            for tag, cap in (("", None), ("cap8_", 8)):
+                ei, dist, dirn = radius_graph_pbc_single(pos, cell, r, max_neighbors=cap)
+                key = f"{name}_r{r}_{tag}"
+                assert torch.equal(ei, torch.from_numpy(z[key + "edge_index"])), key
+                assert torch.equal(dist, torch.from_numpy(z[key + "dist"])), key
+                assert torch.equal(dirn, torch.from_numpy(z[key + "dir"])), key
+            assert z[f"{name}_r{r}_cap8_dist"].shape[0] < z[f"{name}_r{r}_dist"].shape[0]
+    for i, (r, y) in enumerate(gu.THRESHOLD_PAIRS):
+        pos, cell = torch.from_numpy(z[f"pair{i}_pos"]), torch.from_numpy(z[f"pair{i}_cell"])
+        assert float(z[f"pair{i}_radius"]) == r and torch.equal(pos, gu.threshold_pair(y)[0])
+        d2 = (pos[1] ** 2).sum().numpy()
+        assert d2 == np.float32(r) * np.float32(r) and d2 > np.float32(r * r)
+        assert z[f"pair{i}_edge_index"].shape == (2, 0)
+        assert radius_graph_pbc_single(pos, cell, r)[0].shape == (2, 0)
+        ei, dist, dirn = radius_graph_pbc_single(pos, cell, float(z[f"pair{i}_radius_up"]))
+        assert ei.tolist() == [[1, 0], [0, 1]] and torch.equal(ei, torch.from_numpy(z[f"pair{i}_up_edge_index"]))
+        assert torch.equal(dist, torch.from_numpy(z[f"pair{i}_up_dist"]))
+        assert torch.equal(dirn, torch.from_numpy(z[f"pair{i}_up_dir"]))
+
+
 def test_equivariance_of_the_oracle():
     """Rotating cart_dir by R rotates the predicted ADP tensors: pred' = R^T pred R (reference main.py:96-97)."""
     from cartnet_amd.synthetic import random_rotation

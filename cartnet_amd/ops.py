@@ -550,18 +550,22 @@ def bn_finalize(parts_sum, parts_sq, nparts: int, count: int, Cc: int, eps: floa
              "cartnet_bn_finalize")
 
 
-def _edge_rows(t: Tensor, E: int, W: int, name: str) -> None:
-    _f32_2d(t, name)
+def _edge_rows(t: Tensor, E: int, W: int, name: str, half_ok: bool = False) -> None:
+    _f32_2d(t, name, half_ok=half_ok)
     if tuple(t.shape) != (E, W) or not t.is_contiguous():
         raise ValueError(f"{name}: expected contiguous [{E},{W}], got {tuple(t.shape)}")
 
 
 def gate_scatter_fwd(gs, e_in, env, layout: GraphLayout, mean_rstd, gamma, beta, e_out, aggr, parts_sum,
                      parts_sq, bc=None) -> None:
-    """``bc`` [N, 2D] (optional): cartnet_gate_scatter_fwd_bc -- per target also sum s w | sum s w ghat for the backward pass."""
+    """``bc`` [N, 2D] (optional): cartnet_gate_scatter_fwd_bc -- per target also sum s w | sum s w ghat for the backward pass.
+    A bf16 ``gs`` (half storage) runs cartnet_gate_scatter_fwd_h; the library has no bf16 form with ``bc``."""
     E, N = layout.E, layout.N
     D = int(aggr.shape[1])
-    _edge_rows(gs, E, 2 * D, "gate_scatter_fwd gs")
+    half = torch.is_tensor(gs) and gs.dtype == torch.bfloat16
+    _edge_rows(gs, E, 2 * D, "gate_scatter_fwd gs", half_ok=True)
+    if half and bc is not None:
+        raise ValueError("gate_scatter_fwd: bc needs an fp32 gs (no bf16 form of cartnet_gate_scatter_fwd_bc)")
     if (e_in is None) != (e_out is None):
         raise ValueError("gate_scatter_fwd: e_in and e_out must both be given or both be None")
     if e_in is not None:
@@ -583,11 +587,10 @@ def gate_scatter_fwd(gs, e_in, env, layout: GraphLayout, mean_rstd, gamma, beta,
                                                        parts_sq.data_ptr(), bc.data_ptr(), _l.stream_ptr()),
                  "cartnet_gate_scatter_fwd_bc")
         return
-    _l.check(_l.load().cartnet_gate_scatter_fwd(gs.data_ptr(), _l.ptr(e_in), _l.ptr(env), layout.rowptr.data_ptr(),
-                                                mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), N, D,
-                                                _l.ptr(e_out), aggr.data_ptr(), parts_sum.data_ptr(),
-                                                parts_sq.data_ptr(), None, _l.stream_ptr()),
-             "cartnet_gate_scatter_fwd")
+    fn = _l.load().cartnet_gate_scatter_fwd_h if half else _l.load().cartnet_gate_scatter_fwd
+    _l.check(fn(gs.data_ptr(), _l.ptr(e_in), _l.ptr(env), layout.rowptr.data_ptr(), mean_rstd.data_ptr(), gamma.data_ptr(),
+                beta.data_ptr(), N, D, _l.ptr(e_out), aggr.data_ptr(), parts_sum.data_ptr(), parts_sq.data_ptr(), None,
+                _l.stream_ptr()), "cartnet_gate_scatter_fwd")
 
 
 def gate_gemm_eval(pre: Tensor, img_gate: Tensor, img_aggr: Tensor, bias_gate: Tensor, bias_aggr: Tensor, mean_rstd: Tensor,
@@ -629,9 +632,11 @@ def gate_gemm_eval(pre: Tensor, img_gate: Tensor, img_aggr: Tensor, bias_gate: T
 
 def gate_scatter_bwd_stats(gs, de_out, daggr, env, layout: GraphLayout, mean_rstd, gamma, beta, parts_a,
                            parts_b) -> None:
+    """A bf16 ``gs`` (half storage) runs cartnet_gate_scatter_bwd_stats_h."""
     E, N = layout.E, layout.N
     D = int(daggr.shape[1])
-    _edge_rows(gs, E, 2 * D, "gate_scatter_bwd_stats gs")
+    half = torch.is_tensor(gs) and gs.dtype == torch.bfloat16
+    _edge_rows(gs, E, 2 * D, "gate_scatter_bwd_stats gs", half_ok=True)
     if de_out is not None:
         _edge_rows(de_out, E, D, "gate_scatter_bwd_stats de_out")
     _edge_rows(daggr, N, D, "gate_scatter_bwd_stats daggr")
@@ -642,7 +647,8 @@ def gate_scatter_bwd_stats(gs, de_out, daggr, env, layout: GraphLayout, mean_rst
     npart = gate_nparts(N)
     _vec(parts_a, npart * D, "parts_a", torch.float64)
     _vec(parts_b, npart * D, "parts_b", torch.float64)
-    _l.check(_l.load().cartnet_gate_scatter_bwd_stats(
+    fn = _l.load().cartnet_gate_scatter_bwd_stats_h if half else _l.load().cartnet_gate_scatter_bwd_stats
+    _l.check(fn(
         gs.data_ptr(), _l.ptr(de_out), daggr.data_ptr(), _l.ptr(env), layout.rowptr.data_ptr(),
         mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), N, D, parts_a.data_ptr(), parts_b.data_ptr(), None,
         _l.stream_ptr()), "cartnet_gate_scatter_bwd_stats")
@@ -650,9 +656,11 @@ def gate_scatter_bwd_stats(gs, de_out, daggr, env, layout: GraphLayout, mean_rst
 
 def gate_scatter_bwd_apply(gs, de_out, daggr, env, layout: GraphLayout, mean_rstd, gamma, beta, sums, training: bool,
                            parts_dg, parts_ds) -> None:
+    """In place: gs <- dg | ds.  A bf16 ``gs`` (half storage) runs cartnet_gate_scatter_bwd_apply_h, which stores them as bf16."""
     E, N = layout.E, layout.N
     D = int(daggr.shape[1])
-    _edge_rows(gs, E, 2 * D, "gate_scatter_bwd_apply gs")
+    half = torch.is_tensor(gs) and gs.dtype == torch.bfloat16
+    _edge_rows(gs, E, 2 * D, "gate_scatter_bwd_apply gs", half_ok=True)
     if de_out is not None:
         _edge_rows(de_out, E, D, "gate_scatter_bwd_apply de_out")
     _edge_rows(daggr, N, D, "gate_scatter_bwd_apply daggr")
@@ -664,7 +672,8 @@ def gate_scatter_bwd_apply(gs, de_out, daggr, env, layout: GraphLayout, mean_rst
     npart = gate_nparts(N)
     _vec(parts_dg, npart * D, "parts_dg", torch.float64)
     _vec(parts_ds, npart * D, "parts_ds", torch.float64)
-    _l.check(_l.load().cartnet_gate_scatter_bwd_apply(
+    fn = _l.load().cartnet_gate_scatter_bwd_apply_h if half else _l.load().cartnet_gate_scatter_bwd_apply
+    _l.check(fn(
         gs.data_ptr(), _l.ptr(de_out), daggr.data_ptr(), _l.ptr(env), layout.rowptr.data_ptr(),
         mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), sums.data_ptr(), E, int(training), N, D,
         parts_dg.data_ptr(), parts_ds.data_ptr(), None, _l.stream_ptr()), "cartnet_gate_scatter_bwd_apply")

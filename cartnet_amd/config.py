@@ -52,6 +52,7 @@ def _defaults() -> _Node:
         use_atom_types=True,
         workers=0,
         device="cuda:0",
+        shard_dir=None,
     )
 
 

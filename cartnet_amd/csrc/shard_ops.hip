@@ -27,36 +27,6 @@
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// inclusive scan over the 64 lanes of a wavefront
-__device__ __forceinline__ int so_wave_scan(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    const int t = __shfl_up(v, d, WAVE);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-// exclusive prefix of v over the workgroup's 256 threads, `total` = the workgroup's sum; lds: 4 words, reusable on return
-__device__ __forceinline__ int so_block_scan(int v, int* lds, int& total) {
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x >> 6;
-  const int inc = so_wave_scan(v, lane);
-  if (lane == WAVE - 1) lds[wid] = inc;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < SO_THREADS / WAVE; ++w) {
-    const int s = lds[w];
-    if (w < wid) off += s;
-    tot += s;
-  }
-  __syncthreads();
-  total = tot;
-  return off + inc - v;
-}
-
 __device__ __forceinline__ void so_block_sum_store(int v, int* lds, int32_t* out) {
   int total;
   so_block_scan(v, lds, total);
@@ -67,16 +37,6 @@ __device__ __forceinline__ void so_block_sum_store(int v, int* lds, int32_t* out
 __device__ __forceinline__ void so_store_starts(const int64_t* __restrict__ ptr, int64_t* __restrict__ out, int g,
                                                 int64_t i, int64_t rank) {
   for (int q = g; q >= 0 && ptr[q] == i; --q) out[q] = rank;
-}
-
-__device__ __forceinline__ void so_load4(const int32_t* __restrict__ a, int64_t i0, int64_t n, int v[SO_ITEMS], int fill) {
-  if (i0 + SO_ITEMS <= n) {
-    const i32x4 t = *reinterpret_cast<const i32x4*>(a + i0);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < SO_ITEMS; ++k) v[k] = i0 + k < n ? a[i0 + k] : fill;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------- atoms
@@ -100,29 +60,10 @@ __global__ __launch_bounds__(SO_THREADS) void cn_so_atom_count(const int32_t* __
   so_block_sum_store(cnt, lds, tile_sum + blockIdx.x);
 }
 
-// offs[t] = sum of sums[0..t), offs[nT] = *total = the sum of all; one workgroup
 __global__ __launch_bounds__(SO_THREADS) void cn_so_tile_scan(const int32_t* __restrict__ sums, int64_t nT,
                                                               int64_t* __restrict__ offs, int64_t* __restrict__ total) {
-  __shared__ int lds[SO_THREADS / WAVE];
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nT; base += SO_TILE) {
-    const int64_t i0 = base + threadIdx.x * SO_ITEMS;
-    int v[SO_ITEMS];
-    so_load4(sums, i0, nT, v, 0);
-    int tot;
-    const int ex = so_block_scan(v[0] + v[1] + v[2] + v[3], lds, tot);      // <= 1024 * 1024 per round
-    int64_t r = carry + ex;
-#pragma unroll
-    for (int k = 0; k < SO_ITEMS; ++k) {
-      if (i0 + k < nT) offs[i0 + k] = r;
-      r += v[k];
-    }
-    carry += tot;
-  }
-  if (threadIdx.x == 0) {
-    offs[nT] = carry;
-    *total = carry;
-  }
+  __shared__ int64_t lds[SO_THREADS / WAVE];
+  so_tile_scan(sums, nT, offs, total, lds);
 }
 
 __global__ __launch_bounds__(SO_THREADS) void cn_so_atom_rank(const int32_t* __restrict__ z,

@@ -337,6 +337,14 @@ PROTOTYPES = {
                                              c_stream]),
     "cartnet_neighbor_cap_fill": (C.c_int, [c_i64p, c_i64p, c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, C.c_int32,
                                             C.c_int64, C.c_int64, c_i64p, c_f32p, c_f32p, c_stream]),
+    "cartnet_shard_regraph_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "cartnet_shard_regraph_count": (C.c_int, [c_f32p, c_f32p, c_i64p, C.c_int32, C.c_int64, C.c_double, C.c_int32,
+                                              C.c_void_p, C.c_size_t, c_i64p, c_stream]),
+    "cartnet_shard_regraph_cap": (C.c_int, [c_f32p, c_f32p, c_i64p, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_float,
+                                            C.c_int64, C.c_void_p, C.c_size_t, c_f32p, c_i64p, c_stream]),
+    "cartnet_shard_regraph_fill": (C.c_int, [c_f32p, c_f32p, c_i64p, C.c_int32, C.c_int64, C.c_double, C.c_int32,
+                                             C.c_void_p, C.c_size_t, C.c_int64, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p,
+                                             c_stream]),
     "cartnet_loss_nparts": (C.c_int32, [C.c_int64]),
     "cartnet_loss_fwd": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_void_p, c_f32p, c_stream]),
     "cartnet_loss_bwd": (C.c_int, [c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_stream]),

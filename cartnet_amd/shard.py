@@ -14,7 +14,9 @@ as uint64 right after the magic) listing ``{"name": [dtype, shape, offset]}``, t
     cell [G,9] f32 | temperature [G] f32 | y [Y, y_width] f32 (y_width 9: one ADP tensor per non-H atom)
 
 ``pos``, ``non_h_mask``, ``cell`` and ``temperature`` are optional (the Jarvis / MP graphs carry no mask or
-temperature).
+temperature).  A geometry-only shard leaves out ``edge_ptr`` and the four edge arrays and must carry ``pos`` and
+``cell``: ``DeviceShard.with_radius_graph`` builds its graph on the GPU.  The header may record the graph's provenance,
+``"graph": {"radius": r, "max_neighbors": k or null}`` (``read_shard_meta``).
 """
 from __future__ import annotations
 
@@ -31,28 +33,47 @@ from .data import Batch, Data
 MAGIC = b"CNSHARD1"
 _ALIGN = 64
 _OPTIONAL = ("pos", "non_h_mask", "cell", "temperature")
+_EDGE_ARRAYS = ("edge_ptr", "edge_src", "edge_tgt", "cart_dist", "cart_dir")
+
+
+def graph_record(radius: float, max_neighbors: Optional[int] = None) -> Dict[str, object]:
+    """The provenance record of a radius graph: ``{"radius": r, "max_neighbors": k or None}`` (a cap <= 0 is no cap)."""
+    k = int(max_neighbors) if max_neighbors is not None and int(max_neighbors) > 0 else None
+    return {"radius": float(radius), "max_neighbors": k}
 
 
 def pack(data_list: Sequence[Data]) -> Dict[str, np.ndarray]:
-    """Flat CSR arrays of a list of crystals (the attribute set of cartnet_amd.data / SURVEY.md 8a)."""
+    """Flat CSR arrays of a list of crystals (the attribute set of cartnet_amd.data / SURVEY.md 8a).  Crystals without
+    ``edge_index`` -- all of the list or none -- give a geometry-only shard (no ``edge_ptr``, no edge arrays), which needs
+    ``pos`` and ``cell``."""
     if len(data_list) == 0:
         raise ValueError("cannot pack an empty list of crystals")
+    with_edges = [hasattr(d, "edge_index") for d in data_list]
+    if any(with_edges) and not all(with_edges):
+        raise ValueError("crystals with and without edge_index in one list: a shard carries the graph of all its crystals "
+                         "or of none")
+    d0 = data_list[0]
+    if not with_edges[0] and not all(hasattr(d, "pos") and hasattr(d, "cell") for d in data_list):
+        raise ValueError("a crystal without edge_index needs pos and cell (DeviceShard.with_radius_graph builds the graph)")
     n = [int(d.x.shape[0]) for d in data_list]
-    e = [int(d.edge_index.shape[1]) for d in data_list]
-    per_atom = data_list[0].y.dim() == 3
+    per_atom = d0.y.dim() == 3
     ys = [d.y.reshape(-1, 9) if per_atom else d.y.reshape(1, -1) for d in data_list]
+    e = [int(d.edge_index.shape[1]) for d in data_list] if with_edges[0] else []
+
+    def edge(make):                       # an edge array, in its place in the file's array order; None for geometry only
+        return make() if with_edges[0] else None
     out = {
         "atom_ptr": np.concatenate([[0], np.cumsum(n)]).astype(np.int64),
-        "edge_ptr": np.concatenate([[0], np.cumsum(e)]).astype(np.int64),
+        "edge_ptr": edge(lambda: np.concatenate([[0], np.cumsum(e)]).astype(np.int64)),
         "y_ptr": np.concatenate([[0], np.cumsum([y.shape[0] for y in ys])]).astype(np.int64),
         "z": torch.cat([d.x for d in data_list]).numpy().astype(np.int32),
-        "edge_src": torch.cat([d.edge_index[0] for d in data_list]).numpy().astype(np.int32),
-        "edge_tgt": torch.cat([d.edge_index[1] for d in data_list]).numpy().astype(np.int32),
-        "cart_dist": torch.cat([d.cart_dist for d in data_list]).numpy().astype(np.float32),
-        "cart_dir": torch.cat([d.cart_dir for d in data_list]).numpy().astype(np.float32).reshape(-1, 3),
+        "edge_src": edge(lambda: torch.cat([d.edge_index[0] for d in data_list]).numpy().astype(np.int32)),
+        "edge_tgt": edge(lambda: torch.cat([d.edge_index[1] for d in data_list]).numpy().astype(np.int32)),
+        "cart_dist": edge(lambda: torch.cat([d.cart_dist for d in data_list]).numpy().astype(np.float32)),
+        "cart_dir": edge(lambda: torch.cat([d.cart_dir for d in data_list]).numpy().astype(np.float32).reshape(-1, 3)),
         "y": torch.cat(ys).numpy().astype(np.float32),
     }
-    d0 = data_list[0]
+    out = {k: v for k, v in out.items() if v is not None}
     if hasattr(d0, "pos"):
         out["pos"] = torch.cat([d.pos for d in data_list]).numpy().astype(np.float32).reshape(-1, 3)
     if hasattr(d0, "non_H_mask"):
@@ -62,7 +83,7 @@ def pack(data_list: Sequence[Data]) -> Dict[str, np.ndarray]:
     if hasattr(d0, "temperature"):
         out["temperature"] = torch.cat([d.temperature.reshape(1) for d in data_list]).numpy().astype(np.float32)
     for i, d in enumerate(data_list):
-        if e[i] and bool((d.edge_index[1][1:] < d.edge_index[1][:-1]).any()):
+        if with_edges[0] and e[i] and bool((d.edge_index[1][1:] < d.edge_index[1][:-1]).any()):
             raise ValueError(f"crystal {i}: edge_index[1] must be sorted ascending")
     return out
 
@@ -116,13 +137,23 @@ def pack_with_gpu_graph(geometries: Sequence[Data], radius: float = 5.0, device=
     return out
 
 
-def write_shard(path: str, data_list: Sequence[Data]) -> None:
+def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, object]] = None) -> None:
+    """``graph``: how the crystals' edges were built, ``{"radius": r, "max_neighbors": k or None}``; recorded in the
+    header, so that a loader can tell whether the graph it wants is the one stored (the reference's cached-directory test,
+    dataset/utils.py:462-464)."""
     arrays = pack(data_list)
+    if graph is not None:
+        if "edge_ptr" not in arrays:
+            raise ValueError("a geometry-only shard has no graph to record")
+        graph = graph_record(graph["radius"], graph.get("max_neighbors"))
     meta, off = {}, 0
     for k, a in arrays.items():
         meta[k] = [a.dtype.str, list(a.shape), off]
         off += (a.nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
-    header = json.dumps({"arrays": meta, "graphs": len(data_list)}).encode()
+    head = {"arrays": meta, "graphs": len(data_list)}
+    if graph is not None:
+        head["graph"] = graph
+    header = json.dumps(head).encode()
     header += b" " * (-(len(MAGIC) + 8 + len(header)) % _ALIGN)
     with open(path, "wb") as f:
         f.write(MAGIC)
@@ -133,14 +164,22 @@ def write_shard(path: str, data_list: Sequence[Data]) -> None:
             f.write(b"\0" * (-a.nbytes % _ALIGN))
 
 
-def read_shard(path: str) -> Dict[str, np.ndarray]:
-    """Memory-maps the arrays of a shard file (no copy until they are uploaded)."""
+def _read_header(path: str):
     with open(path, "rb") as f:
         if f.read(8) != MAGIC:
             raise ValueError(f"{path}: not a CartNet shard")
         (hlen,) = struct.unpack("<Q", f.read(8))
-        meta = json.loads(f.read(hlen).decode())
-    base = 16 + hlen
+        return json.loads(f.read(hlen).decode()), 16 + hlen
+
+
+def read_shard_meta(path: str) -> Dict[str, object]:
+    """The JSON header of a shard file: ``arrays``, ``graphs`` and, if it was recorded, ``graph``."""
+    return _read_header(path)[0]
+
+
+def read_shard(path: str) -> Dict[str, np.ndarray]:
+    """Memory-maps the arrays of a shard file (no copy until they are uploaded)."""
+    meta, base = _read_header(path)
     out = {}
     for k, (dt, shape, off) in meta["arrays"].items():
         out[k] = np.memmap(path, dtype=np.dtype(dt), mode="r", offset=base + off, shape=tuple(shape))
@@ -148,22 +187,30 @@ def read_shard(path: str) -> Dict[str, np.ndarray]:
 
 
 class DeviceShard:
-    """A shard resident in HBM.  ``collate(sel)`` builds the batch of crystals ``sel`` with one kernel launch."""
+    """A shard resident in HBM.  ``collate(sel)`` builds the batch of crystals ``sel`` with one kernel launch.
+    ``graph``: the provenance of its edges, ``{"radius": r, "max_neighbors": k or None}``, or None when unknown.  A
+    geometry-only shard (``has_graph`` False: ``pos`` and ``cell`` but no edge arrays) only serves ``with_radius_graph``."""
 
-    def __init__(self, arrays: Dict[str, np.ndarray], device="cuda:0"):
+    def __init__(self, arrays: Dict[str, np.ndarray], device="cuda:0", graph: Optional[Dict[str, object]] = None):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError("DeviceShard lives on the GPU; there is no CPU path (use Batch.from_data_list on the host)")
-        need = ("atom_ptr", "edge_ptr", "y_ptr", "z", "edge_src", "edge_tgt", "cart_dist", "cart_dir", "y")
+        need = ("atom_ptr", "y_ptr", "z", "y")
+        if any(k in arrays for k in _EDGE_ARRAYS):
+            need += _EDGE_ARRAYS
+        else:
+            need += ("pos", "cell")                                 # geometry only: with_radius_graph() needs both
         missing = [k for k in need if k not in arrays]
         if missing:
             raise ValueError(f"shard lacks {missing}")
         self.device = dev
+        self.graph = graph_record(graph["radius"], graph.get("max_neighbors")) if graph is not None else None
         # host copies of the offsets: batch sizes are known without a device round trip
         self.atom_ptr = np.asarray(arrays["atom_ptr"], dtype=np.int64)
-        self.edge_ptr = np.asarray(arrays["edge_ptr"], dtype=np.int64)
-        self.y_ptr = np.asarray(arrays["y_ptr"], dtype=np.int64)
         self.num_graphs = int(self.atom_ptr.shape[0] - 1)
+        self.edge_ptr = (np.asarray(arrays["edge_ptr"], dtype=np.int64) if "edge_ptr" in arrays
+                         else np.zeros(self.num_graphs + 1, dtype=np.int64))
+        self.y_ptr = np.asarray(arrays["y_ptr"], dtype=np.int64)
         for name, p in (("atom_ptr", self.atom_ptr), ("edge_ptr", self.edge_ptr), ("y_ptr", self.y_ptr)):
             if p.shape[0] != self.num_graphs + 1 or p[0] != 0 or bool((np.diff(p) < 0).any()):
                 raise ValueError(f"{name} is not a valid offset array")
@@ -192,7 +239,7 @@ class DeviceShard:
 
     @classmethod
     def from_file(cls, path: str, device="cuda:0") -> "DeviceShard":
-        return cls(read_shard(path), device)
+        return cls(read_shard(path), device, graph=read_shard_meta(path).get("graph"))
 
     @classmethod
     def from_data_list(cls, data_list: Sequence[Data], device="cuda:0") -> "DeviceShard":
@@ -201,6 +248,74 @@ class DeviceShard:
     def nbytes(self) -> int:
         return sum(v.numel() * v.element_size() for v in self.t.values())
 
+    @property
+    def has_graph(self) -> bool:
+        return "edge_src" in self.t
+
+    def _need_graph(self, what: str) -> None:
+        if not self.has_graph:
+            raise ValueError(f"{what}: this shard holds only geometry; build its graph first with with_radius_graph()")
+
+    def _derived(self, new: Dict[str, torch.Tensor], atom_ptr: np.ndarray, edge_ptr: np.ndarray,
+                 graph: Optional[Dict[str, object]]) -> "DeviceShard":
+        """A resident shard that owns the tensors in ``new`` and shares every other one with this shard."""
+        out = object.__new__(DeviceShard)
+        out.device, out.num_graphs, out._lib, out.graph = self.device, self.num_graphs, self._lib, graph
+        out.atom_ptr, out.edge_ptr, out.y_ptr = atom_ptr, edge_ptr, self.y_ptr
+        out.t = {**self.t, **new}
+        out._describe()
+        return out
+
+    def with_radius_graph(self, radius: float = 5.0, max_neighbors: Optional[int] = None) -> "DeviceShard":
+        """The same crystals with the periodic radius graph of ``radius`` (capped at ``max_neighbors`` per target atom,
+        None or <= 0: uncapped) rebuilt from ``pos`` and ``cell``, as a new resident shard (this one is untouched): what the
+        reference's ``compute_knn`` does per file on the CPU before an e/iComformer run on ADP (dataset/utils.py:456-486,
+        loader/loader.py:24-26) and ``Figshare_Dataset.process`` for Jarvis / MegNet (dataset/figshare_dataset.py:50-76),
+        done in one pass over the whole shard on the GPU (csrc/radius_graph.hip) -- the edges, order and arithmetic of
+        ``cartnet_amd.graph.radius_graph_pbc``.  The new shard owns ``edge_ptr``, ``edge_src``, ``edge_tgt``,
+        ``cart_dist`` and ``cart_dir``; every other array is shared.  The host reads two sizes and a status word; with a
+        cap that some atom exceeds the only transient edge-sized array is the uncapped rows' d^2 (4 B per edge).  Apply it
+        BEFORE ``without_hydrogens()`` / ``with_optimized_cell()``, as the reference caps the graph of the full crystal in
+        the stored frame."""
+        t, dev, G = self.t, self.device, self.num_graphs
+        if "pos" not in t or "cell" not in t:
+            raise ValueError("with_radius_graph needs the shard's pos and cell")
+        if not float(radius) > 0.0:
+            raise ValueError("radius must be positive")
+        N = int(self.atom_ptr[-1])
+        cap = int(max_neighbors) if max_neighbors is not None and int(max_neighbors) > 0 else 0
+        from .graph import DEGENERACY_TOLERANCE
+        lib = self._lib
+        with torch.cuda.device(dev):
+            args = (t["pos"].data_ptr(), t["cell"].data_ptr(), t["atom_ptr"].data_ptr(), G, N, float(radius))
+            ws_bytes = int(lib.cartnet_shard_regraph_workspace_bytes(G, N, 0))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(4, dtype=torch.int64, device=dev)
+            _l.check(lib.cartnet_shard_regraph_count(*args, cap, ws.data_ptr(), ws_bytes, totals.data_ptr(),
+                                                     _l.stream_ptr()), "cartnet_shard_regraph_count")
+            e_all, _, over, status = totals.tolist()            # device-to-host copy 1: the uncapped size
+            if status != 0:
+                raise ValueError("the shard's atom_ptr is not an ascending offset array over its atoms")
+            E = e_all
+            if over:                                             # some atom has more than `cap` neighbours
+                d2 = torch.empty(e_all, dtype=torch.float32, device=dev)
+                _l.check(lib.cartnet_shard_regraph_cap(*args, cap, DEGENERACY_TOLERANCE, e_all, ws.data_ptr(), ws_bytes,
+                                                       d2.data_ptr(), totals.data_ptr(), _l.stream_ptr()),
+                         "cartnet_shard_regraph_cap")
+                E = int(totals[1].item())                        # device-to-host copy 2: the capped size
+            new = {"edge_ptr": torch.empty(G + 1, dtype=torch.int64, device=dev),
+                   "edge_src": torch.empty(E, dtype=torch.int32, device=dev),
+                   "edge_tgt": torch.empty(E, dtype=torch.int32, device=dev),
+                   "cart_dist": torch.empty(E, dtype=torch.float32, device=dev),
+                   "cart_dir": torch.empty((E, 3), dtype=torch.float32, device=dev)}
+            _l.check(lib.cartnet_shard_regraph_fill(*args, int(bool(over)), ws.data_ptr(), ws_bytes, E,
+                                                    new["edge_ptr"].data_ptr(), new["edge_src"].data_ptr(),
+                                                    new["edge_tgt"].data_ptr(), new["cart_dist"].data_ptr(),
+                                                    new["cart_dir"].data_ptr(), _l.stream_ptr()),
+                     "cartnet_shard_regraph_fill")
+            edge_ptr = new["edge_ptr"].cpu().numpy()            # ShardLoader balances ranks by it
+        return self._derived(new, self.atom_ptr, edge_ptr, graph_record(radius, cap))
+
     def without_hydrogens(self) -> "DeviceShard":
         """The same crystals without their hydrogen atoms, as a new resident shard (this one is untouched): what the
         reference's ``DatasetADP(hydrogens=False)`` does per crystal and per access on the host
@@ -208,6 +323,7 @@ class DeviceShard:
         whole shard by a stable compaction on the GPU (csrc/shard_ops.hip).  ``y``, ``y_ptr``, ``cell`` and
         ``temperature`` are shared with this shard.  Raises ``ValueError`` if a stored ``non_h_mask`` disagrees with
         ``z != 1``: the rows of a per-atom ``y`` would no longer line up with the kept atoms."""
+        self._need_graph("without_hydrogens")
         dev, t, G = self.device, self.t, self.num_graphs
         N, E = int(self.atom_ptr[-1]), int(self.edge_ptr[-1])
         with torch.cuda.device(dev):
@@ -241,12 +357,7 @@ class DeviceShard:
                 new["edge_src"].data_ptr(), new["edge_tgt"].data_ptr(), new["cart_dist"].data_ptr(),
                 new["cart_dir"].data_ptr(), _l.stream_ptr()), "cartnet_shard_drop_h_fill")
             ptrs = torch.stack((atom_ptr, edge_ptr)).cpu().numpy()      # ShardLoader balances ranks by these
-        out = object.__new__(DeviceShard)
-        out.device, out.num_graphs, out._lib = dev, G, self._lib
-        out.atom_ptr, out.edge_ptr, out.y_ptr = ptrs[0].copy(), ptrs[1].copy(), self.y_ptr
-        out.t = {k: new[k] if k in new else v for k, v in t.items()}
-        out._describe()
-        return out
+        return self._derived(new, ptrs[0].copy(), ptrs[1].copy(), self.graph)
 
     def with_optimized_cell(self) -> "DeviceShard":
         """The same crystals, each in the frame of its canonical reduced lattice, as a new resident shard (this one is
@@ -257,6 +368,7 @@ class DeviceShard:
         [G,9] fp32 (R per crystal) and ``basis`` [G,9] int8 (the signed integer coefficients of the three chosen vectors in
         the rows of the old cell).  Composes with ``without_hydrogens()`` in either order.  Raises ``ValueError`` naming
         the first crystal whose cell is degenerate (no three independent vectors among the candidates)."""
+        self._need_graph("with_optimized_cell")
         dev, t, G = self.device, self.t, self.num_graphs
         if "cell" not in t:
             raise ValueError("the shard carries no cell")
@@ -280,17 +392,13 @@ class DeviceShard:
         if bad >= 0:
             raise ValueError(f"crystal {bad}: degenerate cell: no three linearly independent lattice vectors among the "
                              "candidates")
-        out = object.__new__(DeviceShard)
-        out.device, out.num_graphs, out._lib = dev, G, self._lib
-        out.atom_ptr, out.edge_ptr, out.y_ptr = self.atom_ptr, self.edge_ptr, self.y_ptr
-        out.t = {**t, **new}
-        out._describe()
-        return out
+        return self._derived(new, self.atom_ptr, self.edge_ptr, self.graph)
 
     def collate(self, sel: Sequence[int], rot: Optional[torch.Tensor] = None, temp_mean: float = 0.0,
                 temp_std: float = 1.0) -> Batch:
         """Batch of crystals ``sel`` (in that order) with PyG's collation rules (cartnet_amd/data.py), on the GPU.
         ``rot`` [B,3,3] fp32 (device): per-crystal augmentation rotation (dataset/datasetADP.py:33-39)."""
+        self._need_graph("collate")
         sel_np = np.asarray(sel, dtype=np.int64).reshape(-1)
         B = int(sel_np.shape[0])
         if B == 0:

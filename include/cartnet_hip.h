@@ -308,6 +308,41 @@ int cartnet_neighbor_cap_fill(const int64_t* rowptr, const int64_t* rowptr_out, 
                               float* cart_dist_out, float* cart_dir_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * The radius graph of a whole resident shard, rebuilt on the GPU (reference: dataset/utils.py:456-486 compute_knn as
+ * called at loader/loader.py:24-26 -- the capped graph of every ADP crystal rebuilt from pos and cell, one file at a
+ * time on the CPU, dense O(N^2 images) -- and dataset/figshare_dataset.py:50-76, Figshare_Dataset.process at --radius /
+ * --max_neighbours).  Same edges, same order and same arithmetic as cartnet_radius_graph_count / _fill followed by
+ * cartnet_neighbor_cap_count / _fill on the same crystals, written in the shard's format: edge_ptr [G+1] int64,
+ * edge_src / edge_tgt int32 atom indices inside the crystal, cart_dist, cart_dir.  pos [N,3], cell [G,9] and atom_ptr
+ * [G+1] are the shard descriptor's; the crystal of an atom is found on the device.  max_neighbors <= 0: no cap.
+ *   workspace_bytes(G, N, E_uncapped): all the transient memory of a pass.  workspace_bytes(G, N, 0) = O(N + G) bytes is
+ *          the `workspace` of the three calls below (kept from count to fill, 16-byte aligned); the rest, 4 bytes per
+ *          uncapped edge, is the dist_sq scratch of cap -- needed only when some row is longer than the cap.
+ *   count: uncapped in-degree of every atom and its prefix sum.  totals [4] int64 (device): [0] uncapped edge count,
+ *          [1] capped edge count (written by cap), [2] 1 if max_neighbors > 0 and some atom has more neighbours,
+ *          [3] status -- 0 ok, 1 atom_ptr is not an ascending offset array from 0 to N.  The caller reads totals.
+ *   cap:   only if totals[2]: dist_sq [E_uncapped] <- d^2 of the uncapped rows (4 B per edge, no indices, no directions),
+ *          the per-row cutoff by rank counting (dataset/utils.py:240-360 get_max_neighbors_mask, enforce_max_strictly =
+ *          False: d^2 <= (max_neighbors+1)-th smallest + tolerance, ties kept), the capped degrees and their prefix
+ *          sum; totals[1] = capped edge count.  The caller reads it.
+ *   fill:  E = totals[capped ? 1 : 0]; walks the images again and writes the edges with d^2 <= cutoff of their row
+ *          straight into edge_src / edge_tgt [E], cart_dist [E], cart_dir [E,3], and edge_ptr [G+1].
+ * One wavefront per target atom and a wave prefix sum, reduce-then-scan row offsets: no atomics, identical bytes on every
+ * run.  The host reads sizes and the status word, nothing else.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t cartnet_shard_regraph_workspace_bytes(int32_t G, int64_t N, int64_t E_uncapped);
+int cartnet_shard_regraph_count(const float* pos, const float* cell, const int64_t* atom_ptr, int32_t G, int64_t N,
+                                double radius, int32_t max_neighbors, void* workspace, size_t workspace_bytes,
+                                int64_t* totals, void* stream);
+int cartnet_shard_regraph_cap(const float* pos, const float* cell, const int64_t* atom_ptr, int32_t G, int64_t N,
+                              double radius, int32_t max_neighbors, float tolerance, int64_t E_uncapped, void* workspace,
+                              size_t workspace_bytes, float* dist_sq, int64_t* totals, void* stream);
+int cartnet_shard_regraph_fill(const float* pos, const float* cell, const int64_t* atom_ptr, int32_t G, int64_t N,
+                               double radius, int32_t capped, const void* workspace, size_t workspace_bytes, int64_t E,
+                               int64_t* edge_ptr, int32_t* edge_src, int32_t* edge_tgt, float* cart_dist, float* cart_dir,
+                               void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * ADP evaluation metrics (reference: train/metrics.py, called per test batch from
  * train/metrics.py:201-214 and main.py:47-49,101-102).  pred, truth: [M,3,3] fp32 symmetric positive definite.
  *   volume_error[M]     = |V(pred) - V(truth)| / (V(pred) + 1e-8), V = 4/3 pi sqrt(det)      (metrics.py:30-58)

@@ -9,7 +9,9 @@ with the last-iteration flush, best-validation checkpoint ``{"model_state", "opt
 What differs: the datasets (CSD / Jarvis need licences or the network) are replaced by synthetic ADP-shaped crystals
 (``--synthetic N`` graphs, ``--atoms lo hi``), wandb / GraphGym logging are dropped, ``--device`` replaces the hard-coded
 "cuda:0", and under ``torch.distributed.run`` the crystals are sharded across ranks with one gradient all-reduce per
-optimiser step.  There is no CPU path: the model runs on an AMD GPU only.
+optimiser step.  ``--shard_dir DIR`` trains from packed shard files (cartnet_amd/shard.py) instead of synthetic crystals:
+the reference's dataset recipe -- graph, hydrogen removal, canonical cell, temperature standardisation -- is applied to the
+resident shards in the reference's order.  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ import argparse
 import json
 import os
 import time
+from typing import Optional, Tuple
 
 import torch
 
@@ -87,6 +90,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "with --fused_accumulation")
     p.add_argument("--resident_dataset", action="store_true",
                    help="keep the splits as packed shards in HBM and build every batch (and its augmentation) on the GPU")
+    p.add_argument("--shard_dir", type=str, default=None,
+                   help="train from DIR/train.cnshard, val.cnshard and test.cnshard (tools/make_shards.py writes such a "
+                        "directory) instead of synthetic crystals: implies --resident_dataset, ignores --synthetic and "
+                        "--atoms; the radius graph is rebuilt on the GPU where the reference would rebuild it")
     return p
 
 
@@ -109,6 +116,7 @@ def fill_cfg(args) -> None:
     cfg.envelope, cfg.use_H, cfg.use_atom_types = args.disable_envelope, args.disable_H, args.disable_atom_types
     cfg.workers = args.workers
     cfg.device = args.device
+    cfg.shard_dir = args.shard_dir
     cfg.gemm_precision = args.gemm_precision
     cfg.bn_group_size = 0
     cfg.half_storage = bool(args.bf16_storage) and cfg.model == "CartNet" and args.gemm_precision == 2
@@ -120,8 +128,56 @@ def fill_cfg(args) -> None:
         cfg.batch, cfg.batch_accumulation = cfg.batch * cfg.batch_accumulation, 1
 
 
+def graph_request(cfg, shard_graph: Optional[dict], has_graph: bool) -> Optional[Tuple[float, Optional[int]]]:
+    """The radius graph a ``--shard_dir`` run must build on a shard, ``(radius, cap)``, or None to keep the stored one.
+    ``shard_graph``: the shard's recorded provenance ``{"radius", "max_neighbors"}`` or None; ``has_graph``: whether it
+    stores edges at all.
+      ADP + CartNet: the reference reads the edges from its files whatever --radius says (loader/loader.py:29,
+        dataset/datasetADP.py:42); only a geometry-only shard is graphed, at (radius, uncapped).
+      ADP + e/iComformer: compute_knn(cfg.max_neighbours, cfg.radius) (loader/loader.py:24-26).
+      any other dataset: Figshare_Dataset(radius, max_neigh) with -1 -> no cap (loader/loader.py:106-110,
+        dataset/figshare_dataset.py:18,65).
+    A request equal to the recorded graph is skipped, as compute_knn skips a directory it has already written
+    (dataset/utils.py:462-464)."""
+    cap = cfg.max_neighbours if cfg.max_neighbours is not None and cfg.max_neighbours > 0 else None
+    if cfg.dataset.name == "ADP" and cfg.model == "CartNet":
+        return None if has_graph else (float(cfg.radius), None)
+    want = (float(cfg.radius), cap)
+    if has_graph and shard_graph is not None:
+        k = shard_graph.get("max_neighbors")
+        if (float(shard_graph["radius"]), int(k) if k is not None and int(k) > 0 else None) == want:
+            return None
+    return want
+
+
+def shard_loaders(rank: int, world: int):
+    """``--shard_dir``: the three splits from shard files, with the reference's dataset recipe applied on the GPU in the
+    reference's order -- graph (graph_request), hydrogen removal (dataset/datasetADP.py:49-72), canonical cell (:75-80) --
+    and the temperature standardisation of :17-18,43-45 inside the collation kernel (the files hold Kelvin)."""
+    from cartnet_amd.shard import DeviceShard, ShardLoader
+    from cartnet_amd.synthetic import TEMP_MEAN, TEMP_STD
+    adp = cfg.dataset.name == "ADP"
+    shards = [DeviceShard.from_file(os.path.join(cfg.shard_dir, f"{part}.cnshard"), cfg.device)
+              for part in ("train", "val", "test")]
+    for i, s in enumerate(shards):
+        req = graph_request(cfg, s.graph, s.has_graph)
+        if req is not None:
+            shards[i] = s.with_radius_graph(*req)
+    if adp and not cfg.use_H:
+        shards = [s.without_hydrogens() for s in shards]
+    if adp and cfg.model == "icomformer":
+        shards = [s.with_optimized_cell() for s in shards]
+    mean, std = (TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0)
+    return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
+                        augment=cfg.augment, temp_mean=mean, temp_std=std),
+            ShardLoader(shards[1], cfg.batch, temp_mean=mean, temp_std=std),
+            ShardLoader(shards[2], 1 if adp else cfg.batch, temp_mean=mean, temp_std=std)]
+
+
 def create_loaders(args, rank: int, world: int):
     """Synthetic stand-in for loader/loader.py:create_loader: seed-123 80/10/10 split (loader.py:130-141)."""
+    if cfg.shard_dir:
+        return shard_loaders(rank, world)
     adp = cfg.dataset.name == "ADP"
     # every model but CartNet trains on the capped graphs (main.py:176, loader/loader.py:26,108: compute_knn)
     cap = cfg.max_neighbours if cfg.max_neighbours > 0 else None

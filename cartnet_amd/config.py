@@ -53,6 +53,7 @@ def _defaults() -> _Node:
         workers=0,
         device="cuda:0",
         shard_dir=None,
+        eval_batch=1,
     )
 
 

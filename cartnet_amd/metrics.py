@@ -6,7 +6,7 @@ all three metrics of a batch come from one kernel launch (``adp_metrics``).  The
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -54,3 +54,100 @@ def get_similarity_index(pred: torch.Tensor, true: torch.Tensor) -> torch.Tensor
 def compute_3D_IoU(pred: torch.Tensor, true: torch.Tensor, num_points: int = 64) -> torch.Tensor:
     """train/metrics.py:148-180 (with get_ellipsoids :114-146 and iou_pytorch3D :96-112 fused)."""
     return adp_metrics(pred, true, False, False, True, num_points)[2]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Evaluation at any batch size with the results of batch size 1 (csrc/eval_ops.hip): the reference's ADP test loader has
+# batch size 1 (loader/loader.py:121), so its numbers are per-crystal means, its rotations per crystal.
+
+class AdpEval(NamedTuple):
+    """What ``adp_eval`` returns.  ``true``: the truth the metrics were taken against ([M,3,3]; the pseudo-truth with
+    ``rot``); ``abs_err`` [M,3,3]; the three per-atom metrics [M] (``None`` if not requested); ``crystal_sums`` [B,4] fp64:
+    per crystal the sums of abs_err (over 9 * rows elements), volume error, similarity index and IoU; ``rows`` [B] int64."""
+    true: torch.Tensor
+    abs_err: torch.Tensor
+    volume_error: Optional[torch.Tensor]
+    similarity_index: Optional[torch.Tensor]
+    iou: Optional[torch.Tensor]
+    crystal_sums: torch.Tensor
+    rows: torch.Tensor
+
+
+def target_row_ptr(batch) -> torch.Tensor:
+    """[B+1] int64 on the batch's device: crystal g owns rows ``[ptr[g], ptr[g+1])`` of the model's per-atom output (its
+    non-hydrogen atoms).  A shard-collated batch carries these offsets already (``Batch._meta``); otherwise they are counted
+    with device ops on ``batch`` / ``non_H_mask`` / ``ptr``: no host synchronisation either way."""
+    B = int(batch.num_graphs)
+    meta = getattr(batch, "_meta", None)
+    if meta is not None and meta.numel() == 4 * B + 3:              # [sel | atom offsets | edge offsets | target offsets]
+        return meta[3 * B + 2:4 * B + 3].to(batch.x.device)
+    mask = getattr(batch, "non_H_mask", None)
+    if mask is None:
+        return batch.ptr.to(torch.int64)
+    counts = torch.zeros(B, dtype=torch.int64, device=mask.device).index_add_(0, batch.batch, mask.to(torch.int64))
+    return torch.cat([torch.zeros(1, dtype=torch.int64, device=mask.device), torch.cumsum(counts, 0)])
+
+
+def edge_row_ptr(batch) -> torch.Tensor:
+    """[B+1] int64: crystal g owns edges ``[ptr[g], ptr[g+1])``.  The edges of a batch are sorted by target atom, so the
+    first edge of a crystal is the first whose target is not below the crystal's first atom."""
+    return torch.searchsorted(batch.edge_index[1].contiguous(), batch.ptr.to(torch.int64).contiguous())
+
+
+def _check_row_ptr(row_ptr: torch.Tensor, dev) -> Tuple[torch.Tensor, int]:
+    if not (row_ptr.dtype == torch.int64 and row_ptr.dim() == 1 and row_ptr.numel() >= 2 and row_ptr.device == dev):
+        raise ValueError("row_ptr must be an int64 tensor [B+1], B >= 1, on the data's device")
+    return row_ptr.contiguous(), int(row_ptr.numel()) - 1
+
+
+def _check_rot(rot: torch.Tensor, B: int, dev) -> torch.Tensor:
+    if not (rot.dtype == torch.float32 and tuple(rot.shape) == (B, 3, 3) and rot.device == dev):
+        raise ValueError("rot must be an fp32 tensor [B,3,3] on the data's device")
+    return rot.contiguous()
+
+
+def rotate_rows(v: torch.Tensor, row_ptr: torch.Tensor, rot: torch.Tensor, out: Optional[torch.Tensor] = None
+                ) -> torch.Tensor:
+    """``v[r] @ rot[g(r)]`` for the rows of ``v`` [n,3], ``g(r)`` the segment of row ``r`` in ``row_ptr``; one launch, the
+    arithmetic of ``DeviceShard.collate(sel, rot)``.  ``out`` may be ``v`` itself (rotation in place)."""
+    if not (v.is_cuda and v.dtype == torch.float32 and v.dim() == 2 and v.shape[1] == 3 and v.is_contiguous()):
+        raise ValueError("v must be a contiguous CUDA fp32 tensor [n,3]")
+    row_ptr, B = _check_row_ptr(row_ptr, v.device)
+    rot = _check_rot(rot, B, v.device)
+    if out is None:
+        out = torch.empty_like(v)
+    elif not (out.shape == v.shape and out.dtype == v.dtype and out.device == v.device and out.is_contiguous()):
+        raise ValueError("out must have v's shape, dtype and device")
+    _l.check(_l.load().cartnet_rotate_rows(v.data_ptr(), row_ptr.data_ptr(), B, int(v.shape[0]), rot.data_ptr(),
+                                           out.data_ptr(), _l.stream_ptr()), "cartnet_rotate_rows")
+    return out
+
+
+def adp_eval(pred: torch.Tensor, true: torch.Tensor, row_ptr: torch.Tensor, rot: Optional[torch.Tensor] = None,
+             volume: bool = True, similarity: bool = True, iou: bool = True, num_points: int = 64) -> AdpEval:
+    """Everything the three evaluation paths take from a batch, with crystal boundaries kept: per atom the absolute error
+    and the requested metrics (bit-identical to ``adp_metrics``), per crystal their fp64 sums.  With ``rot`` [B,3,3],
+    ``true`` is the first prediction of a Monte-Carlo step and the metrics are taken against ``R_g^T true R_g``."""
+    pred, true, M = _check_pair(pred, true)
+    dev = pred.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    if rot is not None:
+        rot = _check_rot(rot, B, dev)
+    outs = [torch.empty(M, dtype=torch.float32, device=dev) if want else None for want in (volume, similarity, iou)]
+    true_out = torch.empty_like(true) if rot is not None else None
+    abs_err = torch.empty_like(pred)
+    sums = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    grid = torch.linspace(-1, 1, num_points, device=dev, dtype=torch.float32) if iou else None   # metrics.py:128
+    _l.check(_l.load().cartnet_adp_eval(pred.data_ptr(), true.data_ptr(), row_ptr.data_ptr(), B, M, _l.ptr(rot),
+                                        _l.ptr(grid), int(num_points), _l.ptr(true_out), abs_err.data_ptr(),
+                                        *[_l.ptr(o) for o in outs], sums.data_ptr(), _l.stream_ptr()),
+             "cartnet_adp_eval")
+    return AdpEval(true_out if rot is not None else true, abs_err, outs[0], outs[1], outs[2], sums,
+                   row_ptr[1:] - row_ptr[:-1])
+
+
+def split_rows(t: torch.Tensor, rows) -> list:
+    """The per-crystal pieces of a host tensor whose dim 0 runs over the rows of a batch: one transfer per batch, then
+    this split by the crystals' row counts (a sequence of ints) gives the reference's one-entry-per-crystal lists.  Every
+    piece owns its memory: a pickled view would drag the whole batch's storage along."""
+    return [piece.clone() for piece in torch.split(t, [int(r) for r in rows], dim=0)]

@@ -248,14 +248,21 @@ def _train_epoch(loader, model, optimizer, batch_accumulation, scheduler, device
     return {"mae": float(tot_mae.item()) / max(micro, 1), "graphs": graphs, "seconds": dt}
 
 
-def eval_epoch(loader, model, device="cuda:0", adp_metrics=False, test_metrics=False):
+def eval_epoch(loader, model, device="cuda:0", adp_metrics=False, test_metrics=False, per_crystal=False):
     """train/train.py:202-243: eval mode, no grad.  ``adp_metrics`` adds the per-batch means the reference logs for
     the ADP dataset (train/metrics.py:201-225): volume error and similarity index always, the voxel IoU only for the
-    test pass (``test_metrics``); all on the GPU (cartnet_amd/metrics.py)."""
+    test pass (``test_metrics``); all on the GPU (cartnet_amd/metrics.py).
+
+    ``per_crystal``: every crystal contributes its own mean of the MAE and of each requested metric and the epoch value is
+    the mean over crystals -- what this loop gives with a loader of batch size 1 (the reference's ADP test loader,
+    loader/loader.py:121), at any batch size.  One fused launch pair per batch (``adp_eval``), fp64 sums on the device, one
+    read at the end.  Per-atom 3x3 targets only."""
     from .metrics import adp_metrics as _adp_metrics
     model.eval()
     names = ["mae"] + (["volume_percentage_error", "similarity_index"] + (["iou"] if test_metrics else [])
                        if adp_metrics else [])
+    if per_crystal:
+        return _eval_epoch_per_crystal(loader, model, device, names, adp_metrics, test_metrics)
     tot = {k: torch.zeros((), device=device) for k in names}
     n = 0
     with torch.no_grad():
@@ -276,3 +283,31 @@ def eval_epoch(loader, model, device="cuda:0", adp_metrics=False, test_metrics=F
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
     return {k: float(v.item()) / max(n, 1) for k, v in tot.items()}
+
+
+def _eval_epoch_per_crystal(loader, model, device, names, adp_metrics, test_metrics):
+    from .metrics import adp_eval, target_row_ptr
+    tot = torch.zeros(4, dtype=torch.float64, device=device)
+    per_row = torch.tensor([9.0, 1.0, 1.0, 1.0], dtype=torch.float64, device=device)   # elements a row adds to a column
+    n = 0
+    with torch.no_grad():
+        for batch in loader:
+            if batch is None:
+                continue
+            batch.to(device)
+            row_ptr = target_row_ptr(batch)              # before the forward: it overwrites batch.x
+            pred, true = model(batch)
+            if pred.dim() != 3:
+                raise ValueError("per_crystal evaluation needs per-atom 3x3 targets (the ADP dataset)")
+            res = adp_eval(pred, true, row_ptr, None, adp_metrics, adp_metrics, adp_metrics and test_metrics)
+            rows = res.rows.to(torch.float64).unsqueeze(1)
+            # a crystal's means: MAE over its 9 * rows elements, each metric over its rows; 0 / 0 = NaN for a crystal
+            # without rows, as the mean of an empty tensor at batch size 1
+            per = res.crystal_sums / (rows * per_row)
+            tot += per.sum(dim=0)
+            n += int(batch.num_graphs)
+    if hasattr(model, "flush_graph_checks"):
+        model.flush_graph_checks()
+    col = {"mae": 0, "volume_percentage_error": 1, "similarity_index": 2, "iou": 3}
+    vals = tot.tolist()                                  # the one device-to-host copy
+    return {k: vals[col[k]] / max(n, 1) for k in names}

@@ -355,6 +355,34 @@ int cartnet_adp_metrics(const float* pred, const float* truth, int32_t M, const 
                         float* volume_error, float* similarity_index, float* iou, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Evaluation at any batch size with the results of batch size 1 (reference: the ADP test loader has batch size 1,
+ * loader/loader.py:121, so the test pass, train/train.py:202-243, averages per-crystal means, --inference,
+ * main.py:21-60, stores per-crystal lists and --montecarlo, main.py:62-119, draws one rotation per crystal).
+ * row_ptr: [B+1] int64 on the device, ascending, row_ptr[0] = 0, row_ptr[B] = the number of rows; empty segments are
+ * legal.  rot: [B,9] fp32, one row-major 3x3 per crystal.  No atomics, fixed summation order: two runs give the same
+ * bytes.
+ *
+ * cartnet_rotate_rows: out[r] = v[r] @ R[g(r)] for the n rows of v [n,3], g(r) the segment of row r (main.py:95, the
+ *   rotated cart_dir of the Monte-Carlo step), with the arithmetic of cartnet_collate's augmentation: the result equals
+ *   the cart_dir of a batch collated with the same rot bit for bit.  out may be v.
+ *
+ * cartnet_adp_eval: per atom a of crystal g, with pred, truth [M,9] fp32:
+ *   true     = truth[a], or with rot the Monte-Carlo pseudo-truth R_g^T truth[a] R_g (main.py:97; fp32, fixed order, an
+ *              identity rotation returns truth's bits), written to true_out [M,9] (required with rot, else optional;
+ *              it must not alias an input)
+ *   abs_err  = |pred - true| [M,9] (main.py:48,103: F.l1_loss without reduction)
+ *   volume_error, similarity_index, iou [M]: as cartnet_adp_metrics(pred, true), bit for bit
+ *   and per crystal crystal_sums[g] = (sum of abs_err over the crystal's 9 * rows elements, sum of volume_error, sum of
+ *   similarity_index, sum of iou) in fp64, rows in order, one wave per crystal; a metric that was not requested leaves
+ *   its column 0, a crystal without rows gives 0 everywhere.  Every per-atom output may be NULL.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_rotate_rows(const float* v, const int64_t* row_ptr, int32_t B, int64_t n, const float* rot, float* out,
+                        void* stream);
+int cartnet_adp_eval(const float* pred, const float* truth, const int64_t* row_ptr, int32_t B, int32_t M,
+                     const float* rot, const float* grid, int32_t num_points, float* true_out, float* abs_err,
+                     float* volume_error, float* similarity_index, float* iou, double* crystal_sums, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Training loss (reference: train/metrics.py:15-28, called from train/train.py:173-178): L1Loss and MSELoss with mean
  * reduction over the n = M*9 (or Bg) elements of pred / truth, both from one pair of small launches (slices, then
  * their sum), and their gradient from one more:

@@ -11,7 +11,9 @@ What differs: the datasets (CSD / Jarvis need licences or the network) are repla
 "cuda:0", and under ``torch.distributed.run`` the crystals are sharded across ranks with one gradient all-reduce per
 optimiser step.  ``--shard_dir DIR`` trains from packed shard files (cartnet_amd/shard.py) instead of synthetic crystals:
 the reference's dataset recipe -- graph, hydrogen removal, canonical cell, temperature standardisation -- is applied to the
-resident shards in the reference's order.  There is no CPU path: the model runs on an AMD GPU only.
+resident shards in the reference's order.  ``--eval_batch N`` runs the ADP test pass, ``--inference`` and
+``--montecarlo`` with N crystals per forward and keeps the results of the reference's test batch size 1 (per-crystal means,
+rotations and pickle entries).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -94,6 +96,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="train from DIR/train.cnshard, val.cnshard and test.cnshard (tools/make_shards.py writes such a "
                         "directory) instead of synthetic crystals: implies --resident_dataset, ignores --synthetic and "
                         "--atoms; the radius graph is rebuilt on the GPU where the reference would rebuild it")
+    p.add_argument("--eval_batch", type=int, default=1,
+                   help="ADP: crystals per batch of the test pass, --inference and --montecarlo.  The reference tests at "
+                        "batch size 1 (the default, and that code path); N > 1 runs N crystals per forward and still "
+                        "reports batch size 1's results: per-crystal means, one rotation per crystal, one pickle entry "
+                        "per crystal.  Other datasets ignore it (they test at --batch)")
     return p
 
 
@@ -117,6 +124,9 @@ def fill_cfg(args) -> None:
     cfg.workers = args.workers
     cfg.device = args.device
     cfg.shard_dir = args.shard_dir
+    if args.eval_batch < 1:
+        raise ValueError("--eval_batch must be at least 1")
+    cfg.eval_batch = args.eval_batch
     cfg.gemm_precision = args.gemm_precision
     cfg.bn_group_size = 0
     cfg.half_storage = bool(args.bf16_storage) and cfg.model == "CartNet" and args.gemm_precision == 2
@@ -171,7 +181,7 @@ def shard_loaders(rank: int, world: int):
     return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
                         augment=cfg.augment, temp_mean=mean, temp_std=std),
             ShardLoader(shards[1], cfg.batch, temp_mean=mean, temp_std=std),
-            ShardLoader(shards[2], 1 if adp else cfg.batch, temp_mean=mean, temp_std=std)]
+            ShardLoader(shards[2], cfg.eval_batch if adp else cfg.batch, temp_mean=mean, temp_std=std)]
 
 
 def create_loaders(args, rank: int, world: int):
@@ -201,7 +211,7 @@ def create_loaders(args, rank: int, world: int):
             shards = [s.with_optimized_cell() for s in shards]
         return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
                             augment=cfg.augment),
-                ShardLoader(shards[1], cfg.batch), ShardLoader(shards[2], 1 if adp else cfg.batch)]
+                ShardLoader(shards[1], cfg.batch), ShardLoader(shards[2], cfg.eval_batch if adp else cfg.batch)]
     if no_h:
         tr, va, te = ([remove_hydrogens(d) for d in part] for part in (tr, va, te))
     if canonical:
@@ -209,7 +219,7 @@ def create_loaders(args, rank: int, world: int):
     gen = torch.Generator().manual_seed(cfg.seed + 1000 * rank)
     aug = (lambda d: augment_data(d, gen)) if cfg.augment else None
     return [DataLoader(tr, cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world, transform=aug),
-            DataLoader(va, cfg.batch), DataLoader(te, 1 if adp else cfg.batch)]
+            DataLoader(va, cfg.batch), DataLoader(te, cfg.eval_batch if adp else cfg.batch)]
 
 
 def inference(model, loader, device, output_path: str) -> dict:
@@ -290,6 +300,121 @@ def montecarlo(model, loader, device, output_path: str, rounds: int = 100, seed:
             "similarity_index_std": float(sim.std())}
 
 
+def _to_host(tensors: dict) -> dict:
+    """The device tensors of ``tensors`` on the host, through ONE device-to-host copy: their bytes are packed into one
+    buffer on the device, and every tensor is cut back out of its host copy (each owning its memory)."""
+    items = [(k, t.detach().contiguous()) for k, t in tensors.items()]
+    flat = torch.cat([t.view(torch.uint8).reshape(-1) if t.numel() else t.new_empty(0, dtype=torch.uint8)
+                      for _, t in items]).to("cpu")
+    out, at = {}, 0
+    for k, t in items:
+        n = t.numel() * t.element_size()
+        out[k] = flat[at:at + n].clone().view(t.dtype).reshape(t.shape)
+        at += n
+    return out
+
+
+def _batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> None:
+    """Appends one list entry per crystal to ``out``: the tensors of ``per_row`` (dim 0 runs over the batch's non-hydrogen
+    atoms, in crystal order), ``cell``, ``atoms`` and, if asked for, ``pos``.  One transfer brings everything to the host,
+    the crystals' row counts included; the split by those counts happens there -- the lists the batch-size-1 loop writes
+    (main.py:38-49).  ``batch.x`` must hold the atomic numbers."""
+    from cartnet_amd.metrics import split_rows
+    dev = dict(per_row)
+    dev["atoms"] = batch.x[batch.non_H_mask]
+    dev["cell"] = batch.cell
+    if with_pos and hasattr(batch, "pos"):
+        dev["pos"] = batch.pos[batch.non_H_mask]
+    dev["_row_ptr"] = row_ptr
+    host = _to_host(dev)
+    rp = host.pop("_row_ptr")
+    rows = (rp[1:] - rp[:-1]).tolist()
+    out["cell"] += [c.unsqueeze(0) for c in host.pop("cell").unbind(0)]
+    for k, t in host.items():
+        out[k] += split_rows(t, rows)
+
+
+def inference_batched(model, loader, device, output_path: str) -> dict:
+    """``inference`` at any batch size (``--eval_batch N``): one forward and one ``adp_eval`` per batch; the pickle keeps
+    the layout of batch size 1, one list entry per crystal, and the result keys are the same."""
+    import pickle
+    from cartnet_amd.metrics import adp_eval, target_row_ptr
+    model.eval()
+    out = {"pred": [], "true": [], "temp": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "iou": [], "mae": [],
+           "similarity_index": []}
+    with torch.no_grad():
+        for batch in loader:
+            if batch is None:
+                continue
+            batch.to(device)
+            row_ptr = target_row_ptr(batch)
+            atoms = batch.x.clone()                                           # forward overwrites x (main.py:40)
+            pred, true = model(batch)
+            res = adp_eval(pred, true, row_ptr, None, volume=False)
+            batch.x = atoms
+            _batch_entries(out, batch, row_ptr, {"pred": pred, "true": true, "mae": res.abs_err, "iou": res.iou,
+                                                 "similarity_index": res.similarity_index}, with_pos=True)
+    if hasattr(model, "flush_graph_checks"):
+        model.flush_graph_checks()
+    iou, mae, sim = (torch.cat(out[k]) for k in ("iou", "mae", "similarity_index"))
+    with open(output_path, "wb") as f:
+        pickle.dump(out, f)
+    return {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
+            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
+            "similarity_index_std": float(sim.std()), "output": output_path}
+
+
+def montecarlo_batch(model, batch, R: torch.Tensor):
+    """One Monte-Carlo step (main.py:85-103) for a whole batch on the device, crystal g rotated by ``R[g]`` [B,3,3]:
+    clone, forward, rotate the clone's ``cart_dir`` per crystal (``cell`` is not rotated, as in the reference), forward
+    again, and one ``adp_eval`` that forms the pseudo-truth ``R_g^T pred_1 R_g`` and compares.  Returns
+    ``(pred, AdpEval, row_ptr)``; ``batch`` comes back with its atomic numbers in ``x``."""
+    from cartnet_amd.metrics import adp_eval, edge_row_ptr, rotate_rows, target_row_ptr
+    row_ptr = target_row_ptr(batch)
+    copy = batch.clone()                                                      # forward overwrites batch.x (main.py:87)
+    copy.num_graphs = batch.num_graphs
+    atoms = batch.x.clone()
+    first, _ = model(batch)
+    batch.x = atoms
+    copy.cart_dir = rotate_rows(copy.cart_dir.contiguous(), edge_row_ptr(copy), R)
+    pred, _ = model(copy)
+    return pred, adp_eval(pred, first, row_ptr, rot=R, volume=False), row_ptr
+
+
+def montecarlo_batched(model, loader, device, output_path: str, rounds: int = 100, seed: int = 0) -> dict:
+    """``montecarlo`` at any batch size (``--eval_batch N``): ``montecarlo_batch`` per batch with one fresh rotation per
+    crystal; the pickles keep the layout of batch size 1, one list entry per crystal, and the result keys are the same."""
+    import pickle
+    from cartnet_amd.shard import random_rotations
+    model.eval()
+    gen = torch.Generator(device=device).manual_seed(seed)
+    iou_all, mae_all, sim_all = [], [], []
+    with torch.no_grad():
+        for i in range(rounds):
+            out = {"pred": [], "true": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "mae": [], "iou": [],
+                   "similarity_index": []}
+            for batch in loader:
+                if batch is None:
+                    continue
+                batch.to(device)
+                R = random_rotations(int(batch.num_graphs), gen, device)
+                pred, res, row_ptr = montecarlo_batch(model, batch, R)
+                per_row = {"pred": pred, "true": res.true, "mae": res.abs_err, "iou": res.iou,
+                           "similarity_index": res.similarity_index}
+                _batch_entries(out, batch, row_ptr, per_row, with_pos=False)    # (main.py:62-119 stores no pos)
+            with open(output_path.replace(".pkl", f"_montecarlo_{i}.pkl"), "wb") as f:
+                pickle.dump(out, f)
+            iou_all += out["iou"]
+            mae_all += out["mae"]
+            sim_all += out["similarity_index"]
+    if hasattr(model, "flush_graph_checks"):
+        model.flush_graph_checks()
+    iou, mae, sim = torch.cat(iou_all), torch.cat(mae_all), torch.cat(sim_all)
+    return {"rounds": rounds, "iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
+            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
+            "similarity_index_std": float(sim.std())}
+
+
 def main(argv=None) -> dict:
     args = build_parser().parse_args(argv)
     fill_cfg(args)
@@ -308,11 +433,12 @@ def main(argv=None) -> dict:
         assert args.checkpoint_path is not None, "Weights not provided."
         ck = torch.load(args.checkpoint_path, map_location=cfg.device)
         model.load_state_dict(ck["model_state"])
+        batched = cfg.eval_batch > 1                                       # 1: the reference's loop, as it was
         if args.inference:
-            res = inference(model, loaders[-1], cfg.device, args.inference_output)
+            res = (inference_batched if batched else inference)(model, loaders[-1], cfg.device, args.inference_output)
         else:
-            res = montecarlo(model, loaders[-1], cfg.device, args.inference_output, rounds=args.montecarlo_rounds,
-                             seed=cfg.seed)
+            res = (montecarlo_batched if batched else montecarlo)(model, loaders[-1], cfg.device, args.inference_output,
+                                                                  rounds=args.montecarlo_rounds, seed=cfg.seed)
         if rank == 0:
             print(json.dumps(res), flush=True)
         return res
@@ -351,7 +477,8 @@ def main(argv=None) -> dict:
         ck = torch.load(os.path.join(ckpt_dir, "best.ckpt"), map_location=cfg.device)
         model.load_state_dict(ck["model_state"])
         adp = cfg.dataset.name == "ADP"
-        test = eval_epoch(loaders[2], model, device=cfg.device, adp_metrics=adp, test_metrics=adp)
+        test = eval_epoch(loaders[2], model, device=cfg.device, adp_metrics=adp, test_metrics=adp,
+                          per_crystal=adp and cfg.eval_batch > 1)
         result["test_mae"] = test["mae"]
         result["test_metrics"] = test                                      # train/metrics.py:201-214
         print(json.dumps({"params": n_params, "best_val_mae": best, "test": test}), flush=True)

@@ -1,10 +1,24 @@
-// Periodic radius graph on the GPU (reference: dataset/utils.py:57-237 radius_graph_pbc, used by
-// dataset/figshare_dataset.py:65-68).  Emits edges in the reference's order -- target atom, then source atom, then
-// periodic image in cartesian_prod(a1, a2, a3) order -- so edge_index[1] comes out sorted and feeds cartnet_csr_build
-// directly.  Two passes (count, fill), one wavefront per target atom, one lane per source atom (64 sources per round);
-// a lane walks only the periodic images that CAN lie within the radius of its pair (see "image box" below) in the
-// reference's image order; the position of a lane's edges inside the row comes from a wave prefix sum of the lanes'
-// counts, so there are no atomics and the output is deterministic.
+// Periodic radius graph on the GPU (reference: dataset/utils.py:57-237 radius_graph_pbc with the cap of
+// :240-360, as called by dataset/figshare_dataset.py:50-76 and by compute_knn, dataset/utils.py:456-486, one crystal at
+// a time on the CPU).  ONE pass builds the graph of every crystal of (pos [N,3], cell [G,9], atom_ptr [G+1]) -- a whole
+// resident shard or one batch (atom_ptr = the batch's ptr, G = its crystals) -- behind cartnet_shard_regraph_count /
+// _cap / _fill; cartnet_amd/graph.py: radius_graph_csr drives it for DeviceShard.with_radius_graph, radius_graph_pbc
+// and shard.pack_with_gpu_graph.
+// Edges come out in the reference's order -- target atom, then source atom, then periodic image in
+// cartesian_prod(a1, a2, a3) order -- so the targets are ascending and feed cartnet_csr_build directly; the ends of an
+// edge are int32 atom indices inside the crystal (the shard's format), edge_ptr [G+1] the crystals' edge offsets.
+// One wavefront per target atom (its crystal found by a binary search in atom_ptr), one lane per source atom (64
+// sources per round); a lane walks only the periodic images that CAN lie within the radius of its pair (see "image
+// box" below); the position of a lane's edges inside the row comes from a wave prefix sum of the lanes' counts, and row
+// offsets are reduce-then-scan over tiles of 1024 atoms (shard_tiles.h): no atomics, identical bytes on every run.
+//   count:  cn_rg_reps_kernel, cn_sr_kernel<SR_COUNT> (deg[N], *over = some row is longer than the cap), row offsets
+//   cap:    cn_sr_kernel<SR_D2>, cn_cap_count_kernel (cutoff[N], deg[N] <- capped), row offsets     -- only if *over
+//   fill:   cn_sr_kernel<SR_FILL>, cn_sr_edge_ptr_kernel (edge_ptr[g] = row offset of the crystal's first atom)
+// The host reads the sizes between the calls.  Cutoff: a pair is kept when d^2 <= (float)(radius * radius), the product
+// taken in double (cn_rg_threshold), and d^2 > 1e-4.  Cap: a row longer than max_neighbors keeps the edges with d^2 <=
+// its (max_neighbors+1)-th smallest d^2 + tolerance, in their order (cn_cap_count_kernel).  A capped graph is never
+// built uncapped: SR_D2 writes only the d^2 of the uncapped rows, and SR_FILL walks the images once more and emits the
+// edges with d^2 <= the row's cutoff straight into the final arrays.
 // Arithmetic of the distance test mirrors the reference's fp32 operation order with explicitly rounded (non-fused)
 // operations; the image box only decides which candidates are tested, with a margin far above fp32 rounding.
 //
@@ -19,10 +33,10 @@
 
 // This file is compiled with -ffp-contract=off (cartnet_amd/build.py: EXTRA_FLAGS).  HIP's __fmul_rn / __fadd_rn are
 // plain * and +, and under hipcc's default -ffp-contract=fast-honor-pragmas the compiler fused them into FMAs --
-// differently in the count and the fill instantiation of the kernel below, which then disagreed about a pair whose d^2
-// lies within an ulp of radius^2 (2 of 49k atoms in one 256-crystal launch: two slots of the fill pass stayed unwritten
-// and every later crystal of the chunk was shifted).  With contraction off every product and sum is rounded on its own,
-// like the reference's torch ops, and both passes evaluate the same expression.
+// differently in the count and the fill instantiation of a kernel, which then disagreed about a pair whose d^2 lies
+// within an ulp of radius^2 (2 of 49k atoms in one 256-crystal launch: two slots of the fill pass stayed unwritten and
+// every later crystal was shifted).  With contraction off every product and sum is rounded on its own, like the
+// reference's torch ops, and the three instantiations of cn_sr_kernel evaluate one expression for d^2.
 namespace {
 
 constexpr int CN_RG_MAX_REPS = 16;
@@ -64,8 +78,7 @@ __global__ void cn_rg_reps_kernel(const float* __restrict__ cell, int Bg, float 
   }
 }
 
-// One (target, source) pair: the box of periodic images that can lie within the radius and the walk over it.  Shared
-// by the per-batch kernel and the shard-wide one below, so that both evaluate the same expressions.
+// One (target, source) pair: the box of periodic images that can lie within the radius and the walk over it.
 struct RgPair {
   float px, py, pz, qx, qy, qz;
   int lo1, hi1, lo2, hi2, lo3, hi3;
@@ -133,57 +146,6 @@ __device__ __forceinline__ int rg_lane_scan(int mine, int lane) {
   return incl;
 }
 
-template <bool FILL>
-__global__ __launch_bounds__(256) void cn_rg_kernel(const float* __restrict__ pos, const float* __restrict__ cell,
-                                                    const int64_t* __restrict__ graph_ptr,
-                                                    const int64_t* __restrict__ batch, const int* __restrict__ reps,
-                                                    const float* __restrict__ recip, int N, float r2, float eps2,
-                                                    int* __restrict__ deg, const int64_t* __restrict__ rowptr,
-                                                    int64_t* __restrict__ ei, long long E, float* __restrict__ dist,
-                                                    float* __restrict__ dir, float* __restrict__ dist_sq) {
-  const int lane = threadIdx.x & 63;
-  const int i1 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (i1 >= N) return;
-  const int g = (int)batch[i1];
-  const int n0 = (int)graph_ptr[g], n = (int)graph_ptr[g + 1] - n0;
-  const int R1 = reps[g * 3], R2 = reps[g * 3 + 1], R3 = reps[g * 3 + 2];
-  const float* a = cell + (size_t)g * 9;
-  const float* rb = recip + (size_t)g * 12;
-  RgPair pr;
-  pr.target(pos + (size_t)i1 * 3);
-  long long out = FILL ? rowptr[i1] : 0;
-  int count = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int i2 = base + lane;
-    if (i2 < n) pr.source(pos + (size_t)(n0 + i2) * 3, rb, R1, R2, R3); else pr.none();
-    int mine = 0;
-    pr.walk(a, r2, eps2, [&](float, float, float, float) { ++mine; });
-    const int incl = rg_lane_scan(mine, lane);
-    const int round_total = __shfl(incl, 63);
-    if (FILL) {
-      long long p = out + (incl - mine);
-      pr.walk(a, r2, eps2, [&](float dx, float dy, float dz, float d2) {
-        if (p < E) {
-          ei[p] = (int64_t)(n0 + i2);
-          ei[E + p] = (int64_t)i1;
-          const float d = sqrtf(d2);
-          const float dn = fmaxf(d, 1e-12f);      // F.normalize(vec, p=2, dim=-1, eps=1e-12)
-          dist[p] = d;
-          if (dist_sq) dist_sq[p] = d2;
-          dir[p * 3] = dx / dn;
-          dir[p * 3 + 1] = dy / dn;
-          dir[p * 3 + 2] = dz / dn;
-        }
-        ++p;
-      });
-      out += round_total;
-    } else {
-      count += round_total;
-    }
-  }
-  if (!FILL && lane == 0) deg[i1] = count;
-}
-
 // Neighbour cap (dataset/utils.py:240-360 get_max_neighbors_mask, enforce_max_strictly = False): a target with more
 // than k candidate edges keeps those with d^2 <= (k+1)-th smallest d^2 of its row + tolerance, in their original
 // order; shorter rows are kept whole.  One wavefront per target.  The (k+1)-th smallest value is found by rank
@@ -224,54 +186,7 @@ __global__ __launch_bounds__(256) void cn_cap_count_kernel(const int64_t* __rest
   if (lane == 0) { cutoff[i] = c; deg[i] = cnt; }
 }
 
-__global__ __launch_bounds__(256) void cn_cap_fill_kernel(const int64_t* __restrict__ rowptr,
-                                                          const int64_t* __restrict__ rowptr_out,
-                                                          const float* __restrict__ cutoff,
-                                                          const float* __restrict__ d2, const int64_t* __restrict__ ei,
-                                                          const float* __restrict__ dist, const float* __restrict__ dir,
-                                                          int N, long long E, long long E_out,
-                                                          int64_t* __restrict__ ei_out, float* __restrict__ dist_out,
-                                                          float* __restrict__ dir_out) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (i >= N) return;
-  const long long b = rowptr[i];
-  const int n = (int)(rowptr[i + 1] - b);
-  const float c = cutoff[i];
-  long long out = rowptr_out[i];
-  for (int base = 0; base < n; base += 64) {
-    const int e = base + lane;
-    const bool keep = e < n && d2[b + e] <= c;
-    const unsigned long long m = __ballot(keep);
-    if (keep) {
-      const long long p = out + __popcll(m & ((1ull << lane) - 1ull));
-      if (p < E_out) {
-        const long long q = b + e;
-        ei_out[p] = ei[q];
-        ei_out[E_out + p] = ei[E + q];
-        dist_out[p] = dist[q];
-        dir_out[p * 3] = dir[q * 3];
-        dir_out[p * 3 + 1] = dir[q * 3 + 1];
-        dir_out[p * 3 + 2] = dir[q * 3 + 2];
-      }
-    }
-    out += __popcll(m);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The radius graph of a whole resident shard (cartnet_amd/shard.py: DeviceShard.with_radius_graph; reference:
-// dataset/utils.py:456-486 compute_knn and dataset/figshare_dataset.py:50-76, one crystal at a time on the CPU).
-// cn_sr_kernel is cn_rg_kernel over the shard's flat atoms -- one wavefront per target, RgPair's walk, the same wave
-// prefix sum -- with three differences: the crystal of a target is found by a binary search in atom_ptr (a shard has no
-// batch vector), the ends of an edge are int32 atom indices inside the crystal (the shard's format), and a capped graph is
-// never built uncapped: SR_D2 writes only the d^2 of the uncapped rows (what cn_cap_count_kernel ranks), and SR_FILL
-// walks the images once more and emits the edges with d^2 <= the row's cutoff straight into the final arrays.  The three
-// instantiations evaluate one expression for d^2 (this file is built without contraction), so they agree on every edge.
-//   count:  cn_rg_reps_kernel, cn_sr_kernel<SR_COUNT> (deg[N], *over = some row is longer than the cap), row offsets
-//   cap:    cn_sr_kernel<SR_D2>, cn_cap_count_kernel (cutoff[N], deg[N] <- capped), row offsets     -- only if *over
-//   fill:   cn_sr_kernel<SR_FILL>, cn_sr_edge_ptr_kernel (edge_ptr[g] = row offset of the crystal's first atom)
-// Row offsets: reduce-then-scan over tiles of 1024 atoms (shard_tiles.h), no atomics anywhere.
+// The pass over the flat atoms of (pos, cell, atom_ptr); the protocol is at the head of the file.
 enum { SR_COUNT = 0, SR_D2 = 1, SR_FILL = 2 };
 
 __device__ __forceinline__ int64_t sr_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -387,7 +302,7 @@ __global__ void cn_sr_edge_ptr_kernel(const int64_t* __restrict__ atom_ptr, cons
   edge_ptr[g] = rowptr[sr_clamp(atom_ptr[g], 0, N)];
 }
 
-// the shard-wide pass's workspace: [15 G] words of cn_rg_reps_kernel | deg [N] | cutoff [N] | rowptr [N+1] (uncapped) |
+// the workspace of a pass: [15 G] words of cn_rg_reps_kernel | deg [N] | cutoff [N] | rowptr [N+1] (uncapped) |
 // rowptr_cap [N+1] | tile sums and offsets of the scans
 struct SrLayout {
   int64_t nT;
@@ -421,67 +336,6 @@ SrLayout sr_layout(int64_t G, int64_t N) {
 // the repetition counts use the fp32 product radius |b_d|, as the reference's tensor arithmetic does (:140).
 static float cn_rg_threshold(double radius) { return (float)(radius * radius); }
 
-extern "C" int cartnet_radius_graph_count(const float* pos, const float* cell, const int64_t* graph_ptr,
-                                          const int64_t* batch, int32_t N, int32_t Bg, double radius, int32_t* reps,
-                                          int32_t* deg, void* stream) {
-  CN_CHECK(N >= 0 && Bg >= 1 && radius > 0.0, "cartnet_radius_graph_count: bad sizes");
-  CN_CHECK(cell && graph_ptr && reps && (N == 0 || (pos && batch && deg)), "cartnet_radius_graph_count: null pointer");
-  float* recip = reinterpret_cast<float*>(reps + 3 * (size_t)Bg);      // second part of the caller's [15 * Bg] buffer
-  hipLaunchKernelGGL(cn_rg_reps_kernel, dim3(cn_ceil_div(Bg, 64)), dim3(64), 0, ST(stream), cell, Bg, (float)radius, reps, recip);
-  CN_LAUNCH_CHECK("cartnet_radius_graph_count/reps");
-  if (N == 0) return 0;
-  hipLaunchKernelGGL(cn_rg_kernel<false>, dim3(cn_ceil_div(N, 4)), dim3(256), 0, ST(stream), pos, cell, graph_ptr, batch,
-                     reps, recip, N, cn_rg_threshold(radius), 0.0001f, deg, (const int64_t*)nullptr, (int64_t*)nullptr, 0LL,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
-  CN_LAUNCH_CHECK("cartnet_radius_graph_count");
-  return 0;
-}
-
-extern "C" int cartnet_radius_graph_fill(const float* pos, const float* cell, const int64_t* graph_ptr,
-                                         const int64_t* batch, const int32_t* reps, const int64_t* rowptr, int32_t N,
-                                         int32_t Bg, double radius, int64_t E, int64_t* edge_index, float* cart_dist,
-                                         float* cart_dir, float* cart_dist_sq, void* stream) {
-  CN_CHECK(N >= 0 && Bg >= 1 && radius > 0.0 && E >= 0, "cartnet_radius_graph_fill: bad sizes");
-  if (N == 0 || E == 0) return 0;
-  CN_CHECK(pos && cell && graph_ptr && batch && reps && rowptr && edge_index && cart_dist && cart_dir,
-           "cartnet_radius_graph_fill: null pointer");
-  const float* recip = reinterpret_cast<const float*>(reps + 3 * (size_t)Bg);
-  hipLaunchKernelGGL(cn_rg_kernel<true>, dim3(cn_ceil_div(N, 4)), dim3(256), 0, ST(stream), pos, cell, graph_ptr, batch,
-                     reps, recip, N, cn_rg_threshold(radius), 0.0001f, (int*)nullptr, rowptr, edge_index, (long long)E, cart_dist,
-                     cart_dir, cart_dist_sq);
-  CN_LAUNCH_CHECK("cartnet_radius_graph_fill");
-  return 0;
-}
-
-extern "C" int cartnet_neighbor_cap_count(const int64_t* rowptr, const float* dist_sq, int32_t N, int32_t max_neighbors,
-                                          float tolerance, float* cutoff, int32_t* deg, void* stream) {
-  CN_CHECK(N >= 0 && max_neighbors >= 1 && tolerance >= 0.f, "cartnet_neighbor_cap_count: bad sizes");
-  if (N == 0) return 0;
-  CN_CHECK(rowptr && dist_sq && cutoff && deg, "cartnet_neighbor_cap_count: null pointer");
-  hipLaunchKernelGGL(cn_cap_count_kernel, dim3(cn_ceil_div(N, 4)), dim3(256), 0, ST(stream), rowptr, dist_sq, N,
-                     max_neighbors, tolerance, cutoff, deg);
-  CN_LAUNCH_CHECK("cartnet_neighbor_cap_count");
-  return 0;
-}
-
-extern "C" int cartnet_neighbor_cap_fill(const int64_t* rowptr, const int64_t* rowptr_out, const float* cutoff,
-                                         const float* dist_sq, const int64_t* edge_index, const float* cart_dist,
-                                         const float* cart_dir, int32_t N, int64_t E, int64_t E_out,
-                                         int64_t* edge_index_out, float* cart_dist_out, float* cart_dir_out,
-                                         void* stream) {
-  CN_CHECK(N >= 0 && E >= 0 && E_out >= 0 && E_out <= E, "cartnet_neighbor_cap_fill: bad sizes");
-  if (N == 0 || E_out == 0) return 0;
-  CN_CHECK(rowptr && rowptr_out && cutoff && dist_sq && edge_index && cart_dist && cart_dir && edge_index_out &&
-               cart_dist_out && cart_dir_out,
-           "cartnet_neighbor_cap_fill: null pointer");
-  hipLaunchKernelGGL(cn_cap_fill_kernel, dim3(cn_ceil_div(N, 4)), dim3(256), 0, ST(stream), rowptr, rowptr_out, cutoff,
-                     dist_sq, edge_index, cart_dist, cart_dir, N, (long long)E, (long long)E_out, edge_index_out,
-                     cart_dist_out, cart_dir_out);
-  CN_LAUNCH_CHECK("cartnet_neighbor_cap_fill");
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------- shard-wide
 static int sr_check(const float* pos, const float* cell, const int64_t* atom_ptr, int32_t G, int64_t N, double radius,
                     const void* ws, size_t ws_bytes, const char* who) {
   CN_CHECK(G >= 1 && N >= 0 && N < (1LL << 31) - SO_TILE && radius > 0.0, "%s: bad sizes (G=%d)", who, G);

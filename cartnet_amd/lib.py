@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CARTNET_LIB (tools only): a diagnostic / A-B build of the same ABI next to the product library (tools/build_variant.sh)
 LIB_PATH = os.environ.get("CARTNET_LIB") or os.path.join(_HERE, "libcartnet_hip.so")
 MAX_GROUPS = 4
-ABI_VERSION = 14         # cartnet_abi_version() of the library this binding mirrors (include/cartnet_hip.h)
+ABI_VERSION = 15         # cartnet_abi_version() of the library this binding mirrors (include/cartnet_hip.h)
 
 _lib: Optional[C.CDLL] = None
 
@@ -329,14 +329,6 @@ PROTOTYPES = {
                                             c_f32p, c_stream]),
     "cartnet_colsum_partial": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_stream]),
     "cartnet_coldot_bc_partial": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_f32p, c_f32p, c_stream]),
-    "cartnet_radius_graph_count": (C.c_int, [c_f32p, c_f32p, c_i64p, c_i64p, C.c_int32, C.c_int32, C.c_double, c_i32p,
-                                             c_i32p, c_stream]),
-    "cartnet_radius_graph_fill": (C.c_int, [c_f32p, c_f32p, c_i64p, c_i64p, c_i32p, c_i64p, C.c_int32, C.c_int32,
-                                            C.c_double, C.c_int64, c_i64p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "cartnet_neighbor_cap_count": (C.c_int, [c_i64p, c_f32p, C.c_int32, C.c_int32, C.c_float, c_f32p, c_i32p,
-                                             c_stream]),
-    "cartnet_neighbor_cap_fill": (C.c_int, [c_i64p, c_i64p, c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, C.c_int32,
-                                            C.c_int64, C.c_int64, c_i64p, c_f32p, c_f32p, c_stream]),
     "cartnet_shard_regraph_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
     "cartnet_shard_regraph_count": (C.c_int, [c_f32p, c_f32p, c_i64p, C.c_int32, C.c_int64, C.c_double, C.c_int32,
                                               C.c_void_p, C.c_size_t, c_i64p, c_stream]),

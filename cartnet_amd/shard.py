@@ -88,53 +88,13 @@ def pack(data_list: Sequence[Data]) -> Dict[str, np.ndarray]:
     return out
 
 
-def pack_with_gpu_graph(geometries: Sequence[Data], radius: float = 5.0, device="cuda:0", chunk: int = 256,
+def pack_with_gpu_graph(geometries: Sequence[Data], radius: float = 5.0, device="cuda:0",
                         max_neighbors: Optional[int] = None) -> Dict[str, np.ndarray]:
     """Flat CSR arrays (as ``pack``) of crystals given WITHOUT edges -- ``x`` (atomic numbers), ``pos``, ``cell`` and the
-    targets -- whose periodic radius graphs are built on the GPU, ``chunk`` crystals per launch pair
-    (cartnet_amd.graph.radius_graph_pbc: the reference's dataset/utils.py:57-237 edge order, integers bit-exact), and
-    rebased to the crystal.  20,283 crystals of 64-324 atoms (56 M edges): 0.55 s (tools/bench_config4.py)."""
-    from .graph import radius_graph_pbc
-    if len(geometries) == 0:
-        raise ValueError("cannot pack an empty list of crystals")
-    dev = torch.device(device)
-    n = [int(d.x.shape[0]) for d in geometries]
-    src_l, tgt_l, dist_l, dir_l, ecount = [], [], [], [], []
-    for c0 in range(0, len(geometries), chunk):
-        part = geometries[c0:c0 + chunk]
-        pos = torch.cat([d.pos for d in part]).to(dev)
-        cell = torch.cat([d.cell.reshape(1, 3, 3) for d in part]).to(dev)
-        ptr = torch.tensor([0] + n[c0:c0 + chunk], dtype=torch.int64).cumsum(0).to(dev)
-        ei, dist, dirs = radius_graph_pbc(pos, cell, ptr, radius, max_neighbors)
-        gid = torch.repeat_interleave(torch.arange(len(part), device=dev), ptr[1:] - ptr[:-1])
-        g_of_edge = gid[ei[1]]
-        off = ptr[g_of_edge]
-        src_l.append((ei[0] - off).to(torch.int32).cpu())
-        tgt_l.append((ei[1] - off).to(torch.int32).cpu())
-        dist_l.append(dist.cpu())
-        dir_l.append(dirs.cpu())
-        ecount.append(torch.bincount(g_of_edge, minlength=len(part)).cpu())
-    e = torch.cat(ecount).numpy().astype(np.int64)
-    d0 = geometries[0]
-    per_atom = d0.y.dim() == 3
-    ys = [d.y.reshape(-1, 9) if per_atom else d.y.reshape(1, -1) for d in geometries]
-    out = {
-        "atom_ptr": np.concatenate([[0], np.cumsum(n)]).astype(np.int64),
-        "edge_ptr": np.concatenate([[0], np.cumsum(e)]).astype(np.int64),
-        "y_ptr": np.concatenate([[0], np.cumsum([y.shape[0] for y in ys])]).astype(np.int64),
-        "z": torch.cat([d.x for d in geometries]).numpy().astype(np.int32),
-        "pos": torch.cat([d.pos for d in geometries]).numpy().astype(np.float32).reshape(-1, 3),
-        "edge_src": torch.cat(src_l).numpy(), "edge_tgt": torch.cat(tgt_l).numpy(),
-        "cart_dist": torch.cat(dist_l).numpy().astype(np.float32),
-        "cart_dir": torch.cat(dir_l).numpy().astype(np.float32).reshape(-1, 3),
-        "cell": torch.cat([d.cell.reshape(1, 9) for d in geometries]).numpy().astype(np.float32),
-        "y": torch.cat(ys).numpy().astype(np.float32),
-    }
-    if hasattr(d0, "non_H_mask"):
-        out["non_h_mask"] = torch.cat([d.non_H_mask for d in geometries]).numpy().astype(np.uint8)
-    if hasattr(d0, "temperature"):
-        out["temperature"] = torch.cat([d.temperature.reshape(1) for d in geometries]).numpy().astype(np.float32)
-    return out
+    targets -- whose periodic radius graphs are built on the GPU in one pass (``DeviceShard.with_radius_graph``: the
+    reference's dataset/utils.py:57-237 edge order, integers bit-exact) and brought back to the host."""
+    out = DeviceShard(pack(geometries), device).with_radius_graph(radius, max_neighbors)
+    return {k: v.cpu().numpy() for k, v in out.t.items()}
 
 
 def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, object]] = None) -> None:
@@ -271,50 +231,20 @@ class DeviceShard:
         None or <= 0: uncapped) rebuilt from ``pos`` and ``cell``, as a new resident shard (this one is untouched): what the
         reference's ``compute_knn`` does per file on the CPU before an e/iComformer run on ADP (dataset/utils.py:456-486,
         loader/loader.py:24-26) and ``Figshare_Dataset.process`` for Jarvis / MegNet (dataset/figshare_dataset.py:50-76),
-        done in one pass over the whole shard on the GPU (csrc/radius_graph.hip) -- the edges, order and arithmetic of
-        ``cartnet_amd.graph.radius_graph_pbc``.  The new shard owns ``edge_ptr``, ``edge_src``, ``edge_tgt``,
-        ``cart_dist`` and ``cart_dir``; every other array is shared.  The host reads two sizes and a status word; with a
-        cap that some atom exceeds the only transient edge-sized array is the uncapped rows' d^2 (4 B per edge).  Apply it
+        done in one pass over the whole shard on the GPU (csrc/radius_graph.hip, driven by
+        ``cartnet_amd.graph.radius_graph_csr``, which ``radius_graph_pbc`` runs over a batch).  The new shard owns
+        ``edge_ptr``, ``edge_src``, ``edge_tgt``, ``cart_dist`` and ``cart_dir``; every other array is shared.  Apply it
         BEFORE ``without_hydrogens()`` / ``with_optimized_cell()``, as the reference caps the graph of the full crystal in
         the stored frame."""
-        t, dev, G = self.t, self.device, self.num_graphs
+        t = self.t
         if "pos" not in t or "cell" not in t:
             raise ValueError("with_radius_graph needs the shard's pos and cell")
         if not float(radius) > 0.0:
             raise ValueError("radius must be positive")
-        N = int(self.atom_ptr[-1])
-        cap = int(max_neighbors) if max_neighbors is not None and int(max_neighbors) > 0 else 0
-        from .graph import DEGENERACY_TOLERANCE
-        lib = self._lib
-        with torch.cuda.device(dev):
-            args = (t["pos"].data_ptr(), t["cell"].data_ptr(), t["atom_ptr"].data_ptr(), G, N, float(radius))
-            ws_bytes = int(lib.cartnet_shard_regraph_workspace_bytes(G, N, 0))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            totals = torch.empty(4, dtype=torch.int64, device=dev)
-            _l.check(lib.cartnet_shard_regraph_count(*args, cap, ws.data_ptr(), ws_bytes, totals.data_ptr(),
-                                                     _l.stream_ptr()), "cartnet_shard_regraph_count")
-            e_all, _, over, status = totals.tolist()            # device-to-host copy 1: the uncapped size
-            if status != 0:
-                raise ValueError("the shard's atom_ptr is not an ascending offset array over its atoms")
-            E = e_all
-            if over:                                             # some atom has more than `cap` neighbours
-                d2 = torch.empty(e_all, dtype=torch.float32, device=dev)
-                _l.check(lib.cartnet_shard_regraph_cap(*args, cap, DEGENERACY_TOLERANCE, e_all, ws.data_ptr(), ws_bytes,
-                                                       d2.data_ptr(), totals.data_ptr(), _l.stream_ptr()),
-                         "cartnet_shard_regraph_cap")
-                E = int(totals[1].item())                        # device-to-host copy 2: the capped size
-            new = {"edge_ptr": torch.empty(G + 1, dtype=torch.int64, device=dev),
-                   "edge_src": torch.empty(E, dtype=torch.int32, device=dev),
-                   "edge_tgt": torch.empty(E, dtype=torch.int32, device=dev),
-                   "cart_dist": torch.empty(E, dtype=torch.float32, device=dev),
-                   "cart_dir": torch.empty((E, 3), dtype=torch.float32, device=dev)}
-            _l.check(lib.cartnet_shard_regraph_fill(*args, int(bool(over)), ws.data_ptr(), ws_bytes, E,
-                                                    new["edge_ptr"].data_ptr(), new["edge_src"].data_ptr(),
-                                                    new["edge_tgt"].data_ptr(), new["cart_dist"].data_ptr(),
-                                                    new["cart_dir"].data_ptr(), _l.stream_ptr()),
-                     "cartnet_shard_regraph_fill")
-            edge_ptr = new["edge_ptr"].cpu().numpy()            # ShardLoader balances ranks by it
-        return self._derived(new, self.atom_ptr, edge_ptr, graph_record(radius, cap))
+        from .graph import radius_graph_csr
+        new = dict(zip(_EDGE_ARRAYS, radius_graph_csr(t["pos"], t["cell"], t["atom_ptr"], radius, max_neighbors)))
+        edge_ptr = new["edge_ptr"].cpu().numpy()                # ShardLoader balances ranks by it
+        return self._derived(new, self.atom_ptr, edge_ptr, graph_record(radius, max_neighbors))
 
     def without_hydrogens(self) -> "DeviceShard":
         """The same crystals without their hydrogen atoms, as a new resident shard (this one is untouched): what the

@@ -126,7 +126,7 @@ def make_geometry(g: int, n_atoms: Optional[int] = 194, n_range=(64, 324), adp: 
                   base_seed: int = 1234) -> Data:
     """Everything of synthetic crystal ``g`` except its edges (SURVEY.md §8d recipe): atoms, cell, positions, targets.
     ``make_crystal`` adds the periodic radius graph on the host; tools/bench_config4.py builds it on the GPU instead
-    (cartnet_amd.graph.radius_graph_pbc) for tens of thousands of crystals."""
+    (cartnet_amd.shard.pack_with_gpu_graph) for tens of thousands of crystals."""
     gen = torch.Generator().manual_seed(base_seed + g)
     if n_atoms is None:
         n = int(torch.randint(n_range[0], n_range[1] + 1, (1,), generator=gen).item())

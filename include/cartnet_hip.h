@@ -35,7 +35,7 @@ int cartnet_abi_version(void);
 /* sizeof of every struct below, in header order (CartnetGemmArgs, CartnetShard, CartnetCollated, CartnetGemmProfile,
  * CartnetGroups, CartnetLayerParams, CartnetLayerBuffers, CartnetParams, CartnetModel, CartnetBatch,
  * CartnetGateGemmArgs, CartnetIcfConv, CartnetIcfParams, CartnetIcfModel); returns the number of structs.  A binding checks its mirrors against these when it loads the
- * library, and cartnet_abi_version() against the version it was written for (14: cartnet_radius_graph_count / _fill take the radius in double -- the cutoff is the fp32 rounding of the double product; 13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
+ * library, and cartnet_abi_version() against the version it was written for (15: removed in ABI 15: cartnet_radius_graph_count / _fill and cartnet_neighbor_cap_count / _fill -- cartnet_shard_regraph_count / _cap / _fill serve a batch as well as a shard; no layout change; 14: the radius-graph entry points take the radius in double -- the cutoff is the fp32 rounding of the double product; 13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
  * aux_stream in cartnet_model_forward, CartnetGateGemmArgs in the size table; cartnet_gemm_tile_policy() is gone). */
 int cartnet_abi_struct_sizes(size_t* out, int32_t capacity);
 
@@ -276,45 +276,20 @@ int cartnet_coldot_bc_partial(const float* d, int32_t ld, const float* bc, int32
 
 /* ------------------------------------------------------------------------------------------------------
  * Periodic radius graph on the GPU (reference: dataset/utils.py:57-237 radius_graph_pbc as used by
- * dataset/figshare_dataset.py:65-68; pairs with d^2 <= 1e-4 dropped).  Edges come out in the
- * reference's order (target, source, periodic image), i.e. edge_index[1] ascending.
- * radius is a double: a pair is kept when its fp32 d^2 <= (float)(radius * radius), the product taken in double as
- * the reference takes it (dataset/utils.py:202); the fp32 product is one ulp larger for some radii (3.7, 4.3).
- *   count: reps = caller's scratch of 15 * Bg 4-byte words, kept for fill: int32 [Bg,3] periodic repetitions per
- *          lattice direction, then fp32 [Bg,12] reciprocal lattice vectors and radius |b_d| (the per-pair image box:
- *          only images that can lie within the radius are tested); deg[N] = in-degree of every atom.
- *   fill:  rowptr[N+1] = exclusive prefix sum of deg (int64), E = rowptr[N]; writes edge_index [2,E] (int64,
- *          row 0 source, row 1 target), cart_dist [E], cart_dir [E,3] = (pos_target - (pos_source + offset)) / dist,
- *          and, if cart_dist_sq is not NULL, the squared distances [E] the neighbour cap ranks by.
- * Neighbour cap (dataset/utils.py:240-360 get_max_neighbors_mask with enforce_max_strictly = False, as applied at
- * dataset/utils.py:216-233 when figshare_dataset.py passes max_neigh): a target atom with more than max_neighbors
- * edges keeps those with d^2 <= (max_neighbors+1)-th smallest d^2 of its row + tolerance (0.01 in the reference), in
- * their original order; rows with <= max_neighbors edges are kept whole.
- *   cap_count: rowptr[N+1] of the uncapped graph, dist_sq[E] -> cutoff[N] (fp32, +inf for whole rows), deg[N].
- *   cap_fill:  rowptr_out[N+1] = exclusive prefix sum of deg, E_out = rowptr_out[N]; compacts edge_index [2,E] ->
- *              [2,E_out], cart_dist, cart_dir.
- * ---------------------------------------------------------------------------------------------------- */
-int cartnet_radius_graph_count(const float* pos, const float* cell, const int64_t* graph_ptr, const int64_t* batch,
-                               int32_t N, int32_t Bg, double radius, int32_t* reps, int32_t* deg, void* stream);
-int cartnet_radius_graph_fill(const float* pos, const float* cell, const int64_t* graph_ptr, const int64_t* batch,
-                              const int32_t* reps, const int64_t* rowptr, int32_t N, int32_t Bg, double radius,
-                              int64_t E, int64_t* edge_index, float* cart_dist, float* cart_dir, float* cart_dist_sq,
-                              void* stream);
-int cartnet_neighbor_cap_count(const int64_t* rowptr, const float* dist_sq, int32_t N, int32_t max_neighbors,
-                               float tolerance, float* cutoff, int32_t* deg, void* stream);
-int cartnet_neighbor_cap_fill(const int64_t* rowptr, const int64_t* rowptr_out, const float* cutoff,
-                              const float* dist_sq, const int64_t* edge_index, const float* cart_dist,
-                              const float* cart_dir, int32_t N, int64_t E, int64_t E_out, int64_t* edge_index_out,
-                              float* cart_dist_out, float* cart_dir_out, void* stream);
-
-/* ----------------------------------------------------------------------------------------------------
- * The radius graph of a whole resident shard, rebuilt on the GPU (reference: dataset/utils.py:456-486 compute_knn as
- * called at loader/loader.py:24-26 -- the capped graph of every ADP crystal rebuilt from pos and cell, one file at a
- * time on the CPU, dense O(N^2 images) -- and dataset/figshare_dataset.py:50-76, Figshare_Dataset.process at --radius /
- * --max_neighbours).  Same edges, same order and same arithmetic as cartnet_radius_graph_count / _fill followed by
- * cartnet_neighbor_cap_count / _fill on the same crystals, written in the shard's format: edge_ptr [G+1] int64,
- * edge_src / edge_tgt int32 atom indices inside the crystal, cart_dist, cart_dir.  pos [N,3], cell [G,9] and atom_ptr
- * [G+1] are the shard descriptor's; the crystal of an atom is found on the device.  max_neighbors <= 0: no cap.
+ * dataset/figshare_dataset.py:50-76, Figshare_Dataset.process at --radius / --max_neighbours, and by dataset/utils.py:456-486
+ * compute_knn as called at loader/loader.py:24-26 -- one crystal at a time on the CPU, dense O(N^2 images)).  One pass
+ * over pos [N,3], cell [G,9] and atom_ptr [G+1] builds the graph of all G crystals: the three arrays may be a resident
+ * shard's (the shard descriptor's) or a batch's (atom_ptr = the batch's ptr, G = its crystals); the crystal of an atom
+ * is found on the device.  Edges come out in the reference's order (target, source, periodic image), in the shard's
+ * format: edge_ptr [G+1] int64, edge_src / edge_tgt int32 atom indices inside the crystal (edge_tgt ascending per
+ * crystal), cart_dist [E], cart_dir [E,3] = (pos_target - (pos_source + offset)) / dist.
+ * Cutoff: radius is a double; a pair is kept when its fp32 d^2 <= (float)(radius * radius), the product taken in double
+ * as the reference takes it (dataset/utils.py:202; the fp32 product is one ulp larger for some radii: 3.7, 4.3), and
+ * d^2 > 1e-4.
+ * Cap (dataset/utils.py:240-360 get_max_neighbors_mask with enforce_max_strictly = False, as applied at :216-233): a
+ * target atom with more than max_neighbors edges keeps those with d^2 <= (max_neighbors+1)-th smallest d^2 of its row +
+ * tolerance (0.01 in the reference), ties kept, in their original order; rows with <= max_neighbors edges are kept
+ * whole.  max_neighbors <= 0: no cap.
  *   workspace_bytes(G, N, E_uncapped): all the transient memory of a pass.  workspace_bytes(G, N, 0) = O(N + G) bytes is
  *          the `workspace` of the three calls below (kept from count to fill, 16-byte aligned); the rest, 4 bytes per
  *          uncapped edge, is the dist_sq scratch of cap -- needed only when some row is longer than the cap.
@@ -322,9 +297,8 @@ int cartnet_neighbor_cap_fill(const int64_t* rowptr, const int64_t* rowptr_out, 
  *          [1] capped edge count (written by cap), [2] 1 if max_neighbors > 0 and some atom has more neighbours,
  *          [3] status -- 0 ok, 1 atom_ptr is not an ascending offset array from 0 to N.  The caller reads totals.
  *   cap:   only if totals[2]: dist_sq [E_uncapped] <- d^2 of the uncapped rows (4 B per edge, no indices, no directions),
- *          the per-row cutoff by rank counting (dataset/utils.py:240-360 get_max_neighbors_mask, enforce_max_strictly =
- *          False: d^2 <= (max_neighbors+1)-th smallest + tolerance, ties kept), the capped degrees and their prefix
- *          sum; totals[1] = capped edge count.  The caller reads it.
+ *          the per-row cutoff by rank counting, the capped degrees and their prefix sum; totals[1] = capped edge count.
+ *          The caller reads it.
  *   fill:  E = totals[capped ? 1 : 0]; walks the images again and writes the edges with d^2 <= cutoff of their row
  *          straight into edge_src / edge_tgt [E], cart_dist [E], cart_dir [E,3], and edge_ptr [G+1].
  * One wavefront per target atom and a wave prefix sum, reduce-then-scan row offsets: no atomics, identical bytes on every
@@ -460,7 +434,7 @@ int cartnet_collate(const CartnetShard* shard, const int64_t* sel, const int64_t
  * cell and temperature as they are).  Here it is one stable compaction of the shard's flat arrays, run once per
  * dataset (cartnet_amd/csrc/shard_ops.hip): atoms and edges keep their order, so edge_tgt stays ascending per crystal.
  * G crystals, N = atom_ptr[G] atoms, E = edge_ptr[G] edges; every array 16-byte aligned.  Two calls, as
- * cartnet_radius_graph_count / _fill:
+ * cartnet_shard_regraph_count / _fill:
  *   count: workspace of cartnet_shard_drop_h_workspace_bytes(N, E) bytes, kept for fill.  Writes atom_ptr_out [G+1]
  *          and totals [3] int64 (device): kept atoms, kept edges, status -- 0 ok; 1 the shard's non_h_mask disagrees
  *          with z != 1 somewhere (the rows of a per-atom y would no longer match the kept atoms); 2 an edge end lies

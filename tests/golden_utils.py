@@ -4,7 +4,7 @@ import os
 import numpy as np
 import torch
 
-from cartnet_amd.data import Batch
+from cartnet_amd.data import Batch, Data
 from cartnet_amd.model import make_state_dict
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -41,6 +41,26 @@ def crystal(name, n, seed, rotate=False):
 
 def threshold_pair(y):
     return torch.tensor([[0.0, 0.0, 0.0], [3.0, y, 0.0]], dtype=torch.float32), 20.0 * torch.eye(3)
+
+
+def geometry(pos, cell):
+    """A crystal without edges: what a geometry-only shard is packed from."""
+    n = pos.shape[0]
+    return Data(x=torch.full((n,), 6, dtype=torch.int64), pos=pos.clone(), cell=cell.reshape(1, 3, 3).clone(),
+                y=torch.zeros(1))
+
+
+def ragged():
+    """1, 2, 3, 40, 64, 65 and 70 atoms (more than one 64-source round; 251 atoms in all, no multiple of 4), a sheared
+    cell, a cell edge shorter than the radius, and a two-atom crystal in a 30 A cell (no edges) first, in the middle, last."""
+    far = (torch.tensor([[1.0, 2.0, 3.0], [16.0, 17.0, 14.0]]), 30.0 * torch.eye(3))
+    sheared = torch.tensor([[9.0, 0.0, 0.0], [6.5, 8.0, 0.0], [-4.0, 3.0, 10.0]])
+    gen = torch.Generator().manual_seed(11)
+    geo = [far, crystal("hexagonal", 1, 1), crystal("triclinic", 2, 2), crystal("small", 3, 3),
+           (torch.rand(40, 3, generator=gen) @ sheared, sheared), far, crystal("rhombohedral", 64, 4, rotate=True),
+           (torch.rand(65, 3, generator=gen) @ (1.4 * sheared), 1.4 * sheared), crystal("triclinic", 70, 5), far]
+    assert sum(p.shape[0] for p, _ in geo) == 251
+    return [geometry(p, c) for p, c in geo]
 
 
 def load(name):

@@ -26,7 +26,7 @@ def test_eight_rank_epoch_emulated_on_one_card_against_the_oracle():
     cfg.radius = 5.0
     n, batch, D, R, L = 40, 2, 256, 64, 4
     geo = [make_geometry(41000 + g, None) for g in range(n)]                       # 64..324 atoms each
-    arrays = shard.pack_with_gpu_graph(geo, 5.0, "cuda:0", chunk=16)
+    arrays = shard.pack_with_gpu_graph(geo, 5.0, "cuda:0")
     sizes = np.diff(arrays["atom_ptr"])
     assert sizes.min() >= 64 and sizes.max() <= 324
     ds = shard.DeviceShard(arrays)

@@ -138,6 +138,34 @@ def test_degenerate_cells_do_not_hang_or_fault():
     assert torch.allclose(dist[sel].cpu(), ref_dist, rtol=1e-6, atol=0)
 
 
+def test_batch_indices_are_the_one_crystal_indices_plus_ptr():
+    """The library writes atom indices inside the crystal; ``radius_graph_pbc`` adds ``ptr[g]`` per edge on the device.
+    Ten ragged crystals (tests/golden_utils.py: ragged -- 251 atoms; crystals without an edge first, in the middle and
+    last; 64, 65 and 70 atoms) in one call against ten one-crystal calls with the offsets added: identical bytes."""
+    from cartnet_amd.graph import radius_graph_pbc
+    from cartnet_amd.synthetic import radius_graph_pbc_single
+    items = gu.ragged()
+    sizes = [int(d.pos.shape[0]) for d in items]
+    ptr = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0)
+    pos, cell = torch.cat([d.pos for d in items]).cuda(), torch.cat([d.cell for d in items]).cuda()
+    edges = {}
+    for cap in (None, 12):
+        ei, dist, dirs = radius_graph_pbc(pos, cell, ptr.cuda(), 5.0, max_neighbors=cap)
+        one = [radius_graph_pbc(d.pos.cuda(), d.cell.cuda(), torch.tensor([0, n]).cuda(), 5.0, max_neighbors=cap)
+               for d, n in zip(items, sizes)]
+        assert [int(one[g][0].shape[1]) for g in (0, 5, 9)] == [0, 0, 0]          # the far pairs have no edges
+        assert ei.dtype == torch.int64 and ei.shape[0] == 2
+        assert torch.equal(ei, torch.cat([o[0] + int(ptr[g]) for g, o in enumerate(one)], 1)), cap
+        assert torch.equal(dist, torch.cat([o[1] for o in one])), cap
+        assert torch.equal(dirs, torch.cat([o[2] for o in one])), cap
+        assert bool((ei[1][1:] >= ei[1][:-1]).all())
+        host = [radius_graph_pbc_single(d.pos, d.cell[0], 5.0, max_neighbors=cap)[0] + int(ptr[g])
+                for g, d in enumerate(items)]
+        assert torch.equal(ei.cpu(), torch.cat(host, 1)), cap
+        edges[cap] = int(ei.shape[1])
+    assert 0 < edges[12] < edges[None]                                            # the cap bites on this batch
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Away from radius 5 and nearly cubic cells.  The reference is the host builder called per crystal (bit-identical to the
 # reference's dataset/utils.py on these cells, atom counts and radii: tests/golden/make_golden.py asserts it for the

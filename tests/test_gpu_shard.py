@@ -143,7 +143,7 @@ def test_shard_with_gpu_built_graphs_trains_like_the_host_built_one():
     from cartnet_amd.train import train_epoch
     n = 48
     geo = [make_geometry(700 + g, None, n_range=(20, 60)) for g in range(n)]
-    arrays = shard.pack_with_gpu_graph(geo, 5.0, "cuda:0", chunk=20)
+    arrays = shard.pack_with_gpu_graph(geo, 5.0, "cuda:0")
     ref = shard.pack([make_crystal(700 + g, None, n_range=(20, 60)) for g in range(n)])
     for k in ("atom_ptr", "edge_ptr", "y_ptr", "z", "edge_src", "edge_tgt", "non_h_mask"):
         assert np.array_equal(arrays[k], ref[k]), k

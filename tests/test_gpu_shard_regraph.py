@@ -1,25 +1,18 @@
 """``DeviceShard.with_radius_graph``: the radius graph of a whole resident shard rebuilt in one GPU pass
 (csrc/radius_graph.hip, cn_sr_kernel) -- against the reference's own graphs (tests/golden/radius_graph*.npz), bitwise
-against the per-batch GPU path (``pack_with_gpu_graph``), and composed with the other whole-shard steps."""
+against the same pass run one crystal at a time, and composed with the other whole-shard steps."""
 import numpy as np
 import pytest
 import torch
 
 import golden_utils as gu
 from cartnet_amd import shard
-from cartnet_amd.data import Batch, Data, lattice_margins, optimize_cell, remove_hydrogens
+from cartnet_amd.data import Batch, lattice_margins, optimize_cell, remove_hydrogens
 from cartnet_amd.synthetic import make_geometry, radius_graph_pbc_single
 
 pytestmark = pytest.mark.gpu
 
 EDGE_KEYS = ("edge_ptr", "edge_src", "edge_tgt", "cart_dist", "cart_dir")
-
-
-def _geometry(pos, cell):
-    """A crystal without edges: what a geometry-only shard is packed from."""
-    n = pos.shape[0]
-    return Data(x=torch.full((n,), 6, dtype=torch.int64), pos=pos.clone(), cell=cell.reshape(1, 3, 3).clone(),
-                y=torch.zeros(1))
 
 
 def _slice(s, g):
@@ -39,7 +32,7 @@ def test_reference_goldens_packed_as_one_geometry_only_shard():
     names = ["c0", "c1", "c2", "cubic", "hexagonal", "triclinic", "pair0", "pair1"]
     geo = [(t5(f"pos{i}"), t5(f"cell{i}")) for i in range(3)] + [(t5("cubic_pos"), t5("cubic_cell"))]
     geo += [(tr(f"{n}_pos"), tr(f"{n}_cell")) for n in ("hexagonal", "triclinic", "pair0", "pair1")]
-    base = shard.DeviceShard.from_data_list([_geometry(p, c) for p, c in geo])
+    base = shard.DeviceShard.from_data_list([gu.geometry(p, c) for p, c in geo])
     assert not base.has_graph and base.graph is None
     # (radius, cap) -> [(crystal, golden edge_index, dist, dir)]
     cases = {(5.0, None): [(f"c{i}", t5(f"edge_index{i}"), t5(f"dist{i}"), t5(f"dir{i}")) for i in range(3)],
@@ -81,36 +74,33 @@ def test_reference_goldens_packed_as_one_geometry_only_shard():
     assert int(torch.bincount(ei[1]).max()) == 18
 
 
-def _ragged():
-    """1, 2, 3, 40, 64, 65 and 70 atoms (more than one 64-source round; 251 atoms in all, no multiple of 4), a sheared
-    cell, a cell edge shorter than the radius, and a two-atom crystal in a 30 A cell (no edges) first, in the middle, last."""
-    far = (torch.tensor([[1.0, 2.0, 3.0], [16.0, 17.0, 14.0]]), 30.0 * torch.eye(3))
-    sheared = torch.tensor([[9.0, 0.0, 0.0], [6.5, 8.0, 0.0], [-4.0, 3.0, 10.0]])
-    gen = torch.Generator().manual_seed(11)
-    geo = [far, gu.crystal("hexagonal", 1, 1), gu.crystal("triclinic", 2, 2), gu.crystal("small", 3, 3),
-           (torch.rand(40, 3, generator=gen) @ sheared, sheared), far, gu.crystal("rhombohedral", 64, 4, rotate=True),
-           (torch.rand(65, 3, generator=gen) @ (1.4 * sheared), 1.4 * sheared), gu.crystal("triclinic", 70, 5), far]
-    assert sum(p.shape[0] for p, _ in geo) == 251
-    return [_geometry(p, c) for p, c in geo]
-
-
 @pytest.fixture(scope="module")
 def ragged():
-    items = _ragged()
+    items = gu.ragged()
     return items, shard.DeviceShard.from_data_list(items)
 
 
 @pytest.mark.parametrize("radius", [4.0, 5.0, 6.0])
-def test_bitwise_equal_to_the_per_batch_gpu_path(ragged, radius):
+def test_many_crystals_in_one_pass_bitwise_equal_to_one_crystal_per_pass(ragged, radius):
+    """The shard-wide pass over ten ragged crystals against ``radius_graph_pbc`` called once per crystal -- the same pass
+    over a single crystal, which tests/test_gpu_radius_graph.py pins to the reference."""
+    from cartnet_amd.graph import radius_graph_pbc
     items, base = ragged
     uncapped, bites = base.with_radius_graph(radius), 0
     for cap in (None, 12, 25, 10_000):
-        want = shard.pack_with_gpu_graph(items, radius, max_neighbors=cap)
+        one = [radius_graph_pbc(d.pos.cuda(), d.cell.cuda(), torch.tensor([0, d.pos.shape[0]]).cuda(), radius, cap)
+               for d in items]
+        e = [int(ei.shape[1]) for ei, _, _ in one]
+        want = {"edge_ptr": torch.tensor([0] + e, dtype=torch.int64).cumsum(0),
+                "edge_src": torch.cat([ei[0] for ei, _, _ in one]).cpu().to(torch.int32),
+                "edge_tgt": torch.cat([ei[1] for ei, _, _ in one]).cpu().to(torch.int32),
+                "cart_dist": torch.cat([d for _, d, _ in one]).cpu(), "cart_dir": torch.cat([v for _, _, v in one]).cpu()}
+        assert all(ei.dtype == torch.int64 for ei, _, _ in one) and want["cart_dir"].shape == (sum(e), 3)
         got = base.with_radius_graph(radius, cap)
         for k in EDGE_KEYS:
-            ref = torch.from_numpy(np.ascontiguousarray(want[k]))
+            ref = want[k]
             assert got.t[k].dtype == ref.dtype and torch.equal(got.t[k].cpu(), ref), (radius, cap, k)
-        assert np.array_equal(got.edge_ptr, want["edge_ptr"])
+        assert np.array_equal(got.edge_ptr, want["edge_ptr"].numpy())
         ep = got.edge_ptr
         assert ep[1] == 0 and ep[6] == ep[5] and ep[10] == ep[9]            # the far pairs have no edges
         bites += int(ep[-1]) < int(uncapped.edge_ptr[-1])
@@ -186,7 +176,7 @@ def test_composes_with_hydrogen_removal_canonical_cell_and_collate():
 
 
 def test_errors_and_degenerate_cells():
-    items = _ragged()[1:5]
+    items = gu.ragged()[1:5]
     geo = shard.DeviceShard.from_data_list(items)
     for what in (lambda: geo.collate([0]), geo.without_hydrogens, geo.with_optimized_cell):
         with pytest.raises(ValueError, match="with_radius_graph"):
@@ -203,7 +193,7 @@ def test_errors_and_degenerate_cells():
     good = items[3]
     flat = torch.tensor([[4.0, 0, 0], [0, 4.0, 0], [4.0, 4.0, 0]])
     pts = torch.rand(5, 3, generator=torch.Generator().manual_seed(3)) * 3
-    bad = shard.DeviceShard.from_data_list([_geometry(pts, flat), _geometry(pts, torch.zeros(3, 3)), good])
+    bad = shard.DeviceShard.from_data_list([gu.geometry(pts, flat), gu.geometry(pts, torch.zeros(3, 3)), good])
     for cap in (None, 8):
         out = bad.with_radius_graph(5.0, cap)
         torch.cuda.synchronize()

@@ -30,7 +30,6 @@ from cartnet_amd.train import train_epoch
 ap = argparse.ArgumentParser()
 ap.add_argument("--crystals", type=int, default=162270 // 8)
 ap.add_argument("--precision", type=int, default=0)
-ap.add_argument("--chunk", type=int, default=256, help="crystals per radius-graph launch")
 ap.add_argument("--grouped", action="store_true", help="also run batch 64 with BatchNorm / loss per group of 4")
 ap.add_argument("--only-batch64", action="store_true", help="skip the literal micro-batch recipe (full-epoch runs)")
 ap.add_argument("--no-hydrogens", action="store_true", help="train on the hydrogen-free copy of the shard")
@@ -46,10 +45,10 @@ for i in range(n):            # host-side geometry, single process (a progress l
     if (i + 1) % 10000 == 0:
         print(f"geometry {i + 1}/{n} {time.perf_counter() - t0:.0f} s", file=sys.stderr, flush=True)
 t_geo = time.perf_counter() - t0
-# ---- edges on the GPU (cartnet_amd.shard.pack_with_gpu_graph: `chunk` crystals per launch pair, rebased to the crystal)
+# ---- edges on the GPU (cartnet_amd.shard.pack_with_gpu_graph: one pass over all crystals)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-arrays = pack_with_gpu_graph(geo, 5.0, dev, args.chunk)
+arrays = pack_with_gpu_graph(geo, 5.0, dev)
 torch.cuda.synchronize()
 t_graph = time.perf_counter() - t0
 atom_ptr = arrays["atom_ptr"]

@@ -146,8 +146,84 @@ def adp_eval(pred: torch.Tensor, true: torch.Tensor, row_ptr: torch.Tensor, rot:
                    row_ptr[1:] - row_ptr[:-1])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Export in CIF convention (csrc/export_ops.hip): the inverse of the transform that brought the dataset's targets into
+# the Cartesian frame (the reference's dataset/extract_csd_data.py:115-123).
+
+ADP_EXPORT_TILE = 1024      # rows per workgroup tile of the export kernel (csrc/shard_tiles.h: SO_TILE)
+
+
+class AdpExport(NamedTuple):
+    """What ``adp_export`` returns, all on the device.  ``u_cif`` [M,6] fp32: U11 U22 U33 U23 U13 U12 on the unit
+    reciprocal axes; ``u_eq`` [M]; ``principal`` [M,3] ascending; ``axes`` [M,3,3], rows = unit principal axes, largest
+    component positive (``None`` if not requested); ``crystal_stats`` [B,3] fp64: per crystal the sum of ``u_eq``, the
+    smallest principal value (+inf without rows) and the number of rows whose smallest principal value is <= 0 (``None``
+    if not requested); ``status`` [B] int32: bit 0 set for a singular cell, whose rows are NaN."""
+    u_cif: torch.Tensor
+    u_eq: torch.Tensor
+    principal: torch.Tensor
+    axes: Optional[torch.Tensor]
+    crystal_stats: Optional[torch.Tensor]
+    status: torch.Tensor
+
+
+def check_export_status(status, names=None) -> None:
+    """Raises ``ValueError`` naming the first crystal whose ``AdpExport.status`` is set.  ``status``: a host tensor or
+    sequence (bring it over with the results: one transfer); ``names``: the crystals' names, if they have any."""
+    for g, s in enumerate(status.tolist() if hasattr(status, "tolist") else status):
+        if int(s) & 1:
+            who = f"crystal {g}" + (f" ({names[g]})" if names is not None else "")
+            raise ValueError(f"{who}: singular cell (its lattice vectors span no volume): no reciprocal axes to export "
+                             "the ADPs on")
+
+
+def adp_export(pred: torch.Tensor, row_ptr: torch.Tensor, cell: torch.Tensor, axes: bool = True, stats: bool = True,
+               check: bool = True) -> AdpExport:
+    """The predictions ``pred`` [M,3,3] (Cartesian frame of the dataset) in CIF convention, with their equivalent isotropic
+    value and principal values / axes: one call of ``cartnet_adp_export``.  ``row_ptr`` [B+1]: crystal g owns rows
+    ``[row_ptr[g], row_ptr[g+1])``; ``cell`` [B,3,3] fp32, rows = lattice vectors.  With ``check`` the status is read back
+    (one small device-to-host copy) and a singular cell raises ``ValueError`` naming the crystal; with ``check=False`` the
+    caller passes ``AdpExport.status`` to ``check_export_status`` once it has brought the results to the host."""
+    if not (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 3 and tuple(pred.shape[1:]) == (3, 3)):
+        raise ValueError("pred must be a CUDA fp32 tensor [M,3,3]")
+    pred, M, dev = pred.detach().contiguous(), int(pred.shape[0]), pred.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    if not (cell.dtype == torch.float32 and tuple(cell.shape) == (B, 3, 3) and cell.device == dev):
+        raise ValueError("cell must be an fp32 tensor [B,3,3] on the data's device")
+    cell = cell.detach().contiguous()
+    u_cif = torch.empty((M, 6), dtype=torch.float32, device=dev)
+    u_eq = torch.empty(M, dtype=torch.float32, device=dev)
+    principal = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    ax = torch.empty((M, 3, 3), dtype=torch.float32, device=dev) if axes else None
+    if M == 0:                                   # the entry point launches nothing: no rows, nothing to flag
+        st = torch.tensor([0.0, float("inf"), 0.0], dtype=torch.float64, device=dev).repeat(B, 1) if stats else None
+        return AdpExport(u_cif, u_eq, principal, ax, st, torch.zeros(B, dtype=torch.int32, device=dev))
+    st = torch.empty((B, 3), dtype=torch.float64, device=dev) if stats else None
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    _l.check(_l.load().cartnet_adp_export(pred.data_ptr(), row_ptr.data_ptr(), cell.data_ptr(), B, M, u_cif.data_ptr(),
+                                          u_eq.data_ptr(), principal.data_ptr(), _l.ptr(ax), _l.ptr(st),
+                                          status.data_ptr(), _l.stream_ptr()), "cartnet_adp_export")
+    if check:
+        check_export_status(status.cpu())
+    return AdpExport(u_cif, u_eq, principal, ax, st, status)
+
+
 def split_rows(t: torch.Tensor, rows) -> list:
     """The per-crystal pieces of a host tensor whose dim 0 runs over the rows of a batch: one transfer per batch, then
     this split by the crystals' row counts (a sequence of ints) gives the reference's one-entry-per-crystal lists.  Every
     piece owns its memory: a pickled view would drag the whole batch's storage along."""
     return [piece.clone() for piece in torch.split(t, [int(r) for r in rows], dim=0)]
+
+
+def to_host(tensors: dict) -> dict:
+    """The device tensors of ``tensors`` on the host, through ONE device-to-host copy: their bytes are packed into one
+    buffer on the device, and every tensor is cut back out of its host copy (each owning its memory)."""
+    items = [(k, t.detach().contiguous()) for k, t in tensors.items()]
+    flat = torch.cat([t.view(torch.uint8).reshape(-1) if t.numel() else t.new_empty(0, dtype=torch.uint8)
+                      for _, t in items]).to("cpu")
+    out, at = {}, 0
+    for k, t in items:
+        n = t.numel() * t.element_size()
+        out[k] = flat[at:at + n].clone().view(t.dtype).reshape(t.shape)
+        at += n
+    return out

@@ -1,0 +1,129 @@
+"""ADPs for crystals that have no targets, in the convention crystallographic tools read.
+
+``predict_adps`` is the prediction-side counterpart of ``main.inference_batched``: per batch of a resident shard (labeled or
+not) one forward, one ``adp_export`` (csrc/export_ops.hip: the predictions on the unit reciprocal axes -- the inverse of the
+transform the reference applied to the dataset's targets, dataset/extract_csd_data.py:115-123 -- with U_eq and the
+principal values / axes), the fractional coordinates, ONE device-to-host copy (``metrics.to_host``) and a split by row
+counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List
+
+import torch
+
+from .metrics import adp_export, check_export_status, split_rows, target_row_ptr, to_host
+
+KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
+
+SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
+           "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
+           "Au Hg Tl Pb Bi Po At Rn Fr Ra Ac Th Pa U Np Pu Am Cm Bk Cf Es Fm Md No Lr Rf Db Sg Bh Hs Mt Ds Rg Cn Nh Fl Mc "
+           "Lv Ts Og").split()
+
+
+def _inverse_cells(cell: torch.Tensor) -> torch.Tensor:
+    """inv(cell) for [B,3,3] cells by the adjugate (its columns are the reciprocal vectors): plain torch on the device."""
+    a, b, c = cell.unbind(1)
+    adj = torch.stack((torch.linalg.cross(b, c), torch.linalg.cross(c, a), torch.linalg.cross(a, b)), dim=2)
+    det = (a * torch.linalg.cross(b, c)).sum(1)
+    return adj / det.view(-1, 1, 1)
+
+
+def predict_adps(model, loader, device) -> Dict[str, List]:
+    """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
+    dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
+    the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
+    shard has none); ``u_cart`` [n,3,3] (the model's output); ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12); ``u_eq`` [n];
+    ``principal`` [n,3] ascending; ``axes`` [n,3,3]; ``stats`` [3] fp64 (sum of u_eq, smallest principal value, rows with a
+    non-positive one).  A singular cell raises ``ValueError`` naming the crystal."""
+    shard = loader.shard
+    if not shard.per_atom_target:
+        raise ValueError("predict_adps needs an ADP shard (per-atom 3x3 rows)")
+    if not all(k in shard.t for k in ("pos", "cell", "non_h_mask")):
+        raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
+    model.eval()
+    out: Dict[str, List] = {k: [] for k in KEYS}
+    with torch.no_grad():
+        for batch in loader:
+            if batch is None:
+                continue
+            batch.to(device)
+            B = int(batch.num_graphs)
+            row_ptr = target_row_ptr(batch)
+            sel = batch._meta[:B]
+            z = batch.x.clone()                                               # forward overwrites x
+            dev = {"z": z, "atoms": z[batch.non_H_mask], "cell": batch.cell, "_sel": sel, "_row_ptr": row_ptr,
+                   "_atom_ptr": batch.ptr,
+                   "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
+            if "temperature" in shard.t:
+                dev["temp"] = shard.t["temperature"][sel]                     # the collated one is standardised
+            pred, _ = model(batch)
+            ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
+            dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
+                       stats=ex.crystal_stats, _status=ex.status)
+            host = to_host(dev)
+            ids = host.pop("_sel").tolist()
+            names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
+            check_export_status(host.pop("_status"), names)
+            rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
+            rows, atoms = (rp[1:] - rp[:-1]).tolist(), (ap[1:] - ap[:-1]).tolist()
+            out["name"] += names
+            out["temp"] += host.pop("temp").tolist() if "temp" in host else [float("nan")] * B
+            for k in ("cell", "stats"):
+                out[k] += [t.clone() for t in host.pop(k).unbind(0)]
+            for k in ("frac", "z"):
+                out[k] += split_rows(host.pop(k), atoms)
+            for k, t in host.items():
+                out[k] += split_rows(t, rows)
+    if hasattr(model, "flush_graph_checks"):
+        model.flush_graph_checks()
+    return out
+
+
+def entry(result: Dict[str, List], k: int) -> dict:
+    """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` takes."""
+    return {key: result[key][k] for key in KEYS}
+
+
+def cell_parameters(cell) -> tuple:
+    """(a, b, c, alpha, beta, gamma) in Angstrom and degrees of a cell whose rows are the lattice vectors."""
+    v = [[float(x) for x in row] for row in (cell.tolist() if hasattr(cell, "tolist") else cell)]
+    n = [math.sqrt(sum(x * x for x in r)) for r in v]
+
+    def angle(i, j):
+        c = sum(p * q for p, q in zip(v[i], v[j])) / (n[i] * n[j])
+        return math.degrees(math.acos(max(-1.0, min(1.0, c))))
+    return n[0], n[1], n[2], angle(1, 2), angle(0, 2), angle(0, 1)
+
+
+def write_cif(path: str, entry: dict) -> None:
+    """One crystal as a P1 CIF: the cell, the temperature, every atom (label = element symbol + running number) and the
+    anisotropic displacement parameters of the non-hydrogen atoms, ``U_11 U_22 U_33 U_23 U_13 U_12``."""
+    z = [int(v) for v in entry["z"].tolist()]
+    labels = [f"{SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'}{i + 1}" for i, v in enumerate(z)]
+    heavy = [i for i, v in enumerate(z) if v != 1]
+    u = entry["u_cif"].tolist()
+    if len(heavy) != len(u):
+        raise ValueError(f"{len(u)} ADP rows for {len(heavy)} non-hydrogen atoms")
+    a, b, c, al, be, ga = cell_parameters(entry["cell"])
+    name = "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in str(entry["name"])) or "crystal"
+    lines = [f"data_{name}",
+             f"_cell_length_a {a:.6f}", f"_cell_length_b {b:.6f}", f"_cell_length_c {c:.6f}",
+             f"_cell_angle_alpha {al:.5f}", f"_cell_angle_beta {be:.5f}", f"_cell_angle_gamma {ga:.5f}"]
+    temp = float(entry["temp"])
+    if not math.isnan(temp):
+        lines.append(f"_diffrn_ambient_temperature {temp:.2f}")
+    lines += ["_symmetry_space_group_name_H-M 'P 1'", "_symmetry_Int_Tables_number 1",
+              "loop_", "_symmetry_equiv_pos_as_xyz", "'x, y, z'"]
+    lines += ["loop_", "_atom_site_label", "_atom_site_type_symbol", "_atom_site_fract_x", "_atom_site_fract_y",
+              "_atom_site_fract_z"]
+    for lab, v, f in zip(labels, z, entry["frac"].tolist()):
+        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}")
+    lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
+              "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
+    for i, row in zip(heavy, u):
+        lines.append(labels[i] + " " + " ".join(f"{x:.6f}" for x in row))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")

@@ -17,6 +17,10 @@ as uint64 right after the magic) listing ``{"name": [dtype, shape, offset]}``, t
 temperature).  A geometry-only shard leaves out ``edge_ptr`` and the four edge arrays and must carry ``pos`` and
 ``cell``: ``DeviceShard.with_radius_graph`` builds its graph on the GPU.  The header may record the graph's provenance,
 ``"graph": {"radius": r, "max_neighbors": k or null}`` (``read_shard_meta``).
+
+An unlabeled shard (crystals to predict ADPs for: the header says ``"targets": false``) has no ``y``; its ``y_ptr`` counts
+the non-hydrogen atoms (``z != 1``), the rows the per-atom head produces, and it always stores ``non_h_mask``.  The header
+may also carry ``"names"``, one string per crystal.
 """
 from __future__ import annotations
 
@@ -45,19 +49,29 @@ def graph_record(radius: float, max_neighbors: Optional[int] = None) -> Dict[str
 def pack(data_list: Sequence[Data]) -> Dict[str, np.ndarray]:
     """Flat CSR arrays of a list of crystals (the attribute set of cartnet_amd.data / SURVEY.md 8a).  Crystals without
     ``edge_index`` -- all of the list or none -- give a geometry-only shard (no ``edge_ptr``, no edge arrays), which needs
-    ``pos`` and ``cell``."""
+    ``pos`` and ``cell``.  Crystals without ``y`` -- again all or none -- give an unlabeled ADP shard: no ``y`` array,
+    ``y_ptr`` over the non-hydrogen atoms, ``non_h_mask`` from ``z != 1`` where the crystals carry none."""
     if len(data_list) == 0:
         raise ValueError("cannot pack an empty list of crystals")
     with_edges = [hasattr(d, "edge_index") for d in data_list]
     if any(with_edges) and not all(with_edges):
         raise ValueError("crystals with and without edge_index in one list: a shard carries the graph of all its crystals "
                          "or of none")
+    with_y = [hasattr(d, "y") for d in data_list]
+    if any(with_y) and not all(with_y):
+        raise ValueError("crystals with and without y in one list: a shard carries the targets of all its crystals or of "
+                         "none")
+    labeled = with_y[0]
     d0 = data_list[0]
     if not with_edges[0] and not all(hasattr(d, "pos") and hasattr(d, "cell") for d in data_list):
         raise ValueError("a crystal without edge_index needs pos and cell (DeviceShard.with_radius_graph builds the graph)")
     n = [int(d.x.shape[0]) for d in data_list]
-    per_atom = d0.y.dim() == 3
-    ys = [d.y.reshape(-1, 9) if per_atom else d.y.reshape(1, -1) for d in data_list]
+    if labeled:
+        per_atom = d0.y.dim() == 3
+        ys = [d.y.reshape(-1, 9) if per_atom else d.y.reshape(1, -1) for d in data_list]
+        rows = [y.shape[0] for y in ys]
+    else:
+        rows = [int((d.x != 1).sum()) for d in data_list]      # the rows the per-atom head will produce
     e = [int(d.edge_index.shape[1]) for d in data_list] if with_edges[0] else []
 
     def edge(make):                       # an edge array, in its place in the file's array order; None for geometry only
@@ -65,19 +79,21 @@ def pack(data_list: Sequence[Data]) -> Dict[str, np.ndarray]:
     out = {
         "atom_ptr": np.concatenate([[0], np.cumsum(n)]).astype(np.int64),
         "edge_ptr": edge(lambda: np.concatenate([[0], np.cumsum(e)]).astype(np.int64)),
-        "y_ptr": np.concatenate([[0], np.cumsum([y.shape[0] for y in ys])]).astype(np.int64),
+        "y_ptr": np.concatenate([[0], np.cumsum(rows)]).astype(np.int64),
         "z": torch.cat([d.x for d in data_list]).numpy().astype(np.int32),
         "edge_src": edge(lambda: torch.cat([d.edge_index[0] for d in data_list]).numpy().astype(np.int32)),
         "edge_tgt": edge(lambda: torch.cat([d.edge_index[1] for d in data_list]).numpy().astype(np.int32)),
         "cart_dist": edge(lambda: torch.cat([d.cart_dist for d in data_list]).numpy().astype(np.float32)),
         "cart_dir": edge(lambda: torch.cat([d.cart_dir for d in data_list]).numpy().astype(np.float32).reshape(-1, 3)),
-        "y": torch.cat(ys).numpy().astype(np.float32),
+        "y": torch.cat(ys).numpy().astype(np.float32) if labeled else None,
     }
     out = {k: v for k, v in out.items() if v is not None}
     if hasattr(d0, "pos"):
         out["pos"] = torch.cat([d.pos for d in data_list]).numpy().astype(np.float32).reshape(-1, 3)
     if hasattr(d0, "non_H_mask"):
         out["non_h_mask"] = torch.cat([d.non_H_mask for d in data_list]).numpy().astype(np.uint8)
+    elif not labeled:
+        out["non_h_mask"] = (out["z"] != 1).astype(np.uint8)
     if hasattr(d0, "cell"):
         out["cell"] = torch.cat([d.cell.reshape(1, 9) for d in data_list]).numpy().astype(np.float32)
     if hasattr(d0, "temperature"):
@@ -93,14 +109,16 @@ def pack_with_gpu_graph(geometries: Sequence[Data], radius: float = 5.0, device=
     """Flat CSR arrays (as ``pack``) of crystals given WITHOUT edges -- ``x`` (atomic numbers), ``pos``, ``cell`` and the
     targets -- whose periodic radius graphs are built on the GPU in one pass (``DeviceShard.with_radius_graph``: the
     reference's dataset/utils.py:57-237 edge order, integers bit-exact) and brought back to the host."""
-    out = DeviceShard(pack(geometries), device).with_radius_graph(radius, max_neighbors)
+    arrays = pack(geometries)
+    out = DeviceShard(arrays, device, labeled="y" in arrays).with_radius_graph(radius, max_neighbors)
     return {k: v.cpu().numpy() for k, v in out.t.items()}
 
 
-def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, object]] = None) -> None:
-    """``graph``: how the crystals' edges were built, ``{"radius": r, "max_neighbors": k or None}``; recorded in the
-    header, so that a loader can tell whether the graph it wants is the one stored (the reference's cached-directory test,
-    dataset/utils.py:462-464)."""
+def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, object]] = None,
+                names: Optional[Sequence[str]] = None) -> None:
+    """``names``: one string per crystal, stored in the header.  ``graph``: how the crystals' edges were built,
+    ``{"radius": r, "max_neighbors": k or None}``; recorded in the header, so that a loader can tell whether the graph it
+    wants is the one stored (the reference's cached-directory test, dataset/utils.py:462-464)."""
     arrays = pack(data_list)
     if graph is not None:
         if "edge_ptr" not in arrays:
@@ -113,6 +131,13 @@ def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, 
     head = {"arrays": meta, "graphs": len(data_list)}
     if graph is not None:
         head["graph"] = graph
+    if "y" not in arrays:
+        head["targets"] = False
+    if names is not None:
+        names = [str(n) for n in names]
+        if len(names) != len(data_list):
+            raise ValueError(f"{len(names)} names for {len(data_list)} crystals")
+        head["names"] = names
     header = json.dumps(head).encode()
     header += b" " * (-(len(MAGIC) + 8 + len(header)) % _ALIGN)
     with open(path, "wb") as f:
@@ -133,7 +158,8 @@ def _read_header(path: str):
 
 
 def read_shard_meta(path: str) -> Dict[str, object]:
-    """The JSON header of a shard file: ``arrays``, ``graphs`` and, if it was recorded, ``graph``."""
+    """The JSON header of a shard file: ``arrays``, ``graphs`` and, if they were recorded, ``graph``, ``names`` and
+    ``"targets": false`` (an unlabeled shard)."""
     return _read_header(path)[0]
 
 
@@ -149,13 +175,20 @@ def read_shard(path: str) -> Dict[str, np.ndarray]:
 class DeviceShard:
     """A shard resident in HBM.  ``collate(sel)`` builds the batch of crystals ``sel`` with one kernel launch.
     ``graph``: the provenance of its edges, ``{"radius": r, "max_neighbors": k or None}``, or None when unknown.  A
-    geometry-only shard (``has_graph`` False: ``pos`` and ``cell`` but no edge arrays) only serves ``with_radius_graph``."""
+    geometry-only shard (``has_graph`` False: ``pos`` and ``cell`` but no edge arrays) only serves ``with_radius_graph``.
+    ``labeled=False``: an unlabeled ADP shard, arrays without ``y`` (None means labeled; ``from_file`` takes it from the
+    header); its batches carry a zero ``y`` of the right size.  ``names``: one string per crystal, or None."""
 
-    def __init__(self, arrays: Dict[str, np.ndarray], device="cuda:0", graph: Optional[Dict[str, object]] = None):
+    def __init__(self, arrays: Dict[str, np.ndarray], device="cuda:0", graph: Optional[Dict[str, object]] = None,
+                 labeled: Optional[bool] = None, names: Optional[Sequence[str]] = None):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise ValueError("DeviceShard lives on the GPU; there is no CPU path (use Batch.from_data_list on the host)")
-        need = ("atom_ptr", "y_ptr", "z", "y")
+        self._labeled = True if labeled is None else bool(labeled)
+        if not self._labeled and "y" in arrays:
+            raise ValueError("an unlabeled shard carries no y")
+        # unlabeled: per-atom ADP prediction only, whose rows are the non-hydrogen atoms
+        need = ("atom_ptr", "y_ptr", "z") + (("y",) if self._labeled else ("non_h_mask",))
         if any(k in arrays for k in _EDGE_ARRAYS):
             need += _EDGE_ARRAYS
         else:
@@ -168,6 +201,9 @@ class DeviceShard:
         # host copies of the offsets: batch sizes are known without a device round trip
         self.atom_ptr = np.asarray(arrays["atom_ptr"], dtype=np.int64)
         self.num_graphs = int(self.atom_ptr.shape[0] - 1)
+        self.names = [str(n) for n in names] if names is not None else None
+        if self.names is not None and len(self.names) != self.num_graphs:
+            raise ValueError(f"{len(self.names)} names for {self.num_graphs} crystals")
         self.edge_ptr = (np.asarray(arrays["edge_ptr"], dtype=np.int64) if "edge_ptr" in arrays
                          else np.zeros(self.num_graphs + 1, dtype=np.int64))
         self.y_ptr = np.asarray(arrays["y_ptr"], dtype=np.int64)
@@ -187,7 +223,10 @@ class DeviceShard:
 
     def _describe(self) -> None:
         """The C descriptor of the device tensors in ``self.t``."""
-        self.y_width = int(self.t["y"].shape[1]) if self.t["y"].dim() == 2 else 1
+        if self._labeled:
+            self.y_width = int(self.t["y"].shape[1]) if self.t["y"].dim() == 2 else 1
+        else:
+            self.y_width = 9                    # the per-atom head's 3x3 rows; the descriptor's y stays NULL
         self.per_atom_target = self.y_width == 9
         d = _l.Shard()
         for k in ("atom_ptr", "edge_ptr", "y_ptr", "z", "pos", "non_h_mask", "edge_src", "edge_tgt", "cart_dist",
@@ -199,11 +238,20 @@ class DeviceShard:
 
     @classmethod
     def from_file(cls, path: str, device="cuda:0") -> "DeviceShard":
-        return cls(read_shard(path), device, graph=read_shard_meta(path).get("graph"))
+        meta = read_shard_meta(path)
+        return cls(read_shard(path), device, graph=meta.get("graph"), labeled=bool(meta.get("targets", True)),
+                   names=meta.get("names"))
 
     @classmethod
     def from_data_list(cls, data_list: Sequence[Data], device="cuda:0") -> "DeviceShard":
-        return cls(pack(data_list), device)
+        arrays = pack(data_list)
+        return cls(arrays, device, labeled="y" in arrays)
+
+    @property
+    def labeled(self) -> bool:
+        """False for an unlabeled shard: no ``y``; ``collate`` gives its batches a zero ``y`` with one row per non-hydrogen
+        atom."""
+        return self._labeled
 
     def nbytes(self) -> int:
         return sum(v.numel() * v.element_size() for v in self.t.values())
@@ -221,6 +269,7 @@ class DeviceShard:
         """A resident shard that owns the tensors in ``new`` and shares every other one with this shard."""
         out = object.__new__(DeviceShard)
         out.device, out.num_graphs, out._lib, out.graph = self.device, self.num_graphs, self._lib, graph
+        out._labeled, out.names = self._labeled, self.names
         out.atom_ptr, out.edge_ptr, out.y_ptr = atom_ptr, edge_ptr, self.y_ptr
         out.t = {**self.t, **new}
         out._describe()
@@ -299,6 +348,9 @@ class DeviceShard:
         the rows of the old cell).  Composes with ``without_hydrogens()`` in either order.  Raises ``ValueError`` naming
         the first crystal whose cell is degenerate (no three independent vectors among the candidates)."""
         self._need_graph("with_optimized_cell")
+        if not self._labeled:
+            raise ValueError("with_optimized_cell: not on an unlabeled shard (predictions in the frame of the reduced cell "
+                             "are not mapped back to the stored cell)")
         dev, t, G = self.device, self.t, self.num_graphs
         if "cell" not in t:
             raise ValueError("the shard carries no cell")
@@ -342,6 +394,7 @@ class DeviceShard:
             seg[0] = 0
             np.cumsum(p[sel_np + 1] - p[sel_np], out=seg[1:])
         N, E, M = (int(meta[B + j * (B + 1) + B]) for j in range(3))
+        M_copy = M if self._labeled else 0                         # unlabeled: the kernel copies no targets
         dev = self.device
         meta_d = torch.from_numpy(meta).pin_memory().to(dev, non_blocking=True)
         if rot is not None:
@@ -355,8 +408,11 @@ class DeviceShard:
         b.edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
         b.cart_dist = torch.empty(E, dtype=torch.float32, device=dev)
         b.cart_dir = torch.empty((E, 3), dtype=torch.float32, device=dev)
-        b.y = torch.empty((M, 3, 3) if self.per_atom_target else ((M,) if self.y_width == 1 else (M, self.y_width)),
-                          dtype=torch.float32, device=dev)
+        if self._labeled:
+            b.y = torch.empty((M, 3, 3) if self.per_atom_target else ((M,) if self.y_width == 1 else (M, self.y_width)),
+                              dtype=torch.float32, device=dev)
+        else:                                 # the models size their output by y.shape[0]; nothing reads the values
+            b.y = torch.zeros((M, 3, 3), dtype=torch.float32, device=dev)
         if "pos" in self.t:
             b.pos = torch.empty((N, 3), dtype=torch.float32, device=dev)
         if "non_h_mask" in self.t:
@@ -375,7 +431,7 @@ class DeviceShard:
         o.temperature = b.temperature.data_ptr() if "temperature" in self.t else None
         base = meta_d.data_ptr()
         _l.check(self._lib.cartnet_collate(_l.C.byref(self._desc), base, base + 8 * B, base + 8 * (2 * B + 1),
-                                           base + 8 * (3 * B + 2), B, N, E, M,
+                                           base + 8 * (3 * B + 2), B, N, E, M_copy,
                                            rot.data_ptr() if rot is not None else None, float(temp_mean),
                                            float(temp_std), _l.C.byref(o), _l.stream_ptr()), "cartnet_collate")
         b.num_graphs = B
@@ -405,6 +461,8 @@ class ShardLoader:
                  temp_std: float = 1.0, indices: Optional[Sequence[int]] = None):
         self.shard, self.batch_size, self.shuffle, self.seed = shard, int(batch_size), shuffle, seed
         self.rank, self.world_size, self.drop_last, self.augment = rank, world_size, drop_last, augment
+        if augment and not shard.labeled:
+            raise ValueError("augment=True on an unlabeled shard: there are no targets to rotate")
         self.temp_mean, self.temp_std = temp_mean, temp_std
         self.indices = list(range(shard.num_graphs)) if indices is None else list(indices)
         self.epoch = 0

@@ -357,6 +357,29 @@ int cartnet_adp_eval(const float* pred, const float* truth, const int64_t* row_p
                      float* volume_error, float* similarity_index, float* iou, double* crystal_sums, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Export of predicted ADPs in CIF convention.  The reference's dataset/extract_csd_data.py:115-123 brought the
+ * dataset's targets into the Cartesian frame: U_cart = A (N U_cif N) A^T with A = cell^T (columns a, b, c) and
+ * N = diag(|a*|, |b*|, |c*|).  This entry point inverts that transform: with r^_i the unit vector along the reciprocal
+ * vector a*_i (row i of inv(cell^T)), U_cif[i][j] = r^_i^T U r^_j.
+ *   u_cart [M,9] fp32: one row-major 3x3 per row (the model's per-atom output); row_ptr [B+1] int64 as above;
+ *   cell [B,9] fp32: the rows are the lattice vectors.
+ * Per row, in fp64 from the fp32 inputs, every result stored as fp32:
+ *   U = (U + U^T) / 2
+ *   u_cif [M,6]      = U11 U22 U33 U23 U13 U12 of U_cif (the order of a CIF's _atom_site_aniso_ loop)
+ *   u_eq [M]         = tr(U) / 3
+ *   principal [M,3]  = the eigenvalues of U, ascending; axes [M,9] (or NULL) = their unit eigenvectors as rows, each with
+ *                      its largest component positive.  Cyclic Jacobi iteration, a fixed number of sweeps.
+ * Per crystal (one wave each, fixed order; from the fp32 values as stored):
+ *   status [B] int32: bit 0 set for a singular cell (det == 0 or not finite); every output row of such a crystal is NaN
+ *   crystal_stats [B,3] fp64 (or NULL) = (sum of u_eq over the crystal's rows, its smallest principal value, the number
+ *                      of rows whose smallest principal value is <= 0); a crystal without rows gives (0, +inf, 0).
+ * M == 0 or B == 0: returns 0 without a launch and writes nothing.  No atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_export(const float* u_cart, const int64_t* row_ptr, const float* cell, int32_t B, int64_t M,
+                       float* u_cif, float* u_eq, float* principal, float* axes, double* crystal_stats,
+                       int32_t* status, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Training loss (reference: train/metrics.py:15-28, called from train/train.py:173-178): L1Loss and MSELoss with mean
  * reduction over the n = M*9 (or Bg) elements of pred / truth, both from one pair of small launches (slices, then
  * their sum), and their gradient from one more:

@@ -13,7 +13,9 @@ optimiser step.  ``--shard_dir DIR`` trains from packed shard files (cartnet_amd
 the reference's dataset recipe -- graph, hydrogen removal, canonical cell, temperature standardisation -- is applied to the
 resident shards in the reference's order.  ``--eval_batch N`` runs the ADP test pass, ``--inference`` and
 ``--montecarlo`` with N crystals per forward and keeps the results of the reference's test batch size 1 (per-crystal means,
-rotations and pickle entries).  There is no CPU path: the model runs on an AMD GPU only.
+rotations and pickle entries).  ``--predict`` applies a checkpoint to the crystals of ONE shard file, labeled or not
+(``--predict_input``), and writes their ADPs in CIF convention (cartnet_amd/predict.py).  There is no CPU path: the model
+runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ from cartnet_amd import distributed as cdist
 from cartnet_amd.config import cfg, set_cfg
 from cartnet_amd.data import DataLoader, optimize_cell, remove_hydrogens
 from cartnet_amd.master import create_model
+from cartnet_amd.metrics import to_host as _to_host
 from cartnet_amd.optim import FlatAdam, one_cycle_lr, one_cycle_momentum
 from cartnet_amd.synthetic import augment_data, make_crystal
 from cartnet_amd.train import eval_epoch, train_epoch
@@ -101,6 +104,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "batch size 1 (the default, and that code path); N > 1 runs N crystals per forward and still "
                         "reports batch size 1's results: per-crystal means, one rotation per crystal, one pickle entry "
                         "per crystal.  Other datasets ignore it (they test at --batch)")
+    p.add_argument("--predict", action="store_true",
+                   help="ADP, CartNet / eComformer: apply --checkpoint_path to the crystals of --predict_input (targets not "
+                        "needed) and write their ADPs, Cartesian and in CIF convention, to --predict_output")
+    p.add_argument("--predict_input", type=str, default=None, help="the shard file --predict reads (FILE.cnshard)")
+    p.add_argument("--predict_output", type=str, default="./predictions.pkl")
+    p.add_argument("--predict_cif_dir", type=str, default=None, help="--predict: also write one P1 CIF per crystal here")
     return p
 
 
@@ -160,15 +169,13 @@ def graph_request(cfg, shard_graph: Optional[dict], has_graph: bool) -> Optional
     return want
 
 
-def shard_loaders(rank: int, world: int):
-    """``--shard_dir``: the three splits from shard files, with the reference's dataset recipe applied on the GPU in the
-    reference's order -- graph (graph_request), hydrogen removal (dataset/datasetADP.py:49-72), canonical cell (:75-80) --
-    and the temperature standardisation of :17-18,43-45 inside the collation kernel (the files hold Kelvin)."""
-    from cartnet_amd.shard import DeviceShard, ShardLoader
+def shard_recipe(shards: list):
+    """The reference's dataset recipe on resident shards, in the reference's order -- graph (graph_request), hydrogen
+    removal (dataset/datasetADP.py:49-72), canonical cell (:75-80).  Returns the new shards and the (mean, std) of the
+    temperature standardisation of :17-18,43-45, which the collation kernel applies (the files hold Kelvin)."""
     from cartnet_amd.synthetic import TEMP_MEAN, TEMP_STD
     adp = cfg.dataset.name == "ADP"
-    shards = [DeviceShard.from_file(os.path.join(cfg.shard_dir, f"{part}.cnshard"), cfg.device)
-              for part in ("train", "val", "test")]
+    shards = list(shards)
     for i, s in enumerate(shards):
         req = graph_request(cfg, s.graph, s.has_graph)
         if req is not None:
@@ -177,7 +184,15 @@ def shard_loaders(rank: int, world: int):
         shards = [s.without_hydrogens() for s in shards]
     if adp and cfg.model == "icomformer":
         shards = [s.with_optimized_cell() for s in shards]
-    mean, std = (TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0)
+    return shards, ((TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0))
+
+
+def shard_loaders(rank: int, world: int):
+    """``--shard_dir``: the three splits from shard files with ``shard_recipe`` applied."""
+    from cartnet_amd.shard import DeviceShard, ShardLoader
+    adp = cfg.dataset.name == "ADP"
+    shards, (mean, std) = shard_recipe([DeviceShard.from_file(os.path.join(cfg.shard_dir, f"{part}.cnshard"), cfg.device)
+                                        for part in ("train", "val", "test")])
     return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
                         augment=cfg.augment, temp_mean=mean, temp_std=std),
             ShardLoader(shards[1], cfg.batch, temp_mean=mean, temp_std=std),
@@ -300,20 +315,6 @@ def montecarlo(model, loader, device, output_path: str, rounds: int = 100, seed:
             "similarity_index_std": float(sim.std())}
 
 
-def _to_host(tensors: dict) -> dict:
-    """The device tensors of ``tensors`` on the host, through ONE device-to-host copy: their bytes are packed into one
-    buffer on the device, and every tensor is cut back out of its host copy (each owning its memory)."""
-    items = [(k, t.detach().contiguous()) for k, t in tensors.items()]
-    flat = torch.cat([t.view(torch.uint8).reshape(-1) if t.numel() else t.new_empty(0, dtype=torch.uint8)
-                      for _, t in items]).to("cpu")
-    out, at = {}, 0
-    for k, t in items:
-        n = t.numel() * t.element_size()
-        out[k] = flat[at:at + n].clone().view(t.dtype).reshape(t.shape)
-        at += n
-    return out
-
-
 def _batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> None:
     """Appends one list entry per crystal to ``out``: the tensors of ``per_row`` (dim 0 runs over the batch's non-hydrogen
     atoms, in crystal order), ``cell``, ``atoms`` and, if asked for, ``pos``.  One transfer brings everything to the host,
@@ -415,9 +416,47 @@ def montecarlo_batched(model, loader, device, output_path: str, rounds: int = 10
             "similarity_index_std": float(sim.std())}
 
 
+def check_predict_args(args) -> None:
+    """``--predict``'s requirements, checked before anything touches the device."""
+    if cfg.dataset.name != "ADP":
+        raise SystemExit("--predict: ADPs are predicted for the ADP dataset only")
+    if args.checkpoint_path is None:
+        raise SystemExit("--predict: weights not provided (--checkpoint_path)")
+    if args.predict_input is None:
+        raise SystemExit("--predict: no input shard (--predict_input FILE.cnshard)")
+    if cfg.model == "icomformer":
+        raise SystemExit("--predict does not serve --model icomformer: its recipe reads crystals in the frame of the "
+                         "reduced cell, and mapping U back to the stored cell is not implemented (use CartNet or "
+                         "ecomformer)")
+
+
+def predict(model, args) -> dict:
+    """``--predict``: the one shard of ``--predict_input`` through ``shard_recipe`` as the test split goes through it, in
+    batches of ``--eval_batch``; the pickle of ``cartnet_amd.predict.predict_adps`` and, if asked for, one CIF per
+    crystal."""
+    import pickle
+    from cartnet_amd.predict import entry, predict_adps, write_cif
+    from cartnet_amd.shard import DeviceShard, ShardLoader
+    shards, (mean, std) = shard_recipe([DeviceShard.from_file(args.predict_input, cfg.device)])
+    out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device)
+    with open(args.predict_output, "wb") as f:
+        pickle.dump(out, f)
+    n = len(out["name"])
+    if args.predict_cif_dir:
+        os.makedirs(args.predict_cif_dir, exist_ok=True)
+        for k in range(n):
+            write_cif(os.path.join(args.predict_cif_dir, f"{out['name'][k]}.cif"), entry(out, k))
+    rows = sum(int(t.shape[0]) for t in out["u_eq"])
+    stats = torch.stack(out["stats"]) if n else torch.zeros(0, 3, dtype=torch.float64)
+    return {"crystals": n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
+            "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
+
+
 def main(argv=None) -> dict:
     args = build_parser().parse_args(argv)
     fill_cfg(args)
+    if args.predict:
+        check_predict_args(args)
     torch.set_num_threads(args.threads)
     rank, world, local = cdist.init_from_env()
     if world > 1:
@@ -425,6 +464,13 @@ def main(argv=None) -> dict:
             local %= max(1, torch.cuda.device_count())
         cfg.device = f"cuda:{local}"
     torch.manual_seed(cfg.seed)
+    if args.predict:
+        model = create_model()
+        model.load_state_dict(torch.load(args.checkpoint_path, map_location=cfg.device)["model_state"])
+        res = predict(model, args)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        return res
     loaders = create_loaders(args, rank, world)
     model = create_model()
     n_params = sum(p.numel() for p in model.parameters())

@@ -6,11 +6,14 @@ test.cnshard (cartnet_amd/shard.py), the crystals of ``--synthetic N --atoms lo 
     python tools/make_shards.py DIR --synthetic 2000 --atoms 30 70                  # uncapped radius-5 graphs
     python tools/make_shards.py DIR --synthetic 2000 --max_neighbours 25            # capped graphs (e/iComformer)
     python tools/make_shards.py DIR --synthetic 2000 --geometry_only                # no edges: graphed on the GPU at load
+    python tools/make_shards.py DIR --synthetic 2000 --unlabeled                    # also DIR/predict.cnshard (see below)
 
 Graphs are built on the host (the reference's edge order) and their radius / cap recorded in the header.  ADP temperatures
 are stored in Kelvin, as the reference's files hold them (dataset/datasetADP.py:43-45 standardises at load, and so does
 ``--shard_dir``); ``--standardized_temperature`` stores the synthetic crystals' standardised values instead, for runs with
-``--no_standarize_temp``.  Runs on the host: no GPU needed."""
+``--no_standarize_temp``.  ``--unlabeled`` (ADP) additionally writes DIR/predict.cnshard for ``main.py --predict``: the test
+crystals once more, geometry only and without targets, named ``syn<k>`` after their synthetic index.  Runs on the host: no
+GPU needed."""
 from __future__ import annotations
 
 import argparse
@@ -41,8 +44,9 @@ def to_kelvin(d):
 
 
 def write_split(out_dir: str, n: int, atoms=(30, 70), adp: bool = True, radius: float = 5.0, max_neighbors=None,
-                geometry_only: bool = False, kelvin: bool = True):
-    """Writes the three shard files and returns the three lists of crystals as they were stored."""
+                geometry_only: bool = False, kelvin: bool = True, unlabeled: bool = False):
+    """Writes the three shard files and returns the three lists of crystals as they were stored.  ``unlabeled``: also
+    predict.cnshard, the test crystals as geometry without ``y``, named ``syn<k>``."""
     cap = max_neighbors if max_neighbors is not None and max_neighbors > 0 else None
     if geometry_only:
         items = [make_geometry(g, None, tuple(atoms), adp) for g in range(n)]
@@ -55,6 +59,15 @@ def write_split(out_dir: str, n: int, atoms=(30, 70), adp: bool = True, radius: 
     graph = None if geometry_only else {"radius": radius, "max_neighbors": cap}
     for name, part in zip(PARTS, parts):
         write_shard(os.path.join(out_dir, name + ".cnshard"), part, graph=graph)
+    if unlabeled:
+        if not adp:
+            raise ValueError("--unlabeled: only ADP shards are predicted for")
+        ids = split(list(range(n)))[2]
+        geo = [make_geometry(g, None, tuple(atoms), True) for g in ids]
+        for d in geo:
+            del d.y
+        write_shard(os.path.join(out_dir, "predict.cnshard"), [to_kelvin(d) for d in geo] if kelvin else geo,
+                    names=[f"syn{g}" for g in ids])
     return parts
 
 
@@ -68,9 +81,11 @@ def main(argv=None):
     p.add_argument("--max_neighbours", type=int, default=-1)
     p.add_argument("--geometry_only", action="store_true")
     p.add_argument("--standardized_temperature", action="store_true")
+    p.add_argument("--unlabeled", action="store_true",
+                   help="also write DIR/predict.cnshard: the test crystals, geometry only, without targets, named syn<k>")
     a = p.parse_args(argv)
     parts = write_split(a.out_dir, a.synthetic, a.atoms, a.dataset == "ADP", a.radius, a.max_neighbours, a.geometry_only,
-                        not a.standardized_temperature)
+                        not a.standardized_temperature, a.unlabeled)
     print({name: len(part) for name, part in zip(PARTS, parts)})
 
 

@@ -179,6 +179,9 @@ class Collated(C.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/cartnet_hip.h declares
+# the expansion's inputs (cartnet_symmetry_expand_count / _fill): ten arrays, then G, A, S, C, n_tiles
+_SYM_IN = [C.c_void_p] * 10 + [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+
 PROTOTYPES = {
     "cartnet_last_error": (C.c_char_p, []),
     "cartnet_abi_version": (C.c_int, []),
@@ -359,6 +362,16 @@ PROTOTYPES = {
                                                      c_stream]),
     "cartnet_shard_optimize_cell_rotate": (C.c_int, [C.POINTER(Shard), C.c_int32, C.c_int64, C.c_int64, c_f32p, c_f32p,
                                                      c_f32p, c_stream]),
+    "cartnet_symmetry_expand_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "cartnet_symmetry_expand_count": (C.c_int, _SYM_IN + [C.c_void_p, C.c_size_t, c_i64p, c_i64p, c_i64p, c_stream]),
+    "cartnet_symmetry_expand_fill": (C.c_int, _SYM_IN + [C.c_void_p, C.c_size_t, c_i64p, c_i32p, c_i64p, C.c_int64,
+                                                         C.c_int64, c_i32p, c_f32p, c_u8p, c_i32p, c_i32p, c_i32p, c_f32p,
+                                                         c_stream]),
+    "cartnet_symmetry_targets": (C.c_int, [c_i64p, C.c_void_p, c_i64p, C.c_void_p, C.c_void_p, c_i64p, c_i32p, c_i32p,
+                                           C.c_int32, C.c_int64, c_f32p, c_stream]),
+    "cartnet_symmetry_average": (C.c_int, [c_f32p, c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int64, C.c_int64, c_i64p,
+                                           C.c_void_p, c_i64p, c_i32p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, c_f32p,
+                                           c_f32p, c_stream]),
     "cartnet_profile_gemm": (C.c_int, [C.c_int32]),
     "cartnet_profile_gemm_only": (C.c_int, [C.c_int32]),
     "cartnet_profile_gemm_every": (C.c_int, [C.c_int32]),

@@ -4,7 +4,9 @@
 not) one forward, one ``adp_export`` (csrc/export_ops.hip: the predictions on the unit reciprocal axes -- the inverse of the
 transform the reference applied to the dataset's targets, dataset/extract_csd_data.py:115-123 -- with U_eq and the
 principal values / axes), the fractional coordinates, ONE device-to-host copy (``metrics.to_host``) and a split by row
-counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.
+counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.  For crystals that came from CIF files
+(``cartnet_amd.symmetry.expand``) the same copy also brings one site-averaged ADP per atom of the asymmetric unit, and
+``write_cif_symmetric`` writes the crystal in the file's own setting.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ import torch
 from .metrics import adp_export, check_export_status, split_rows, target_row_ptr, to_host
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
+SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -31,20 +34,23 @@ def _inverse_cells(cell: torch.Tensor) -> torch.Tensor:
     return adj / det.view(-1, 1, 1)
 
 
-def predict_adps(model, loader, device) -> Dict[str, List]:
+def predict_adps(model, loader, device, sym=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
     shard has none); ``u_cart`` [n,3,3] (the model's output); ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12); ``u_eq`` [n];
     ``principal`` [n,3] ascending; ``axes`` [n,3,3]; ``stats`` [3] fp64 (sum of u_eq, smallest principal value, rows with a
-    non-positive one).  A singular cell raises ``ValueError`` naming the crystal."""
+    non-positive one).  A singular cell raises ``ValueError`` naming the crystal.  ``sym``: the ``CifSymmetry`` of a shard
+    expanded from CIF files; the result then also has, per crystal, ``asym_labels`` / ``asym_frac`` [a,3] / ``asym_z`` [a]
+    (the asymmetric unit as the file gives it), ``symops`` (strings, identity first), ``u_cif_asym`` [h,6] (one row per
+    non-hydrogen atom of the asymmetric unit, the mean over its orbit, ``symmetry.site_average``) and ``spread`` [h]."""
     shard = loader.shard
     if not shard.per_atom_target:
         raise ValueError("predict_adps needs an ADP shard (per-atom 3x3 rows)")
     if not all(k in shard.t for k in ("pos", "cell", "non_h_mask")):
         raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
     model.eval()
-    out: Dict[str, List] = {k: [] for k in KEYS}
+    out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())}
     with torch.no_grad():
         for batch in loader:
             if batch is None:
@@ -63,8 +69,19 @@ def predict_adps(model, loader, device) -> Dict[str, List]:
             ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
             dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
                        stats=ex.crystal_stats, _status=ex.status)
+            if sym is not None:
+                from .symmetry import site_average
+                dev["_u_asym"], dev["_spread"] = site_average(pred, row_ptr, batch._sel, sym)
             host = to_host(dev)
             ids = host.pop("_sel").tolist()
+            if sym is not None:
+                sites = [int(sym.site_count[i]) for i in ids]
+                out["u_cif_asym"] += split_rows(host.pop("_u_asym"), sites)
+                out["spread"] += split_rows(host.pop("_spread"), sites)
+                out["asym_labels"] += [sym.labels[i] for i in ids]
+                out["asym_frac"] += [torch.from_numpy(sym.frac[i]) for i in ids]
+                out["asym_z"] += [torch.from_numpy(sym.z[i]) for i in ids]
+                out["symops"] += [sym.symops[i] for i in ids]
             names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
             check_export_status(host.pop("_status"), names)
             rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
@@ -83,8 +100,9 @@ def predict_adps(model, loader, device) -> Dict[str, List]:
 
 
 def entry(result: Dict[str, List], k: int) -> dict:
-    """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` takes."""
-    return {key: result[key][k] for key in KEYS}
+    """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
+    ``write_cif_symmetric``) takes."""
+    return {key: result[key][k] for key in KEYS + SYM_KEYS if key in result}
 
 
 def cell_parameters(cell) -> tuple:
@@ -121,6 +139,39 @@ def write_cif(path: str, entry: dict) -> None:
               "_atom_site_fract_z"]
     for lab, v, f in zip(labels, z, entry["frac"].tolist()):
         lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}")
+    lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
+              "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
+    for i, row in zip(heavy, u):
+        lines.append(labels[i] + " " + " ".join(f"{x:.6f}" for x in row))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def write_cif_symmetric(path: str, entry: dict) -> None:
+    """One crystal in the setting of the file it came from: the cell, the temperature, the symmetry operators, the
+    asymmetric unit with the input's labels and coordinates, and the site-averaged anisotropic displacement parameters of
+    its non-hydrogen atoms (``u_cif_asym``: ``U_11 U_22 U_33 U_23 U_13 U_12``)."""
+    z = [int(v) for v in entry["asym_z"].tolist()]
+    labels = list(entry["asym_labels"])
+    heavy = [i for i, v in enumerate(z) if v != 1]
+    u = entry["u_cif_asym"].tolist()
+    if len(heavy) != len(u):
+        raise ValueError(f"{len(u)} ADP rows for {len(heavy)} non-hydrogen atoms of the asymmetric unit")
+    a, b, c, al, be, ga = cell_parameters(entry["cell"])
+    name = "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in str(entry["name"])) or "crystal"
+    lines = [f"data_{name}",
+             f"_cell_length_a {a:.6f}", f"_cell_length_b {b:.6f}", f"_cell_length_c {c:.6f}",
+             f"_cell_angle_alpha {al:.5f}", f"_cell_angle_beta {be:.5f}", f"_cell_angle_gamma {ga:.5f}"]
+    temp = float(entry["temp"])
+    if not math.isnan(temp):
+        lines.append(f"_diffrn_ambient_temperature {temp:.2f}")
+    lines += ["loop_", "_space_group_symop_id", "_space_group_symop_operation_xyz"]
+    lines += [f"{k + 1} '{op}'" for k, op in enumerate(entry["symops"])]
+    lines += ["loop_", "_atom_site_label", "_atom_site_type_symbol", "_atom_site_fract_x", "_atom_site_fract_y",
+              "_atom_site_fract_z", "_atom_site_adp_type"]
+    for lab, v, f in zip(labels, z, entry["asym_frac"].tolist()):
+        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f} "
+                     f"{'Uani' if v != 1 else '.'}")
     lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
               "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
     for i, row in zip(heavy, u):

@@ -119,7 +119,17 @@ def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, 
     """``names``: one string per crystal, stored in the header.  ``graph``: how the crystals' edges were built,
     ``{"radius": r, "max_neighbors": k or None}``; recorded in the header, so that a loader can tell whether the graph it
     wants is the one stored (the reference's cached-directory test, dataset/utils.py:462-464)."""
-    arrays = pack(data_list)
+    write_arrays(path, pack(data_list), graph=graph, names=names)
+
+
+def write_arrays(path: str, arrays: Dict[str, np.ndarray], graph: Optional[Dict[str, object]] = None,
+                 names: Optional[Sequence[str]] = None) -> None:
+    """``write_shard`` for crystals that are flat CSR arrays already (``pack``'s result, or the host copy of a resident
+    shard's tensors): arrays without ``y`` give an unlabeled shard."""
+    order = ("atom_ptr", "edge_ptr", "y_ptr", "z", "edge_src", "edge_tgt", "cart_dist", "cart_dir", "y", "pos", "non_h_mask",
+             "cell", "temperature")
+    arrays = {k: np.asarray(arrays[k]) for k in order if k in arrays}
+    n_graphs = int(arrays["atom_ptr"].shape[0]) - 1
     if graph is not None:
         if "edge_ptr" not in arrays:
             raise ValueError("a geometry-only shard has no graph to record")
@@ -128,15 +138,15 @@ def write_shard(path: str, data_list: Sequence[Data], graph: Optional[Dict[str, 
     for k, a in arrays.items():
         meta[k] = [a.dtype.str, list(a.shape), off]
         off += (a.nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
-    head = {"arrays": meta, "graphs": len(data_list)}
+    head = {"arrays": meta, "graphs": n_graphs}
     if graph is not None:
         head["graph"] = graph
     if "y" not in arrays:
         head["targets"] = False
     if names is not None:
         names = [str(n) for n in names]
-        if len(names) != len(data_list):
-            raise ValueError(f"{len(names)} names for {len(data_list)} crystals")
+        if len(names) != n_graphs:
+            raise ValueError(f"{len(names)} names for {n_graphs} crystals")
         head["names"] = names
     header = json.dumps(head).encode()
     header += b" " * (-(len(MAGIC) + 8 + len(header)) % _ALIGN)
@@ -435,6 +445,7 @@ class DeviceShard:
                                            rot.data_ptr() if rot is not None else None, float(temp_mean),
                                            float(temp_std), _l.C.byref(o), _l.stream_ptr()), "cartnet_collate")
         b.num_graphs = B
+        b._sel = sel_np                       # the crystals of the batch, on the host
         b._meta = meta_d                      # keeps the offsets alive until the kernel has run
         return b
 

@@ -498,6 +498,74 @@ int cartnet_shard_optimize_cell_select(const float* cell, int32_t G, float* cell
 int cartnet_shard_optimize_cell_rotate(const CartnetShard* shard, int32_t G, int64_t E, int64_t M, const float* rotation,
                                        float* cart_dir_out, float* y_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * From the asymmetric unit of a CIF to the contents of the unit cell, and back (cartnet_amd/csrc/symmetry_ops.hip;
+ * cartnet_amd.symmetry.expand_host is the host form).  Reference: dataset/extract_csd_data.py:84-88 takes the packed
+ * cell from the CSD API (crystal.packing) and drops repeated atoms with delete_repeated (:28-40); :115-123 bring the
+ * file's U_ij into the Cartesian frame.  Here the file's own symmetry operators generate the candidates, for all G
+ * crystals of a call in one pass.  Inputs (device, CSR over the crystals):
+ *   asym_ptr [G+1] int64, asym_frac [A,3] fp64, asym_z [A] int32: the atoms of the asymmetric units
+ *   op_ptr [G+1] int64, op_rot [S,9] int8 (W, row-major, entries in {-1, 0, 1}), op_trans [S,3] fp64 (w): the
+ *     operators x -> W x + w; operator 0 of every crystal is the identity
+ *   cell [G,9] fp64: the rows are the lattice vectors
+ *   cand_ptr [G+1] int64: the running sum of n * m (atoms times operators); candidate c = s * n + a of a crystal is atom a
+ *     under operator s, so the asymmetric unit comes first.  Every crystal has at least one atom and one operator.
+ *   tile_crystal [n_tiles] int32, tile_start [n_tiles] int64: the tiles of 256 consecutive candidates of one crystal each
+ *     (crystal, first candidate), in candidate order; C = cand_ptr[G].
+ * The rule:
+ *   candidate  f' = ((W0 f0 + W1 f1) + W2 f2) + w per component in fp64, minus its floor, rounded to fp32, then the
+ *              normalisation of :29-31 (< 0: + 1; > 1: - 1; isclose(x, 1, atol = 1e-4, rtol = 1e-5): 0)
+ *   duplicate  rep[i] = the lowest j < i of the crystal whose fp32 Euclidean distance to i (normalised fractions, no
+ *              periodic wrap) is below 1e-4f, else i; candidate i is kept iff rep[i] == i (mask_to_keep of :32-40).
+ *              The compaction is stable: kept atoms stay in candidate order.
+ * Two calls, as cartnet_shard_drop_h_count / _fill:
+ *   count: workspace of cartnet_symmetry_expand_workspace_bytes(G, C, n_tiles) bytes, kept for fill.  Writes
+ *          atom_ptr_out [G+1], y_ptr_out [G+1] (the kept atoms with z != 1) and totals [4] int64 (device): kept atoms,
+ *          kept non-hydrogen atoms, status (bit 0: some cell is singular or not finite; bit 1: in some crystal
+ *          rep[rep[i]] != rep[i], atoms between one and two thresholds apart), and the first crystal with a non-zero
+ *          status or -1.  The caller reads totals (the one device-to-host copy), allocates, and calls
+ *   fill:  z_out [N_out] int32, pos_out [N_out,3] fp32 (the normalised fraction times cell in fp64, rounded once),
+ *          non_h_mask_out [N_out] (z != 1), cell_out [G,9] fp32; per non-hydrogen row row_asym / row_op [Y_out] int32
+ *          (the asymmetric atom and the operator it came from, both counted inside the crystal); orbit_row [O] int32:
+ *          with asym_site [A] int32 (the number of an asymmetric atom among the non-hydrogen ones of its crystal, from
+ *          the host; -1 for hydrogen) and orb_ptr [G+1] int64 (running sum of sites times operators),
+ *          orbit_row[orb_ptr[g] + site * m + s] = the crystal-local row of the representative of that atom under
+ *          operator s.
+ * cartnet_symmetry_targets (labeled crystals): asym_ucif [A,6] fp64 = U11 U22 U33 U23 U13 U12 of the file.  Per row, in
+ *   fp64, stored as fp32: beta = N U N with N = diag(|a*|, |b*|, |c*|), beta' = W beta W^T, y [Y,9] = cell^T beta' cell
+ *   (:115-123 for the image of the atom under its operator).
+ * cartnet_symmetry_average (predictions): pred [M,9] fp32 and row_ptr [B+1] of a batch whose crystal b is crystal sel[b]
+ *   (int64) of the expansion; site_ptr [B+1] int64 = running sum of the crystals' non-hydrogen asymmetric atoms,
+ *   H = site_ptr[B]; O = orb_ptr[G].  Per site, in fp64, over the m operators in order: U = (P + P^T) / 2 of row
+ *   orbit_row[..], beta_r = cell^-T U cell^-1, W^-1 beta_r W^-T (W^-1 = adjugate times determinant); their mean is the
+ *   site's beta, u_cif_asym [H,6] fp32 = beta_ij / (|a*_i| |a*_j|) in the order above, and spread [H] fp32 = the largest
+ *   |member - mean| over members and components, in the units of u_cif.  An atom on a special position averages over
+ *   its stabiliser, so the result obeys the site symmetry.  A site whose crystal, cell or rows are invalid gives NaN.
+ * No atomics, no workgroup waits for another, identical bytes on every run.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t cartnet_symmetry_expand_workspace_bytes(int32_t G, int64_t C, int64_t n_tiles);
+int cartnet_symmetry_expand_count(const int64_t* asym_ptr, const double* asym_frac, const int32_t* asym_z,
+                                  const int64_t* op_ptr, const int8_t* op_rot, const double* op_trans, const double* cell,
+                                  const int64_t* cand_ptr, const int32_t* tile_crystal, const int64_t* tile_start,
+                                  int32_t G, int64_t A, int64_t S, int64_t C, int64_t n_tiles, void* workspace,
+                                  size_t workspace_bytes, int64_t* atom_ptr_out, int64_t* y_ptr_out, int64_t* totals,
+                                  void* stream);
+int cartnet_symmetry_expand_fill(const int64_t* asym_ptr, const double* asym_frac, const int32_t* asym_z,
+                                 const int64_t* op_ptr, const int8_t* op_rot, const double* op_trans, const double* cell,
+                                 const int64_t* cand_ptr, const int32_t* tile_crystal, const int64_t* tile_start,
+                                 int32_t G, int64_t A, int64_t S, int64_t C, int64_t n_tiles, const void* workspace,
+                                 size_t workspace_bytes, const int64_t* y_ptr_out, const int32_t* asym_site,
+                                 const int64_t* orb_ptr, int64_t N_out, int64_t Y_out, int32_t* z_out, float* pos_out,
+                                 uint8_t* non_h_mask_out, int32_t* row_asym, int32_t* row_op, int32_t* orbit_row,
+                                 float* cell_out, void* stream);
+int cartnet_symmetry_targets(const int64_t* asym_ptr, const double* asym_ucif, const int64_t* op_ptr,
+                             const int8_t* op_rot, const double* cell, const int64_t* y_ptr, const int32_t* row_asym,
+                             const int32_t* row_op, int32_t G, int64_t Y, float* y, void* stream);
+int cartnet_symmetry_average(const float* pred, const int64_t* row_ptr, const int64_t* sel, const int64_t* site_ptr,
+                             int32_t B, int64_t M, int64_t H, const int64_t* op_ptr, const int8_t* op_rot,
+                             const int64_t* orb_ptr, const int32_t* orbit_row, const double* cell, int32_t G, int64_t S,
+                             int64_t O, float* u_cif_asym, float* spread, void* stream);
+
 /* Opt-in timing of cartnet_gemm launches (the only PROCESS-global state in the library; used by bench.py, off by default
  * and not for concurrent use from several threads):
  * while enabled, every cartnet_gemm call -- also those issued inside cartnet_model_forward/backward -- is bracketed

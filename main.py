@@ -14,8 +14,9 @@ the reference's dataset recipe -- graph, hydrogen removal, canonical cell, tempe
 resident shards in the reference's order.  ``--eval_batch N`` runs the ADP test pass, ``--inference`` and
 ``--montecarlo`` with N crystals per forward and keeps the results of the reference's test batch size 1 (per-crystal means,
 rotations and pickle entries).  ``--predict`` applies a checkpoint to the crystals of ONE shard file, labeled or not
-(``--predict_input``), and writes their ADPs in CIF convention (cartnet_amd/predict.py).  There is no CPU path: the model
-runs on an AMD GPU only.
+(``--predict_input``), and writes their ADPs in CIF convention (cartnet_amd/predict.py); the input may also be a CIF
+file or a directory of them, whose asymmetric units are expanded on the GPU (cartnet_amd/symmetry.py) and get one
+site-averaged ADP per atom back.  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -107,9 +108,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--predict", action="store_true",
                    help="ADP, CartNet / eComformer: apply --checkpoint_path to the crystals of --predict_input (targets not "
                         "needed) and write their ADPs, Cartesian and in CIF convention, to --predict_output")
-    p.add_argument("--predict_input", type=str, default=None, help="the shard file --predict reads (FILE.cnshard)")
+    p.add_argument("--predict_input", type=str, default=None,
+                   help="what --predict reads: a shard file (FILE.cnshard), a CIF file (FILE.cif) or a directory of CIF files")
+    p.add_argument("--predict_temperature", type=float, default=None,
+                   help="--predict from CIF files: the temperature in Kelvin of a crystal whose file gives none")
     p.add_argument("--predict_output", type=str, default="./predictions.pkl")
-    p.add_argument("--predict_cif_dir", type=str, default=None, help="--predict: also write one P1 CIF per crystal here")
+    p.add_argument("--predict_cif_dir", type=str, default=None, help="--predict: also write one CIF per crystal here (a shard's crystals in P1, a CIF's in its own setting)")
     return p
 
 
@@ -433,23 +437,44 @@ def check_predict_args(args) -> None:
 def predict(model, args) -> dict:
     """``--predict``: the one shard of ``--predict_input`` through ``shard_recipe`` as the test split goes through it, in
     batches of ``--eval_batch``; the pickle of ``cartnet_amd.predict.predict_adps`` and, if asked for, one CIF per
-    crystal."""
+    crystal.  CIF input (a file or a directory): the crystals the reference's filters accept are expanded to their unit
+    cells on the GPU and take the same path; the pickle and the CIFs then carry one site-averaged ADP per atom of the
+    asymmetric unit, and the result counts the ``rejected`` crystals (names and reasons go to stderr)."""
     import pickle
-    from cartnet_amd.predict import entry, predict_adps, write_cif
+    from cartnet_amd.predict import entry, predict_adps, write_cif, write_cif_symmetric
     from cartnet_amd.shard import DeviceShard, ShardLoader
-    shards, (mean, std) = shard_recipe([DeviceShard.from_file(args.predict_input, cfg.device)])
-    out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device)
+    sym, rejected = None, None
+    if os.path.isdir(args.predict_input) or args.predict_input.lower().endswith(".cif"):
+        # CIF files: expanded in memory (no shard file is written), then through the recipe exactly as a shard
+        import sys
+        from cartnet_amd.cif import load_crystals
+        from cartnet_amd.symmetry import expand
+        crystals, rejected = load_crystals(args.predict_input, False, args.predict_temperature)
+        for name, why in rejected:
+            print(f"rejected\t{name}\t{why}", file=sys.stderr)
+        if not crystals:
+            raise SystemExit(f"--predict: no usable crystal in {args.predict_input}")
+        arrays, sym = expand(crystals, cfg.device, labeled=False, temperature=args.predict_temperature)
+        source = DeviceShard(arrays, cfg.device, labeled=False, names=sym.names)
+    else:
+        source = DeviceShard.from_file(args.predict_input, cfg.device)
+    shards, (mean, std) = shard_recipe([source])
+    out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     n = len(out["name"])
     if args.predict_cif_dir:
         os.makedirs(args.predict_cif_dir, exist_ok=True)
         for k in range(n):
-            write_cif(os.path.join(args.predict_cif_dir, f"{out['name'][k]}.cif"), entry(out, k))
+            (write_cif if sym is None else write_cif_symmetric)(
+                os.path.join(args.predict_cif_dir, f"{out['name'][k]}.cif"), entry(out, k))
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
     stats = torch.stack(out["stats"]) if n else torch.zeros(0, 3, dtype=torch.float64)
-    return {"crystals": n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
-            "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
+    res = {"crystals": n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
+           "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
+    if rejected is not None:
+        res["rejected"] = len(rejected)
+    return res
 
 
 def main(argv=None) -> dict:

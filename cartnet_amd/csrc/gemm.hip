@@ -10,6 +10,9 @@ namespace cn_gemm {
 // GEMM 1) -- the one variant where a third resident workgroup pays: 402 vs 425 us sustained at the benchmark shape, the
 // training step 15.40 vs 15.57 ms (same box, interleaved).  Every other variant is equal or slower on the narrow tile
 // (SiLU on the A operand: -15 %, its prologue runs once per column tile).
+// (Asked only where the persistent kernel does not take the launch -- plan_gemm asks use_f32p first: at the benchmark batch
+// layer GEMM 1 and the dE products below have 1,384+ tiles and a persistent form, so these rules decide for them from 64 up
+// to 1,023 tiles.  tests/test_gemm_plan_host.py pins the family of every launch of the training step.)
 static bool use_f32nn128(const CartnetGemmArgs& a) {
   if (a.tile_policy == 128) return true;
   if (a.tile_policy == 256) return false;
@@ -444,7 +447,10 @@ static int run_plan(const GemmPlan& p, const CartnetGemmArgs& in, hipStream_t st
   return 0;
 }
 
-extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
+// The argument checks of a launch and its plan: everything cartnet_gemm decides before it enqueues, shared with the
+// plan query (cartnet_gemm_plan) so that the two cannot drift apart.  *empty: M == 0 or N == 0, nothing to launch (no plan).
+static int checked_plan(const CartnetGemmArgs* args, GemmPlan* plan, bool* empty) {
+  *empty = false;
   CN_CHECK(args != nullptr, "cartnet_gemm: null args");
   const CartnetGemmArgs& a = *args;
   CN_CHECK(a.M >= 0 && a.N >= 0 && a.K >= 0, "cartnet_gemm: negative shape M=%d N=%d K=%d", a.M, a.N, a.K);
@@ -453,7 +459,10 @@ extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
   CN_CHECK(!(a.ngroups > 1 && a.nsegs > 1), "cartnet_gemm: groups and K-segments are mutually exclusive");
   CN_CHECK(a.splitk >= 1, "cartnet_gemm: splitk=%d", a.splitk);
   CN_CHECK(a.splitk == 1 || a.K >= 2 * cn_gemm::BK, "cartnet_gemm: split-K needs K >= %d", 2 * cn_gemm::BK);
-  if (a.M == 0 || a.N == 0) return 0;
+  if (a.M == 0 || a.N == 0) {
+    *empty = true;
+    return 0;
+  }
   const int nptr = a.ngroups > 1 ? a.ngroups : a.nsegs;
   for (int i = 0; i < nptr; ++i) CN_CHECK(a.A[i] && a.B[i], "cartnet_gemm: null operand %d", i);
   for (int gI = 0; gI < a.ngroups; ++gI) {
@@ -480,7 +489,8 @@ extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
            "cartnet_gemm: tile_policy=%d (0 = automatic, 1 = narrow tiles for grouped N = 256 products too, 3 = the persistent "
            "kernel wherever it has the form, 128 / 256 = force)",
            a.tile_policy);
-  const GemmPlan p = plan_gemm(a);
+  *plan = plan_gemm(a);
+  const GemmPlan& p = *plan;
   CN_CHECK(!a.gst_g || (gate_stats_args(a) && gate_stats_planned(p)),
            "cartnet_gemm: gst_g is set but this launch does not reach the kernel with the gate-statistics epilogue "
            "(precision 0 / 1, N = 256, weight image, one group, colsum + colsq (+ resid) and nothing else, >= 64 / 96 row tiles: "
@@ -501,6 +511,41 @@ extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
            "cartnet_gemm: no half-storage kernel for this launch (needs the pre-split weight image of an activation x "
            "weight product, or a weight gradient with M %% 4 == 0; 16-byte aligned rows; a compiled operand combination: "
            "csrc/gemm_h.hip)");
+  return 0;
+}
+
+static const int kFamilyCode[] = {
+    CARTNET_GEMM_GENERAL, CARTNET_GEMM_GENERAL_X3, CARTNET_GEMM_F32P, CARTNET_GEMM_F32NN, CARTNET_GEMM_F32NN_ACTOUT,
+    CARTNET_GEMM_F32NN128, CARTNET_GEMM_F32TN, CARTNET_GEMM_X3NN16, CARTNET_GEMM_X3NN, CARTNET_GEMM_X3NN_ACTOUT,
+    CARTNET_GEMM_X3TN, CARTNET_GEMM_HNN, CARTNET_GEMM_HTN};
+
+extern "C" int cartnet_gemm_plan(const CartnetGemmArgs* args, CartnetGemmPlanInfo* out) {
+  CN_CHECK(out != nullptr, "cartnet_gemm_plan: null out");
+  *out = CartnetGemmPlanInfo{};
+  out->family = CARTNET_GEMM_NONE;
+  GemmPlan p{};
+  bool empty = false;
+  const int rc = checked_plan(args, &p, &empty);
+  // (a refused launch still reports what the plan found: reject says which kernel was missing)
+  out->reject = (int32_t)p.reject;
+  if (rc != 0 || empty) return rc;
+  out->family = kFamilyCode[(int)p.family];
+  out->width = p.family == Family::f32nn128 ? 128 : p.bn;
+  out->prepass = p.prepass ? 1 : 0;
+  out->k_folded = p.a.K;
+  out->nsegs_run = p.a.nsegs;
+  out->gate_stats = p.gate_stats ? 1 : 0;
+  out->variant = p.variant;
+  return 0;
+}
+
+extern "C" int cartnet_gemm(const CartnetGemmArgs* args, void* stream) {
+  GemmPlan p{};
+  bool empty = false;
+  const int refused = checked_plan(args, &p, &empty);
+  if (refused != 0 || empty) return refused;
+  const CartnetGemmArgs& a = *args;
+  const int nptr = a.ngroups > 1 ? a.ngroups : a.nsegs;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!g_prof_on) return run_plan(p, a, st);
   if (g_prof_only >= 0 && p.variant != g_prof_only) return run_plan(p, a, st);

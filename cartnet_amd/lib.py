@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CARTNET_LIB (tools only): a diagnostic / A-B build of the same ABI next to the product library (tools/build_variant.sh)
 LIB_PATH = os.environ.get("CARTNET_LIB") or os.path.join(_HERE, "libcartnet_hip.so")
 MAX_GROUPS = 4
-ABI_VERSION = 15         # cartnet_abi_version() of the library this binding mirrors (include/cartnet_hip.h)
+ABI_VERSION = 16         # cartnet_abi_version() of the library this binding mirrors (include/cartnet_hip.h)
 
 _lib: Optional[C.CDLL] = None
 
@@ -60,6 +60,16 @@ class GemmArgs(C.Structure):
         ("gather_rows", C.c_int32),
     ]
 
+
+class GemmPlanInfo(C.Structure):
+    """CartnetGemmPlanInfo (include/cartnet_hip.h): what cartnet_gemm would do with a launch."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "width", "prepass", "k_folded", "nsegs_run", "gate_stats", "variant",
+                                         "reject")]
+
+
+# CARTNET_GEMM_* (include/cartnet_hip.h), by number
+GEMM_FAMILIES = ("general", "general_x3", "f32p", "f32nn", "f32nn_actout", "f32nn128", "f32tn", "x3nn16", "x3nn",
+                 "x3nn_actout", "x3tn", "hnn", "htn")
 
 MAX_LAYERS = 16
 
@@ -187,6 +197,7 @@ PROTOTYPES = {
     "cartnet_abi_version": (C.c_int, []),
     "cartnet_abi_struct_sizes": (C.c_int, [C.POINTER(C.c_size_t), C.c_int32]),
     "cartnet_gemm": (C.c_int, [C.POINTER(GemmArgs), c_stream]),
+    "cartnet_gemm_plan": (C.c_int, [C.POINTER(GemmArgs), C.POINTER(GemmPlanInfo)]),
     "cartnet_gate_gemm_eval_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
     "cartnet_gate_gemm_eval": (C.c_int, [C.POINTER(GateGemmArgs), c_stream]),
     "cartnet_gemm_split_b_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
@@ -414,9 +425,9 @@ def load() -> C.CDLL:
         raise CartnetHipError(f"{LIB_PATH}: ABI version {lib.cartnet_abi_version()}, this binding is written for "
                               f"{ABI_VERSION} -- rebuild the library (python -m cartnet_amd.build)")
     mirrors = [GemmArgs, Shard, Collated, GemmProfile, Groups, LayerParams, LayerBuffers, Params, Model, BatchDesc,
-               GateGemmArgs, IcfConv, IcfParams, IcfModel]
-    sizes = (C.c_size_t * 16)()
-    n = lib.cartnet_abi_struct_sizes(sizes, 16)
+               GateGemmArgs, IcfConv, IcfParams, IcfModel, GemmPlanInfo]
+    sizes = (C.c_size_t * 32)()
+    n = lib.cartnet_abi_struct_sizes(sizes, 32)
     if n != len(mirrors):
         raise CartnetHipError(f"{LIB_PATH}: {n} ABI structs, this binding mirrors {len(mirrors)} -- rebuild the library")
     for cls, sz in zip(mirrors, sizes):

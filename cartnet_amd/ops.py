@@ -75,13 +75,50 @@ def _aslist(x, n):
     return list(x)
 
 
-def gemm(A: Sequence[Tensor] | Tensor, B: Sequence[Tensor] | Tensor, C_out: Sequence[Tensor] | Tensor, *,
-         a_kstrided: bool = False, b_kstrided: bool = False, a_act: bool = False, b_act: bool = False,
-         out_act: bool = False, segments: bool = False, bias=None, gather_i=None, gather_j=None, tgt=None, src=None,
-         resid=None, dact=None, cpre=None, colsum=None, colsq=None, splitk: int = 1, precision: int = 0,
-         b_split=None, b_split_folded=None, a_act_out=None, tile_policy: int = 0, gate_stats=None,
-         dact_kind: int = 0) -> None:
-    """C[g] = epilogue(sum_s opA(A[s]) @ opB(B[s])) on the fp32 matrix cores (see include/cartnet_hip.h).
+def gemm(A: Sequence[Tensor] | Tensor, B: Sequence[Tensor] | Tensor, C_out: Sequence[Tensor] | Tensor, **kw) -> None:
+    """C[g] = epilogue(sum_s opA(A[s]) @ opB(B[s])) on the fp32 matrix cores: the launch ``_gemm_args`` describes (its
+    keywords), enqueued on torch's current stream."""
+    lib = _l.load()
+    args = _gemm_args(A, B, C_out, **kw)
+    if args.gst_g and not lib.cartnet_gemm_gate_stats_ok(C.byref(args)):
+        raise ValueError("gemm gate_stats: this launch does not reach the kernel with the gate-statistics epilogue "
+                         "(precision 0 / 1, N = 256, weight image, resid + colsum + colsq only, >= 64 row tiles; g, "
+                         "mean_rstd, gamma, beta 16-byte aligned and g's row stride a multiple of 4 elements)")
+    _l.check(lib.cartnet_gemm(C.byref(args), _l.stream_ptr()), "cartnet_gemm")
+
+
+class GemmPlan:
+    """What cartnet_gemm does with a launch (CartnetGemmPlanInfo): ``family`` is the kernel family by name, the general
+    kernel with its tile width ("general64" / "general128" / "general256"); the other fields as in the header."""
+    __slots__ = ("family", "width", "prepass", "k_folded", "nsegs_run", "gate_stats", "variant", "reject")
+
+    def __init__(self, info: "_l.GemmPlanInfo"):
+        name = _l.GEMM_FAMILIES[info.family] if info.family >= 0 else "none"
+        self.family = name + str(info.width) if name == "general" else name
+        self.width, self.k_folded, self.nsegs_run = int(info.width), int(info.k_folded), int(info.nsegs_run)
+        self.prepass, self.gate_stats = bool(info.prepass), bool(info.gate_stats)
+        self.variant, self.reject = int(info.variant), int(info.reject)
+
+    def __repr__(self):
+        return "GemmPlan(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+def gemm_plan(A: Sequence[Tensor] | Tensor, B: Sequence[Tensor] | Tensor, C_out: Sequence[Tensor] | Tensor, **kw) -> GemmPlan:
+    """The plan of the launch ``gemm`` would make of the same arguments (cartnet_gemm_plan: host only, nothing runs).
+    Raises where ``gemm`` would, with the same message."""
+    info = _l.GemmPlanInfo()
+    _l.check(_l.load().cartnet_gemm_plan(C.byref(_gemm_args(A, B, C_out, **kw)), C.byref(info)), "cartnet_gemm_plan")
+    return GemmPlan(info)
+
+
+def _gemm_args(A: Sequence[Tensor] | Tensor, B: Sequence[Tensor] | Tensor, C_out: Sequence[Tensor] | Tensor, *,
+               a_kstrided: bool = False, b_kstrided: bool = False, a_act: bool = False, b_act: bool = False,
+               out_act: bool = False, segments: bool = False, bias=None, gather_i=None, gather_j=None, tgt=None, src=None,
+               resid=None, dact=None, cpre=None, colsum=None, colsq=None, splitk: int = 1, precision: int = 0,
+               b_split=None, b_split_folded=None, a_act_out=None, tile_policy: int = 0, gate_stats=None,
+               dact_kind: int = 0) -> "_l.GemmArgs":
+    """The CartnetGemmArgs of C[g] = epilogue(sum_s opA(A[s]) @ opB(B[s])) (see include/cartnet_hip.h), validated: what
+    ``gemm`` launches and ``gemm_plan`` asks about.
 
     A / B / C_out: one tensor or a list.  With ``segments=False`` the lists are independent problems (groups) of
     identical shape; with ``segments=True`` A and B list K-segments that are summed into the single output.
@@ -235,11 +272,7 @@ def gemm(A: Sequence[Tensor] | Tensor, B: Sequence[Tensor] | Tensor, C_out: Sequ
         _vec(gbet, N, "gemm gate_stats beta")
         args.gst_g, args.gst_ld, args.gst_env = gg.data_ptr(), _ld(gg), _l.ptr(genv)
         args.gst_mean_rstd, args.gst_gamma, args.gst_beta = gmr.data_ptr(), ggam.data_ptr(), gbet.data_ptr()
-        if not lib.cartnet_gemm_gate_stats_ok(C.byref(args)):
-            raise ValueError("gemm gate_stats: this launch does not reach the kernel with the gate-statistics epilogue "
-                             "(precision 0 / 1, N = 256, weight image, resid + colsum + colsq only, >= 64 row tiles; g, "
-                             "mean_rstd, gamma, beta 16-byte aligned and g's row stride a multiple of 4 elements)")
-    _l.check(lib.cartnet_gemm(C.byref(args), _l.stream_ptr()), "cartnet_gemm")
+    return args
 
 
 def pack_b(mats: Sequence[Tensor], outs: Optional[Sequence[Tensor]] = None) -> list:

@@ -34,8 +34,8 @@ const char* cartnet_last_error(void);
 int cartnet_abi_version(void);
 /* sizeof of every struct below, in header order (CartnetGemmArgs, CartnetShard, CartnetCollated, CartnetGemmProfile,
  * CartnetGroups, CartnetLayerParams, CartnetLayerBuffers, CartnetParams, CartnetModel, CartnetBatch,
- * CartnetGateGemmArgs, CartnetIcfConv, CartnetIcfParams, CartnetIcfModel); returns the number of structs.  A binding checks its mirrors against these when it loads the
- * library, and cartnet_abi_version() against the version it was written for (15: removed in ABI 15: cartnet_radius_graph_count / _fill and cartnet_neighbor_cap_count / _fill -- cartnet_shard_regraph_count / _cap / _fill serve a batch as well as a shard; no layout change; 14: the radius-graph entry points take the radius in double -- the cutoff is the fp32 rounding of the double product; 13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
+ * CartnetGateGemmArgs, CartnetIcfConv, CartnetIcfParams, CartnetIcfModel, and last CartnetGemmPlanInfo); returns the number of structs.  A binding checks its mirrors against these when it loads the
+ * library, and cartnet_abi_version() against the version it was written for (16: cartnet_gemm_plan and CartnetGemmPlanInfo, appended to the size table; no layout change; 15: removed in ABI 15: cartnet_radius_graph_count / _fill and cartnet_neighbor_cap_count / _fill -- cartnet_shard_regraph_count / _cap / _fill serve a batch as well as a shard; no layout change; 14: the radius-graph entry points take the radius in double -- the cutoff is the fp32 rounding of the double product; 13: three entry points nothing called are gone -- the bf16 form of the single segment sum and the one-launch layer prototype; no layout change; 12: CartnetGemmArgs.gather_rows closes the struct -- the persistent kernel's node-term gather form; 11: CartnetGemmArgs.tile_policy = 3, the persistent activation x weight kernel; no layout change; 10: dact_kind closes CartnetGemmArgs, the *_sums / cartnet_att_gate_bwd_apply entry points; 9: gst_* in CartnetGemmArgs (8 also carried seg_*: per-target sums in an epilogue, measured and removed); 7: tile_policy in CartnetGemmArgs,
  * aux_stream in cartnet_model_forward, CartnetGateGemmArgs in the size table; cartnet_gemm_tile_policy() is gone). */
 int cartnet_abi_struct_sizes(size_t* out, int32_t capacity);
 
@@ -89,7 +89,9 @@ typedef struct CartnetGemmArgs {
                           such kernel exists (narrow tiles, ragged K tail, unaligned operands).
                           2: plain bf16 operands (round-to-nearest), ONE bf16 MFMA per product, fp32 accumulate and
                           fp32 storage -- the reduced-precision mode of BASELINE configs[2]; only the pre-split /
-                          transposing-read kernels implement it (256-wide tiles), every other shape runs precision 0. */
+                          transposing-read kernels implement it (256-wide tiles), every other shape runs precision 0 --
+                          and so do the last K % 16 rows of a split-K weight gradient (their slab is summed in fp32 from
+                          the operands as stored, at any precision). */
   const void* b_split[CARTNET_MAX_GROUPS];
                        /* optional, b_kstrided = 1 and a_kstrided = 0: B[i] pre-arranged as the kernel's LDS image --
                           by cartnet_gemm_split_b for precision 1 / 2 (bf16 planes; the weight operand is split once
@@ -151,6 +153,43 @@ int cartnet_gemm(const CartnetGemmArgs* args, void* stream);
 /* 1 if a launch with these arguments (gst_* set) takes the kernel that carries the gate-statistics epilogue; cartnet_gemm
  * refuses such a launch otherwise.  Host only, no launch. */
 int cartnet_gemm_gate_stats_ok(const CartnetGemmArgs* args);
+
+/* The kernel family that takes a cartnet_gemm launch (CartnetGemmPlanInfo.family).  The numbers are stable: a new family
+ * gets a new number. */
+enum {
+  CARTNET_GEMM_NONE = -1,         /* nothing runs: M == 0 or N == 0, or the launch is refused */
+  CARTNET_GEMM_GENERAL = 0,       /* the general tile kernel at 256 / 128 / 64 columns (CartnetGemmPlanInfo.width) */
+  CARTNET_GEMM_GENERAL_X3 = 1,    /* ... on the bf16x3 kernel that splits both operands in flight (precision 1, no image) */
+  CARTNET_GEMM_F32P = 2,          /* persistent fp32 kernel */
+  CARTNET_GEMM_F32NN = 3,         /* DMA-fed fp32, 128 x 256 tiles */
+  CARTNET_GEMM_F32NN_ACTOUT = 4,  /* ... writing silu(A) as it stages A */
+  CARTNET_GEMM_F32NN128 = 5,      /* DMA-fed fp32, 128 x 128 tiles */
+  CARTNET_GEMM_F32TN = 6,         /* fp32 weight gradient, whole K or split-K */
+  CARTNET_GEMM_X3NN16 = 7,        /* pre-split bf16x3 (precision 1) */
+  CARTNET_GEMM_X3NN = 8,          /* pre-split bf16 (precision 2) */
+  CARTNET_GEMM_X3NN_ACTOUT = 9,   /* ... writing silu(A) (precision 1 / 2) */
+  CARTNET_GEMM_X3TN = 10,         /* bf16x3 / bf16 weight gradient, whole K or split-K */
+  CARTNET_GEMM_HNN = 11,          /* bf16 storage, activation x weight */
+  CARTNET_GEMM_HTN = 12,          /* bf16 storage, weight gradient */
+  CARTNET_GEMM_FAMILIES = 13
+};
+
+/* What cartnet_gemm would do with a launch: every dispatch decision, taken by the same code. */
+typedef struct CartnetGemmPlanInfo {
+  int32_t family;      /* CARTNET_GEMM_* */
+  int32_t width;       /* column-tile width of the kernel that runs: 64, 128 or 256 (128 for CARTNET_GEMM_F32NN128) */
+  int32_t prepass;     /* 1: a_act_out is written by an elementwise pass ahead of the product, not by the GEMM kernel */
+  int32_t k_folded;    /* K of the launch as it runs (K * nsegs where adjacent K-segments fold into one product) */
+  int32_t nsegs_run;   /* K-segments of the launch as it runs (1 after folding) */
+  int32_t gate_stats;  /* 1: the family carries the gate-statistics epilogue (gst_*) */
+  int32_t variant;     /* CartnetGemmProfile.variant of the launch */
+  int32_t reject;      /* 0, or why no compiled kernel takes the launch: 1 = layout / activation combination, 2 = half storage */
+} CartnetGemmPlanInfo;
+
+/* The plan of a launch without the launch: host only, no HIP call, usable on a machine without a GPU (pointers are
+ * looked at -- NULL or not, alignment, adjacency of K-segments -- never dereferenced).  Returns non-zero, with the same
+ * cartnet_last_error() text, wherever cartnet_gemm would refuse the arguments; family is then CARTNET_GEMM_NONE. */
+int cartnet_gemm_plan(const CartnetGemmArgs* args, CartnetGemmPlanInfo* out);
 
 /* bf16x3 pre-split of a k-strided GEMM operand B [K, N] (element (k, n) = src[k*stride_k + n*stride_n]; a weight
  * W [out, in] used as B = W^T has stride_k = 1, stride_n = ld) into the image cartnet_gemm reads through

@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(cdll, name), f"{name} is declared in include/cartnet_hip.h but not exported"
     # the ctypes prototypes cover exactly the declared set
     assert sorted(lib.PROTOTYPES) == declared
-    assert lib.load().cartnet_abi_version() == 15 == lib.ABI_VERSION
+    assert lib.load().cartnet_abi_version() == 16 == lib.ABI_VERSION
 
 
 def test_ctypes_mirrors_have_the_c_struct_layouts():
@@ -35,11 +35,13 @@ def test_ctypes_mirrors_have_the_c_struct_layouts():
     CartnetModel must sit where the C side reads them)."""
     from cartnet_amd import lib
     l = lib.load()
-    sizes = (ctypes.c_size_t * 16)()
-    n = l.cartnet_abi_struct_sizes(sizes, 16)
+    sizes = (ctypes.c_size_t * 32)()
+    n = l.cartnet_abi_struct_sizes(sizes, 32)
     mirrors = [lib.GemmArgs, lib.Shard, lib.Collated, lib.GemmProfile, lib.Groups, lib.LayerParams, lib.LayerBuffers,
-               lib.Params, lib.Model, lib.BatchDesc, lib.GateGemmArgs, lib.IcfConv, lib.IcfParams, lib.IcfModel]
-    assert n == len(mirrors)
+               lib.Params, lib.Model, lib.BatchDesc, lib.GateGemmArgs, lib.IcfConv, lib.IcfParams, lib.IcfModel,
+               lib.GemmPlanInfo]
+    assert n == len(mirrors) == 15
+    assert ctypes.sizeof(lib.GemmPlanInfo) == 32                                                     # ABI 16: eight int32
     assert [ctypes.sizeof(m) for m in mirrors] == list(sizes[:n])
     # round 5: the gst_* block sits between dact_half and tile_policy (five pointers + gst_ld; tile_policy closes the struct)
     assert lib.GemmArgs.gst_g.offset == lib.GemmArgs.dact_half.offset + 4

@@ -21,6 +21,8 @@ import math
 import pytest
 import torch
 
+from gemm_cases import gemm_on
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
@@ -85,29 +87,39 @@ def operands(case, M, K, N, seed):
 CASES = ["row_col_scales", "k_scales", "cancellation", "low_pieces_near_denormal", "mixed_magnitude_rows"]
 
 
-def run_nn_image(ops, A, B, precision):
-    """C = A @ B through the DMA-fed activation x weight kernels (weights as a pre-arranged image)."""
+def run_nn_image(ops, A, B, precision, family):
+    """C = A @ B with the weights as a pre-arranged image: through the DMA-fed activation x weight kernels where the launch
+    has the tiles for them (``family``: what the plan must name)."""
     Ad, Bd = A.to(dev()), B.to(dev())
     img = (ops.pack_b if precision == 0 else ops.split_b)([Bd])
     C = torch.full((A.shape[0], B.shape[1]), float("nan"), device=dev())
-    ops.gemm(Ad, Bd, C, b_kstrided=True, precision=precision, b_split=img)
+    gemm_on(ops, family, Ad, Bd, C, b_kstrided=True, precision=precision, b_split=img)
     return C
 
 
-def run_nt_general(ops, A, B, precision):
+def run_nt_general(ops, A, B, precision, family):
     """C = A @ B through the general kernel (B handed over as [N, K] rows, no image)."""
     Ad, Bt = A.to(dev()), B.t().contiguous().to(dev())
     C = torch.full((A.shape[0], B.shape[1]), float("nan"), device=dev())
-    ops.gemm(Ad, Bt, C, precision=precision)
+    gemm_on(ops, family, Ad, Bt, C, precision=precision)
     return C
 
 
-def run_tn(ops, A, B, precision):
+def run_tn(ops, A, B, precision, family):
     """C = A @ B as a weight gradient: the reduction runs over the ROWS of two k-strided operands (A^T [K,M], B [K,N])."""
     At, Bd = A.t().contiguous().to(dev()), B.to(dev())
     C = torch.full((A.shape[0], B.shape[1]), float("nan"), device=dev())
-    ops.gemm(At, Bd, C, a_kstrided=True, b_kstrided=True, precision=precision)
+    gemm_on(ops, family, At, Bd, C, a_kstrided=True, b_kstrided=True, precision=precision)
     return C
+
+
+# (form, M, K) -> the kernel family at precision 0 and at precision 1.  The NT form has no bf16x3 kernel (general_x3 takes
+# k-strided B only) and a weight gradient over a K that is no multiple of 16 runs un-split on the general kernel: those two
+# shapes compare fp32 with fp32; the bf16x3 weight gradient with a K tail is a split-K case of tests/test_gpu_gemm_families.py
+STRESS_FAMILY = {("nn_image", 33000, 256): ("f32nn128", "x3nn16"), ("nn_image", 13000, 512): ("f32nn128", "x3nn16"),
+                 ("nt_general", 13000, 208): ("general128", "general256"), ("tn", 256, 6000): ("f32tn", "x3tn"),
+                 ("tn", 256, 20001): ("general256", "general256"), ("nn_image", 1000, 512): ("general64", "general64"),
+                 ("tn", 128, 777): ("general64", "general64")}
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -122,7 +134,10 @@ def test_gemm_stress_operands_both_precisions(ops, case, form, M, K, N):
     A, B = operands(case, M, K, N, seed=100)
     A64, B64 = A.double(), B.double()
     ref = A64 @ B64
-    e = {p: comp_err_u(run(ops, A, B, p), A64, B64, ref) for p in (0, 1)}
+    family = STRESS_FAMILY[form, M, K]
+    if (form, K, case) == ("tn", 20001, "cancellation"):      # this case pairs its columns: K = 20,000, whole K-steps
+        family = ("f32tn", "x3tn")
+    e = {p: comp_err_u(run(ops, A, B, p, family[p]), A64, B64, ref) for p in (0, 1)}
     # the error of a K-term fp32 dot product grows at most like K u (typically sqrt(K) u); both precisions are far below
     bound = BOUND_U * max(1.0, math.sqrt(K / 512.0))
     print(f"ACCURACY {case:26s} {form:10s} M={M:6d} K={K:5d} N={N:4d}  fp32 MFMA {e[0]:7.2f} u   bf16x3 {e[1]:7.2f} u")
@@ -139,8 +154,8 @@ def test_gemm_denormal_low_pieces_are_a_documented_limit(ops):
     A, B = rnd(M, K, seed=5) * 2.0 ** -112, rnd(K, N, seed=6) * 2.0 ** 70
     A64, B64 = A.double(), B.double()
     ref = A64 @ B64
-    e0 = comp_err_u(run_nn_image(ops, A, B, 0), A64, B64, ref)
-    e1 = comp_err_u(run_nn_image(ops, A, B, 1), A64, B64, ref)
+    e0 = comp_err_u(run_nn_image(ops, A, B, 0, "f32nn128"), A64, B64, ref)
+    e1 = comp_err_u(run_nn_image(ops, A, B, 1, "x3nn16"), A64, B64, ref)
     print(f"ACCURACY denormal low pieces: fp32 MFMA {e0:.2f} u, bf16x3 {e1:.2f} u")
     assert e0 < BOUND_U
     assert e1 < 2.0 ** 10, (e0, e1)      # <= 2^-14 relative to sum |a||b|: two pieces always survive
@@ -295,7 +310,8 @@ GEMM_SP_FORMS = [("general", 0), ("general", 1), ("dma", 0), ("dma", 1), ("persi
 
 def gemm_softplus(ops, A, bias, form, precision):
     """out = softplus(A I + bias) with the pre-activation kept (cpre), through the kernel family `form` takes:
-    general -- no weight image (the general tile kernel; at precision 1 its bf16x3 form); dma -- weight image with
+    general -- no weight image (the general tile kernel, 64-wide at these 97 tiles; at precision 1 its 256-wide bf16x3
+    form); dma -- weight image with
     tile_policy 256 (the DMA-fed 256-wide kernels: f32nn / x3nn16); persistent -- weight image with tile_policy 3, K = 256
     (gemm_f32p.h, precision 0 only: the bf16x3 path has no persistent kernel)."""
     eye = torch.eye(SP_COLS, device=dev())
@@ -305,7 +321,10 @@ def gemm_softplus(ops, A, bias, form, precision):
     if form != "general":
         kw["b_split"] = (ops.pack_b if precision == 0 else ops.split_b)([eye])[0]
         kw["tile_policy"] = 256 if form == "dma" else 3
-    ops.gemm(A.to(dev()), eye, out, **kw)
+    family = {("general", 0): "general64", ("general", 1): "general_x3", ("dma", 0): "f32nn", ("dma", 1): "x3nn16",
+              ("persistent", 0): "f32p"}[form, precision]
+    assert A.shape[0] == SP_ROWS
+    gemm_on(ops, family, A.to(dev()), eye, out, **kw)
     return out, pre
 
 
@@ -385,9 +404,11 @@ def test_dsoftplus_eltwise_and_bwd_sums_edge_values(ops):
 
 @pytest.mark.parametrize("form,precision", [("general", 0), ("general", 1), ("dma", 0), ("dma", 1)])
 def test_dsoftplus_gemm_epilogue_edge_values(ops, form, precision):
-    """dact with dact_kind = 1: C = (A I) * sigmoid(pre), A I = a exactly, the edge values in `pre`."""
+    """dact with dact_kind = 1: C = (A I) * sigmoid(pre), A I = a exactly, the edge values in `pre`.  general: the 64-wide
+    general kernel (precision 0, two tiles) and its bf16x3 form; dma: f32nn and x3nn16 (tile_policy 256) -- which need 64 and
+    96 tiles: with 256 rows the precision-0 "dma" case ran on the general kernel too."""
     A, B = dsoftplus_operands()
-    M = SP_ROWS if precision == 1 else 256          # precision 1: enough row tiles for the bf16x3 kernels
+    M = SP_ROWS if precision == 1 or form == "dma" else 256          # enough row tiles for the DMA-fed / bf16x3 kernels
     A, B = A.repeat(M // 64, 1), B.repeat(M // 64, 1)
     eye = torch.eye(SP_COLS, device=dev())
     C = torch.full((M, SP_COLS), float("nan"), device=dev())
@@ -395,7 +416,8 @@ def test_dsoftplus_gemm_epilogue_edge_values(ops, form, precision):
     if form == "dma":
         kw["b_split"] = (ops.pack_b if precision == 0 else ops.split_b)([eye])[0]
         kw["tile_policy"] = 256
-    ops.gemm(A.to(dev()), eye, C, **kw)
+    family = {("general", 0): "general64", ("general", 1): "general_x3", ("dma", 0): "f32nn", ("dma", 1): "x3nn16"}[form, precision]
+    gemm_on(ops, family, A.to(dev()), eye, C, **kw)
     dsoftplus_check(f"gemm dact {form} p{precision}", C, A, B)
 
 

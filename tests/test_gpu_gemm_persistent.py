@@ -6,11 +6,17 @@ without a transcendental in the epilogue must equal bit for bit (same MFMA chain
 Shapes exercise what the kernel's structure can get wrong: workgroups without a tile / with one / with an odd and an even
 number of tiles (the two accumulator sets, the drain behind either loop exit), a ragged last row tile (rows dropped by the
 buffer descriptors' range check, statistics masked), two and four groups and two column tiles (the workgroup -> (group,
-column tile) map), column-block views (row strides wider than N)."""
+column tile) map), column-block views (row strides wider than N).
+
+Every launch asserts the kernel family its plan names (gemm_cases.gemm_on).  Below 64 tiles (M = 1, 128, 300 here) the plan
+narrows a launch to the 64-wide general kernel whatever tile_policy says (choose_bn in csrc/gemm.hip), so those sizes
+compare the general kernel with itself; the persistent kernel's smallest launches -- 64 tiles, workgroups without a tile
+-- are cases of tests/test_gpu_gemm_families.py."""
 import pytest
 import torch
 
 from conftest import rel_err
+from gemm_cases import gemm_on
 
 pytestmark = pytest.mark.gpu
 
@@ -47,11 +53,20 @@ def dsilu64(x):
 # M: 1 row; one full tile; 2 tiles + ragged; 257 row tiles (every workgroup of a group pair gets one, some two);
 # 700 tiles + ragged (2-3 per workgroup: both loop exits)
 SHAPES = [1, 128, 300, 128 * 257, 89500]
+NARROWED = (1, 128, 300)       # fewer than 64 tiles with two groups of N = 256: the 64-wide general kernel, any tile_policy
+
+
+def _family(pol, M, actout=False):
+    """The family of a launch of these tests: M rows, tile_policy 3 / 0 at 177,140 rows (persistent), 256 or 128."""
+    if M in NARROWED:
+        return "general64"
+    return {3: "f32p", 0: "f32p", 128: "f32nn128", 256: "f32nn_actout" if actout else "f32nn"}[pol]
 
 
 def _run(ops, pol, M, groups, N, form, seed=0):
     """One launch of `form` with tile_policy `pol`; returns the outputs and the fp64 references."""
     G = groups
+    run = lambda *a, **k: gemm_on(ops, _family(pol, M, actout=form == "stats_actout"), *a, **k)
     A = rnd(M, G * D, seed=seed + 1)                                   # groups read column blocks of one matrix
     W = [rnd(D, N, seed=seed + 10 + g, scale=0.06) for g in range(G)]  # [K, N]: b_kstrided
     img = ops.pack_b(W)
@@ -66,10 +81,10 @@ def _run(ops, pol, M, groups, N, form, seed=0):
     A64 = [a.double() for a in Av]
     W64 = [w.double() for w in W]
     if form == "plain":
-        ops.gemm(Av, W, Cv, **kw)
+        run(Av, W, Cv, **kw)
         ref["out"] = torch.cat([A64[g] @ W64[g] for g in range(G)], 1)
     elif form == "bias":
-        ops.gemm(Av, W, Cv, bias=bias, **kw)
+        run(Av, W, Cv, bias=bias, **kw)
         ref["out"] = torch.cat([A64[g] @ W64[g] + bias[g].double() for g in range(G)], 1)
     elif form in ("act", "stats", "stats_actout"):
         cs = [torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev()) for _ in range(G)]
@@ -83,7 +98,7 @@ def _run(ops, pol, M, groups, N, form, seed=0):
         if form == "stats_actout":
             extra.update(a_act_out=[act[:, g * D:(g + 1) * D] for g in range(G)])
             res["act"] = act
-        ops.gemm(Av, W, Cv, a_act=True, bias=bias, **extra, **kw)
+        run(Av, W, Cv, a_act=True, bias=bias, **extra, **kw)
         v = [silu64(A64[g]) @ W64[g] + bias[g].double() for g in range(G)]
         ref["out"] = torch.cat(v, 1)
         if form != "act":
@@ -100,7 +115,7 @@ def _run(ops, pol, M, groups, N, form, seed=0):
         if form == "dpre_colsum":
             cs = [torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev()) for _ in range(G)]
             extra["colsum"] = cs
-        ops.gemm(Av, W, Cv, dact=Pv, **extra, **kw)
+        run(Av, W, Cv, dact=Pv, **extra, **kw)
         if form == "dpre_colsum":
             res["cs_all"] = torch.stack(cs)
         v = [(A64[g] @ W64[g]) * dsilu64(Pv[g].double()) for g in range(G)]
@@ -121,7 +136,7 @@ def _run(ops, pol, M, groups, N, form, seed=0):
             tgt[0], tgt[-1], src[0], src[-1] = 0, atoms - 1, atoms - 1, 0
         gi = [P[:, g * N:(g + 1) * N] for g in range(G)]
         gj = [P[:, (G + g) * N:(G + g + 1) * N] for g in range(G)]
-        ops.gemm(Av, W, Cv, bias=bias, gather_i=gi, gather_j=gj, tgt=tgt, src=src, **kw)
+        run(Av, W, Cv, bias=bias, gather_i=gi, gather_j=gj, tgt=tgt, src=src, **kw)
         ref["out"] = torch.cat([A64[g] @ W64[g] + bias[g].double() + gi[g].double()[tgt.long()] + gj[g].double()[src.long()]
                                 for g in range(G)], 1)
     else:
@@ -169,8 +184,8 @@ def test_is_bitwise_repeatable_and_leaves_the_rest_of_the_buffers_alone(ops):
     outs = []
     for rep in range(2):
         out = torch.full((M, G * N + 32), 7.25, device=dev())
-        ops.gemm([A[:, g * D:(g + 1) * D] for g in range(G)], W, [out[:, g * N:(g + 1) * N] for g in range(G)],
-                 b_kstrided=True, b_split=img, tile_policy=3)
+        gemm_on(ops, "f32p", [A[:, g * D:(g + 1) * D] for g in range(G)], W, [out[:, g * N:(g + 1) * N] for g in range(G)],
+                b_kstrided=True, b_split=img, tile_policy=3)
         torch.cuda.synchronize()
         assert torch.all(out[:, G * N:] == 7.25)
         outs.append(out)
@@ -180,8 +195,9 @@ def test_is_bitwise_repeatable_and_leaves_the_rest_of_the_buffers_alone(ops):
 
 
 def test_the_library_picks_it_for_the_model_sized_launches_only(ops):
-    """tile_policy 0: the edge-sized two-group layer products take the persistent kernel (same bits as policy 3), small
-    launches keep the 2,768-workgroup kernels (same bits as policy 256) -- and either way the results agree."""
+    """tile_policy 0: the edge-sized two-group layer products take the persistent kernel (same bits as policy 3); a small
+    launch (M = 300: six tiles) runs on the 64-wide general kernel under every policy -- and either way the results agree
+    (_run asserts the family of each launch)."""
     for M in (300, 177140):
         a, _ = _run(ops, 0, M, 2, D, "stats", seed=9)
         b, _ = _run(ops, 3, M, 2, D, "stats", seed=9)
@@ -209,14 +225,14 @@ def test_forms_of_the_second_unit(ops, M):
     res = {}
     for pol in (3, 256):
         o = {k: torch.full((M, 2 * D), float("nan"), device=dev()) for k in ("c1", "h1", "c2", "p2", "c3", "h3", "c4")}
-        ops.gemm(Av, W, [o["c1"][:, :D], o["c1"][:, D:]], b_kstrided=True, b_split=img, a_act=True, bias=bias,
-                 a_act_out=[o["h1"][:, :D], o["h1"][:, D:]], tile_policy=pol)
-        ops.gemm(Av, W, [o["c2"][:, :D], o["c2"][:, D:]], b_kstrided=True, b_split=img, bias=bias,
-                 cpre=[o["p2"][:, :D], o["p2"][:, D:]], out_act=True, dact_kind=1, tile_policy=pol)
-        ops.gemm(A, W512, o["c3"][:, :D], b_kstrided=True, b_split=img512, a_act=True, out_act=True, bias=bias[0],
-                 cpre=o["c3"][:, D:], a_act_out=o["h3"], tile_policy=pol)
-        ops.gemm(Av, Wseg, o["c4"][:, :D], b_kstrided=True, segments=True, resid=resid, b_split_folded=img_fold,
-                 tile_policy=pol)
+        gemm_on(ops, _family(pol, M, actout=True), Av, W, [o["c1"][:, :D], o["c1"][:, D:]], b_kstrided=True, b_split=img,
+                a_act=True, bias=bias, a_act_out=[o["h1"][:, :D], o["h1"][:, D:]], tile_policy=pol)
+        gemm_on(ops, _family(pol, M), Av, W, [o["c2"][:, :D], o["c2"][:, D:]], b_kstrided=True, b_split=img, bias=bias,
+                cpre=[o["p2"][:, :D], o["p2"][:, D:]], out_act=True, dact_kind=1, tile_policy=pol)
+        gemm_on(ops, _family(pol, M, actout=True), A, W512, o["c3"][:, :D], b_kstrided=True, b_split=img512, a_act=True,
+                out_act=True, bias=bias[0], cpre=o["c3"][:, D:], a_act_out=o["h3"], tile_policy=pol)
+        gemm_on(ops, _family(pol, M), Av, Wseg, o["c4"][:, :D], b_kstrided=True, segments=True, resid=resid,
+                b_split_folded=img_fold, tile_policy=pol)
         torch.cuda.synchronize()
         res[pol] = o
     for k in res[3]:
@@ -256,23 +272,24 @@ def test_forms_of_the_third_unit(ops, M):
     for pol in (3, 256):
         o = {k: torch.full((M, D), float("nan"), device=dev()) for k in ("c1", "c2", "c3", "c4")}
         s = {k: torch.full((tiles * D,), float("nan"), dtype=torch.float64, device=dev()) for k in ("s2", "s3", "q3", "s4")}
-        ops.gemm(Av, Wseg, o["c1"], b_kstrided=True, segments=True, b_split_folded=img_fold, tile_policy=pol)
-        ops.gemm(A[:, :D], W, o["c2"], b_kstrided=True, b_split=img, colsum=s["s2"], tile_policy=pol)
-        ops.gemm(A[:, :D], W, o["c3"], b_kstrided=True, b_split=img, colsum=s["s3"], colsq=s["q3"], tile_policy=pol)
-        ops.gemm(Av, Wseg, o["c4"], b_kstrided=True, segments=True, b_split_folded=img_fold, dact=pre, dact_kind=1,
-                 colsum=s["s4"], tile_policy=pol)
+        fam = _family(pol, M)
+        gemm_on(ops, fam, Av, Wseg, o["c1"], b_kstrided=True, segments=True, b_split_folded=img_fold, tile_policy=pol)
+        gemm_on(ops, fam, A[:, :D], W, o["c2"], b_kstrided=True, b_split=img, colsum=s["s2"], tile_policy=pol)
+        gemm_on(ops, fam, A[:, :D], W, o["c3"], b_kstrided=True, b_split=img, colsum=s["s3"], colsq=s["q3"], tile_policy=pol)
+        gemm_on(ops, fam, Av, Wseg, o["c4"], b_kstrided=True, segments=True, b_split_folded=img_fold, dact=pre, dact_kind=1,
+                colsum=s["s4"], tile_policy=pol)
         torch.cuda.synchronize()
         res[pol] = {**o, **s}
         # K = 768: three folded segments + residual
         o["c5"] = torch.full((M, D), float("nan"), device=dev())
-        ops.gemm([A3[:, g * D:(g + 1) * D] for g in range(3)], Wseg3, o["c5"], b_kstrided=True, segments=True, resid=pre,
-                 b_split_folded=img_fold3, tile_policy=pol)
+        gemm_on(ops, fam, [A3[:, g * D:(g + 1) * D] for g in range(3)], Wseg3, o["c5"], b_kstrided=True, segments=True,
+                resid=pre, b_split_folded=img_fold3, tile_policy=pol)
         # K = 512 + residual, times the activation's derivative (both families), bias gradient: two epilogue operands
         for name, kind in (("6", 0), ("7", 1)):
             o["c" + name] = torch.full((M, D), float("nan"), device=dev())
             o["s" + name] = torch.full((tiles * D,), float("nan"), dtype=torch.float64, device=dev())
-            ops.gemm(Av, Wseg, o["c" + name], b_kstrided=True, segments=True, b_split_folded=img_fold, resid=resid2, dact=pre,
-                     dact_kind=kind, colsum=o["s" + name], tile_policy=pol)
+            gemm_on(ops, fam, Av, Wseg, o["c" + name], b_kstrided=True, segments=True, b_split_folded=img_fold, resid=resid2,
+                    dact=pre, dact_kind=kind, colsum=o["s" + name], tile_policy=pol)
         torch.cuda.synchronize()
         res[pol].update({k: o[k] for k in ("c5", "c6", "s6", "c7", "s7")})
     v5 = sum(A3.double()[:, g * D:(g + 1) * D] @ Wseg3[g].double() for g in range(3)) + pre.double()
@@ -325,8 +342,9 @@ def test_gate_statistics_form(ops, M, with_resid):
     for pol in (3, 128):
         o = torch.full((M, D), float("nan"), device=dev())
         ca, cb = (torch.full((tiles * D,), float("nan"), device=dev(), dtype=torch.float64) for _ in range(2))
-        ops.gemm([dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], o, segments=True, b_kstrided=True, resid=resid, b_split=img,
-                 b_split_folded=folded, colsum=ca, colsq=cb, tile_policy=pol, gate_stats=(gs[:, :D], env, mean_rstd, gamma, beta))
+        gemm_on(ops, _family(pol, M), [dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], o, segments=True, b_kstrided=True,
+                resid=resid, b_split=img, b_split_folded=folded, colsum=ca, colsq=cb, tile_policy=pol,
+                gate_stats=(gs[:, :D], env, mean_rstd, gamma, beta))
         torch.cuda.synchronize()
         assert not torch.isnan(o).any() and not torch.isnan(ca).any() and not torch.isnan(cb).any()
         got[pol] = (o, ca.view(tiles, D).sum(0), cb.view(tiles, D).sum(0))
@@ -356,7 +374,8 @@ def test_the_launch_timer_names_the_kernel_that_runs_a_folded_product(ops):
         torch.cuda.synchronize()
         ops.profile_gemm(True)
         try:
-            ops.gemm([A[:, :D], A[:, D:]], Wseg, out, b_kstrided=True, segments=True, b_split_folded=folded, tile_policy=pol)
+            gemm_on(ops, _family(pol, M), [A[:, :D], A[:, D:]], Wseg, out, b_kstrided=True, segments=True,
+                    b_split_folded=folded, tile_policy=pol)
             torch.cuda.synchronize()
             names[pol] = {k: v["launches"] for k, v in ops.profile_gemm_read().items()}
         finally:

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from gemm_cases import gemm_on
 
 pytestmark = pytest.mark.gpu
 
@@ -169,15 +170,19 @@ def test_gemm_rejects_bad_shapes(ops):
                                               (12416, 256, 256, 1, True), (9000, 64, 512, 1, False),
                                               (8200, 48, 256, 2, False)])
 def test_gemm_with_weight_images(ops, precision, M, K, N, groups, act):
-    """Y[g] = (silu?)(X[g]) W[g]^T + b[g] through the DMA-fed kernels: K from one K-step (pipeline head only) to 32
-    (steady-state loop), ragged and single-row M, one and two column tiles, grouped launches."""
+    """Y[g] = (silu?)(X[g]) W[g]^T + b[g] with weight images.  Only the three shapes of 8,200 rows and more reach a DMA-fed
+    kernel (the 128-wide fp32 one at precision 0, the bf16x3 one at precision 1; K = 48, 64, 256): the others have 1 to 16
+    tiles, which the plan narrows to the 64-wide general kernel (choose_bn in csrc/gemm.hip) -- they cover that kernel with
+    image arguments.  Every K-loop length, ragged and single-row M, one and two column tiles and groups ON the DMA-fed
+    kernels are cases of tests/test_gpu_gemm_families.py."""
+    family = ("f32nn128" if precision == 0 else "x3nn16") if M >= 8200 else "general64"
     Xs = [rnd(M, K, seed=10 + g) for g in range(groups)]
     Ws = [rnd(N, K, seed=20 + g, scale=0.1) for g in range(groups)]
     bs = [rnd(N, seed=30 + g) for g in range(groups)]
     Bt = [w.t().contiguous() for w in Ws]
     imgs = (ops.pack_b if precision == 0 else ops.split_b)([w.t() for w in Ws])
     Cs = [torch.full((M, N), float("nan"), device=dev()) for _ in range(groups)]
-    ops.gemm(Xs, Bt, Cs, b_kstrided=True, a_act=act, bias=bs, precision=precision, b_split=imgs)
+    gemm_on(ops, family, Xs, Bt, Cs, b_kstrided=True, a_act=act, bias=bs, precision=precision, b_split=imgs)
     for g in range(groups):
         x = Xs[g].double()
         ref = (silu64(x) if act else x) @ Ws[g].double().t() + bs[g].double()
@@ -195,7 +200,8 @@ def test_gemm_plain_bf16_operands_every_pipeline_length(ops, M, pad, act):
         x = X[:, :K]
         W = rnd(256, K, seed=1, scale=0.1)
         C = torch.full((M, 256), float("nan"), device=dev())
-        ops.gemm([x], [W.t().contiguous()], [C], b_kstrided=True, a_act=act, b_split=ops.split_b([W.t()]), precision=2)
+        gemm_on(ops, "x3nn", [x], [W.t().contiguous()], [C], b_kstrided=True, a_act=act, b_split=ops.split_b([W.t()]),
+                precision=2)
         a = silu64(x.double()).float() if act else x
         ref = a.bfloat16().double() @ W.bfloat16().double().t()
         assert rel_err(C, ref) < (1e-3 if act else 1e-6), K     # the kernel's own SiLU may round a few operands the other way
@@ -216,7 +222,8 @@ def test_plain_bf16_products_are_bitwise_repeatable_when_the_chip_is_oversubscri
     for rep in range(12):
         imgs = ops.split_b([w.t() for w in Ws])
         C = [torch.full((M, N), float("nan"), device=dev()) for _ in range(groups)]
-        ops.gemm(Xs, Bt, C, b_kstrided=True, a_act=True, b_split=imgs, precision=2)
+        gemm_on(ops, "x3nn" if a_dtype == torch.float32 else "hnn", Xs, Bt, C, b_kstrided=True, a_act=True, b_split=imgs,
+                precision=2)
         if first is None:
             first = C
             x = Xs[0][:4096].double()
@@ -232,7 +239,13 @@ def test_plain_bf16_products_are_bitwise_repeatable_when_the_chip_is_oversubscri
 def test_gemm_writes_the_activated_operand(ops, precision, M, K, N, groups):
     """a_act_out: Y = silu(X) W^T + b as before (bitwise the kernel without the by-product) and silu(X) written with X's
     row stride -- the groups are column blocks of one [M, groups*K] matrix as in the model (pre = [gate | aggr]); cells
-    outside the written blocks stay untouched; every pipeline length; ragged / single-row M; two column tiles."""
+    outside the written blocks stay untouched; ragged / single-row M; two column tiles.  At precision 0 and 1 only M = 33,000
+    reaches the kernels that write silu(X) in passing (f32nn_actout / x3nn_actout); every other shape has too few tiles, is
+    narrowed to the 64-wide general kernel and gets silu(X) from the elementwise pre-pass.  Precision 2 takes the bf16 kernel
+    at every shape.  The K-loop lengths of the fused kernels are cases of tests/test_gpu_gemm_families.py."""
+    fused = precision == 2 or M == 33000
+    fam_plain = {0: "f32nn", 1: "x3nn16", 2: "x3nn"}[precision] if fused else "general64"
+    fam_out = ("f32nn_actout" if precision == 0 else "x3nn_actout") if fused else "general64"
     X = rnd(M, groups * K + 16, seed=11)
     Xs = [X[:, g * K:(g + 1) * K] for g in range(groups)]
     Ws = [rnd(N, K, seed=20 + g, scale=0.1) for g in range(groups)]
@@ -245,9 +258,10 @@ def test_gemm_writes_the_activated_operand(ops, precision, M, K, N, groups):
     Hs = [H[:, g * K:(g + 1) * K] for g in range(groups)]
     tiles = ops.gemm_tiles_m(M)
     cs = [torch.zeros(tiles * N, dtype=torch.float64, device=dev()) for _ in range(groups)]
-    ops.gemm(Xs, Bt, C0, b_kstrided=True, a_act=True, bias=bs, b_split=imgs, precision=precision)
-    ops.gemm(Xs, Bt, Cs, b_kstrided=True, a_act=True, bias=bs, b_split=imgs, a_act_out=Hs, precision=precision,
-             colsum=[cs[0]] + [None] * (groups - 1))
+    gemm_on(ops, fam_plain, Xs, Bt, C0, b_kstrided=True, a_act=True, bias=bs, b_split=imgs, precision=precision)
+    plan = gemm_on(ops, fam_out, Xs, Bt, Cs, b_kstrided=True, a_act=True, bias=bs, b_split=imgs, a_act_out=Hs,
+                   precision=precision, colsum=[cs[0]] + [None] * (groups - 1))
+    assert plan.prepass == (not fused)
     for g in range(groups):
         if precision == 1:
             # bf16x3: the plain launch runs on the 16x16x32 MFMA shape (csrc/gemm_x3s.h), the one with the by-product on
@@ -277,7 +291,9 @@ def test_gemm_activated_operand_without_the_fused_kernel(ops, precision):
     X, W = rnd(70, 40, seed=1)[:, :32], rnd(256, 32, seed=2)
     C_ = torch.empty(70, 256, device=dev())
     H = torch.full((70, 40), -7.0, device=dev())
-    ops.gemm(X, W.t().contiguous(), C_, b_kstrided=True, a_act=True, a_act_out=H[:, :32], precision=precision)
+    plan = gemm_on(ops, "general64", X, W.t().contiguous(), C_, b_kstrided=True, a_act=True, a_act_out=H[:, :32],
+                   precision=precision)
+    assert plan.prepass
     assert rel_err(H[:, :32], silu64(X.double())) < 1e-6 and bool((H[:, 32:] == -7.0).all())
     assert rel_err(C_, silu64(X.double()) @ W.double().t()) < (TOL if precision == 0 else 1e-5)
     with pytest.raises(RuntimeError, match="a_act_out"):
@@ -287,7 +303,7 @@ def test_gemm_activated_operand_without_the_fused_kernel(ops, precision):
 @pytest.mark.parametrize("precision", [0, 1])
 def test_gemm_atom_sized_rows_folded_segments(ops, precision):
     """The dX product of the node terms at the benchmark shape: M = 12,416 atoms (97 row tiles: at precision 0 the
-    128-wide DMA-fed kernel), four K-segments that are column blocks of one [M, 1024] matrix, residual, silu' and bias
+    128-wide DMA-fed kernel, at precision 1 the bf16x3 one, both over the folded K = 1024), four K-segments that are column blocks of one [M, 1024] matrix, residual, silu' and bias
     gradient sums (layer 0's form)."""
     M, K, N = 12416 + 5, 256, 256
     X = rnd(M, 4 * K, seed=3)
@@ -297,8 +313,9 @@ def test_gemm_atom_sized_rows_folded_segments(ops, precision):
     cs = torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev())
     C_ = torch.full((M, N), float("nan"), device=dev())
     img = torch.cat((ops.pack_b if precision == 0 else ops.split_b)(Ws))
-    ops.gemm([X[:, i * K:(i + 1) * K] for i in range(4)], Ws, C_, b_kstrided=True, segments=True, resid=resid, dact=pre,
-             colsum=cs, b_split_folded=img, precision=precision)
+    plan = gemm_on(ops, "f32nn128" if precision == 0 else "x3nn16", [X[:, i * K:(i + 1) * K] for i in range(4)], Ws, C_,
+                   b_kstrided=True, segments=True, resid=resid, dact=pre, colsum=cs, b_split_folded=img, precision=precision)
+    assert (plan.k_folded, plan.nsegs_run) == (4 * K, 1)
     ref = (sum(X[:, i * K:(i + 1) * K].double() @ Ws[i].double() for i in range(4)) + resid.double()) * dsilu64(pre.double())
     assert rel_err(C_, ref) < TOL
     assert rel_err(cs.view(tiles, N).sum(0), C_.double().sum(0)) < 1e-6
@@ -307,8 +324,8 @@ def test_gemm_atom_sized_rows_folded_segments(ops, precision):
 @pytest.mark.parametrize("case", ["plain", "gather", "dact_colsum", "resid_folded"])
 def test_gemm_edge_sized_rows_through_every_model_epilogue(ops, case):
     """M > 32768 rows at precision 0 with a weight image (hundreds of row tiles, ragged last tile), through every
-    epilogue the model gives the DMA-fed kernel: bias, node-term gather, silu' with bias-gradient sums, residual with
-    folded K-segments."""
+    epilogue the model gives the DMA-fed kernels: bias and silu' with bias-gradient sums on the 256-wide one, the node-term
+    gather and the residual with folded K-segments on the 128-wide one (518 tiles: below the persistent kernel's 1,024)."""
     M = 32768 + (300 if case != "plain" else 77)
     K, N, G = 256, 256, 2
     Xs = [rnd(M, K, seed=40 + g) for g in range(G)]
@@ -319,7 +336,7 @@ def test_gemm_edge_sized_rows_through_every_model_epilogue(ops, case):
     ref = [x.double() @ w.double().t() for x, w in zip(Xs, Ws)]
     if case == "plain":
         bs = [rnd(N, seed=60 + g) for g in range(G)]
-        ops.gemm(Xs, Bt, Cs, b_kstrided=True, bias=bs, b_split=imgs)
+        gemm_on(ops, "f32nn", Xs, Bt, Cs, b_kstrided=True, bias=bs, b_split=imgs)
         ref = [r + b.double() for r, b in zip(ref, bs)]
     elif case == "gather":
         nn = 999
@@ -327,15 +344,15 @@ def test_gemm_edge_sized_rows_through_every_model_epilogue(ops, case):
         g_ = torch.Generator().manual_seed(3)
         tgt = torch.sort(torch.randint(0, nn, (M,), generator=g_)).values.to(torch.int32).to(dev())
         src = torch.randint(0, nn, (M,), generator=g_).to(torch.int32).to(dev())
-        ops.gemm(Xs, Bt, Cs, b_kstrided=True, gather_i=[P[:, :N], P[:, N:2 * N]], gather_j=[P[:, 2 * N:3 * N], P[:, 3 * N:]],
-                 tgt=tgt, src=src, b_split=imgs)
+        gemm_on(ops, "f32nn128", Xs, Bt, Cs, b_kstrided=True, gather_i=[P[:, :N], P[:, N:2 * N]],
+                gather_j=[P[:, 2 * N:3 * N], P[:, 3 * N:]], tgt=tgt, src=src, b_split=imgs)
         Pd = P.double()
         ref = [ref[0] + Pd[tgt.long(), :N] + Pd[src.long(), 2 * N:3 * N], ref[1] + Pd[tgt.long(), N:2 * N] + Pd[src.long(), 3 * N:]]
     elif case == "dact_colsum":
         pre = [rnd(M, N, seed=70 + g) for g in range(G)]
         tiles = ops.gemm_tiles_m(M)
         cs = [torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev()) for _ in range(G)]
-        ops.gemm(Xs, Bt, Cs, b_kstrided=True, dact=pre, colsum=cs, b_split=imgs)
+        gemm_on(ops, "f32nn", Xs, Bt, Cs, b_kstrided=True, dact=pre, colsum=cs, b_split=imgs)
         ref = [r * dsilu64(p_.double()) for r, p_ in zip(ref, pre)]
         for g in range(G):
             assert rel_err(cs[g].view(tiles, N).sum(0), ref[g].sum(0)) < 1e-6
@@ -344,8 +361,8 @@ def test_gemm_edge_sized_rows_through_every_model_epilogue(ops, case):
         X2 = rnd(M, 2 * K, seed=81)
         W2 = [rnd(K, N, seed=82 + s, scale=0.1) for s in range(2)]
         C1 = torch.full((M, N), float("nan"), device=dev())
-        ops.gemm([X2[:, :K], X2[:, K:]], W2, C1, b_kstrided=True, segments=True, resid=resid,
-                 b_split_folded=torch.cat(ops.pack_b(W2)))
+        gemm_on(ops, "f32nn128", [X2[:, :K], X2[:, K:]], W2, C1, b_kstrided=True, segments=True, resid=resid,
+                b_split_folded=torch.cat(ops.pack_b(W2)))
         r2 = X2[:, :K].double() @ W2[0].double() + X2[:, K:].double() @ W2[1].double() + resid.double()
         assert rel_err(C1, r2) < TOL
         return
@@ -368,8 +385,9 @@ def test_gemm_softplus_backward_epilogue(ops, precision, M, with_resid, image):
     cs = torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev())
     C_ = torch.full((M, N), float("nan"), device=dev())
     img = torch.cat((ops.pack_b if precision == 0 else ops.split_b)(Ws)) if image else None
-    ops.gemm([X[:, :K], X[:, K:]], Ws, C_, b_kstrided=True, segments=True, resid=resid, dact=pre, colsum=cs,
-             b_split_folded=img, precision=precision, dact_kind=1)
+    family = ("f32nn128" if precision == 0 else "x3nn16") if image else "general64"
+    gemm_on(ops, family, [X[:, :K], X[:, K:]], Ws, C_, b_kstrided=True, segments=True, resid=resid, dact=pre, colsum=cs,
+            b_split_folded=img, precision=precision, dact_kind=1)
     ref = X[:, :K].double() @ Ws[0].double() + X[:, K:].double() @ Ws[1].double()
     if with_resid:
         ref = ref + resid.double()
@@ -389,7 +407,9 @@ def test_gemm_softplus_forward_epilogue(ops, precision, M, image):
     pre = torch.full((M, N), float("nan"), device=dev())
     out = torch.full((M, N), float("nan"), device=dev())
     img = (ops.pack_b if precision == 0 else ops.split_b)([W])[0] if image else None
-    ops.gemm(X, W, out, b_kstrided=True, bias=b, cpre=pre, out_act=True, b_split=img, precision=precision, dact_kind=1)
+    family = ("f32nn128" if precision == 0 else "x3nn16") if image else "general64"
+    gemm_on(ops, family, X, W, out, b_kstrided=True, bias=b, cpre=pre, out_act=True, b_split=img, precision=precision,
+            dact_kind=1)
     ref = X.double() @ W.double() + b.double()
     assert rel_err(pre, ref) < TOL
     assert float(pre.max()) > 20.0 and float(pre.min()) < -10.0          # both tails of the softplus are exercised
@@ -401,8 +421,11 @@ def test_gemm_softplus_forward_epilogue(ops, precision, M, image):
 
 @pytest.mark.parametrize("precision", [0, 1, 2])
 def test_gemm_folded_segments_with_images(ops, precision):
-    """sum_s X[:, sK:(s+1)K] W_s: K-segments that are adjacent column blocks run as one product (b_split_folded); the
-    same call without the folded image must give the same numbers (segment form)."""
+    """sum_s X[:, sK:(s+1)K] W_s: K-segments that are adjacent column blocks run as one product (b_split_folded) -- at
+    precision 2.  At precision 0 and 1 these 700 rows are six tiles: the plan narrows the launch to the 64-wide general
+    kernel, which sums the four segments (the folded products of the fp32 and bf16x3 kernels are cases of
+    tests/test_gpu_gemm_families.py and test_gemm_atom_sized_rows_folded_segments).  The same call without the folded image
+    must give the same numbers (segment form)."""
     M, K, N, S = 700, 256, 256, 4
     X = rnd(M, S * K, seed=1)
     Ws = [rnd(K, N, seed=2 + s, scale=0.1) for s in range(S)]         # operands as [K, N] (backward form)
@@ -412,13 +435,15 @@ def test_gemm_folded_segments_with_images(ops, precision):
     make = ops.pack_b if precision == 0 else ops.split_b
     folded = torch.cat(make(Ws))
     C1 = torch.empty(M, N, device=dev())
-    ops.gemm(segs, Ws, C1, b_kstrided=True, segments=True, resid=resid, precision=precision, b_split_folded=folded)
+    plan = gemm_on(ops, "x3nn" if precision == 2 else "general64", segs, Ws, C1, b_kstrided=True, segments=True, resid=resid,
+                   precision=precision, b_split_folded=folded)
+    assert plan.nsegs_run == (1 if precision == 2 else S)
     tol = TOL if precision < 2 else 2e-2
     assert rel_err(C1, ref) < tol
     if precision == 2:
         assert rel_err(C1, ref) > 1e-6          # the bf16 kernel really ran
     C2 = torch.empty(M, N, device=dev())
-    ops.gemm(segs, Ws, C2, b_kstrided=True, segments=True, resid=resid, precision=min(precision, 1))
+    gemm_on(ops, "general64", segs, Ws, C2, b_kstrided=True, segments=True, resid=resid, precision=min(precision, 1))
     assert rel_err(C2, ref) < TOL
 
 
@@ -429,14 +454,15 @@ def test_gemm_weight_gradient_ragged_rows(ops, precision, E, M, N, splitk, act):
     """dW = dY^T (silu?)(X) with a ragged last row tile (M % 128 != 0), two column tiles, a K tail (E % 16 != 0) and
     the un-split form, at both precisions (the transposing-read kernel takes all of them at precision 1)."""
     dY, X = rnd(E, M, seed=3), rnd(E, N, seed=4)
+    family = "f32tn" if precision == 0 else "x3tn"
     ref = dY.double().t() @ (silu64(X.double()) if act else X.double())
     out = torch.full((M, N), float("nan"), device=dev())
     if splitk > 1:
         slabs = torch.full((splitk * M, N), float("nan"), device=dev())
-        ops.gemm(dY, X, slabs, a_kstrided=True, b_kstrided=True, b_act=act, splitk=splitk, precision=precision)
+        gemm_on(ops, family, dY, X, slabs, a_kstrided=True, b_kstrided=True, b_act=act, splitk=splitk, precision=precision)
         ops.splitk_reduce(slabs, splitk, out)
     else:
-        ops.gemm(dY, X, out, a_kstrided=True, b_kstrided=True, b_act=act, precision=precision)
+        gemm_on(ops, family, dY, X, out, a_kstrided=True, b_kstrided=True, b_act=act, precision=precision)
     assert rel_err(out, ref) < TOL
 
 
@@ -1106,7 +1132,7 @@ def _half_storage_activation_products(ops, M, K, N):
     tgt = torch.sort(torch.randint(0, nn, (M,), generator=g_)).values.to(torch.int32).to(dev())
     src = torch.randint(0, nn, (M,), generator=g_).to(torch.int32).to(dev())
     Ch = torch.full((M, G * N), float("nan"), device=dev(), dtype=torch.bfloat16)
-    ops.gemm(Xs, Bt, [Ch[:, :N], Ch[:, N:]], b_kstrided=True, b_split=imgs, precision=2,
+    gemm_on(ops, "hnn", Xs, Bt, [Ch[:, :N], Ch[:, N:]], b_kstrided=True, b_split=imgs, precision=2,
              gather_i=[P[:, :N], P[:, N:2 * N]], gather_j=[P[:, 2 * N:3 * N], P[:, 3 * N:]], tgt=tgt, src=src)
     Pd = P.double()
     for g in range(G):
@@ -1121,8 +1147,8 @@ def _half_storage_activation_products(ops, M, K, N):
         C2 = torch.full((M, G * N), float("nan"), device=dev(), dtype=out_dtype)
         cs = torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev())
         cq = torch.full((tiles * N,), float("nan"), dtype=torch.float64, device=dev())
-        ops.gemm(Ahs, Bt, [C2[:, :N], C2[:, N:]], b_kstrided=True, b_split=imgs, precision=2, a_act=True,
-                 colsum=[cs, None], colsq=[cq, None])
+        gemm_on(ops, "hnn", Ahs, Bt, [C2[:, :N], C2[:, N:]], b_kstrided=True, b_split=imgs, precision=2, a_act=True,
+                colsum=[cs, None], colsq=[cq, None])
         name = "fp32" if out_dtype == torch.float32 else "bf16"
         for g in range(G):
             fig.output(f"(2) silu(bf16 A) -> {name} C, group {g}", C2[:, g * N:(g + 1) * N], ref2[g], H_ACT)
@@ -1136,8 +1162,8 @@ def _half_storage_activation_products(ops, M, K, N):
         A3 = Ah if a_half else X
         A3s = [A3[:, g * K:(g + 1) * K] for g in range(G)]
         C3 = torch.full((M, G * N), float("nan"), device=dev(), dtype=torch.bfloat16 if c_half else torch.float32)
-        ops.gemm(A3s, Bt, [C3[:, :N], C3[:, N:]], b_kstrided=True, b_split=imgs, precision=2,
-                 dact=[pre[:, :N], pre[:, N:]])
+        gemm_on(ops, "hnn", A3s, Bt, [C3[:, :N], C3[:, N:]], b_kstrided=True, b_split=imgs, precision=2,
+                dact=[pre[:, :N], pre[:, N:]])
         for g in range(G):
             ref = (_mfma(A3s[g]) @ Wd[g]) * dsilu64(pre[:, g * N:(g + 1) * N].double())
             # no SiLU on an operand here either: a per-element fp32 factor of relative error e moves a value across a
@@ -1147,7 +1173,7 @@ def _half_storage_activation_products(ops, M, K, N):
     # (4) dE: bf16 A -> fp32 C + residual
     resid = rnd(M, N, seed=12)
     C4 = torch.full((M, N), float("nan"), device=dev())
-    ops.gemm(Ahs[0], Bt[0], C4, b_kstrided=True, b_split=imgs[:1], precision=2, resid=resid)
+    gemm_on(ops, "hnn", Ahs[0], Bt[0], C4, b_kstrided=True, b_split=imgs[:1], precision=2, resid=resid)
     fig.output("(4) bf16 A -> fp32 C + residual", C4, _mfma(Ahs[0]) @ Wd[0] + resid.double(), H_PLAIN)
     fig.check()
 
@@ -1192,10 +1218,10 @@ def test_gemm_half_storage_weight_gradients(ops, K):
                 continue
             outs = [torch.full((M, N), float("nan"), device=dev()) for _ in range(G)]
             if S == 1:
-                ops.gemm(As, Bs, outs, a_kstrided=True, b_kstrided=True, b_act=act, precision=2)
+                gemm_on(ops, "htn", As, Bs, outs, a_kstrided=True, b_kstrided=True, b_act=act, precision=2)
             else:
                 slabs = [torch.full((S * M, N), float("nan"), device=dev()) for _ in range(G)]
-                ops.gemm(As, Bs, slabs, a_kstrided=True, b_kstrided=True, b_act=act, precision=2, splitk=S)
+                gemm_on(ops, "htn", As, Bs, slabs, a_kstrided=True, b_kstrided=True, b_act=act, precision=2, splitk=S)
                 ops.splitk_reduce(slabs, S, outs)
             for g in range(G):
                 fig.add(f"K={K} a_half={a_half} b_half={b_half} act={act} splitk={S} group {g}",
@@ -1353,21 +1379,22 @@ def test_gate_backward_sums_without_the_statistics_pass(ops, with_env, precision
     de_out = torch.empty(E, D, device=dev())
     tiles = ops.gemm_tiles_m(E)
     ca, cb = (torch.full((tiles * D,), 3.0, device=dev(), dtype=torch.float64) for _ in range(2))
-    ops.gemm([dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], de_out, segments=True, b_kstrided=True, resid=resid,
-             b_split=img, b_split_folded=folded, colsum=ca, colsq=cb, precision=precision,
-             gate_stats=(gs[:, :D], env, mean_rstd, gamma, beta))
+    family = "f32nn128" if precision == 0 else "x3nn16"          # (fewer than 1,024 tiles: not the persistent kernel)
+    gemm_on(ops, family, [dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], de_out, segments=True, b_kstrided=True, resid=resid,
+            b_split=img, b_split_folded=folded, colsum=ca, colsq=cb, precision=precision,
+            gate_stats=(gs[:, :D], env, mean_rstd, gamma, beta))
     de_ref = c(resid) + c(dpre) @ c(W)
     assert rel_err(de_out, de_ref) < TOL
     plain = torch.empty(E, D, device=dev())
-    ops.gemm([dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], plain, segments=True, b_kstrided=True, resid=resid, b_split=img,
-             b_split_folded=folded, precision=precision)
+    gemm_on(ops, family, [dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], plain, segments=True, b_kstrided=True, resid=resid,
+            b_split=img, b_split_folded=folded, precision=precision)
     assert torch.equal(plain, de_out)                         # the statistics do not touch the product
     # the last layer's form: no edge residual (the head does not read the edge features)
     nores = torch.empty(E, D, device=dev())
     ca2, cb2 = (torch.full((tiles * D,), 3.0, device=dev(), dtype=torch.float64) for _ in range(2))
-    ops.gemm([dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], nores, segments=True, b_kstrided=True, b_split=img,
-             b_split_folded=folded, colsum=ca2, colsq=cb2, precision=precision,
-             gate_stats=(gs[:, :D], env, mean_rstd, gamma, beta))
+    gemm_on(ops, family, [dpre[:, :D], dpre[:, D:]], [W[:D], W[D:]], nores, segments=True, b_kstrided=True, b_split=img,
+            b_split_folded=folded, colsum=ca2, colsq=cb2, precision=precision,
+            gate_stats=(gs[:, :D], env, mean_rstd, gamma, beta))
     assert rel_err(nores, c(dpre) @ c(W)) < TOL
     assert rel_err(ca2.view(tiles, D).sum(0).cpu(), (c(nores) * w).sum(0)) < 2e-6
     assert rel_err(cb2.view(tiles, D).sum(0).cpu(), (c(nores) * w * ghat).sum(0)) < 2e-6

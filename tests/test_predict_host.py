@@ -155,7 +155,7 @@ def test_export_entry_point_is_declared_bound_and_launches_nothing_without_rows(
     m = re.search(r"\bint\s+cartnet_adp_export\s*\(([^)]*)\)\s*;", hdr)
     assert m and len(m.group(1).split(",")) == 12 == len(lib.PROTOTYPES["cartnet_adp_export"][1])
     l = lib.load()
-    assert lib.ABI_VERSION == 15 == l.cartnet_abi_version()
+    assert lib.ABI_VERSION == 16 == l.cartnet_abi_version()
     assert l.cartnet_adp_export(None, None, None, 4, 0, None, None, None, None, None, None, None) == 0
     assert l.cartnet_adp_export(None, None, None, 0, 0, None, None, None, None, None, None, None) == 0
     assert l.cartnet_adp_export(None, None, None, 1, -1, None, None, None, None, None, None, None) != 0

@@ -116,7 +116,7 @@ def test_regraph_prototypes_are_declared_and_bound():
     declared = set(re.findall(r"\b(cartnet_[a-z0-9_]+)\s*\(", hdr))
     names = {n for n in lib.PROTOTYPES if n.startswith("cartnet_shard_regraph_")}
     assert {"cartnet_shard_regraph_workspace_bytes", "cartnet_shard_regraph_count", "cartnet_shard_regraph_fill"} <= names
-    assert names <= declared and lib.ABI_VERSION == 15
+    assert names <= declared and lib.ABI_VERSION == 16
     for gone in ("cartnet_radius_graph_count", "cartnet_radius_graph_fill", "cartnet_neighbor_cap_count",
                  "cartnet_neighbor_cap_fill"):
         assert gone not in lib.PROTOTYPES and gone not in declared

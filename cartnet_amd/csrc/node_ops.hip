@@ -900,6 +900,8 @@ extern "C" int cartnet_cholesky_head_bwd(const float* hid, const int32_t* out_in
 extern "C" int cartnet_scalar_head_fwd(const float* hid, const float* w2, const float* b2, const int64_t* graph_ptr,
                                        int32_t Bg, int32_t H, float* out, void* stream) {
   CN_CHECK(Bg >= 0 && H >= 1, "cartnet_scalar_head_fwd: bad sizes");
+  // the kernel reads hid and w2 four columns at a time: a width that is no multiple of 4 would read past both rows
+  CN_CHECK(H % 4 == 0, "cartnet_scalar_head_fwd: H=%d must be a multiple of 4", H);
   if (Bg == 0) return 0;
   CN_CHECK(hid && w2 && b2 && graph_ptr && out, "cartnet_scalar_head_fwd: null pointer");
   hipLaunchKernelGGL(cn_scalar_head_fwd_kernel, dim3(Bg), dim3(64), 0, ST(stream), hid, w2, b2, graph_ptr, Bg, H, out);

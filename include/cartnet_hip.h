@@ -947,7 +947,8 @@ int cartnet_cholesky_head_bwd(const float* hid, const int32_t* out_index, const 
                               const float* dpred, int32_t N, int32_t H, float* dhid, float* parts, void* stream);
 
 /* Scalar head (models/cartnet.py:323-327): v[n] = w2 . silu(hid[n]) + b2 ; out[g] = mean of v over the atoms of
- * crystal g (graph_ptr int64 [Bg+1]). */
+ * crystal g (graph_ptr int64 [Bg+1]).  The forward reads hid and w2 in 16-byte pieces: H % 4 == 0, anything else is
+ * refused (the model's H = D/2 with D % 8 == 0 always is). */
 int cartnet_scalar_head_fwd(const float* hid, const float* w2, const float* b2, const int64_t* graph_ptr,
                             int32_t Bg, int32_t H, float* out, void* stream);
 int cartnet_scalar_head_bwd(const float* hid, const float* w2, const int64_t* graph_ptr, const int64_t* batch,

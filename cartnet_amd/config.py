@@ -54,6 +54,7 @@ def _defaults() -> _Node:
         device="cuda:0",
         shard_dir=None,
         eval_batch=1,
+        rotations=1,
     )
 
 

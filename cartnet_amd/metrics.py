@@ -208,6 +208,47 @@ def adp_export(pred: torch.Tensor, row_ptr: torch.Tensor, cell: torch.Tensor, ax
     return AdpExport(u_cif, u_eq, principal, ax, st, status)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Mean over rotated frames (csrc/frame_ops.hip): the predictions of K rotated copies of a batch, each brought back to the
+# stored frame (the inverse of the Monte-Carlo pseudo-truth, main.py:95-97), and how far the members scatter about it.
+
+class FrameMean(NamedTuple):
+    """What ``frame_mean`` returns, all on the device.  ``mean`` [M,3,3] fp32: per row the mean over the K frames of
+    ``R P_k R^T``; ``spread`` [M]: the largest deviation of a member from that mean over the nine components;
+    ``crystal_spread`` [B,2] fp64: per crystal the sum of ``spread`` over its rows and its maximum, (0, 0) without rows
+    (``None`` if not requested)."""
+    mean: torch.Tensor
+    spread: torch.Tensor
+    crystal_spread: Optional[torch.Tensor]
+
+
+def frame_mean(pred: torch.Tensor, rot: torch.Tensor, row_ptr: torch.Tensor, stats: bool = True) -> FrameMean:
+    """The mean of a batch's predictions over K frames: one call of ``cartnet_adp_frame_mean``.  ``pred`` [K*M,3,3]
+    replica-major (rows ``k*M ... (k+1)*M-1``: the batch's M rows as predicted from ``cart_dir @ rot[k, g]``); ``rot``
+    [K,B,3,3] fp32; ``row_ptr`` [B+1] over ONE replica's rows.  Member k comes back as ``R P_k R^T`` (fp64 arithmetic, one
+    rounding to fp32); K = 1 with the identity returns ``pred``'s values and a zero spread."""
+    if not (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 3 and tuple(pred.shape[1:]) == (3, 3)):
+        raise ValueError("pred must be a CUDA fp32 tensor [K*M,3,3]")
+    dev = pred.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    if not (rot.dtype == torch.float32 and rot.dim() == 4 and rot.shape[0] >= 1 and tuple(rot.shape[1:]) == (B, 3, 3)
+            and rot.device == dev):
+        raise ValueError("rot must be an fp32 tensor [K,B,3,3], K >= 1, on the data's device")
+    K, rot = int(rot.shape[0]), rot.contiguous()
+    if int(pred.shape[0]) % K:
+        raise ValueError(f"pred holds {int(pred.shape[0])} rows: no multiple of the {K} frames of rot")
+    pred, M = pred.detach().contiguous(), int(pred.shape[0]) // K
+    mean = torch.empty((M, 3, 3), dtype=torch.float32, device=dev)
+    spread = torch.empty(M, dtype=torch.float32, device=dev)
+    if M == 0:                                   # the entry point launches nothing
+        return FrameMean(mean, spread, torch.zeros((B, 2), dtype=torch.float64, device=dev) if stats else None)
+    cs = torch.empty((B, 2), dtype=torch.float64, device=dev) if stats else None
+    _l.check(_l.load().cartnet_adp_frame_mean(pred.data_ptr(), rot.data_ptr(), K, row_ptr.data_ptr(), B, M,
+                                              mean.data_ptr(), spread.data_ptr(), _l.ptr(cs), _l.stream_ptr()),
+             "cartnet_adp_frame_mean")
+    return FrameMean(mean, spread, cs)
+
+
 def split_rows(t: torch.Tensor, rows) -> list:
     """The per-crystal pieces of a host tensor whose dim 0 runs over the rows of a batch: one transfer per batch, then
     this split by the crystals' row counts (a sequence of ints) gives the reference's one-entry-per-crystal lists.  Every

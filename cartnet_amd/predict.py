@@ -15,10 +15,12 @@ from typing import Dict, List
 
 import torch
 
-from .metrics import adp_export, check_export_status, split_rows, target_row_ptr, to_host
+from .metrics import (adp_export, check_export_status, edge_row_ptr, frame_mean, rotate_rows, split_rows, target_row_ptr,
+                      to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
+ROT_KEYS = ("rot_spread", "frames", "rot_stats")                                          # with rotations > 1 only
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -34,7 +36,50 @@ def _inverse_cells(cell: torch.Tensor) -> torch.Tensor:
     return adj / det.view(-1, 1, 1)
 
 
-def predict_adps(model, loader, device, sym=None) -> Dict[str, List]:
+def frames(B: int, K: int, gen: torch.Generator, device) -> torch.Tensor:
+    """[K,B,3,3] fp32 on ``device``: the K frames of B crystals.  Frame 0 is the identity for every crystal (the frame the
+    crystal is stored in); frames 1 ... K-1 come from ONE ``shard.random_rotations`` draw of ``(K-1)*B`` matrices."""
+    from .shard import random_rotations
+    if B < 1 or K < 1:
+        raise ValueError("frames needs B >= 1 crystals and K >= 1 frames")
+    out = torch.eye(3, dtype=torch.float32, device=device).repeat(K, B, 1, 1)
+    if K > 1:
+        out[1:] = random_rotations((K - 1) * B, gen, device).view(K - 1, B, 3, 3)
+    return out
+
+
+def replicate(batch, K: int, R: torch.Tensor):
+    """``batch`` (on the device, atomic numbers in ``x``) K times over as ONE batch of ``K*B`` crystals with PyG's offsets,
+    replica-major: crystal ``k*B + g`` is crystal g with ``cart_dir @ R[k, g]`` (one ``rotate_rows`` over the replica
+    batch's edge segments: the arithmetic of ``DeviceShard.collate(list(sel) * K, R.view(K*B,3,3))``).  Everything else
+    (``x``, ``cart_dist``, ``pos``, ``non_H_mask``, ``cell``, ``temperature``, ``y``) is repeated.  Plain torch on the
+    device; ``batch`` is not modified.  Works on a batch of either loader (``ShardLoader``, ``data.DataLoader``)."""
+    B, N, E = int(batch.num_graphs), int(batch.x.shape[0]), int(batch.edge_index.shape[1])
+    dev = batch.x.device
+    if not (torch.is_tensor(R) and tuple(R.shape) == (K, B, 3, 3)):
+        raise ValueError("R must be a tensor [K,B,3,3]")
+    if batch.x.dtype != torch.int64 or batch.x.dim() != 1:
+        raise ValueError("replicate needs the atomic numbers in batch.x (a forward has overwritten them)")
+    k = torch.arange(K, dtype=torch.int64, device=dev)
+    out = batch.__class__()
+    out.x = batch.x.repeat(K)
+    out.batch = (batch.batch.unsqueeze(0) + (k * B).unsqueeze(1)).reshape(-1)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    out.ptr = torch.cat([zero, (batch.ptr[1:].to(torch.int64).unsqueeze(0) + (k * N).unsqueeze(1)).reshape(-1)])
+    out.edge_index = (batch.edge_index.unsqueeze(1) + (k * N).view(1, K, 1)).reshape(2, K * E)
+    out.cart_dist = batch.cart_dist.repeat(K)
+    edge_ptr = torch.cat([zero, (edge_row_ptr(batch)[1:].unsqueeze(0) + (k * E).unsqueeze(1)).reshape(-1)])
+    out.cart_dir = rotate_rows(batch.cart_dir.repeat(K, 1).contiguous(), edge_ptr,
+                               R.reshape(K * B, 3, 3).to(torch.float32))
+    for name in ("pos", "non_H_mask", "cell", "temperature", "y"):
+        t = getattr(batch, name, None)
+        if torch.is_tensor(t):
+            setattr(out, name, t.repeat(K, *([1] * (t.dim() - 1))))
+    out.num_graphs = K * B
+    return out
+
+
+def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
@@ -43,14 +88,25 @@ def predict_adps(model, loader, device, sym=None) -> Dict[str, List]:
     non-positive one).  A singular cell raises ``ValueError`` naming the crystal.  ``sym``: the ``CifSymmetry`` of a shard
     expanded from CIF files; the result then also has, per crystal, ``asym_labels`` / ``asym_frac`` [a,3] / ``asym_z`` [a]
     (the asymmetric unit as the file gives it), ``symops`` (strings, identity first), ``u_cif_asym`` [h,6] (one row per
-    non-hydrogen atom of the asymmetric unit, the mean over its orbit, ``symmetry.site_average``) and ``spread`` [h]."""
+    non-hydrogen atom of the asymmetric unit, the mean over its orbit, ``symmetry.site_average``) and ``spread`` [h].
+    ``rotations`` = K > 1: every batch is predicted in K frames by ONE forward of ``replicate(batch, K, R)`` with
+    ``R = frames(B, K, gen, device)`` (one generator seeded with ``seed`` for the whole pass), the members are brought back
+    and averaged (``metrics.frame_mean``), and everything above derives from that mean: ``u_cart`` is the mean.  The result
+    then also has, per crystal, ``rot_spread`` [n] (per row the largest deviation of a frame's prediction from the mean),
+    ``frames`` [K,3,3] (the rotations used, the identity first) and ``rot_stats`` [2] fp64 (sum and maximum of
+    ``rot_spread``).  ``rotations`` = 1 is the pass as it always was."""
+    rotations = int(rotations)
+    if rotations < 1:
+        raise ValueError("rotations must be at least 1")
     shard = loader.shard
     if not shard.per_atom_target:
         raise ValueError("predict_adps needs an ADP shard (per-atom 3x3 rows)")
     if not all(k in shard.t for k in ("pos", "cell", "non_h_mask")):
         raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
     model.eval()
-    out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())}
+    out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
+                            + (ROT_KEYS if rotations > 1 else ())}
+    gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     with torch.no_grad():
         for batch in loader:
             if batch is None:
@@ -65,7 +121,14 @@ def predict_adps(model, loader, device, sym=None) -> Dict[str, List]:
                    "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
             if "temperature" in shard.t:
                 dev["temp"] = shard.t["temperature"][sel]                     # the collated one is standardised
-            pred, _ = model(batch)
+            if rotations == 1:
+                pred, _ = model(batch)
+            else:
+                R = frames(B, rotations, gen, device)
+                members, _ = model(replicate(batch, rotations, R))
+                fm = frame_mean(members, R, row_ptr, stats=True)
+                pred = fm.mean
+                dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
             ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
             dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
                        stats=ex.crystal_stats, _status=ex.status)
@@ -88,7 +151,7 @@ def predict_adps(model, loader, device, sym=None) -> Dict[str, List]:
             rows, atoms = (rp[1:] - rp[:-1]).tolist(), (ap[1:] - ap[:-1]).tolist()
             out["name"] += names
             out["temp"] += host.pop("temp").tolist() if "temp" in host else [float("nan")] * B
-            for k in ("cell", "stats"):
+            for k in ("cell", "stats") + (("frames", "rot_stats") if rotations > 1 else ()):
                 out[k] += [t.clone() for t in host.pop(k).unbind(0)]
             for k in ("frac", "z"):
                 out[k] += split_rows(host.pop(k), atoms)
@@ -102,7 +165,7 @@ def predict_adps(model, loader, device, sym=None) -> Dict[str, List]:
 def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
-    return {key: result[key][k] for key in KEYS + SYM_KEYS if key in result}
+    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS if key in result}
 
 
 def cell_parameters(cell) -> tuple:

@@ -419,6 +419,29 @@ int cartnet_adp_export(const float* u_cart, const int64_t* row_ptr, const float*
                        int32_t* status, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Mean of a batch's predictions over K rotated frames.  The reference's Monte-Carlo step (main.py:95-97) feeds the model
+ * cart_dir @ R and compares with R^T U R, what an equivariant model would return; a model that is only approximately
+ * equivariant predicts a little differently in every frame.  This entry point brings the prediction of every frame back
+ * to the stored one and averages:
+ *   pred [K*M,9] fp32, replica-major: rows k*M ... (k+1)*M-1 are the batch's M rows as predicted in frame k;
+ *   rot [K*B,9] fp32, one row-major 3x3 each: frame k of crystal g is R = rot[k*B + g], and the replica's input was
+ *   cart_dir @ R (the convention of cartnet_rotate_rows / cartnet_collate); row_ptr [B+1] int64 over ONE replica's M rows,
+ *   as for cartnet_adp_eval (empty crystals are legal).
+ * Per row, in fp64 from the fp32 inputs, k ascending, a fixed association order, every result stored as fp32 with one
+ * rounding:
+ *   U_k         = R P_k R^T                  (member k in the stored frame; no symmetrisation, R used as given)
+ *   mean [M,9]  = (1/K) sum_k U_k
+ *   spread [M]  = the largest |U_k - mean| over the members and the nine components, against the fp64 mean
+ * K = 1 with the identity returns pred's values and spread 0.
+ * Per crystal (one wave each, rows in order, from the fp32 spread as stored):
+ *   crystal_spread [B,2] fp64 (or NULL) = (sum of spread over the crystal's rows, its maximum); without rows (0, 0).
+ * M == 0 or B == 0: returns 0 without a launch and writes nothing.  No output may alias pred.  No atomics: two runs give
+ * the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_frame_mean(const float* pred, const float* rot, int32_t K, const int64_t* row_ptr, int32_t B, int64_t M,
+                           float* mean, float* spread, double* crystal_spread, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Training loss (reference: train/metrics.py:15-28, called from train/train.py:173-178): L1Loss and MSELoss with mean
  * reduction over the n = M*9 (or Bg) elements of pred / truth, both from one pair of small launches (slices, then
  * their sum), and their gradient from one more:

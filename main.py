@@ -16,7 +16,9 @@ resident shards in the reference's order.  ``--eval_batch N`` runs the ADP test 
 rotations and pickle entries).  ``--predict`` applies a checkpoint to the crystals of ONE shard file, labeled or not
 (``--predict_input``), and writes their ADPs in CIF convention (cartnet_amd/predict.py); the input may also be a CIF
 file or a directory of them, whose asymmetric units are expanded on the GPU (cartnet_amd/symmetry.py) and get one
-site-averaged ADP per atom back.  There is no CPU path: the model runs on an AMD GPU only.
+site-averaged ADP per atom back.  ``--rotations K`` makes ``--predict`` and ``--inference`` predict every crystal in K
+frames (the stored one and K - 1 random rotations), bring the predictions back and report their mean, with the largest
+deviation of a frame from it per atom.  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -114,6 +116,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--predict from CIF files: the temperature in Kelvin of a crystal whose file gives none")
     p.add_argument("--predict_output", type=str, default="./predictions.pkl")
     p.add_argument("--predict_cif_dir", type=str, default=None, help="--predict: also write one CIF per crystal here (a shard's crystals in P1, a CIF's in its own setting)")
+    p.add_argument("--rotations", type=int, default=1,
+                   help="--predict / --inference: predict every crystal in K frames (the stored one and K - 1 random "
+                        "rotations drawn from --seed), bring the predictions back to the stored frame and report their "
+                        "mean, with the largest deviation of a frame from it per atom (rot_spread).  One forward then "
+                        "holds --eval_batch * K crystals.  1 (the default): the pass as it always was.  --montecarlo and "
+                        "training ignore it")
     return p
 
 
@@ -140,6 +148,9 @@ def fill_cfg(args) -> None:
     if args.eval_batch < 1:
         raise ValueError("--eval_batch must be at least 1")
     cfg.eval_batch = args.eval_batch
+    if args.rotations < 1:
+        raise ValueError("--rotations must be at least 1")
+    cfg.rotations = args.rotations
     cfg.gemm_precision = args.gemm_precision
     cfg.bn_group_size = 0
     cfg.half_storage = bool(args.bf16_storage) and cfg.model == "CartNet" and args.gemm_precision == 2
@@ -339,34 +350,53 @@ def _batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> 
         out[k] += split_rows(t, rows)
 
 
-def inference_batched(model, loader, device, output_path: str) -> dict:
+def inference_batched(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0) -> dict:
     """``inference`` at any batch size (``--eval_batch N``): one forward and one ``adp_eval`` per batch; the pickle keeps
-    the layout of batch size 1, one list entry per crystal, and the result keys are the same."""
+    the layout of batch size 1, one list entry per crystal, and the result keys are the same.  ``rotations`` = K > 1: the
+    prediction that is evaluated against the truth is the mean over K frames (cartnet_amd.predict: ``frames``,
+    ``replicate``, one forward of ``N * K`` crystals, ``metrics.frame_mean``; one generator seeded with ``seed`` for the
+    whole pass); the pickle then also has ``rot_spread`` per crystal, the result ``rotations`` and ``rot_spread_max``."""
     import pickle
-    from cartnet_amd.metrics import adp_eval, target_row_ptr
+    from cartnet_amd.metrics import adp_eval, frame_mean, target_row_ptr
+    from cartnet_amd.predict import frames, replicate
     model.eval()
     out = {"pred": [], "true": [], "temp": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "iou": [], "mae": [],
            "similarity_index": []}
+    gen = None
+    if rotations > 1:
+        out["rot_spread"] = []
+        gen = torch.Generator(device=device).manual_seed(seed)
     with torch.no_grad():
         for batch in loader:
             if batch is None:
                 continue
             batch.to(device)
             row_ptr = target_row_ptr(batch)
-            atoms = batch.x.clone()                                           # forward overwrites x (main.py:40)
-            pred, true = model(batch)
+            if rotations == 1:
+                atoms = batch.x.clone()                                       # forward overwrites x (main.py:40)
+                pred, true = model(batch)
+                extra = {}
+                batch.x = atoms
+            else:                                                             # the forward runs on the replica batch
+                R = frames(int(batch.num_graphs), rotations, gen, device)
+                members, _ = model(replicate(batch, rotations, R))
+                fm = frame_mean(members, R, row_ptr, stats=False)
+                pred, true, extra = fm.mean, batch.y, {"rot_spread": fm.spread}
             res = adp_eval(pred, true, row_ptr, None, volume=False)
-            batch.x = atoms
             _batch_entries(out, batch, row_ptr, {"pred": pred, "true": true, "mae": res.abs_err, "iou": res.iou,
-                                                 "similarity_index": res.similarity_index}, with_pos=True)
+                                                 "similarity_index": res.similarity_index, **extra}, with_pos=True)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
     iou, mae, sim = (torch.cat(out[k]) for k in ("iou", "mae", "similarity_index"))
     with open(output_path, "wb") as f:
         pickle.dump(out, f)
-    return {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
-            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
-            "similarity_index_std": float(sim.std()), "output": output_path}
+    result = {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
+              "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
+              "similarity_index_std": float(sim.std()), "output": output_path}
+    if rotations > 1:
+        spread = torch.cat(out["rot_spread"])
+        result.update(rotations=rotations, rot_spread_max=float(spread.max()) if spread.numel() else 0.0)
+    return result
 
 
 def montecarlo_batch(model, batch, R: torch.Tensor):
@@ -459,7 +489,8 @@ def predict(model, args) -> dict:
     else:
         source = DeviceShard.from_file(args.predict_input, cfg.device)
     shards, (mean, std) = shard_recipe([source])
-    out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym)
+    out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
+                       rotations=cfg.rotations, seed=cfg.seed)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     n = len(out["name"])
@@ -474,6 +505,10 @@ def predict(model, args) -> dict:
            "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
     if rejected is not None:
         res["rejected"] = len(rejected)
+    if cfg.rotations > 1:                             # per row, from the fp64 per-crystal (sum, maximum) of rot_spread
+        rot = torch.stack(out["rot_stats"]) if n else torch.zeros(0, 2, dtype=torch.float64)
+        res.update(rotations=cfg.rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
+                   rot_spread_mean=float(rot[:, 0].sum()) / max(rows, 1))
     return res
 
 
@@ -505,7 +540,10 @@ def main(argv=None) -> dict:
         ck = torch.load(args.checkpoint_path, map_location=cfg.device)
         model.load_state_dict(ck["model_state"])
         batched = cfg.eval_batch > 1                                       # 1: the reference's loop, as it was
-        if args.inference:
+        if args.inference and cfg.rotations > 1:                           # the frame mean is a batched pass at any size
+            res = inference_batched(model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations,
+                                    seed=cfg.seed)
+        elif args.inference:
             res = (inference_batched if batched else inference)(model, loaders[-1], cfg.device, args.inference_output)
         else:
             res = (montecarlo_batched if batched else montecarlo)(model, loaders[-1], cfg.device, args.inference_output,

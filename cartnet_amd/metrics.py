@@ -249,6 +249,107 @@ def frame_mean(pred: torch.Tensor, rot: torch.Tensor, row_ptr: torch.Tensor, sta
     return FrameMean(mean, spread, cs)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Rigid-bond test (csrc/bond_ops.hip): how well the displacement amplitudes of bonded atoms agree along their bond --
+# what a crystallographer checks first on a set of ADPs, and it needs no truth.  The bond rule and the radii: bonds.py.
+
+class BondTest(NamedTuple):
+    """What ``bond_test`` returns, all on the device, per row (= non-hydrogen atom) over its bonds: ``bonds`` [M] int32;
+    ``delta_sum`` [M] fp32, the sum of ``|D|`` with ``D = d^T U_i d - d^T U_j d``; ``delta_max`` [M] fp32, the largest
+    ``|D|`` (0 without bonds); ``worst`` [M] int64, the batch's atom index of the partner with the largest ``|D|`` (-1
+    without bonds); ``over`` [M] int32, the bonds with ``|D| > threshold``; ``ueq_ratio`` [M] fp32, ``tr(U_i)`` over the
+    mean of ``tr(U_j)`` of the partners (NaN without bonds); ``crystal_stats`` [B,4] fp64: per crystal the sum of
+    ``bonds``, the sum of ``delta_sum``, the maximum of ``delta_max`` and the sum of ``over``.  Every bond is seen from both
+    of its ends, so the counts and sums are DIRECTED: a crystal with n bonds has ``crystal_stats[g, 0] == 2 n``."""
+    bonds: torch.Tensor
+    delta_sum: torch.Tensor
+    delta_max: torch.Tensor
+    worst: torch.Tensor
+    over: torch.Tensor
+    ueq_ratio: torch.Tensor
+    crystal_stats: torch.Tensor
+
+
+_radii_cache: dict = {}
+
+
+def covalent_radii(device) -> torch.Tensor:
+    """``bonds.COVALENT_RADII`` as an fp32 tensor on ``device``: uploaded once per device."""
+    from .bonds import COVALENT_RADII
+    key = torch.device(device)
+    if key.type == "cuda" and key.index is None:
+        key = torch.device("cuda", torch.cuda.current_device())
+    if key not in _radii_cache:
+        _radii_cache[key] = torch.tensor(COVALENT_RADII, dtype=torch.float32, device=key)
+    return _radii_cache[key]
+
+
+def _batch_field(batch, *names):
+    for name in names:
+        t = batch.get(name) if isinstance(batch, dict) else getattr(batch, name, None)
+        if t is not None:
+            return t
+    return None
+
+
+def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, threshold: float = 1e-3) -> BondTest:
+    """Hirshfeld's rigid-bond test of the ADPs ``u`` [M,3,3] on the bonds of ``batch``: one call of
+    ``cartnet_adp_bond_test``.  ``batch``: a batch of either loader, or a dict of its arrays -- ``x`` (or ``z``) [N] int64
+    atomic numbers, ``edge_index`` [2,E] int64 sorted by target (every loader's order), ``cart_dist`` [E], ``cart_dir``
+    [E,3] and, if some atoms have no row, ``non_H_mask`` [N] (without it every atom has a row, as ``target_row_ptr``
+    assumes) -- with ``u`` holding one row per atom of the mask, in atom order.  ``row_ptr`` [B+1]: ``target_row_ptr``.
+    An edge ``j -> i`` is a bond by the rule of ``cartnet_amd.bonds`` (``r_i + r_j + tol``, both ends non-hydrogen, no
+    self image); only edges the graph holds are seen.  The two lookups the kernel needs -- an atom's row and its edge
+    segment -- are built here with static-shape device ops; nothing is read back."""
+    if not (u.is_cuda and u.dtype == torch.float32 and u.dim() == 3 and tuple(u.shape[1:]) == (3, 3)):
+        raise ValueError("u must be a CUDA fp32 tensor [M,3,3]")
+    u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    z = _batch_field(batch, "x", "z")
+    if not (torch.is_tensor(z) and z.dtype == torch.int64 and z.dim() == 1 and z.device == dev):
+        raise ValueError("bond_test needs the atomic numbers in batch.x (a forward has overwritten them)")
+    z, N = z.contiguous(), int(z.shape[0])
+    ei, dist, dirs = (_batch_field(batch, k) for k in ("edge_index", "cart_dist", "cart_dir"))
+    if not (torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.shape[0] == 2 and ei.device == dev):
+        raise ValueError("edge_index must be an int64 tensor [2,E] on the data's device")
+    ei, E = ei.contiguous(), int(ei.shape[1])
+    if not (torch.is_tensor(dist) and dist.dtype == torch.float32 and tuple(dist.shape) == (E,) and dist.device == dev
+            and torch.is_tensor(dirs) and dirs.dtype == torch.float32 and tuple(dirs.shape) == (E, 3)
+            and dirs.device == dev):
+        raise ValueError("cart_dist [E] and cart_dir [E,3] must be fp32 tensors on the data's device")
+    dist, dirs = dist.detach().contiguous(), dirs.detach().contiguous()
+    mask = _batch_field(batch, "non_H_mask")
+    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
+        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
+    if mask is None and M != N:
+        raise ValueError(f"u holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    bonds = torch.empty(M, dtype=torch.int32, device=dev)
+    delta_sum = torch.empty(M, dtype=torch.float32, device=dev)
+    delta_max = torch.empty(M, dtype=torch.float32, device=dev)
+    worst = torch.empty(M, dtype=torch.int64, device=dev)
+    over = torch.empty(M, dtype=torch.int32, device=dev)
+    ratio = torch.empty(M, dtype=torch.float32, device=dev)
+    if M == 0 or N == 0:                         # the entry point launches nothing
+        return BondTest(bonds, delta_sum, delta_max, worst, over, ratio,
+                        torch.zeros((B, 4), dtype=torch.float64, device=dev))
+    if mask is None:
+        atom_row = torch.arange(N, dtype=torch.int64, device=dev)
+    else:
+        mask = mask.to(torch.bool)
+        atom_row = torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
+    # the edges are sorted by target: atom i owns the edges between the first target >= i and the first target >= i + 1
+    seg_ptr = torch.searchsorted(ei[1].contiguous(), torch.arange(N + 1, dtype=torch.int64, device=dev))
+    stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        radii = covalent_radii(dev)
+        _l.check(_l.load().cartnet_adp_bond_test(
+            u.data_ptr(), z.data_ptr(), ei.data_ptr(), dist.data_ptr(), dirs.data_ptr(), atom_row.data_ptr(), seg_ptr.data_ptr(), row_ptr.data_ptr(), radii.data_ptr(),
+            int(radii.numel()), float(tol), float(threshold), B, N, M, E, bonds.data_ptr(), delta_sum.data_ptr(),
+            delta_max.data_ptr(), worst.data_ptr(), over.data_ptr(), ratio.data_ptr(), stats.data_ptr(),
+            _l.stream_ptr()), "cartnet_adp_bond_test")
+    return BondTest(bonds, delta_sum, delta_max, worst, over, ratio, stats)
+
+
 def split_rows(t: torch.Tensor, rows) -> list:
     """The per-crystal pieces of a host tensor whose dim 0 runs over the rows of a batch: one transfer per batch, then
     this split by the crystals' row counts (a sequence of ints) gives the reference's one-entry-per-crystal lists.  Every

@@ -6,7 +6,8 @@ transform the reference applied to the dataset's targets, dataset/extract_csd_da
 principal values / axes), the fractional coordinates, ONE device-to-host copy (``metrics.to_host``) and a split by row
 counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.  For crystals that came from CIF files
 (``cartnet_amd.symmetry.expand``) the same copy also brings one site-averaged ADP per atom of the asymmetric unit, and
-``write_cif_symmetric`` writes the crystal in the file's own setting.
+``write_cif_symmetric`` writes the crystal in the file's own setting.  With ``rigid_bond`` the copy also brings Hirshfeld's
+rigid-bond figures of the exported ADPs (``metrics.bond_test``, csrc/bond_ops.hip): a plausibility report that needs no truth.
 """
 from __future__ import annotations
 
@@ -15,12 +16,14 @@ from typing import Dict, List
 
 import torch
 
-from .metrics import (adp_export, check_export_status, edge_row_ptr, frame_mean, rotate_rows, split_rows, target_row_ptr,
-                      to_host)
+from .metrics import (adp_export, bond_test, check_export_status, edge_row_ptr, frame_mean, rotate_rows, split_rows,
+                      target_row_ptr, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
 ROT_KEYS = ("rot_spread", "frames", "rot_stats")                                          # with rotations > 1 only
+BOND_KEYS = ("bond_count", "bond_delta_mean", "bond_delta_max", "bond_worst", "bond_over", "bond_ueq_ratio",
+             "bond_stats")                                                                # with rigid_bond only
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -79,7 +82,19 @@ def replicate(batch, K: int, R: torch.Tensor):
     return out
 
 
-def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0) -> Dict[str, List]:
+def bond_entries(bt, batch) -> dict:
+    """The per-row keys of ``BOND_KEYS`` (and ``bond_stats`` per crystal) from a ``metrics.BondTest`` of ``batch``, on the
+    device: ``bond_delta_mean`` = ``delta_sum / bonds`` (0 without bonds), ``bond_worst`` as an atom index inside its
+    crystal (-1 without bonds).  Static-shape device ops: nothing is read back."""
+    partner = bt.worst.clamp(min=0)
+    first = batch.ptr.to(torch.int64)[batch.batch[partner]]                   # the partner's crystal is the row's own
+    return {"bond_count": bt.bonds, "bond_delta_max": bt.delta_max, "bond_over": bt.over, "bond_ueq_ratio": bt.ueq_ratio,
+            "bond_delta_mean": bt.delta_sum / bt.bonds.clamp(min=1).to(torch.float32),      # delta_sum is 0 without bonds
+            "bond_worst": torch.where(bt.worst >= 0, partner - first, bt.worst), "bond_stats": bt.crystal_stats}
+
+
+def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None
+                 ) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
@@ -94,7 +109,13 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     and averaged (``metrics.frame_mean``), and everything above derives from that mean: ``u_cart`` is the mean.  The result
     then also has, per crystal, ``rot_spread`` [n] (per row the largest deviation of a frame's prediction from the mean),
     ``frames`` [K,3,3] (the rotations used, the identity first) and ``rot_stats`` [2] fp64 (sum and maximum of
-    ``rot_spread``).  ``rotations`` = 1 is the pass as it always was."""
+    ``rot_spread``).  ``rotations`` = 1 is the pass as it always was.  ``rigid_bond`` = ``(tol, threshold)``: one
+    ``metrics.bond_test`` per batch on the ``u_cart`` that is exported (with rotations the frame mean; with CIF input the
+    rows of the expanded cell, before site averaging), travelling in the same copy.  The result then also has, per crystal,
+    ``bond_count`` [n], ``bond_delta_mean`` [n] (mean ``|D|`` over the atom's bonds, 0 without bonds), ``bond_delta_max``
+    [n], ``bond_worst`` [n] (the partner of the worst bond as an atom index inside the crystal, -1 without bonds),
+    ``bond_over`` [n], ``bond_ueq_ratio`` [n] and ``bond_stats`` [4] fp64 (directed bonds, sum of ``|D|``, largest ``|D|``,
+    bonds over the threshold).  ``None`` is the pass as it always was."""
     rotations = int(rotations)
     if rotations < 1:
         raise ValueError("rotations must be at least 1")
@@ -105,7 +126,7 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
         raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
     model.eval()
     out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
-                            + (ROT_KEYS if rotations > 1 else ())}
+                            + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     with torch.no_grad():
         for batch in loader:
@@ -132,6 +153,9 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
             dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
                        stats=ex.crystal_stats, _status=ex.status)
+            if rigid_bond is not None:
+                batch.x = z                                                   # the graph and the atomic numbers again
+                dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
             if sym is not None:
                 from .symmetry import site_average
                 dev["_u_asym"], dev["_spread"] = site_average(pred, row_ptr, batch._sel, sym)
@@ -151,7 +175,8 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             rows, atoms = (rp[1:] - rp[:-1]).tolist(), (ap[1:] - ap[:-1]).tolist()
             out["name"] += names
             out["temp"] += host.pop("temp").tolist() if "temp" in host else [float("nan")] * B
-            for k in ("cell", "stats") + (("frames", "rot_stats") if rotations > 1 else ()):
+            for k in (("cell", "stats") + (("frames", "rot_stats") if rotations > 1 else ())
+                      + (("bond_stats",) if rigid_bond is not None else ())):
                 out[k] += [t.clone() for t in host.pop(k).unbind(0)]
             for k in ("frac", "z"):
                 out[k] += split_rows(host.pop(k), atoms)
@@ -165,7 +190,7 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
 def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
-    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS if key in result}
+    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS if key in result}
 
 
 def cell_parameters(cell) -> tuple:

@@ -442,6 +442,40 @@ int cartnet_adp_frame_mean(const float* pred, const float* rot, int32_t K, const
                            float* mean, float* spread, double* crystal_spread, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Hirshfeld's rigid-bond test on the ADPs of one batch: a plausibility figure that needs no truth.  The reference can
+ * judge a prediction only against targets (main.py:47-49: IoU, MAE and similarity index per atom); for two covalently
+ * bonded atoms the mean-square displacement amplitudes along the bond are nearly equal, whatever the truth is.
+ *   u [M,9] fp32: one row-major 3x3 per row (row m = the m-th non-hydrogen atom of the batch); z [N] int64 atomic numbers;
+ *   edge_index [2,E] int64 = (source, target) in the batch's atom indices, sorted by target; cart_dist [E], cart_dir [E,3]
+ *   fp32 (the radius graph's: periodic images are solved; cart_dir is used as stored, not renormalised);
+ *   atom_row [N] int64: the row of atom i, or -1 if it has none (a hydrogen); every row is named exactly once;
+ *   seg_ptr [N+1] int64: atom i is the target of the edges [seg_ptr[i], seg_ptr[i+1]);
+ *   row_ptr [B+1] int64 as for cartnet_adp_eval; radii [n_radii] fp32 covalent radii indexed by Z (index 0 unused).
+ * A directed edge e = (j -> i) is a bond when i != j, 1 < z_i, z_j < n_radii, both ends have a row, and
+ *   cart_dist[e] <= (radii[z_i] + radii[z_j]) + tol         in fp32, in exactly that order.
+ * Only edges the graph holds are considered.  Per bond, in fp64 from the fp32 inputs:
+ *   D = d^T U_i d - d^T U_j d, d = cart_dir[e]               (only the symmetric part of U enters)
+ * Per row m = atom i, over its bonds in edge order, floats stored with one rounding:
+ *   bonds [M] int32       the number of bonds
+ *   delta_sum [M] fp32    sum of |D|, summed in fp64 in edge order
+ *   delta_max [M] fp32    the largest |D|; 0 without bonds
+ *   worst [M] int64       the batch's atom index of the partner with the largest |D| (a tie: the lowest edge); -1 without
+ *   over [M] int32        the bonds with |D| > threshold, compared in fp64
+ *   ueq_ratio [M] fp32    tr(U_i) / mean of tr(U_j) over the partners; NaN without bonds
+ * Per crystal (one wave each, rows in order, from the values as stored):
+ *   crystal_stats [B,4] fp64 (or NULL) = (sum of bonds, sum of delta_sum, maximum of delta_max, sum of over); without rows
+ *   (0, 0, 0, 0).  Every bond is seen from both of its ends: these are directed counts.
+ * A row whose atom has no edge, or whose Z is 1, 0 or beyond the table, gets the values "without bonds".  E == 0 needs no
+ * edge arrays.  M == 0, N == 0 or B == 0: returns 0 without a launch and writes nothing.  No atomics: two runs give the
+ * same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_bond_test(const float* u, const int64_t* z, const int64_t* edge_index, const float* cart_dist,
+                          const float* cart_dir, const int64_t* atom_row, const int64_t* seg_ptr, const int64_t* row_ptr,
+                          const float* radii, int32_t n_radii, float tol, double threshold, int32_t B, int64_t N, int64_t M,
+                          int64_t E, int32_t* bonds, float* delta_sum, float* delta_max, int64_t* worst, int32_t* over,
+                          float* ueq_ratio, double* crystal_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Training loss (reference: train/metrics.py:15-28, called from train/train.py:173-178): L1Loss and MSELoss with mean
  * reduction over the n = M*9 (or Bg) elements of pred / truth, both from one pair of small launches (slices, then
  * their sum), and their gradient from one more:

@@ -18,7 +18,9 @@ rotations and pickle entries).  ``--predict`` applies a checkpoint to the crysta
 file or a directory of them, whose asymmetric units are expanded on the GPU (cartnet_amd/symmetry.py) and get one
 site-averaged ADP per atom back.  ``--rotations K`` makes ``--predict`` and ``--inference`` predict every crystal in K
 frames (the stored one and K - 1 random rotations), bring the predictions back and report their mean, with the largest
-deviation of a frame from it per atom.  There is no CPU path: the model runs on an AMD GPU only.
+deviation of a frame from it per atom.  ``--rigid_bond`` adds Hirshfeld's rigid-bond test to ``--predict`` and
+``--inference``: a plausibility figure per bonded pair of atoms that needs no truth (cartnet_amd/bonds.py,
+``metrics.bond_test``).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ from typing import Optional, Tuple
 import torch
 
 from cartnet_amd import distributed as cdist
+from cartnet_amd.bonds import BOND_TOLERANCE, RIGID_BOND_THRESHOLD
 from cartnet_amd.config import cfg, set_cfg
 from cartnet_amd.data import DataLoader, optimize_cell, remove_hydrogens
 from cartnet_amd.master import create_model
@@ -122,6 +125,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "mean, with the largest deviation of a frame from it per atom (rot_spread).  One forward then "
                         "holds --eval_batch * K crystals.  1 (the default): the pass as it always was.  --montecarlo and "
                         "training ignore it")
+    p.add_argument("--rigid_bond", action="store_true",
+                   help="--predict / --inference: Hirshfeld's rigid-bond test on the ADPs (and, with --inference, on the "
+                        "truth as the baseline): per bonded pair of non-hydrogen atoms the difference of the mean-square "
+                        "displacement amplitudes along the bond, which well-refined structures keep below about 0.001 "
+                        "A^2.  Bonds are the edges of the radius graph within r_i + r_j + --bond_tolerance.  --montecarlo "
+                        "and training ignore it")
+    p.add_argument("--bond_tolerance", type=float, default=BOND_TOLERANCE,
+                   help="--rigid_bond: an edge is a bond up to the sum of the covalent radii plus this many Angstrom")
+    p.add_argument("--rigid_bond_threshold", type=float, default=RIGID_BOND_THRESHOLD,
+                   help="--rigid_bond: bonds whose amplitudes differ by more than this (A^2) are counted as over")
     return p
 
 
@@ -350,14 +363,19 @@ def _batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> 
         out[k] += split_rows(t, rows)
 
 
-def inference_batched(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0) -> dict:
+def inference_batched(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0, rigid_bond=None
+                      ) -> dict:
     """``inference`` at any batch size (``--eval_batch N``): one forward and one ``adp_eval`` per batch; the pickle keeps
     the layout of batch size 1, one list entry per crystal, and the result keys are the same.  ``rotations`` = K > 1: the
     prediction that is evaluated against the truth is the mean over K frames (cartnet_amd.predict: ``frames``,
     ``replicate``, one forward of ``N * K`` crystals, ``metrics.frame_mean``; one generator seeded with ``seed`` for the
-    whole pass); the pickle then also has ``rot_spread`` per crystal, the result ``rotations`` and ``rot_spread_max``."""
+    whole pass); the pickle then also has ``rot_spread`` per crystal, the result ``rotations`` and ``rot_spread_max``.
+    ``rigid_bond`` = ``(tol, threshold)``: ``metrics.bond_test`` on the prediction and on the truth of every batch; the
+    pickle then also has ``bond_delta_max`` and ``bond_delta_max_true`` per crystal (one value per row), the result
+    ``rigid_bond_mean`` and ``rigid_bond_mean_true`` (the mean ``|D|`` over the directed bonds of the pass, 0 without
+    bonds): the truth's figure is the baseline the prediction's is to be compared with."""
     import pickle
-    from cartnet_amd.metrics import adp_eval, frame_mean, target_row_ptr
+    from cartnet_amd.metrics import adp_eval, bond_test, frame_mean, target_row_ptr
     from cartnet_amd.predict import frames, replicate
     model.eval()
     out = {"pred": [], "true": [], "temp": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "iou": [], "mae": [],
@@ -366,6 +384,10 @@ def inference_batched(model, loader, device, output_path: str, rotations: int = 
     if rotations > 1:
         out["rot_spread"] = []
         gen = torch.Generator(device=device).manual_seed(seed)
+    bond_sums = None                                      # [2,4] fp64 on the device: crystal_stats summed, prediction / truth
+    if rigid_bond is not None:
+        out["bond_delta_max"], out["bond_delta_max_true"] = [], []
+        bond_sums = torch.zeros((2, 4), dtype=torch.float64, device=device)
     with torch.no_grad():
         for batch in loader:
             if batch is None:
@@ -382,6 +404,11 @@ def inference_batched(model, loader, device, output_path: str, rotations: int = 
                 members, _ = model(replicate(batch, rotations, R))
                 fm = frame_mean(members, R, row_ptr, stats=False)
                 pred, true, extra = fm.mean, batch.y, {"rot_spread": fm.spread}
+            if rigid_bond is not None:                                        # batch.x holds the atomic numbers again
+                for k, (name, u) in enumerate((("bond_delta_max", pred), ("bond_delta_max_true", true))):
+                    bt = bond_test(u, batch, row_ptr, *rigid_bond)
+                    extra[name] = bt.delta_max
+                    bond_sums[k] += bt.crystal_stats.sum(0)
             res = adp_eval(pred, true, row_ptr, None, volume=False)
             _batch_entries(out, batch, row_ptr, {"pred": pred, "true": true, "mae": res.abs_err, "iou": res.iou,
                                                  "similarity_index": res.similarity_index, **extra}, with_pos=True)
@@ -396,6 +423,9 @@ def inference_batched(model, loader, device, output_path: str, rotations: int = 
     if rotations > 1:
         spread = torch.cat(out["rot_spread"])
         result.update(rotations=rotations, rot_spread_max=float(spread.max()) if spread.numel() else 0.0)
+    if rigid_bond is not None:
+        (n_p, s_p, _, _), (n_t, s_t, _, _) = bond_sums.tolist()
+        result.update(rigid_bond_mean=s_p / n_p if n_p else 0.0, rigid_bond_mean_true=s_t / n_t if n_t else 0.0)
     return result
 
 
@@ -489,8 +519,9 @@ def predict(model, args) -> dict:
     else:
         source = DeviceShard.from_file(args.predict_input, cfg.device)
     shards, (mean, std) = shard_recipe([source])
+    bond = {"rigid_bond": (args.bond_tolerance, args.rigid_bond_threshold)} if args.rigid_bond else {}
     out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
-                       rotations=cfg.rotations, seed=cfg.seed)
+                       rotations=cfg.rotations, seed=cfg.seed, **bond)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     n = len(out["name"])
@@ -509,6 +540,11 @@ def predict(model, args) -> dict:
         rot = torch.stack(out["rot_stats"]) if n else torch.zeros(0, 2, dtype=torch.float64)
         res.update(rotations=cfg.rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
                    rot_spread_mean=float(rot[:, 0].sum()) / max(rows, 1))
+    if args.rigid_bond:                               # over the directed bonds of the pass, from the fp64 per-crystal stats
+        bs = torch.stack(out["bond_stats"]) if n else torch.zeros(0, 4, dtype=torch.float64)
+        count = int(bs[:, 0].sum())
+        res.update(bonds=count, rigid_bond_mean=float(bs[:, 1].sum()) / count if count else 0.0,
+                   rigid_bond_max=float(bs[:, 2].max()) if n else 0.0, rigid_bond_over=int(bs[:, 3].sum()))
     return res
 
 
@@ -540,7 +576,10 @@ def main(argv=None) -> dict:
         ck = torch.load(args.checkpoint_path, map_location=cfg.device)
         model.load_state_dict(ck["model_state"])
         batched = cfg.eval_batch > 1                                       # 1: the reference's loop, as it was
-        if args.inference and cfg.rotations > 1:                           # the frame mean is a batched pass at any size
+        if args.inference and args.rigid_bond:                             # the rigid-bond test is a batched pass too
+            res = inference_batched(model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations,
+                                    seed=cfg.seed, rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold))
+        elif args.inference and cfg.rotations > 1:                         # the frame mean is a batched pass at any size
             res = inference_batched(model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations,
                                     seed=cfg.seed)
         elif args.inference:

@@ -292,6 +292,45 @@ def _batch_field(batch, *names):
     return None
 
 
+def _check_graph(batch, dev, M: int, who: str, rows: str, need_dir: bool):
+    """The arrays ``bond_test`` and ``riding_h`` read from a batch (or a dict of its arrays), checked: ``(z, N, edge_index,
+    E, cart_dist, cart_dir or None, non_H_mask or None)``."""
+    z = _batch_field(batch, "x", "z")
+    if not (torch.is_tensor(z) and z.dtype == torch.int64 and z.dim() == 1 and z.device == dev):
+        raise ValueError(f"{who} needs the atomic numbers in batch.x (a forward has overwritten them)")
+    z, N = z.contiguous(), int(z.shape[0])
+    ei, dist = (_batch_field(batch, k) for k in ("edge_index", "cart_dist"))
+    dirs = _batch_field(batch, "cart_dir") if need_dir else None
+    if not (torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.shape[0] == 2 and ei.device == dev):
+        raise ValueError("edge_index must be an int64 tensor [2,E] on the data's device")
+    ei, E = ei.contiguous(), int(ei.shape[1])
+    if not (torch.is_tensor(dist) and dist.dtype == torch.float32 and tuple(dist.shape) == (E,) and dist.device == dev
+            and (not need_dir or (torch.is_tensor(dirs) and dirs.dtype == torch.float32 and tuple(dirs.shape) == (E, 3)
+                                  and dirs.device == dev))):
+        raise ValueError("cart_dist [E] and cart_dir [E,3] must be fp32 tensors on the data's device" if need_dir else
+                         "cart_dist [E] must be an fp32 tensor on the data's device")
+    dist, dirs = dist.detach().contiguous(), dirs.detach().contiguous() if need_dir else None
+    mask = _batch_field(batch, "non_H_mask")
+    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
+        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
+    if mask is None and M != N:
+        raise ValueError(f"{rows} holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    return z, N, ei, E, dist, dirs, mask
+
+
+def _atom_lookups(mask, ei: torch.Tensor, N: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(atom_row [N], seg_ptr [N+1])`` int64: an atom's row (-1 outside the mask; without a mask every atom has one) and
+    its edge segment, with static-shape device ops."""
+    if mask is None:
+        atom_row = torch.arange(N, dtype=torch.int64, device=dev)
+    else:
+        mask = mask.to(torch.bool)
+        atom_row = torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
+    # the edges are sorted by target: atom i owns the edges between the first target >= i and the first target >= i + 1
+    seg_ptr = torch.searchsorted(ei[1].contiguous(), torch.arange(N + 1, dtype=torch.int64, device=dev))
+    return atom_row, seg_ptr
+
+
 def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, threshold: float = 1e-3) -> BondTest:
     """Hirshfeld's rigid-bond test of the ADPs ``u`` [M,3,3] on the bonds of ``batch``: one call of
     ``cartnet_adp_bond_test``.  ``batch``: a batch of either loader, or a dict of its arrays -- ``x`` (or ``z``) [N] int64
@@ -305,24 +344,7 @@ def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, t
         raise ValueError("u must be a CUDA fp32 tensor [M,3,3]")
     u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
-    z = _batch_field(batch, "x", "z")
-    if not (torch.is_tensor(z) and z.dtype == torch.int64 and z.dim() == 1 and z.device == dev):
-        raise ValueError("bond_test needs the atomic numbers in batch.x (a forward has overwritten them)")
-    z, N = z.contiguous(), int(z.shape[0])
-    ei, dist, dirs = (_batch_field(batch, k) for k in ("edge_index", "cart_dist", "cart_dir"))
-    if not (torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.shape[0] == 2 and ei.device == dev):
-        raise ValueError("edge_index must be an int64 tensor [2,E] on the data's device")
-    ei, E = ei.contiguous(), int(ei.shape[1])
-    if not (torch.is_tensor(dist) and dist.dtype == torch.float32 and tuple(dist.shape) == (E,) and dist.device == dev
-            and torch.is_tensor(dirs) and dirs.dtype == torch.float32 and tuple(dirs.shape) == (E, 3)
-            and dirs.device == dev):
-        raise ValueError("cart_dist [E] and cart_dir [E,3] must be fp32 tensors on the data's device")
-    dist, dirs = dist.detach().contiguous(), dirs.detach().contiguous()
-    mask = _batch_field(batch, "non_H_mask")
-    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
-        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
-    if mask is None and M != N:
-        raise ValueError(f"u holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "bond_test", "u", True)
     bonds = torch.empty(M, dtype=torch.int32, device=dev)
     delta_sum = torch.empty(M, dtype=torch.float32, device=dev)
     delta_max = torch.empty(M, dtype=torch.float32, device=dev)
@@ -332,13 +354,7 @@ def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, t
     if M == 0 or N == 0:                         # the entry point launches nothing
         return BondTest(bonds, delta_sum, delta_max, worst, over, ratio,
                         torch.zeros((B, 4), dtype=torch.float64, device=dev))
-    if mask is None:
-        atom_row = torch.arange(N, dtype=torch.int64, device=dev)
-    else:
-        mask = mask.to(torch.bool)
-        atom_row = torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
-    # the edges are sorted by target: atom i owns the edges between the first target >= i and the first target >= i + 1
-    seg_ptr = torch.searchsorted(ei[1].contiguous(), torch.arange(N + 1, dtype=torch.int64, device=dev))
+    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
     stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         radii = covalent_radii(dev)
@@ -348,6 +364,59 @@ def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, t
             delta_max.data_ptr(), worst.data_ptr(), over.data_ptr(), ratio.data_ptr(), stats.data_ptr(),
             _l.stream_ptr()), "cartnet_adp_bond_test")
     return BondTest(bonds, delta_sum, delta_max, worst, over, ratio, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Riding hydrogens (csrc/riding_ops.hip): the model predicts no ADP for a hydrogen; the riding model gives it an isotropic
+# U that is a fixed multiple of its parent's U_eq.  The rule: bonds.py.
+
+class RidingH(NamedTuple):
+    """What ``riding_h`` returns, all on the device, per atom of the batch: ``parent`` [N] int64, the batch's atom index of
+    the atom a hydrogen rides on (-1 for an orphan and for every non-hydrogen atom); ``count`` [N] int32, the hydrogens
+    that ride on a non-hydrogen atom (0 for a hydrogen); ``mult`` [N] fp32, a hydrogen's multiplier (0 for an orphan and for
+    every non-hydrogen atom); ``u_iso`` [N] fp32, ``mult * u_eq[parent's row]`` for a hydrogen (NaN for an orphan) and the
+    atom's own ``u_eq`` for a non-hydrogen atom (NaN without a row); ``crystal_stats`` [B,4] fp64: per crystal its
+    hydrogens, its orphans, the sum of the finite ``u_iso`` of its hydrogens and the hydrogens whose parent's ``u_eq`` is
+    not positive."""
+    parent: torch.Tensor
+    count: torch.Tensor
+    mult: torch.Tensor
+    u_iso: torch.Tensor
+    crystal_stats: torch.Tensor
+
+
+def riding_h(u_eq: torch.Tensor, batch, tol: float = 0.4, f: float = 1.2, f_rot: float = 1.5) -> RidingH:
+    """An isotropic U for every hydrogen of ``batch`` from ``u_eq`` [M] (``AdpExport.u_eq``: one row per atom of the mask,
+    in atom order): one call of ``cartnet_adp_riding_h``.  ``batch``: as for ``bond_test`` -- ``x`` (or ``z``),
+    ``edge_index`` sorted by target, ``cart_dist``, ``non_H_mask`` if some atoms have no row -- and ``ptr`` [B+1], the
+    crystals' atom offsets.  A hydrogen's parent is the nearest non-hydrogen atom with a row within
+    ``r_H + r_parent + tol`` among the edges the graph holds; the multiplier is ``f_rot`` on oxygen and on a carbon that
+    carries three or more hydrogens, ``f`` otherwise (the rule: ``cartnet_amd.bonds``).  The two lookups are built as in
+    ``bond_test``; nothing is read back."""
+    if not (u_eq.is_cuda and u_eq.dtype == torch.float32 and u_eq.dim() == 1):
+        raise ValueError("u_eq must be a CUDA fp32 tensor [M]")
+    u_eq, M, dev = u_eq.detach().contiguous(), int(u_eq.shape[0]), u_eq.device
+    ptr = _batch_field(batch, "ptr")
+    if not torch.is_tensor(ptr):
+        raise ValueError("riding_h needs the crystals' atom offsets in batch.ptr")
+    atom_ptr, B = _check_row_ptr(ptr.to(torch.int64), dev)
+    z, N, ei, E, dist, _, mask = _check_graph(batch, dev, M, "riding_h", "u_eq", False)
+    parent = torch.empty(N, dtype=torch.int64, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    mult = torch.empty(N, dtype=torch.float32, device=dev)
+    u_iso = torch.empty(N, dtype=torch.float32, device=dev)
+    if N == 0:                                   # the entry point launches nothing
+        return RidingH(parent, count, mult, u_iso, torch.zeros((B, 4), dtype=torch.float64, device=dev))
+    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
+    stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        radii = covalent_radii(dev)
+        _l.check(_l.load().cartnet_adp_riding_h(
+            _l.ptr(u_eq) if M else None, z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None,
+            atom_row.data_ptr(), seg_ptr.data_ptr(), atom_ptr.data_ptr(), radii.data_ptr(), int(radii.numel()), float(tol),
+            float(f), float(f_rot), B, N, M, E, parent.data_ptr(), count.data_ptr(), mult.data_ptr(), u_iso.data_ptr(),
+            stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_riding_h")
+    return RidingH(parent, count, mult, u_iso, stats)
 
 
 def split_rows(t: torch.Tensor, rows) -> list:

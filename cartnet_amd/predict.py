@@ -8,6 +8,8 @@ counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.
 (``cartnet_amd.symmetry.expand``) the same copy also brings one site-averaged ADP per atom of the asymmetric unit, and
 ``write_cif_symmetric`` writes the crystal in the file's own setting.  With ``rigid_bond`` the copy also brings Hirshfeld's
 rigid-bond figures of the exported ADPs (``metrics.bond_test``, csrc/bond_ops.hip): a plausibility report that needs no truth.
+With ``riding_h`` it brings an isotropic U for every hydrogen, a multiple of its parent's exported U_eq
+(``metrics.riding_h``, csrc/riding_ops.hip), and both writers fill ``_atom_site_U_iso_or_equiv`` for every atom.
 """
 from __future__ import annotations
 
@@ -16,14 +18,16 @@ from typing import Dict, List
 
 import torch
 
-from .metrics import (adp_export, bond_test, check_export_status, edge_row_ptr, frame_mean, rotate_rows, split_rows,
-                      target_row_ptr, to_host)
+from .metrics import (adp_export, bond_test, check_export_status, edge_row_ptr, frame_mean, riding_h as riding_h_call,
+                      rotate_rows, split_rows, target_row_ptr, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
 ROT_KEYS = ("rot_spread", "frames", "rot_stats")                                          # with rotations > 1 only
 BOND_KEYS = ("bond_count", "bond_delta_mean", "bond_delta_max", "bond_worst", "bond_over", "bond_ueq_ratio",
              "bond_stats")                                                                # with rigid_bond only
+H_KEYS = ("u_iso", "h_parent", "h_count", "h_mult", "h_stats")                            # with riding_h only
+H_SYM_KEYS = ("u_iso_asym", "h_parent_asym")                                              # ... and a CifSymmetry
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -93,7 +97,55 @@ def bond_entries(bt, batch) -> dict:
             "bond_worst": torch.where(bt.worst >= 0, partner - first, bt.worst), "bond_stats": bt.crystal_stats}
 
 
-def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None
+def riding_entries(rh, batch) -> dict:
+    """The per-atom keys of ``H_KEYS`` (and ``h_stats`` per crystal) from a ``metrics.RidingH`` of ``batch``, on the device:
+    ``h_parent`` as an atom index inside its crystal (-1 where there is none), converted as ``bond_entries`` converts
+    ``bond_worst``.  Static-shape device ops: nothing is read back."""
+    partner = rh.parent.clamp(min=0)
+    first = batch.ptr.to(torch.int64)[batch.batch[partner]]                   # the parent's crystal is the hydrogen's own
+    return {"u_iso": rh.u_iso, "h_parent": torch.where(rh.parent >= 0, partner - first, rh.parent), "h_count": rh.count,
+            "h_mult": rh.mult, "h_stats": rh.crystal_stats}
+
+
+def u_eq_of_cif(u_cif: torch.Tensor, cell: torch.Tensor) -> torch.Tensor:
+    """[n] fp64: the equivalent isotropic U of ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12 on the unit reciprocal axes) in
+    ``cell`` ([3,3], or [n,3,3] with one cell per row; rows = lattice vectors):
+    ``(1/3) sum_ij U_ij |a*_i| |a*_j| (a_i . a_j)``, the trace of the Cartesian tensor ``sum_ij U_ij |a*_i| |a*_j| a_i a_j^T``
+    over three (the inverse of ``adp_export``'s transform; in an orthogonal cell ``|a*_i| = 1 / |a_i|`` and it is the mean
+    of the diagonal).  Plain torch, fp64."""
+    u, c = u_cif.to(torch.float64), cell.to(torch.float64)
+    if c.dim() == 2:
+        c = c.unsqueeze(0).expand(u.shape[0], 3, 3)
+    n = torch.linalg.norm(_inverse_cells(c), dim=1)                           # |a*_i|: the columns of inv(cell)
+    g = (c @ c.transpose(1, 2)) * (n.unsqueeze(2) * n.unsqueeze(1))           # (a_i . a_j) |a*_i| |a*_j|
+    return ((u[:, 0] * g[:, 0, 0] + u[:, 1] * g[:, 1, 1] + u[:, 2] * g[:, 2, 2])
+            + 2.0 * (u[:, 3] * g[:, 1, 2] + u[:, 4] * g[:, 0, 2] + u[:, 5] * g[:, 0, 1])) / 3.0
+
+
+def riding_asym(name: str, asym_z, z, h_parent, h_mult, parent_asym, u_eq_sites):
+    """The riding hydrogens of one crystal from a CIF, per atom of its asymmetric unit, on the host:
+    ``(u_iso_asym [a] fp32, h_parent_asym [a] int64)``.  Candidate ``s * n + a`` with operator 0 the identity
+    (csrc/symmetry_ops.hip) makes the first ``a`` atoms of the expanded crystal the asymmetric unit in file order; that is
+    checked against ``z`` here and a mismatch raises ``ValueError`` naming the crystal.  The asymmetric hydrogen ``k`` takes
+    the parent and the multiplier of expanded atom ``k``; ``parent_asym`` [N] names the asymmetric atom every expanded
+    atom's parent is an image of (-1 without a parent), and ``u_eq_sites`` [sites] fp64 is the U_eq of the site-averaged
+    tensors, so ``u_iso_asym = mult * U_eq(site of the parent)`` agrees with the anisotropic rows of the same file.
+    Non-hydrogen atoms get the U_eq of their own site."""
+    asym_z = torch.as_tensor(asym_z).to(torch.int64)
+    n = int(asym_z.shape[0])
+    if int(z.shape[0]) < n or not torch.equal(z[:n].to(torch.int64), asym_z):
+        raise ValueError(f"crystal {name}: the first {n} atoms of the expanded cell are not its asymmetric unit in file order")
+    heavy = asym_z != 1
+    site = torch.cumsum(heavy, 0) - 1                                         # the site of a non-hydrogen asymmetric atom
+    pa = torch.where(heavy, torch.full_like(asym_z, -1), parent_asym[:n].to(torch.int64))
+    pa = torch.where((h_parent[:n] >= 0) & (pa >= 0) & (pa < n), pa, torch.full_like(pa, -1))
+    ueq = torch.cat([u_eq_sites.to(torch.float64), torch.full((1,), float("nan"), dtype=torch.float64)])
+    own = ueq[torch.where(heavy, site, torch.full_like(site, -1))]
+    of_parent = h_mult[:n].to(torch.float64) * ueq[torch.where(pa >= 0, site[pa.clamp(min=0)], torch.full_like(pa, -1))]
+    return torch.where(heavy, own, of_parent).to(torch.float32), pa
+
+
+def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None
                  ) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
@@ -115,7 +167,14 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     ``bond_count`` [n], ``bond_delta_mean`` [n] (mean ``|D|`` over the atom's bonds, 0 without bonds), ``bond_delta_max``
     [n], ``bond_worst`` [n] (the partner of the worst bond as an atom index inside the crystal, -1 without bonds),
     ``bond_over`` [n], ``bond_ueq_ratio`` [n] and ``bond_stats`` [4] fp64 (directed bonds, sum of ``|D|``, largest ``|D|``,
-    bonds over the threshold).  ``None`` is the pass as it always was."""
+    bonds over the threshold).  ``None`` is the pass as it always was.  ``riding_h`` = ``(tol, f, f_rot)``: one
+    ``metrics.riding_h`` per batch on the ``u_eq`` that is exported (with rotations the frame mean's), travelling in the same
+    copy.  The result then also has, per crystal, ``u_iso`` [N] (every atom: a hydrogen's ``mult * u_eq[parent]``, NaN for
+    an orphan; a non-hydrogen atom's own ``u_eq``), ``h_parent`` [N] (an atom index inside the crystal, -1 where there is
+    none), ``h_count`` [N] (hydrogens riding on a non-hydrogen atom), ``h_mult`` [N] and ``h_stats`` [4] fp64 (hydrogens,
+    orphans, sum of the finite hydrogen ``u_iso``, hydrogens with a non-positive parent ``u_eq``); with ``sym`` also
+    ``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``).  ``None`` is the pass
+    as it always was."""
     rotations = int(rotations)
     if rotations < 1:
         raise ValueError("rotations must be at least 1")
@@ -126,7 +185,9 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
         raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
     model.eval()
     out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
-                            + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())}
+                            + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())
+                            + (H_KEYS if riding_h is not None else ())
+                            + (H_SYM_KEYS if riding_h is not None and sym is not None else ())}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     with torch.no_grad():
         for batch in loader:
@@ -156,9 +217,28 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             if rigid_bond is not None:
                 batch.x = z                                                   # the graph and the atomic numbers again
                 dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
+            if riding_h is not None:
+                batch.x = z
+                rh = riding_h_call(ex.u_eq, batch, *riding_h)
+                dev.update(riding_entries(rh, batch))
             if sym is not None:
                 from .symmetry import site_average
                 dev["_u_asym"], dev["_spread"] = site_average(pred, row_ptr, batch._sel, sym)
+                if riding_h is not None:
+                    # the asymmetric atom every parent is an image of: its row in the batch, then in the expansion
+                    counts = torch.from_numpy(sym.site_count[batch._sel]).to(device)
+                    first = torch.from_numpy(sym.y_ptr[batch._sel]).to(device)
+                    crystal = torch.repeat_interleave(torch.arange(B, device=device), counts,
+                                                      output_size=int(dev["_u_asym"].shape[0]))
+                    dev["_ueq_asym"] = u_eq_of_cif(dev["_u_asym"], sym.cell[sel].view(B, 3, 3)[crystal])
+                    if int(sym.row_asym.shape[0]):
+                        p = rh.parent.clamp(min=0)
+                        row = (torch.cumsum(batch.non_H_mask.to(torch.int64), 0) - 1)[p]
+                        g = batch.batch[p]
+                        grow = (first[g] + (row - row_ptr[g])).clamp(0, int(sym.row_asym.shape[0]) - 1)
+                        dev["_parent_asym"] = torch.where(rh.parent >= 0, sym.row_asym[grow].to(torch.int64), rh.parent)
+                    else:
+                        dev["_parent_asym"] = torch.full_like(rh.parent, -1)
             host = to_host(dev)
             ids = host.pop("_sel").tolist()
             if sym is not None:
@@ -169,6 +249,8 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
                 out["asym_frac"] += [torch.from_numpy(sym.frac[i]) for i in ids]
                 out["asym_z"] += [torch.from_numpy(sym.z[i]) for i in ids]
                 out["symops"] += [sym.symops[i] for i in ids]
+                if riding_h is not None:
+                    host["_ueq_asym"] = split_rows(host["_ueq_asym"], sites)
             names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
             check_export_status(host.pop("_status"), names)
             rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
@@ -176,10 +258,19 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             out["name"] += names
             out["temp"] += host.pop("temp").tolist() if "temp" in host else [float("nan")] * B
             for k in (("cell", "stats") + (("frames", "rot_stats") if rotations > 1 else ())
-                      + (("bond_stats",) if rigid_bond is not None else ())):
+                      + (("bond_stats",) if rigid_bond is not None else ())
+                      + (("h_stats",) if riding_h is not None else ())):
                 out[k] += [t.clone() for t in host.pop(k).unbind(0)]
-            for k in ("frac", "z"):
+            for k in ("frac", "z") + (H_KEYS[:4] if riding_h is not None else ()):
                 out[k] += split_rows(host.pop(k), atoms)
+            if riding_h is not None and sym is not None:
+                ueq_sites, parent_asym = host.pop("_ueq_asym"), split_rows(host.pop("_parent_asym"), atoms)
+                for g, i in enumerate(ids):
+                    k = len(out["z"]) - B + g
+                    u, pa = riding_asym(names[g], sym.z[i], out["z"][k], out["h_parent"][k], out["h_mult"][k],
+                                        parent_asym[g], ueq_sites[g])
+                    out["u_iso_asym"].append(u)
+                    out["h_parent_asym"].append(pa)
             for k, t in host.items():
                 out[k] += split_rows(t, rows)
     if hasattr(model, "flush_graph_checks"):
@@ -190,7 +281,7 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
 def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
-    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS if key in result}
+    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS + H_KEYS + H_SYM_KEYS if key in result}
 
 
 def cell_parameters(cell) -> tuple:
@@ -204,9 +295,22 @@ def cell_parameters(cell) -> tuple:
     return n[0], n[1], n[2], angle(1, 2), angle(0, 2), angle(0, 1)
 
 
+def _iso_columns(u_iso, z):
+    """Per atom the text of ``_atom_site_U_iso_or_equiv`` and ``_atom_site_adp_type`` (with a leading blank), or ``None``
+    for an entry without riding hydrogens.  A value that is no number (an orphan) is written ``?``."""
+    if u_iso is None:
+        return None
+    u = [float(v) for v in u_iso.tolist()]
+    if len(u) != len(z):
+        raise ValueError(f"{len(u)} isotropic values for {len(z)} atoms")
+    return [f" {'?' if math.isnan(x) else format(x, '.6f')} {'Uani' if v != 1 else 'Uiso'}" for x, v in zip(u, z)]
+
+
 def write_cif(path: str, entry: dict) -> None:
     """One crystal as a P1 CIF: the cell, the temperature, every atom (label = element symbol + running number) and the
-    anisotropic displacement parameters of the non-hydrogen atoms, ``U_11 U_22 U_33 U_23 U_13 U_12``."""
+    anisotropic displacement parameters of the non-hydrogen atoms, ``U_11 U_22 U_33 U_23 U_13 U_12``.  An entry with
+    ``u_iso`` (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv`` and ``_atom_site_adp_type`` in the atom
+    loop: ``Uani`` with U_eq for a non-hydrogen atom, ``Uiso`` with the riding value for a hydrogen, ``?`` for an orphan."""
     z = [int(v) for v in entry["z"].tolist()]
     labels = [f"{SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'}{i + 1}" for i, v in enumerate(z)]
     heavy = [i for i, v in enumerate(z) if v != 1]
@@ -225,8 +329,12 @@ def write_cif(path: str, entry: dict) -> None:
               "loop_", "_symmetry_equiv_pos_as_xyz", "'x, y, z'"]
     lines += ["loop_", "_atom_site_label", "_atom_site_type_symbol", "_atom_site_fract_x", "_atom_site_fract_y",
               "_atom_site_fract_z"]
-    for lab, v, f in zip(labels, z, entry["frac"].tolist()):
-        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}")
+    iso = _iso_columns(entry.get("u_iso"), z)
+    if iso is not None:
+        lines += ["_atom_site_U_iso_or_equiv", "_atom_site_adp_type"]
+    for k, (lab, v, f) in enumerate(zip(labels, z, entry["frac"].tolist())):
+        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}"
+                     + (iso[k] if iso is not None else ""))
     lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
               "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
     for i, row in zip(heavy, u):
@@ -238,7 +346,8 @@ def write_cif(path: str, entry: dict) -> None:
 def write_cif_symmetric(path: str, entry: dict) -> None:
     """One crystal in the setting of the file it came from: the cell, the temperature, the symmetry operators, the
     asymmetric unit with the input's labels and coordinates, and the site-averaged anisotropic displacement parameters of
-    its non-hydrogen atoms (``u_cif_asym``: ``U_11 U_22 U_33 U_23 U_13 U_12``)."""
+    its non-hydrogen atoms (``u_cif_asym``: ``U_11 U_22 U_33 U_23 U_13 U_12``).  An entry with ``u_iso_asym``
+    (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv``, and its hydrogens the type ``Uiso``."""
     z = [int(v) for v in entry["asym_z"].tolist()]
     labels = list(entry["asym_labels"])
     heavy = [i for i, v in enumerate(z) if v != 1]
@@ -256,10 +365,12 @@ def write_cif_symmetric(path: str, entry: dict) -> None:
     lines += ["loop_", "_space_group_symop_id", "_space_group_symop_operation_xyz"]
     lines += [f"{k + 1} '{op}'" for k, op in enumerate(entry["symops"])]
     lines += ["loop_", "_atom_site_label", "_atom_site_type_symbol", "_atom_site_fract_x", "_atom_site_fract_y",
-              "_atom_site_fract_z", "_atom_site_adp_type"]
-    for lab, v, f in zip(labels, z, entry["asym_frac"].tolist()):
-        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f} "
-                     f"{'Uani' if v != 1 else '.'}")
+              "_atom_site_fract_z"]
+    iso = _iso_columns(entry.get("u_iso_asym"), z)
+    lines += ["_atom_site_adp_type"] if iso is None else ["_atom_site_U_iso_or_equiv", "_atom_site_adp_type"]
+    for k, (lab, v, f) in enumerate(zip(labels, z, entry["asym_frac"].tolist())):
+        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}"
+                     + (f" {'Uani' if v != 1 else '.'}" if iso is None else iso[k]))
     lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
               "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
     for i, row in zip(heavy, u):

@@ -476,6 +476,34 @@ int cartnet_adp_bond_test(const float* u, const int64_t* z, const int64_t* edge_
                           float* ueq_ratio, double* crystal_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Riding hydrogens: an isotropic U for every hydrogen of one batch from the U_eq of the atom it is bonded to.  The
+ * reference has no counterpart: its dataset keeps only the rows of non_H_mask (dataset/datasetADP.py:49), so a hydrogen
+ * never gets a displacement parameter.
+ *   u_eq [M] fp32 (cartnet_adp_export's); z, edge_index, cart_dist, atom_row, seg_ptr, radii as for
+ *   cartnet_adp_bond_test; atom_ptr [B+1] int64: crystal g owns the atoms [atom_ptr[g], atom_ptr[g+1]).
+ * An edge between a hydrogen and the atom p is an H bond when 1 < z_p < n_radii and
+ *   cart_dist[e] <= (radii[1] + radii[z_p]) + tol           in fp32, in exactly that order; a NaN distance is none.
+ * Only edges the graph holds are considered.  Per atom i:
+ *   parent [N] int64      z_i == 1: the source of the edge j -> i with the smallest cart_dist (a tie: the lowest edge) among
+ *                         those with j != i, j non-hydrogen with a row, and an H bond; -1 without one (an orphan) and for
+ *                         every non-hydrogen atom.  A batch atom index.
+ *   count [N] int32       z_i != 1: the edges s -> i with z_s == 1, parent[s] == i and an H bond; 0 for a hydrogen
+ *   mult [N] fp32         a hydrogen with parent p and n = max(count[p], 1): f_rot if z_p == 8, or z_p == 6 and n >= 3;
+ *                         f otherwise; 0 for an orphan and for every non-hydrogen atom
+ *   u_iso [N] fp32        a hydrogen: fp32(fp64(mult) * fp64(u_eq[atom_row[p]])), one rounding, NaN for an orphan; a
+ *                         non-hydrogen atom: u_eq[atom_row[i]], NaN without a row
+ * Per crystal (one wave each, atoms in order, from the values as stored):
+ *   crystal_stats [B,4] fp64 (or NULL) = (hydrogens, orphans, sum of the finite u_iso of the hydrogens, hydrogens whose
+ *   parent's u_eq is not positive or NaN); without atoms (0, 0, 0, 0).
+ * E == 0 needs no edge arrays, M == 0 no u_eq (every hydrogen is then an orphan).  N == 0 or B == 0: returns 0 without
+ * a launch and writes nothing.  No atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_riding_h(const float* u_eq, const int64_t* z, const int64_t* edge_index, const float* cart_dist,
+                         const int64_t* atom_row, const int64_t* seg_ptr, const int64_t* atom_ptr, const float* radii,
+                         int32_t n_radii, float tol, float f, float f_rot, int32_t B, int64_t N, int64_t M, int64_t E,
+                         int64_t* parent, int32_t* count, float* mult, float* u_iso, double* crystal_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Training loss (reference: train/metrics.py:15-28, called from train/train.py:173-178): L1Loss and MSELoss with mean
  * reduction over the n = M*9 (or Bg) elements of pred / truth, both from one pair of small launches (slices, then
  * their sum), and their gradient from one more:

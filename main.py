@@ -20,7 +20,8 @@ site-averaged ADP per atom back.  ``--rotations K`` makes ``--predict`` and ``--
 frames (the stored one and K - 1 random rotations), bring the predictions back and report their mean, with the largest
 deviation of a frame from it per atom.  ``--rigid_bond`` adds Hirshfeld's rigid-bond test to ``--predict`` and
 ``--inference``: a plausibility figure per bonded pair of atoms that needs no truth (cartnet_amd/bonds.py,
-``metrics.bond_test``).  There is no CPU path: the model runs on an AMD GPU only.
+``metrics.bond_test``).  ``--riding_h`` gives every hydrogen of a ``--predict`` pass an isotropic U by the riding model, a
+multiple of its parent's predicted U_eq (``metrics.riding_h``).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ from typing import Optional, Tuple
 import torch
 
 from cartnet_amd import distributed as cdist
-from cartnet_amd.bonds import BOND_TOLERANCE, RIGID_BOND_THRESHOLD
+from cartnet_amd.bonds import BOND_TOLERANCE, RIDING_FACTOR, RIDING_FACTOR_ROTATING, RIGID_BOND_THRESHOLD
 from cartnet_amd.config import cfg, set_cfg
 from cartnet_amd.data import DataLoader, optimize_cell, remove_hydrogens
 from cartnet_amd.master import create_model
@@ -135,6 +136,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--rigid_bond: an edge is a bond up to the sum of the covalent radii plus this many Angstrom")
     p.add_argument("--rigid_bond_threshold", type=float, default=RIGID_BOND_THRESHOLD,
                    help="--rigid_bond: bonds whose amplitudes differ by more than this (A^2) are counted as over")
+    p.add_argument("--riding_h", action="store_true",
+                   help="--predict: give every hydrogen an isotropic U by the riding model, a multiple of the predicted U_eq "
+                        "of the atom it is bonded to (the nearest non-hydrogen atom within r_H + r + --bond_tolerance among "
+                        "the edges of the radius graph), and write _atom_site_U_iso_or_equiv for every atom of the CIFs.  "
+                        "Not with --disable_H; --inference, --montecarlo and training ignore it (the truth has no hydrogen "
+                        "values)")
+    p.add_argument("--riding_h_factor", type=float, default=RIDING_FACTOR,
+                   help="--riding_h: U_iso(H) / U_eq(parent)")
+    p.add_argument("--riding_h_factor_rotating", type=float, default=RIDING_FACTOR_ROTATING,
+                   help="--riding_h: the same for hydrogens on oxygen (hydroxyl, water) and on a carbon that carries three "
+                        "or more (methyl)")
     return p
 
 
@@ -492,6 +504,8 @@ def check_predict_args(args) -> None:
         raise SystemExit("--predict does not serve --model icomformer: its recipe reads crystals in the frame of the "
                          "reduced cell, and mapping U back to the stored cell is not implemented (use CartNet or "
                          "ecomformer)")
+    if args.riding_h and not cfg.use_H:
+        raise SystemExit("--riding_h with --disable_H: the hydrogens are gone, so there is nothing to ride")
 
 
 def predict(model, args) -> dict:
@@ -520,8 +534,10 @@ def predict(model, args) -> dict:
         source = DeviceShard.from_file(args.predict_input, cfg.device)
     shards, (mean, std) = shard_recipe([source])
     bond = {"rigid_bond": (args.bond_tolerance, args.rigid_bond_threshold)} if args.rigid_bond else {}
+    ride = ({"riding_h": (args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating)}
+            if args.riding_h else {})
     out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
-                       rotations=cfg.rotations, seed=cfg.seed, **bond)
+                       rotations=cfg.rotations, seed=cfg.seed, **bond, **ride)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     n = len(out["name"])
@@ -545,6 +561,12 @@ def predict(model, args) -> dict:
         count = int(bs[:, 0].sum())
         res.update(bonds=count, rigid_bond_mean=float(bs[:, 1].sum()) / count if count else 0.0,
                    rigid_bond_max=float(bs[:, 2].max()) if n else 0.0, rigid_bond_over=int(bs[:, 3].sum()))
+    if args.riding_h:                                 # from the fp64 per-crystal stats; the mean is over the non-orphans
+        hs = torch.stack(out["h_stats"]) if n else torch.zeros(0, 4, dtype=torch.float64)
+        hydrogens, orphans = int(hs[:, 0].sum()), int(hs[:, 1].sum())
+        res.update(hydrogens=hydrogens, h_orphans=orphans,
+                   h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,
+                   h_non_positive=int(hs[:, 3].sum()))
     return res
 
 

@@ -16,12 +16,13 @@
 //                                and every lane of the group reads them one by one with a shuffle from the named lane.  So
 //                                the sum is the sequential fp64 sum over the edges, and a tie of |D| keeps the lowest edge.
 //   cn_bond_test_crystal_kernel  one wave per crystal: crystal_stats[g] = (sum of bonds, sum of delta_sum, maximum of
-//                                delta_max, sum of over) of the values as stored, rows l, l + 64, ... per lane in row order,
-//                                the lanes folded by a butterfly, as cn_adp_export_crystal_kernel (export_ops.hip) does.
+//                                delta_max, sum of over) of the values as stored (crystal_reduce.h; the maximum keeps a
+//                                NaN).
 //
 // No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.  64-bit offsets throughout.
 // Neither kernel uses scratch or LDS.
 #include "common.h"
+#include "crystal_reduce.h"
 
 #include <math.h>
 
@@ -131,25 +132,20 @@ __global__ __launch_bounds__(WAVE) void cn_bond_test_crystal_kernel(const int64_
                                                                     const int32_t* __restrict__ over,
                                                                     double* __restrict__ stats) {
   const int g = blockIdx.x, lane = threadIdx.x;
-  int64_t r0 = ptr[g], r1 = ptr[g + 1];
-  r0 = r0 < 0 ? 0 : r0;
-  r1 = r1 > M ? M : r1;
+  int64_t r0, r1;
+  cr_rows(ptr, g, M, r0, r1);
   double nb = 0.0, sum = 0.0, hi = 0.0, no = 0.0;
   for (int64_t r = r0 + lane; r < r1; r += WAVE) {
     const double s = (double)delta_max[r];
     nb += (double)bonds[r];
     sum += (double)delta_sum[r];
-    hi = (s > hi || s != s) ? s : hi;
+    hi = cr_max_nan(hi, s);
     no += (double)over[r];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nb += __shfl_xor(nb, o);
-    sum += __shfl_xor(sum, o);
-    const double other = __shfl_xor(hi, o);
-    hi = (other > hi || other != other) ? other : hi;
-    no += __shfl_xor(no, o);
-  }
+  nb = cr_wave_sum(nb);
+  sum = cr_wave_sum(sum);
+  hi = cr_wave_max_nan(hi);
+  no = cr_wave_sum(no);
   if (lane == 0) {
     stats[(size_t)g * 4 + 0] = nb;
     stats[(size_t)g * 4 + 1] = sum;

@@ -12,6 +12,7 @@
 // No atomics, fixed summation order, fp64 sums: two runs give the same bytes.  No kernel of this unit uses scratch.
 #include "common.h"
 #include "adp_metrics.h"
+#include "crystal_reduce.h"
 #include "shard_tiles.h"
 
 namespace {
@@ -37,15 +38,14 @@ __global__ __launch_bounds__(SO_THREADS) void cn_rotate_rows_kernel(const float*
   float a[3 * SO_ITEMS], o[3 * SO_ITEMS];
 #pragma unroll
   for (int q = 0; q < 3 * SO_ITEMS; ++q) a[q] = i0 * 3 + q < n * 3 ? v[i0 * 3 + q] : 0.f;   // all reads before any write:
-  int g = so_first_crystal(ptr, B, n, t0, i0);                                              // out may be v
-  if (g > B - 1) g = B - 1;
+  int g = so_walk_first(ptr, B, n, t0, i0);                                                 // out may be v
   int loaded = -1;
   float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
 #pragma unroll
   for (int k = 0; k < SO_ITEMS; ++k) {
     const int64_t i = i0 + k;
     if (i < n) {
-      while (g < B - 1 && ptr[g + 1] <= i) ++g;                   // steps over empty segments
+      g = so_walk_to(ptr, B, g, i);                               // steps over empty segments
       if (g != loaded) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) R[q] = rot[(size_t)g * 9 + q];
@@ -102,9 +102,9 @@ __global__ __launch_bounds__(256) void cn_adp_eval_kernel(const float* __restric
   if (vol_err || sim || iou) cn_adp_atom_metrics(pf, tf, a, grid, P, vol_err, sim, iou);
 }
 
-// One wave per crystal: lane l adds rows l, l + 64, ... of the crystal in row order, the 64 lane sums are folded by a
-// butterfly (the same pairs in the same order on every run).  sums[g] = (sum |pred - true| over the 9 * rows elements,
-// sum volume error, sum similarity index, sum IoU); a metric that was not computed leaves 0, a crystal without rows 0.
+// One wave per crystal (crystal_reduce.h).  sums[g] = (sum |pred - true| over the 9 * rows elements, the nine of a row one
+// after another; sum volume error, sum similarity index, sum IoU); a metric that was not computed leaves 0, a crystal
+// without rows 0.
 __global__ __launch_bounds__(WAVE) void cn_crystal_sums_kernel(const float* __restrict__ pred,
                                                                const float* __restrict__ tru,
                                                                const int64_t* __restrict__ ptr, int M,
@@ -113,9 +113,8 @@ __global__ __launch_bounds__(WAVE) void cn_crystal_sums_kernel(const float* __re
                                                                const float* __restrict__ iou,
                                                                double* __restrict__ sums) {
   const int g = blockIdx.x, lane = threadIdx.x;
-  int64_t r0 = ptr[g], r1 = ptr[g + 1];
-  r0 = r0 < 0 ? 0 : r0;
-  r1 = r1 > M ? M : r1;
+  int64_t r0, r1;
+  cr_rows(ptr, g, M, r0, r1);
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t r = r0 + lane; r < r1; r += WAVE) {
 #pragma unroll
@@ -125,9 +124,7 @@ __global__ __launch_bounds__(WAVE) void cn_crystal_sums_kernel(const float* __re
     if (iou) s[3] += (double)iou[r];
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s[q] += __shfl_xor(s[q], o);
+  for (int q = 0; q < 4; ++q) s[q] = cr_wave_sum(s[q]);
   if (lane == 0)
 #pragma unroll
     for (int q = 0; q < 4; ++q) sums[(size_t)g * 4 + q] = s[q];

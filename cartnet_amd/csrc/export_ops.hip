@@ -10,10 +10,11 @@
 //                          binary-search scheme of shard_tiles.h, as cn_rotate_rows_kernel (eval_ops.hip) does.
 //   cn_adp_export_crystal_kernel  one wave per crystal: status[g] (bit 0: singular cell) and crystal_stats[g] = (sum of
 //                          U_eq, smallest principal value, rows whose smallest principal value <= 0) from the fp32 values as
-//                          stored, rows l, l + 64, ... per lane in row order, the lanes folded by a butterfly.
+//                          stored (crystal_reduce.h).
 //
 // No atomics, fixed order: two runs give the same bytes.  Neither kernel uses scratch or LDS.
 #include "common.h"
+#include "crystal_reduce.h"
 #include "shard_tiles.h"
 
 #include <math.h>
@@ -145,15 +146,14 @@ __global__ __launch_bounds__(SO_THREADS) void cn_adp_export_kernel(const float* 
                                                                    float* __restrict__ axes) {
   const int64_t t0 = (int64_t)blockIdx.x * SO_TILE, i0 = t0 + (int64_t)threadIdx.x * SO_ITEMS;
   if (i0 >= M) return;
-  int g = so_first_crystal(ptr, B, M, t0, i0);
-  if (g > B - 1) g = B - 1;
+  int g = so_walk_first(ptr, B, M, t0, i0);
   int loaded = -1;
   double r[3][3];
 #pragma unroll 1
   for (int k = 0; k < SO_ITEMS; ++k) {
     const int64_t i = i0 + k;
     if (i >= M) break;
-    while (g < B - 1 && ptr[g + 1] <= i) ++g;                     // steps over empty crystals
+    g = so_walk_to(ptr, B, g, i);                                 // steps over empty crystals
     if (g != loaded) {
       ex_reciprocal_units(cell + (size_t)g * 9, r);                // NaN for a singular cell: its rows come out NaN
       loaded = g;
@@ -174,9 +174,8 @@ __global__ __launch_bounds__(WAVE) void cn_adp_export_crystal_kernel(const int64
     status[g] = ex_reciprocal_units(cell + (size_t)g * 9, r) ? 0 : 1;
   }
   if (!stats) return;
-  int64_t r0 = ptr[g], r1 = ptr[g + 1];
-  r0 = r0 < 0 ? 0 : r0;
-  r1 = r1 > M ? M : r1;
+  int64_t r0, r1;
+  cr_rows(ptr, g, M, r0, r1);
   double sum = 0.0, lo = (double)INFINITY, bad = 0.0;
   for (int64_t r = r0 + lane; r < r1; r += WAVE) {
     const double p = (double)principal[r * 3];
@@ -184,12 +183,9 @@ __global__ __launch_bounds__(WAVE) void cn_adp_export_crystal_kernel(const int64
     lo = fmin(lo, p);
     bad += p <= 0.0 ? 1.0 : 0.0;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    lo = fmin(lo, __shfl_xor(lo, o));
-    bad += __shfl_xor(bad, o);
-  }
+  sum = cr_wave_sum(sum);
+  lo = cr_wave_min(lo);
+  bad = cr_wave_sum(bad);
   if (lane == 0) {
     stats[(size_t)g * 3 + 0] = sum;
     stats[(size_t)g * 3 + 1] = lo;

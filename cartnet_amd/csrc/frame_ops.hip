@@ -11,12 +11,13 @@
 //                                 formed twice (sum, then deviations) so that K stays a run-time number without scratch.  A
 //                                 row finds its crystal by the tile / binary-search scheme of shard_tiles.h, as
 //                                 cn_adp_export_kernel (export_ops.hip) does.
-//   cn_frame_mean_crystal_kernel  one wave per crystal: crystal_spread[g] = (sum, maximum) of the fp32 spread as stored,
-//                                 rows l, l + 64, ... per lane in row order, the lanes folded by a butterfly.
+//   cn_frame_mean_crystal_kernel  one wave per crystal: crystal_spread[g] = (sum, maximum) of the fp32 spread as stored
+//                                 (crystal_reduce.h; the maximum keeps a NaN).
 //
 // No symmetrisation (the export does its own), the rotations are used as given.  No atomics, fixed order: two runs give the
 // same bytes.  Neither kernel uses scratch or LDS.
 #include "common.h"
+#include "crystal_reduce.h"
 #include "shard_tiles.h"
 
 #include <math.h>
@@ -82,13 +83,12 @@ __global__ __launch_bounds__(SO_THREADS) void cn_frame_mean_kernel(const float* 
                                                                    float* __restrict__ mean, float* __restrict__ spread) {
   const int64_t t0 = (int64_t)blockIdx.x * SO_TILE, i0 = t0 + (int64_t)threadIdx.x * SO_ITEMS;
   if (i0 >= M) return;
-  int g = so_first_crystal(ptr, B, M, t0, i0);
-  if (g > B - 1) g = B - 1;
+  int g = so_walk_first(ptr, B, M, t0, i0);
 #pragma unroll 1
   for (int k = 0; k < SO_ITEMS; ++k) {
     const int64_t i = i0 + k;
     if (i >= M) break;
-    while (g < B - 1 && ptr[g + 1] <= i) ++g;                     // steps over empty crystals
+    g = so_walk_to(ptr, B, g, i);                                 // steps over empty crystals
     fm_frame_mean_row(pred + i * 9, M * 9, rot + (size_t)g * 9, (int64_t)B * 9, K, mean + i * 9, spread + i);
   }
 }
@@ -97,21 +97,16 @@ __global__ __launch_bounds__(WAVE) void cn_frame_mean_crystal_kernel(const int64
                                                                      const float* __restrict__ spread,
                                                                      double* __restrict__ stats) {
   const int g = blockIdx.x, lane = threadIdx.x;
-  int64_t r0 = ptr[g], r1 = ptr[g + 1];
-  r0 = r0 < 0 ? 0 : r0;
-  r1 = r1 > M ? M : r1;
+  int64_t r0, r1;
+  cr_rows(ptr, g, M, r0, r1);
   double sum = 0.0, hi = 0.0;
   for (int64_t r = r0 + lane; r < r1; r += WAVE) {
     const double s = (double)spread[r];
     sum += s;
-    hi = (s > hi || s != s) ? s : hi;
+    hi = cr_max_nan(hi, s);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    const double other = __shfl_xor(hi, o);
-    hi = (other > hi || other != other) ? other : hi;
-  }
+  sum = cr_wave_sum(sum);
+  hi = cr_wave_max_nan(hi);
   if (lane == 0) {
     stats[(size_t)g * 2 + 0] = sum;
     stats[(size_t)g * 2 + 1] = hi;

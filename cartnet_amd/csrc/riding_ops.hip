@@ -21,12 +21,13 @@
 //                             the multiplier (f_rot for z_t == 8, or z_t == 6 with n >= 3; f otherwise) and
 //                             u_iso = fp32(fp64(mult) * fp64(u_eq[row of t])): exact product, one rounding.
 //   cn_riding_crystal_kernel  one wave per crystal over its atoms: crystal_stats[g] = (hydrogens, orphans, sum of the
-//                             finite hydrogen u_iso, hydrogens whose parent's u_eq is not positive), atoms l, l + 64, ...
-//                             per lane in order, the lanes folded by a butterfly, as cn_bond_test_crystal_kernel does.
+//                             finite hydrogen u_iso, hydrogens whose parent's u_eq is not positive), the crystal's atoms
+//                             taking the place of rows in crystal_reduce.h.
 //
 // No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.  64-bit offsets throughout.  No
 // kernel uses scratch or LDS.
 #include "common.h"
+#include "crystal_reduce.h"
 
 #include <math.h>
 
@@ -147,9 +148,8 @@ __global__ __launch_bounds__(WAVE) void cn_riding_crystal_kernel(const int64_t* 
                                                                  const float* __restrict__ u_iso,
                                                                  double* __restrict__ stats) {
   const int g = blockIdx.x, lane = threadIdx.x;
-  int64_t a0 = atom_ptr[g], a1 = atom_ptr[g + 1];
-  a0 = a0 < 0 ? 0 : a0;
-  a1 = a1 > N ? N : a1;
+  int64_t a0, a1;
+  cr_rows(atom_ptr, g, N, a0, a1);
   double nh = 0.0, orphans = 0.0, sum = 0.0, bad = 0.0;
   for (int64_t a = a0 + lane; a < a1; a += WAVE) {
     if (z[a] != 1) continue;
@@ -164,13 +164,10 @@ __global__ __launch_bounds__(WAVE) void cn_riding_crystal_kernel(const int64_t* 
     if (v - v == 0.f) sum += (double)v;                           // finite
     if (!(u_eq[m] > 0.f)) bad += 1.0;                             // not positive, or NaN
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    nh += __shfl_xor(nh, o);
-    orphans += __shfl_xor(orphans, o);
-    sum += __shfl_xor(sum, o);
-    bad += __shfl_xor(bad, o);
-  }
+  nh = cr_wave_sum(nh);
+  orphans = cr_wave_sum(orphans);
+  sum = cr_wave_sum(sum);
+  bad = cr_wave_sum(bad);
   if (lane == 0) {
     stats[(size_t)g * 4 + 0] = nh;
     stats[(size_t)g * 4 + 1] = orphans;

@@ -27,6 +27,19 @@ __device__ __forceinline__ int so_first_crystal(const int64_t* __restrict__ ptr,
   return so_find(ptr, g_lo, g_hi + 1, i0);
 }
 
+// The crystal walk of a row kernel whose thread takes its items in ascending order: so_walk_first gives the crystal of the
+// thread's first item i0 (never beyond the last crystal), so_walk_to steps from the crystal g of an earlier item to the
+// crystal of item i, over empty crystals.
+__device__ __forceinline__ int so_walk_first(const int64_t* __restrict__ ptr, int G, int64_t n, int64_t t0, int64_t i0) {
+  const int g = so_first_crystal(ptr, G, n, t0, i0);
+  return g > G - 1 ? G - 1 : g;
+}
+
+__device__ __forceinline__ int so_walk_to(const int64_t* __restrict__ ptr, int G, int g, int64_t i) {
+  while (g < G - 1 && ptr[g + 1] <= i) ++g;
+  return g;
+}
+
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // inclusive scan over the 64 lanes of a wavefront

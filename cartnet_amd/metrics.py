@@ -15,10 +15,16 @@ from . import lib as _l
 SMOOTH = 1e-8          # train/metrics.py:11
 
 
+def _check_fp32(name: str, t: torch.Tensor, trailing: tuple = (3, 3), shape: str = "[M,3,3]") -> None:
+    """``t`` must be a CUDA fp32 tensor of one leading dimension followed by ``trailing``; ``shape`` is how the message
+    writes that."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 + len(trailing) and tuple(t.shape[1:]) == trailing):
+        raise ValueError(f"{name} must be a CUDA fp32 tensor {shape}")
+
+
 def _check_pair(pred: torch.Tensor, true: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, int]:
-    for name, t in (("pred", pred), ("true", true)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[1:]) == (3, 3)):
-            raise ValueError(f"{name} must be a CUDA fp32 tensor [M,3,3]")
+    _check_fp32("pred", pred)
+    _check_fp32("true", true)
     if pred.shape[0] != true.shape[0]:
         raise ValueError("pred and true must hold the same number of atoms")
     return pred.detach().contiguous(), true.detach().contiguous(), int(pred.shape[0])
@@ -184,8 +190,7 @@ def adp_export(pred: torch.Tensor, row_ptr: torch.Tensor, cell: torch.Tensor, ax
     ``[row_ptr[g], row_ptr[g+1])``; ``cell`` [B,3,3] fp32, rows = lattice vectors.  With ``check`` the status is read back
     (one small device-to-host copy) and a singular cell raises ``ValueError`` naming the crystal; with ``check=False`` the
     caller passes ``AdpExport.status`` to ``check_export_status`` once it has brought the results to the host."""
-    if not (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 3 and tuple(pred.shape[1:]) == (3, 3)):
-        raise ValueError("pred must be a CUDA fp32 tensor [M,3,3]")
+    _check_fp32("pred", pred)
     pred, M, dev = pred.detach().contiguous(), int(pred.shape[0]), pred.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
     if not (cell.dtype == torch.float32 and tuple(cell.shape) == (B, 3, 3) and cell.device == dev):
@@ -227,8 +232,7 @@ def frame_mean(pred: torch.Tensor, rot: torch.Tensor, row_ptr: torch.Tensor, sta
     replica-major (rows ``k*M ... (k+1)*M-1``: the batch's M rows as predicted from ``cart_dir @ rot[k, g]``); ``rot``
     [K,B,3,3] fp32; ``row_ptr`` [B+1] over ONE replica's rows.  Member k comes back as ``R P_k R^T`` (fp64 arithmetic, one
     rounding to fp32); K = 1 with the identity returns ``pred``'s values and a zero spread."""
-    if not (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 3 and tuple(pred.shape[1:]) == (3, 3)):
-        raise ValueError("pred must be a CUDA fp32 tensor [K*M,3,3]")
+    _check_fp32("pred", pred, shape="[K*M,3,3]")
     dev = pred.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
     if not (rot.dtype == torch.float32 and rot.dim() == 4 and rot.shape[0] >= 1 and tuple(rot.shape[1:]) == (B, 3, 3)
@@ -340,8 +344,7 @@ def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, t
     An edge ``j -> i`` is a bond by the rule of ``cartnet_amd.bonds`` (``r_i + r_j + tol``, both ends non-hydrogen, no
     self image); only edges the graph holds are seen.  The two lookups the kernel needs -- an atom's row and its edge
     segment -- are built here with static-shape device ops; nothing is read back."""
-    if not (u.is_cuda and u.dtype == torch.float32 and u.dim() == 3 and tuple(u.shape[1:]) == (3, 3)):
-        raise ValueError("u must be a CUDA fp32 tensor [M,3,3]")
+    _check_fp32("u", u)
     u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
     z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "bond_test", "u", True)
@@ -393,8 +396,7 @@ def riding_h(u_eq: torch.Tensor, batch, tol: float = 0.4, f: float = 1.2, f_rot:
     ``r_H + r_parent + tol`` among the edges the graph holds; the multiplier is ``f_rot`` on oxygen and on a carbon that
     carries three or more hydrogens, ``f`` otherwise (the rule: ``cartnet_amd.bonds``).  The two lookups are built as in
     ``bond_test``; nothing is read back."""
-    if not (u_eq.is_cuda and u_eq.dtype == torch.float32 and u_eq.dim() == 1):
-        raise ValueError("u_eq must be a CUDA fp32 tensor [M]")
+    _check_fp32("u_eq", u_eq, (), "[M]")
     u_eq, M, dev = u_eq.detach().contiguous(), int(u_eq.shape[0]), u_eq.device
     ptr = _batch_field(batch, "ptr")
     if not torch.is_tensor(ptr):

@@ -86,25 +86,28 @@ def replicate(batch, K: int, R: torch.Tensor):
     return out
 
 
+def _in_crystal(index: torch.Tensor, batch) -> torch.Tensor:
+    """Atom indices of the batch (a bond's partner, a hydrogen's parent: atoms of the crystal they are recorded in) as atom
+    indices inside that crystal; -1 (no atom) is kept."""
+    at = index.clamp(min=0)
+    return torch.where(index >= 0, at - batch.ptr.to(torch.int64)[batch.batch[at]], index)
+
+
 def bond_entries(bt, batch) -> dict:
     """The per-row keys of ``BOND_KEYS`` (and ``bond_stats`` per crystal) from a ``metrics.BondTest`` of ``batch``, on the
     device: ``bond_delta_mean`` = ``delta_sum / bonds`` (0 without bonds), ``bond_worst`` as an atom index inside its
     crystal (-1 without bonds).  Static-shape device ops: nothing is read back."""
-    partner = bt.worst.clamp(min=0)
-    first = batch.ptr.to(torch.int64)[batch.batch[partner]]                   # the partner's crystal is the row's own
     return {"bond_count": bt.bonds, "bond_delta_max": bt.delta_max, "bond_over": bt.over, "bond_ueq_ratio": bt.ueq_ratio,
             "bond_delta_mean": bt.delta_sum / bt.bonds.clamp(min=1).to(torch.float32),      # delta_sum is 0 without bonds
-            "bond_worst": torch.where(bt.worst >= 0, partner - first, bt.worst), "bond_stats": bt.crystal_stats}
+            "bond_worst": _in_crystal(bt.worst, batch), "bond_stats": bt.crystal_stats}
 
 
 def riding_entries(rh, batch) -> dict:
     """The per-atom keys of ``H_KEYS`` (and ``h_stats`` per crystal) from a ``metrics.RidingH`` of ``batch``, on the device:
     ``h_parent`` as an atom index inside its crystal (-1 where there is none), converted as ``bond_entries`` converts
     ``bond_worst``.  Static-shape device ops: nothing is read back."""
-    partner = rh.parent.clamp(min=0)
-    first = batch.ptr.to(torch.int64)[batch.batch[partner]]                   # the parent's crystal is the hydrogen's own
-    return {"u_iso": rh.u_iso, "h_parent": torch.where(rh.parent >= 0, partner - first, rh.parent), "h_count": rh.count,
-            "h_mult": rh.mult, "h_stats": rh.crystal_stats}
+    return {"u_iso": rh.u_iso, "h_parent": _in_crystal(rh.parent, batch), "h_count": rh.count, "h_mult": rh.mult,
+            "h_stats": rh.crystal_stats}
 
 
 def u_eq_of_cif(u_cif: torch.Tensor, cell: torch.Tensor) -> torch.Tensor:
@@ -145,6 +148,118 @@ def riding_asym(name: str, asym_z, z, h_parent, h_mult, parent_asym, u_eq_sites)
     return torch.where(heavy, own, of_parent).to(torch.float32), pa
 
 
+# How every key of the result that travels to the host as a tensor is cut into the crystals' entries: one slice of dim 0
+# per "crystal", or the pieces of dim 0 that hold a crystal's atoms ("atom"), its non-hydrogen rows ("row") or the
+# non-hydrogen atoms of its asymmetric unit ("site").  The other keys of the result are assembled on the host.
+SPLIT = {"atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "u_cart": "row", "u_cif": "row", "u_eq": "row",
+         "principal": "row", "axes": "row", "stats": "crystal",
+         "u_cif_asym": "site", "spread": "site",
+         "rot_spread": "row", "frames": "crystal", "rot_stats": "crystal",
+         "bond_count": "row", "bond_delta_mean": "row", "bond_delta_max": "row", "bond_worst": "row", "bond_over": "row",
+         "bond_ueq_ratio": "row", "bond_stats": "crystal",
+         "u_iso": "atom", "h_parent": "atom", "h_count": "atom", "h_mult": "atom", "h_stats": "crystal"}
+
+
+def _check_pass(loader, rotations: int):
+    """What ``predict_adps`` requires of its arguments; returns the loader's shard."""
+    if rotations < 1:
+        raise ValueError("rotations must be at least 1")
+    shard = loader.shard
+    if not shard.per_atom_target:
+        raise ValueError("predict_adps needs an ADP shard (per-atom 3x3 rows)")
+    if not all(k in shard.t for k in ("pos", "cell", "non_h_mask")):
+        raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
+    return shard
+
+
+def parent_asym(parent: torch.Tensor, batch, row_ptr: torch.Tensor, sym) -> torch.Tensor:
+    """[N] int64 on the device: for every atom of ``batch`` the atom of the asymmetric unit that its riding parent
+    (``RidingH.parent``, an atom index of the batch) is an image of, -1 without a parent: the parent's row in the batch,
+    then in the expansion (``sym.y_ptr``), then ``sym.row_asym``."""
+    n = int(sym.row_asym.shape[0])
+    if not n:
+        return torch.full_like(parent, -1)
+    first = torch.from_numpy(sym.y_ptr[batch._sel]).to(parent.device)
+    p = parent.clamp(min=0)
+    row = (torch.cumsum(batch.non_H_mask.to(torch.int64), 0) - 1)[p]
+    g = batch.batch[p]
+    grow = (first[g] + (row - row_ptr[g])).clamp(0, n - 1)
+    return torch.where(parent >= 0, sym.row_asym[grow].to(torch.int64), parent)
+
+
+def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h) -> dict:
+    """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
+    one ``to_host``: tensors under their key of ``SPLIT``, and under names with a leading underscore what ``_host_stage``
+    needs to cut and check them."""
+    device = batch.x.device
+    B = int(batch.num_graphs)
+    row_ptr = target_row_ptr(batch)
+    sel = batch._meta[:B]
+    z = batch.x.clone()                                                       # forward overwrites x
+    dev = {"z": z, "atoms": z[batch.non_H_mask], "cell": batch.cell, "_sel": sel, "_row_ptr": row_ptr,
+           "_atom_ptr": batch.ptr,
+           "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
+    if "temperature" in shard.t:
+        dev["_temp"] = shard.t["temperature"][sel]                            # the collated one is standardised
+    if rotations == 1:
+        pred, _ = model(batch)
+    else:
+        R = frames(B, rotations, gen, device)
+        members, _ = model(replicate(batch, rotations, R))
+        fm = frame_mean(members, R, row_ptr, stats=True)
+        pred = fm.mean
+        dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
+    ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
+    dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
+               stats=ex.crystal_stats, _status=ex.status)
+    batch.x = z                                                               # the graph and the atomic numbers again
+    if rigid_bond is not None:
+        dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
+    if riding_h is not None:
+        rh = riding_h_call(ex.u_eq, batch, *riding_h)
+        dev.update(riding_entries(rh, batch))
+    if sym is not None:
+        from .symmetry import site_average
+        dev["u_cif_asym"], dev["spread"] = site_average(pred, row_ptr, batch._sel, sym)
+        if riding_h is not None:                                              # what riding_asym takes, per site and per atom
+            counts = torch.from_numpy(sym.site_count[batch._sel]).to(device)
+            crystal = torch.repeat_interleave(torch.arange(B, device=device), counts,
+                                              output_size=int(dev["u_cif_asym"].shape[0]))
+            dev["_ueq_asym"] = u_eq_of_cif(dev["u_cif_asym"], sym.cell[sel].view(B, 3, 3)[crystal])
+            dev["_parent_asym"] = parent_asym(rh.parent, batch, row_ptr, sym)
+    return dev
+
+
+def _host_stage(out: Dict[str, List], host: dict, shard, sym) -> None:
+    """Appends the crystals of one batch to ``out`` from the host copy of ``_device_stage``'s dict."""
+    ids = host.pop("_sel").tolist()
+    names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
+    check_export_status(host.pop("_status"), names)
+    rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
+    counts = {"row": (rp[1:] - rp[:-1]).tolist(), "atom": (ap[1:] - ap[:-1]).tolist(),
+              "site": [int(sym.site_count[i]) for i in ids] if sym is not None else None}
+    out["name"] += names
+    out["temp"] += host.pop("_temp").tolist() if "_temp" in host else [float("nan")] * len(ids)
+    riding = "_ueq_asym" in host                                              # what riding_asym takes, per site and per atom
+    ueq_sites = split_rows(host.pop("_ueq_asym"), counts["site"]) if riding else None
+    parents = split_rows(host.pop("_parent_asym"), counts["atom"]) if riding else None
+    for k, t in host.items():
+        kind = SPLIT[k]
+        out[k] += [c.clone() for c in t.unbind(0)] if kind == "crystal" else split_rows(t, counts[kind])
+    if sym is not None:
+        out["asym_labels"] += [sym.labels[i] for i in ids]
+        out["asym_frac"] += [torch.from_numpy(sym.frac[i]) for i in ids]
+        out["asym_z"] += [torch.from_numpy(sym.z[i]) for i in ids]
+        out["symops"] += [sym.symops[i] for i in ids]
+    if riding:
+        for g, i in enumerate(ids):
+            k = len(out["z"]) - len(ids) + g
+            u, pa = riding_asym(names[g], sym.z[i], out["z"][k], out["h_parent"][k], out["h_mult"][k], parents[g],
+                                ueq_sites[g])
+            out["u_iso_asym"].append(u)
+            out["h_parent_asym"].append(pa)
+
+
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None
                  ) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
@@ -176,13 +291,7 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     ``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``).  ``None`` is the pass
     as it always was."""
     rotations = int(rotations)
-    if rotations < 1:
-        raise ValueError("rotations must be at least 1")
-    shard = loader.shard
-    if not shard.per_atom_target:
-        raise ValueError("predict_adps needs an ADP shard (per-atom 3x3 rows)")
-    if not all(k in shard.t for k in ("pos", "cell", "non_h_mask")):
-        raise ValueError("predict_adps needs the shard's pos, cell and non_h_mask")
+    shard = _check_pass(loader, rotations)
     model.eval()
     out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
                             + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())
@@ -194,85 +303,8 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             if batch is None:
                 continue
             batch.to(device)
-            B = int(batch.num_graphs)
-            row_ptr = target_row_ptr(batch)
-            sel = batch._meta[:B]
-            z = batch.x.clone()                                               # forward overwrites x
-            dev = {"z": z, "atoms": z[batch.non_H_mask], "cell": batch.cell, "_sel": sel, "_row_ptr": row_ptr,
-                   "_atom_ptr": batch.ptr,
-                   "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
-            if "temperature" in shard.t:
-                dev["temp"] = shard.t["temperature"][sel]                     # the collated one is standardised
-            if rotations == 1:
-                pred, _ = model(batch)
-            else:
-                R = frames(B, rotations, gen, device)
-                members, _ = model(replicate(batch, rotations, R))
-                fm = frame_mean(members, R, row_ptr, stats=True)
-                pred = fm.mean
-                dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
-            ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
-            dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
-                       stats=ex.crystal_stats, _status=ex.status)
-            if rigid_bond is not None:
-                batch.x = z                                                   # the graph and the atomic numbers again
-                dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
-            if riding_h is not None:
-                batch.x = z
-                rh = riding_h_call(ex.u_eq, batch, *riding_h)
-                dev.update(riding_entries(rh, batch))
-            if sym is not None:
-                from .symmetry import site_average
-                dev["_u_asym"], dev["_spread"] = site_average(pred, row_ptr, batch._sel, sym)
-                if riding_h is not None:
-                    # the asymmetric atom every parent is an image of: its row in the batch, then in the expansion
-                    counts = torch.from_numpy(sym.site_count[batch._sel]).to(device)
-                    first = torch.from_numpy(sym.y_ptr[batch._sel]).to(device)
-                    crystal = torch.repeat_interleave(torch.arange(B, device=device), counts,
-                                                      output_size=int(dev["_u_asym"].shape[0]))
-                    dev["_ueq_asym"] = u_eq_of_cif(dev["_u_asym"], sym.cell[sel].view(B, 3, 3)[crystal])
-                    if int(sym.row_asym.shape[0]):
-                        p = rh.parent.clamp(min=0)
-                        row = (torch.cumsum(batch.non_H_mask.to(torch.int64), 0) - 1)[p]
-                        g = batch.batch[p]
-                        grow = (first[g] + (row - row_ptr[g])).clamp(0, int(sym.row_asym.shape[0]) - 1)
-                        dev["_parent_asym"] = torch.where(rh.parent >= 0, sym.row_asym[grow].to(torch.int64), rh.parent)
-                    else:
-                        dev["_parent_asym"] = torch.full_like(rh.parent, -1)
-            host = to_host(dev)
-            ids = host.pop("_sel").tolist()
-            if sym is not None:
-                sites = [int(sym.site_count[i]) for i in ids]
-                out["u_cif_asym"] += split_rows(host.pop("_u_asym"), sites)
-                out["spread"] += split_rows(host.pop("_spread"), sites)
-                out["asym_labels"] += [sym.labels[i] for i in ids]
-                out["asym_frac"] += [torch.from_numpy(sym.frac[i]) for i in ids]
-                out["asym_z"] += [torch.from_numpy(sym.z[i]) for i in ids]
-                out["symops"] += [sym.symops[i] for i in ids]
-                if riding_h is not None:
-                    host["_ueq_asym"] = split_rows(host["_ueq_asym"], sites)
-            names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
-            check_export_status(host.pop("_status"), names)
-            rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
-            rows, atoms = (rp[1:] - rp[:-1]).tolist(), (ap[1:] - ap[:-1]).tolist()
-            out["name"] += names
-            out["temp"] += host.pop("temp").tolist() if "temp" in host else [float("nan")] * B
-            for k in (("cell", "stats") + (("frames", "rot_stats") if rotations > 1 else ())
-                      + (("bond_stats",) if rigid_bond is not None else ())
-                      + (("h_stats",) if riding_h is not None else ())):
-                out[k] += [t.clone() for t in host.pop(k).unbind(0)]
-            for k in ("frac", "z") + (H_KEYS[:4] if riding_h is not None else ()):
-                out[k] += split_rows(host.pop(k), atoms)
-            if riding_h is not None and sym is not None:
-                ueq_sites, parent_asym = host.pop("_ueq_asym"), split_rows(host.pop("_parent_asym"), atoms)
-                for g, i in enumerate(ids):
-                    k = len(out["z"]) - B + g
-                    u, pa = riding_asym(names[g], sym.z[i], out["z"][k], out["h_parent"][k], out["h_mult"][k],
-                                        parent_asym[g], ueq_sites[g])
-                    out["u_iso_asym"].append(u)
-                    out["h_parent_asym"].append(pa)
-            for k, t in host.items():
-                out[k] += split_rows(t, rows)
+            _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h)),
+                        shard, sym)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
     return out
@@ -306,17 +338,14 @@ def _iso_columns(u_iso, z):
     return [f" {'?' if math.isnan(x) else format(x, '.6f')} {'Uani' if v != 1 else 'Uiso'}" for x, v in zip(u, z)]
 
 
-def write_cif(path: str, entry: dict) -> None:
-    """One crystal as a P1 CIF: the cell, the temperature, every atom (label = element symbol + running number) and the
-    anisotropic displacement parameters of the non-hydrogen atoms, ``U_11 U_22 U_33 U_23 U_13 U_12``.  An entry with
-    ``u_iso`` (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv`` and ``_atom_site_adp_type`` in the atom
-    loop: ``Uani`` with U_eq for a non-hydrogen atom, ``Uiso`` with the riding value for a hydrogen, ``?`` for an orphan."""
-    z = [int(v) for v in entry["z"].tolist()]
-    labels = [f"{SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'}{i + 1}" for i, v in enumerate(z)]
+def _write(path: str, entry: dict, z, labels, frac, u, whose: str, symmetry: list, iso, type_column: bool) -> None:
+    """What the two writers share: the cell, the temperature, ``symmetry`` (the lines that state the setting), the atom loop
+    (``labels``, ``z``, ``frac``) and the anisotropic loop of the non-hydrogen atoms (``u``: one row each, ``U_11 U_22 U_33
+    U_23 U_13 U_12``).  ``iso``: the entry's isotropic values or ``None``; without them the atom loop has no further column,
+    or with ``type_column`` the type alone (``Uani``, ``.`` for a hydrogen)."""
     heavy = [i for i, v in enumerate(z) if v != 1]
-    u = entry["u_cif"].tolist()
     if len(heavy) != len(u):
-        raise ValueError(f"{len(u)} ADP rows for {len(heavy)} non-hydrogen atoms")
+        raise ValueError(f"{len(u)} ADP rows for {len(heavy)} non-hydrogen atoms{whose}")
     a, b, c, al, be, ga = cell_parameters(entry["cell"])
     name = "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in str(entry["name"])) or "crystal"
     lines = [f"data_{name}",
@@ -325,22 +354,37 @@ def write_cif(path: str, entry: dict) -> None:
     temp = float(entry["temp"])
     if not math.isnan(temp):
         lines.append(f"_diffrn_ambient_temperature {temp:.2f}")
-    lines += ["_symmetry_space_group_name_H-M 'P 1'", "_symmetry_Int_Tables_number 1",
-              "loop_", "_symmetry_equiv_pos_as_xyz", "'x, y, z'"]
+    lines += symmetry
     lines += ["loop_", "_atom_site_label", "_atom_site_type_symbol", "_atom_site_fract_x", "_atom_site_fract_y",
               "_atom_site_fract_z"]
-    iso = _iso_columns(entry.get("u_iso"), z)
-    if iso is not None:
+    tails = _iso_columns(iso, z)
+    if tails is not None:
         lines += ["_atom_site_U_iso_or_equiv", "_atom_site_adp_type"]
-    for k, (lab, v, f) in enumerate(zip(labels, z, entry["frac"].tolist())):
-        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}"
-                     + (iso[k] if iso is not None else ""))
+    elif type_column:
+        lines.append("_atom_site_adp_type")
+        tails = [f" {'Uani' if v != 1 else '.'}" for v in z]
+    else:
+        tails = [""] * len(z)
+    for lab, v, f, tail in zip(labels, z, frac, tails):
+        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}" + tail)
     lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
               "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
     for i, row in zip(heavy, u):
         lines.append(labels[i] + " " + " ".join(f"{x:.6f}" for x in row))
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
+
+
+def write_cif(path: str, entry: dict) -> None:
+    """One crystal as a P1 CIF: the cell, the temperature, every atom (label = element symbol + running number) and the
+    anisotropic displacement parameters of the non-hydrogen atoms, ``U_11 U_22 U_33 U_23 U_13 U_12``.  An entry with
+    ``u_iso`` (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv`` and ``_atom_site_adp_type`` in the atom
+    loop: ``Uani`` with U_eq for a non-hydrogen atom, ``Uiso`` with the riding value for a hydrogen, ``?`` for an orphan."""
+    z = [int(v) for v in entry["z"].tolist()]
+    labels = [f"{SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'}{i + 1}" for i, v in enumerate(z)]
+    p1 = ["_symmetry_space_group_name_H-M 'P 1'", "_symmetry_Int_Tables_number 1",
+          "loop_", "_symmetry_equiv_pos_as_xyz", "'x, y, z'"]
+    _write(path, entry, z, labels, entry["frac"].tolist(), entry["u_cif"].tolist(), "", p1, entry.get("u_iso"), False)
 
 
 def write_cif_symmetric(path: str, entry: dict) -> None:
@@ -349,31 +393,7 @@ def write_cif_symmetric(path: str, entry: dict) -> None:
     its non-hydrogen atoms (``u_cif_asym``: ``U_11 U_22 U_33 U_23 U_13 U_12``).  An entry with ``u_iso_asym``
     (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv``, and its hydrogens the type ``Uiso``."""
     z = [int(v) for v in entry["asym_z"].tolist()]
-    labels = list(entry["asym_labels"])
-    heavy = [i for i, v in enumerate(z) if v != 1]
-    u = entry["u_cif_asym"].tolist()
-    if len(heavy) != len(u):
-        raise ValueError(f"{len(u)} ADP rows for {len(heavy)} non-hydrogen atoms of the asymmetric unit")
-    a, b, c, al, be, ga = cell_parameters(entry["cell"])
-    name = "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in str(entry["name"])) or "crystal"
-    lines = [f"data_{name}",
-             f"_cell_length_a {a:.6f}", f"_cell_length_b {b:.6f}", f"_cell_length_c {c:.6f}",
-             f"_cell_angle_alpha {al:.5f}", f"_cell_angle_beta {be:.5f}", f"_cell_angle_gamma {ga:.5f}"]
-    temp = float(entry["temp"])
-    if not math.isnan(temp):
-        lines.append(f"_diffrn_ambient_temperature {temp:.2f}")
-    lines += ["loop_", "_space_group_symop_id", "_space_group_symop_operation_xyz"]
-    lines += [f"{k + 1} '{op}'" for k, op in enumerate(entry["symops"])]
-    lines += ["loop_", "_atom_site_label", "_atom_site_type_symbol", "_atom_site_fract_x", "_atom_site_fract_y",
-              "_atom_site_fract_z"]
-    iso = _iso_columns(entry.get("u_iso_asym"), z)
-    lines += ["_atom_site_adp_type"] if iso is None else ["_atom_site_U_iso_or_equiv", "_atom_site_adp_type"]
-    for k, (lab, v, f) in enumerate(zip(labels, z, entry["asym_frac"].tolist())):
-        lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}"
-                     + (f" {'Uani' if v != 1 else '.'}" if iso is None else iso[k]))
-    lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
-              "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
-    for i, row in zip(heavy, u):
-        lines.append(labels[i] + " " + " ".join(f"{x:.6f}" for x in row))
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    ops = ["loop_", "_space_group_symop_id", "_space_group_symop_operation_xyz"]
+    ops += [f"{k + 1} '{op}'" for k, op in enumerate(entry["symops"])]
+    _write(path, entry, z, list(entry["asym_labels"]), entry["asym_frac"].tolist(), entry["u_cif_asym"].tolist(),
+           " of the asymmetric unit", ops, entry.get("u_iso_asym"), True)

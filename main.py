@@ -277,6 +277,21 @@ def create_loaders(args, rank: int, world: int):
             DataLoader(va, cfg.batch), DataLoader(te, cfg.eval_batch if adp else cfg.batch)]
 
 
+def _summary(iou: torch.Tensor, mae: torch.Tensor, sim: torch.Tensor) -> dict:
+    """Mean and standard deviation over all atoms of a pass (main.py:52-60, 112-119)."""
+    return {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
+            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
+            "similarity_index_std": float(sim.std())}
+
+
+def _pickle_lists(montecarlo: bool = False) -> dict:
+    """The empty lists of a batched pass's pickle: the keys of the batch-size-1 loop it stands in for, in that loop's
+    order (``inference``; ``montecarlo``, whose rounds store no temperature)."""
+    if montecarlo:
+        return {k: [] for k in ("pred", "true", "cell", "refcode", "pos", "atoms", "mae", "iou", "similarity_index")}
+    return {k: [] for k in ("pred", "true", "temp", "cell", "refcode", "pos", "atoms", "iou", "mae", "similarity_index")}
+
+
 def inference(model, loader, device, output_path: str) -> dict:
     """main.py:21-60: eval mode, per test batch (batch size 1 on ADP, loader/loader.py:121) the prediction, the target
     and the per-atom IoU / MAE / similarity index (train/metrics.py, here on the GPU); everything is pickled to
@@ -306,9 +321,7 @@ def inference(model, loader, device, output_path: str) -> dict:
     iou, mae, sim = (torch.cat(out[k]) for k in ("iou", "mae", "similarity_index"))
     with open(output_path, "wb") as f:
         pickle.dump(out, f)
-    return {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
-            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
-            "similarity_index_std": float(sim.std()), "output": output_path}
+    return {**_summary(iou, mae, sim), "output": output_path}
 
 
 def montecarlo(model, loader, device, output_path: str, rounds: int = 100, seed: int = 0) -> dict:
@@ -350,9 +363,7 @@ def montecarlo(model, loader, device, output_path: str, rounds: int = 100, seed:
             mae_all += out["mae"]
             sim_all += out["similarity_index"]
     iou, mae, sim = torch.cat(iou_all), torch.cat(mae_all), torch.cat(sim_all)
-    return {"rounds": rounds, "iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
-            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
-            "similarity_index_std": float(sim.std())}
+    return {"rounds": rounds, **_summary(iou, mae, sim)}
 
 
 def _batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> None:
@@ -390,8 +401,7 @@ def inference_batched(model, loader, device, output_path: str, rotations: int = 
     from cartnet_amd.metrics import adp_eval, bond_test, frame_mean, target_row_ptr
     from cartnet_amd.predict import frames, replicate
     model.eval()
-    out = {"pred": [], "true": [], "temp": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "iou": [], "mae": [],
-           "similarity_index": []}
+    out = _pickle_lists()
     gen = None
     if rotations > 1:
         out["rot_spread"] = []
@@ -429,9 +439,7 @@ def inference_batched(model, loader, device, output_path: str, rotations: int = 
     iou, mae, sim = (torch.cat(out[k]) for k in ("iou", "mae", "similarity_index"))
     with open(output_path, "wb") as f:
         pickle.dump(out, f)
-    result = {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
-              "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
-              "similarity_index_std": float(sim.std()), "output": output_path}
+    result = {**_summary(iou, mae, sim), "output": output_path}
     if rotations > 1:
         spread = torch.cat(out["rot_spread"])
         result.update(rotations=rotations, rot_spread_max=float(spread.max()) if spread.numel() else 0.0)
@@ -468,8 +476,7 @@ def montecarlo_batched(model, loader, device, output_path: str, rounds: int = 10
     iou_all, mae_all, sim_all = [], [], []
     with torch.no_grad():
         for i in range(rounds):
-            out = {"pred": [], "true": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "mae": [], "iou": [],
-                   "similarity_index": []}
+            out = _pickle_lists(montecarlo=True)
             for batch in loader:
                 if batch is None:
                     continue
@@ -487,9 +494,7 @@ def montecarlo_batched(model, loader, device, output_path: str, rounds: int = 10
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
     iou, mae, sim = torch.cat(iou_all), torch.cat(mae_all), torch.cat(sim_all)
-    return {"rounds": rounds, "iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
-            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
-            "similarity_index_std": float(sim.std())}
+    return {"rounds": rounds, **_summary(iou, mae, sim)}
 
 
 def check_predict_args(args) -> None:
@@ -547,22 +552,25 @@ def predict(model, args) -> dict:
             (write_cif if sym is None else write_cif_symmetric)(
                 os.path.join(args.predict_cif_dir, f"{out['name'][k]}.cif"), entry(out, k))
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
-    stats = torch.stack(out["stats"]) if n else torch.zeros(0, 3, dtype=torch.float64)
+
+    def stacked(key: str, width: int) -> torch.Tensor:     # [n, width] fp64: the per-crystal figures of one kernel
+        return torch.stack(out[key]) if n else torch.zeros(0, width, dtype=torch.float64)
+    stats = stacked("stats", 3)
     res = {"crystals": n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
            "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
     if rejected is not None:
         res["rejected"] = len(rejected)
     if cfg.rotations > 1:                             # per row, from the fp64 per-crystal (sum, maximum) of rot_spread
-        rot = torch.stack(out["rot_stats"]) if n else torch.zeros(0, 2, dtype=torch.float64)
+        rot = stacked("rot_stats", 2)
         res.update(rotations=cfg.rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
                    rot_spread_mean=float(rot[:, 0].sum()) / max(rows, 1))
     if args.rigid_bond:                               # over the directed bonds of the pass, from the fp64 per-crystal stats
-        bs = torch.stack(out["bond_stats"]) if n else torch.zeros(0, 4, dtype=torch.float64)
+        bs = stacked("bond_stats", 4)
         count = int(bs[:, 0].sum())
         res.update(bonds=count, rigid_bond_mean=float(bs[:, 1].sum()) / count if count else 0.0,
                    rigid_bond_max=float(bs[:, 2].max()) if n else 0.0, rigid_bond_over=int(bs[:, 3].sum()))
     if args.riding_h:                                 # from the fp64 per-crystal stats; the mean is over the non-orphans
-        hs = torch.stack(out["h_stats"]) if n else torch.zeros(0, 4, dtype=torch.float64)
+        hs = stacked("h_stats", 4)
         hydrogens, orphans = int(hs[:, 0].sum()), int(hs[:, 1].sum())
         res.update(hydrogens=hydrogens, h_orphans=orphans,
                    h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,

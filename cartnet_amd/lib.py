@@ -369,6 +369,8 @@ PROTOTYPES = {
     "cartnet_adp_riding_h": (C.c_int, [c_f32p, c_i64p, c_i64p, c_f32p, c_i64p, c_i64p, c_i64p, c_f32p, C.c_int32, C.c_float,
                                        C.c_float, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_i64p, c_i32p,
                                        c_f32p, c_f32p, C.c_void_p, c_stream]),
+    "cartnet_adp_temp_series": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, c_i64p, C.c_int32, C.c_int64, c_f32p, c_f32p,
+                                          c_f32p, c_i32p, C.c_void_p, c_stream]),
     "cartnet_collate": (C.c_int, [C.POINTER(Shard), c_i64p, c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int64, C.c_int64,
                                   C.c_int64, c_f32p, C.c_float, C.c_float, C.POINTER(Collated), c_stream]),
     "cartnet_shard_drop_h_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),

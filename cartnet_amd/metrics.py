@@ -421,6 +421,76 @@ def riding_h(u_eq: torch.Tensor, batch, tol: float = 0.4, f: float = 1.2, f_rot:
     return RidingH(parent, count, mult, u_iso, stats)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Temperature series (csrc/series_ops.hip): the exported ADPs of one batch predicted at T temperatures, as a least-squares
+# line per row and component -- how fast the ellipsoids grow, and whether they grow at all.
+
+class TempSeries(NamedTuple):
+    """What ``temp_series`` returns, all on the device.  ``slope`` [M,6] fp32 (A^2/K) and ``intercept`` [M,6] (the line
+    extrapolated to 0 K) of ``u_cif``'s six components; ``ueq_slope`` [M] and ``ueq_intercept`` [M], the same for ``u_eq``;
+    ``resid`` [M], the largest distance of a member from its line over the temperatures and the seven columns (a NaN is
+    kept); ``drops`` [M] int32, the steps on which ``u_eq`` falls; ``crystal_stats`` [B,4] fp64: per crystal the sum of
+    ``ueq_slope``, the rows whose ``ueq_slope`` is not > 0 (a NaN counts), the rows with ``drops > 0`` and the maximum of
+    ``resid``, (0, 0, 0, 0) without rows (``None`` if not requested)."""
+    slope: torch.Tensor
+    intercept: torch.Tensor
+    ueq_slope: torch.Tensor
+    ueq_intercept: torch.Tensor
+    resid: torch.Tensor
+    drops: torch.Tensor
+    crystal_stats: Optional[torch.Tensor]
+
+
+def check_temperatures(temps, least: int = 2, name: str = "temps") -> list:
+    """``temps`` (a sequence or a tensor of Kelvin values) as a list of floats; raises ``ValueError`` unless it holds at
+    least ``least`` values, all finite and > 0, strictly increasing."""
+    import math
+    values = [float(v) for v in (temps.tolist() if torch.is_tensor(temps) else temps)]
+    if len(values) < least:
+        raise ValueError(f"{name} must hold at least {least} temperature{'s' if least > 1 else ''}")
+    if not all(math.isfinite(v) and v > 0 for v in values):
+        raise ValueError(f"{name} must be finite and > 0 (Kelvin)")
+    if any(b <= a for a, b in zip(values, values[1:])):
+        raise ValueError(f"{name} must be strictly increasing")
+    return values
+
+
+def temp_series(u_cif: torch.Tensor, u_eq: torch.Tensor, temps, row_ptr: torch.Tensor, stats: bool = True) -> TempSeries:
+    """The line through a batch's exported ADPs over T temperatures: one call of ``cartnet_adp_temp_series``.  ``u_cif``
+    [T*M,6] and ``u_eq`` [T*M] temperature-major (rows ``t*M ... (t+1)*M-1``: ``AdpExport.u_cif`` / ``.u_eq`` of the batch
+    at ``temps[t]``); ``temps``: T >= 2 Kelvin values, a sequence or a tensor, finite, > 0 and strictly increasing (checked
+    on the host); ``row_ptr`` [B+1] over ONE temperature's rows.  fp64 arithmetic from the fp32 inputs, one rounding to
+    fp32 per result."""
+    _check_fp32("u_cif", u_cif, (6,), "[T*M,6]")
+    _check_fp32("u_eq", u_eq, (), "[T*M]")
+    dev = u_cif.device
+    if u_eq.device != dev or u_eq.shape[0] != u_cif.shape[0]:
+        raise ValueError("u_eq must hold one value per row of u_cif, on its device")
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    values = check_temperatures(temps)
+    T = len(values)
+    if int(u_cif.shape[0]) % T:
+        raise ValueError(f"u_cif holds {int(u_cif.shape[0])} rows: no multiple of the {T} temperatures of temps")
+    if torch.is_tensor(temps) and temps.device == dev and temps.dtype == torch.float32:
+        t_dev = temps.detach().reshape(-1).contiguous()
+    else:
+        t_dev = torch.tensor(values, dtype=torch.float32, device=dev)
+    u_cif, u_eq, M = u_cif.detach().contiguous(), u_eq.detach().contiguous(), int(u_cif.shape[0]) // T
+    slope = torch.empty((M, 7), dtype=torch.float32, device=dev)
+    intercept = torch.empty((M, 7), dtype=torch.float32, device=dev)
+    resid = torch.empty(M, dtype=torch.float32, device=dev)
+    drops = torch.empty(M, dtype=torch.int32, device=dev)
+    if M == 0:                                   # the entry point launches nothing
+        cs = torch.zeros((B, 4), dtype=torch.float64, device=dev) if stats else None
+    else:
+        cs = torch.empty((B, 4), dtype=torch.float64, device=dev) if stats else None
+        _l.check(_l.load().cartnet_adp_temp_series(u_cif.data_ptr(), u_eq.data_ptr(), t_dev.data_ptr(), T,
+                                                   row_ptr.data_ptr(), B, M, slope.data_ptr(), intercept.data_ptr(),
+                                                   resid.data_ptr(), drops.data_ptr(), _l.ptr(cs), _l.stream_ptr()),
+                 "cartnet_adp_temp_series")
+    return TempSeries(slope[:, :6], intercept[:, :6], slope[:, 6], intercept[:, 6], resid, drops, cs)
+
+
 def split_rows(t: torch.Tensor, rows) -> list:
     """The per-crystal pieces of a host tensor whose dim 0 runs over the rows of a batch: one transfer per batch, then
     this split by the crystals' row counts (a sequence of ints) gives the reference's one-entry-per-crystal lists.  Every

@@ -10,16 +10,19 @@ counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.
 rigid-bond figures of the exported ADPs (``metrics.bond_test``, csrc/bond_ops.hip): a plausibility report that needs no truth.
 With ``riding_h`` it brings an isotropic U for every hydrogen, a multiple of its parent's exported U_eq
 (``metrics.riding_h``, csrc/riding_ops.hip), and both writers fill ``_atom_site_U_iso_or_equiv`` for every atom.
+With ``temperatures`` every batch is predicted at T temperatures by one forward over a replica batch, the result has one
+entry per crystal and temperature, and the copy also brings a least-squares line per row through the T exports
+(``metrics.temp_series``, csrc/series_ops.hip).
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
-from .metrics import (adp_export, bond_test, check_export_status, edge_row_ptr, frame_mean, riding_h as riding_h_call,
-                      rotate_rows, split_rows, target_row_ptr, to_host)
+from .metrics import (adp_export, bond_test, check_export_status, check_temperatures, edge_row_ptr, frame_mean,
+                      riding_h as riding_h_call, rotate_rows, split_rows, target_row_ptr, temp_series, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
@@ -28,6 +31,9 @@ BOND_KEYS = ("bond_count", "bond_delta_mean", "bond_delta_max", "bond_worst", "b
              "bond_stats")                                                                # with rigid_bond only
 H_KEYS = ("u_iso", "h_parent", "h_count", "h_mult", "h_stats")                            # with riding_h only
 H_SYM_KEYS = ("u_iso_asym", "h_parent_asym")                                              # ... and a CifSymmetry
+SERIES_KEYS = ("t_slope", "t_intercept", "t_ueq_slope", "t_ueq_intercept", "t_resid", "t_drops", "t_stats")
+# with two or more temperatures the result has one more key, "series": a dict of lists, one entry per input crystal, with
+# "name", "temps" and SERIES_KEYS
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -55,16 +61,19 @@ def frames(B: int, K: int, gen: torch.Generator, device) -> torch.Tensor:
     return out
 
 
-def replicate(batch, K: int, R: torch.Tensor):
+def replicate(batch, K: int, R: Optional[torch.Tensor]):
     """``batch`` (on the device, atomic numbers in ``x``) K times over as ONE batch of ``K*B`` crystals with PyG's offsets,
     replica-major: crystal ``k*B + g`` is crystal g with ``cart_dir @ R[k, g]`` (one ``rotate_rows`` over the replica
     batch's edge segments: the arithmetic of ``DeviceShard.collate(list(sel) * K, R.view(K*B,3,3))``).  Everything else
-    (``x``, ``cart_dist``, ``pos``, ``non_H_mask``, ``cell``, ``temperature``, ``y``) is repeated.  Plain torch on the
+    (``x``, ``cart_dist``, ``pos``, ``non_H_mask``, ``cell``, ``temperature``, ``y``) is repeated.  ``R = None``: no frame
+    but the stored one, ``cart_dir`` is repeated as well (its bits, no rotation by the identity).  Plain torch on the
     device; ``batch`` is not modified.  Works on a batch of either loader (``ShardLoader``, ``data.DataLoader``)."""
     B, N, E = int(batch.num_graphs), int(batch.x.shape[0]), int(batch.edge_index.shape[1])
     dev = batch.x.device
-    if not (torch.is_tensor(R) and tuple(R.shape) == (K, B, 3, 3)):
+    if R is not None and not (torch.is_tensor(R) and tuple(R.shape) == (K, B, 3, 3)):
         raise ValueError("R must be a tensor [K,B,3,3]")
+    if K < 1:
+        raise ValueError("replicate needs K >= 1 replicas")
     if batch.x.dtype != torch.int64 or batch.x.dim() != 1:
         raise ValueError("replicate needs the atomic numbers in batch.x (a forward has overwritten them)")
     k = torch.arange(K, dtype=torch.int64, device=dev)
@@ -75,14 +84,40 @@ def replicate(batch, K: int, R: torch.Tensor):
     out.ptr = torch.cat([zero, (batch.ptr[1:].to(torch.int64).unsqueeze(0) + (k * N).unsqueeze(1)).reshape(-1)])
     out.edge_index = (batch.edge_index.unsqueeze(1) + (k * N).view(1, K, 1)).reshape(2, K * E)
     out.cart_dist = batch.cart_dist.repeat(K)
-    edge_ptr = torch.cat([zero, (edge_row_ptr(batch)[1:].unsqueeze(0) + (k * E).unsqueeze(1)).reshape(-1)])
-    out.cart_dir = rotate_rows(batch.cart_dir.repeat(K, 1).contiguous(), edge_ptr,
-                               R.reshape(K * B, 3, 3).to(torch.float32))
+    if R is None:
+        out.cart_dir = batch.cart_dir.repeat(K, 1)
+    else:
+        edge_ptr = torch.cat([zero, (edge_row_ptr(batch)[1:].unsqueeze(0) + (k * E).unsqueeze(1)).reshape(-1)])
+        out.cart_dir = rotate_rows(batch.cart_dir.repeat(K, 1).contiguous(), edge_ptr,
+                                   R.reshape(K * B, 3, 3).to(torch.float32))
     for name in ("pos", "non_H_mask", "cell", "temperature", "y"):
         t = getattr(batch, name, None)
         if torch.is_tensor(t):
             setattr(out, name, t.repeat(K, *([1] * (t.dim() - 1))))
     out.num_graphs = K * B
+    return out
+
+
+def standardised(temperatures, temp_mean: float, temp_std: float, device) -> torch.Tensor:
+    """[T] fp32 on ``device``: ``(fp32(T_t) - fp32(mean)) / fp32(std)`` with both steps rounded to fp32, taken on the host:
+    the bits the collation kernel gives a crystal stored at ``T_t`` (csrc/collate.hip: ``__fdiv_rn(__fsub_rn(...))``)."""
+    import numpy as np
+    t = (np.asarray(temperatures, dtype=np.float32) - np.float32(temp_mean)) / np.float32(temp_std)
+    return torch.from_numpy(t.astype(np.float32)).to(device)
+
+
+def replicate_temperatures(batch, temps: torch.Tensor, K: int = 1, R: Optional[torch.Tensor] = None):
+    """``batch`` at the T model-side temperatures ``temps`` ([T] fp32 on the device: ``standardised``) and in K frames as
+    ONE batch of ``T*K*B`` crystals, temperature-major, then frame, then crystal: crystal ``(t*K + k)*B + g`` is crystal g
+    with ``cart_dir @ R[k, g]`` and ``temperature = temps[t]``.  The T temperatures share the K frames ``R`` [K,B,3,3];
+    ``R = None`` (K = 1) rotates nothing.  ``replicate`` does the rest; ``batch`` is not modified."""
+    T, B = int(temps.shape[0]), int(batch.num_graphs)
+    if not (temps.dim() == 1 and T >= 1 and temps.dtype == torch.float32 and temps.device == batch.x.device):
+        raise ValueError("temps must be an fp32 tensor [T], T >= 1, on the batch's device")
+    if R is None and K != 1:
+        raise ValueError("K frames need their rotations R [K,B,3,3]")
+    out = replicate(batch, T * K, None if R is None else R.repeat(T, 1, 1, 1))
+    out.temperature = temps.repeat_interleave(K * B)
     return out
 
 
@@ -158,6 +193,10 @@ SPLIT = {"atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "u_cart
          "bond_count": "row", "bond_delta_mean": "row", "bond_delta_max": "row", "bond_worst": "row", "bond_over": "row",
          "bond_ueq_ratio": "row", "bond_stats": "crystal",
          "u_iso": "atom", "h_parent": "atom", "h_count": "atom", "h_mult": "atom", "h_stats": "crystal"}
+# The same for the keys of result["series"], which has one entry per input crystal: a table of its own, because SPLIT is
+# exactly the tensor keys of an entry (tests/test_cif_writers_golden.py holds it to that).
+SERIES_SPLIT = {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t_ueq_intercept": "row", "t_resid": "row",
+                "t_drops": "row", "t_stats": "crystal"}
 
 
 def _check_pass(loader, rotations: int):
@@ -187,6 +226,14 @@ def parent_asym(parent: torch.Tensor, batch, row_ptr: torch.Tensor, sym) -> torc
     return torch.where(parent >= 0, sym.row_asym[grow].to(torch.int64), parent)
 
 
+def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
+    """What a batch (on the device, before a forward) sends to the host whatever is predicted for it."""
+    z = batch.x.clone()                                                       # forward overwrites x
+    return {"z": z, "atoms": z[batch.non_H_mask], "cell": batch.cell, "_sel": batch._meta[:int(batch.num_graphs)],
+            "_row_ptr": row_ptr, "_atom_ptr": batch.ptr,
+            "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
+
+
 def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h) -> dict:
     """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
     one ``to_host``: tensors under their key of ``SPLIT``, and under names with a leading underscore what ``_host_stage``
@@ -194,13 +241,9 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     device = batch.x.device
     B = int(batch.num_graphs)
     row_ptr = target_row_ptr(batch)
-    sel = batch._meta[:B]
-    z = batch.x.clone()                                                       # forward overwrites x
-    dev = {"z": z, "atoms": z[batch.non_H_mask], "cell": batch.cell, "_sel": sel, "_row_ptr": row_ptr,
-           "_atom_ptr": batch.ptr,
-           "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
+    dev = _of_the_batch(batch, row_ptr)
     if "temperature" in shard.t:
-        dev["_temp"] = shard.t["temperature"][sel]                            # the collated one is standardised
+        dev["_temp"] = shard.t["temperature"][dev["_sel"]]                    # the collated one is standardised
     if rotations == 1:
         pred, _ = model(batch)
     else:
@@ -209,10 +252,20 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
         fm = frame_mean(members, R, row_ptr, stats=True)
         pred = fm.mean
         dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
+    batch.x = dev["z"]                                                        # the graph and the atomic numbers again
+    dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h))
+    return dev
+
+
+def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h) -> dict:
+    """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch`` (its atomic numbers in ``x``):
+    the export and, as asked for, the rigid-bond test, the riding hydrogens and the site average."""
+    device = batch.x.device
+    B = int(batch.num_graphs)
+    sel = batch._meta[:B]
     ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
-    dev.update(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
+    dev = dict(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
                stats=ex.crystal_stats, _status=ex.status)
-    batch.x = z                                                               # the graph and the atomic numbers again
     if rigid_bond is not None:
         dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
     if riding_h is not None:
@@ -230,8 +283,71 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     return dev
 
 
-def _host_stage(out: Dict[str, List], host: dict, shard, sym) -> None:
-    """Appends the crystals of one batch to ``out`` from the host copy of ``_device_stage``'s dict."""
+def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, riding_h, kelvin: list,
+                         temps: torch.Tensor) -> dict:
+    """One batch (on the device) at the T temperatures ``kelvin`` (``temps``: their model-side values, ``standardised``)
+    through ONE forward of ``replicate_temperatures`` and the kernels that follow it, those once per temperature on that
+    temperature's rows.  Returns what travels to the host in one ``to_host``: what does not depend on the temperature
+    under the names of ``_device_stage``, the keys of temperature t under ``"<key>@<t>"`` and, with T >= 2, the keys of
+    ``SERIES_KEYS`` (one ``temp_series`` call on the T exports)."""
+    B, T = int(batch.num_graphs), len(kelvin)
+    row_ptr = target_row_ptr(batch)
+    dev = _of_the_batch(batch, row_ptr)
+    R = frames(B, rotations, gen, batch.x.device) if rotations > 1 else None
+    members, _ = model(replicate_temperatures(batch, temps, rotations, R))    # batch.x stays: the replica's is overwritten
+    if R is not None:
+        dev["frames"] = R.transpose(0, 1)
+    rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
+    per = []
+    for t in range(T):
+        pred, d = members[t * rows:(t + 1) * rows], {}
+        if R is not None:
+            fm = frame_mean(pred, R, row_ptr, stats=True)
+            pred = fm.mean
+            d.update(rot_spread=fm.spread, rot_stats=fm.crystal_spread)
+        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h))
+        per.append(d)
+        dev.update({f"{k}@{t}": v for k, v in d.items()})
+    if T >= 2:
+        ts = temp_series(torch.cat([d["u_cif"] for d in per]), torch.cat([d["u_eq"] for d in per]), kelvin, row_ptr)
+        dev.update(t_slope=ts.slope, t_intercept=ts.intercept, t_ueq_slope=ts.ueq_slope,
+                   t_ueq_intercept=ts.ueq_intercept, t_resid=ts.resid, t_drops=ts.drops, t_stats=ts.crystal_stats)
+    return dev
+
+
+def _host_stage_series(out: Dict[str, List], series: Dict[str, List], host: dict, shard, sym, kelvin: list) -> None:
+    """Appends the entries of one batch to ``out``, crystal-major (crystal g at temperature t is entry ``g*T + t`` of the
+    batch), and its crystals to ``series``, from the host copy of ``_device_stage_series``'s dict: one ``_host_stage`` per
+    temperature on that temperature's keys."""
+    T = len(kelvin)
+    shared = {k: v for k, v in host.items() if "@" not in k and k not in SERIES_KEYS}
+    B = int(shared["_sel"].shape[0])
+    per = []
+    for t, kt in enumerate(kelvin):
+        mine = {k.rpartition("@")[0]: v for k, v in host.items() if k.endswith(f"@{t}")}
+        mine["_temp"] = torch.full((B,), kt, dtype=torch.float64)             # .tolist(): the Kelvin value as given
+        per.append({k: [] for k in out})
+        names, counts = _host_stage(per[t], {**shared, **mine}, shard, sym)
+    for g in range(B):
+        for t, kt in enumerate(kelvin):
+            for k in out:
+                out[k].append(f"{per[t][k][g]}_{kt:g}K" if k == "name" else per[t][k][g])
+    if T >= 2:
+        _split(series, {k: host[k] for k in SERIES_KEYS}, counts, SERIES_SPLIT)
+        series["name"] += names
+        series["temps"] += [torch.tensor(kelvin, dtype=torch.float32) for _ in names]
+
+
+def _split(out: Dict[str, List], host: dict, counts: dict, table: dict = SPLIT) -> None:
+    """Appends to ``out[k]`` the crystals' pieces of every host tensor ``host[k]``, cut as ``table[k]`` says."""
+    for k, t in host.items():
+        kind = table[k]
+        out[k] += [c.clone() for c in t.unbind(0)] if kind == "crystal" else split_rows(t, counts[kind])
+
+
+def _host_stage(out: Dict[str, List], host: dict, shard, sym):
+    """Appends the crystals of one batch to ``out`` from the host copy of ``_device_stage``'s dict.  Returns the crystals'
+    names and their counts of rows, atoms and sites."""
     ids = host.pop("_sel").tolist()
     names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
     check_export_status(host.pop("_status"), names)
@@ -243,9 +359,7 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym) -> None:
     riding = "_ueq_asym" in host                                              # what riding_asym takes, per site and per atom
     ueq_sites = split_rows(host.pop("_ueq_asym"), counts["site"]) if riding else None
     parents = split_rows(host.pop("_parent_asym"), counts["atom"]) if riding else None
-    for k, t in host.items():
-        kind = SPLIT[k]
-        out[k] += [c.clone() for c in t.unbind(0)] if kind == "crystal" else split_rows(t, counts[kind])
+    _split(out, host, counts)
     if sym is not None:
         out["asym_labels"] += [sym.labels[i] for i in ids]
         out["asym_frac"] += [torch.from_numpy(sym.frac[i]) for i in ids]
@@ -258,10 +372,11 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym) -> None:
                                 ueq_sites[g])
             out["u_iso_asym"].append(u)
             out["h_parent_asym"].append(pa)
+    return names, counts
 
 
-def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None
-                 ) -> Dict[str, List]:
+def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
+                 temperatures=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
@@ -289,24 +404,45 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     none), ``h_count`` [N] (hydrogens riding on a non-hydrogen atom), ``h_mult`` [N] and ``h_stats`` [4] fp64 (hydrogens,
     orphans, sum of the finite hydrogen ``u_iso``, hydrogens with a non-positive parent ``u_eq``); with ``sym`` also
     ``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``).  ``None`` is the pass
-    as it always was."""
+    as it always was.  ``temperatures`` = T >= 1 Kelvin values (strictly increasing, finite, > 0; otherwise ``ValueError``):
+    every batch is predicted at all of them by ONE forward of ``replicate_temperatures`` (with ``rotations`` = K that forward
+    holds ``T*K*B`` crystals, and the T temperatures share the batch's K frames), the model-side value of ``T_t`` being
+    ``standardised`` with the loader's ``temp_mean`` / ``temp_std``; the stored temperatures are not read.  The result then
+    has one entry per (crystal, temperature), crystal-major -- entry ``g*T + t`` -- each with the keys and shapes above,
+    ``temp`` = ``T_t`` as given and ``name`` = ``f"{name}_{T_t:g}K"``.  With T >= 2 it has one more key, ``series``: a dict
+    of lists with one entry per input crystal, in the loader's order -- ``name`` (unsuffixed), ``temps`` [T] fp32 and, from
+    one ``metrics.temp_series`` per batch on the exported ``u_cif`` / ``u_eq`` (with rotations the frame means'),
+    ``t_slope`` [n,6] (A^2/K) and ``t_intercept`` [n,6] of ``u_cif``, ``t_ueq_slope`` [n], ``t_ueq_intercept`` [n],
+    ``t_resid`` [n], ``t_drops`` [n] int32 and ``t_stats`` [4] fp64 (sum of ``t_ueq_slope``, rows whose U_eq slope is not
+    > 0, rows with a drop, largest ``t_resid``).  ``None`` is the pass as it always was."""
     rotations = int(rotations)
     shard = _check_pass(loader, rotations)
+    kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
     model.eval()
     out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
                             + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())
                             + (H_KEYS if riding_h is not None else ())
                             + (H_SYM_KEYS if riding_h is not None and sym is not None else ())}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
+    if kelvin is not None:
+        temps = standardised(kelvin, loader.temp_mean, loader.temp_std, device)
+        series: Dict[str, List] = {k: [] for k in ("name", "temps") + SERIES_KEYS}
     with torch.no_grad():
         for batch in loader:
             if batch is None:
                 continue
             batch.to(device)
-            _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h)),
-                        shard, sym)
+            if kelvin is None:
+                _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h)),
+                            shard, sym)
+            else:
+                _host_stage_series(out, series, to_host(_device_stage_series(model, batch, sym, rotations, gen, rigid_bond,
+                                                                             riding_h, kelvin, temps)),
+                                   shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
+    if kelvin is not None and len(kelvin) >= 2:
+        out["series"] = series
     return out
 
 

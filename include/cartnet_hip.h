@@ -504,6 +504,32 @@ int cartnet_adp_riding_h(const float* u_eq, const int64_t* z, const int64_t* edg
                          int64_t* parent, int32_t* count, float* mult, float* u_iso, double* crystal_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * A least-squares line per row and component through the exported ADPs of one batch over T temperatures.  The reference
+ * predicts every crystal at the one temperature it is stored with (main.py:21-60); the model reads the temperature, so
+ * one batch replicated T times answers how the ellipsoids grow.
+ *   u_cif [T*M,6] and u_eq [T*M] fp32, temperature-major: member t of row i sits at t*M + i (the stacked outputs of
+ *   cartnet_adp_export, one call per temperature); temps [T] fp32 Kelvin on the device, strictly increasing (the caller
+ *   checks that on the host); row_ptr [B+1] int64 over ONE temperature's M rows, as for cartnet_adp_eval (empty crystals
+ *   are legal).
+ * Per row, in fp64 from the fp32 inputs, t ascending, no contraction, every result stored as fp32 with one rounding;
+ * seven columns, c = 0..5 for u_cif and c = 6 for u_eq:
+ *   tbar = (sum_t T_t) / T,  Stt = sum_t (T_t - tbar)^2
+ *   centre_c = (sum_t u_tc) / T
+ *   slope [M,7]      slope_c = (sum_t (T_t - tbar) u_tc) / Stt
+ *   intercept [M,7]  centre_c - slope_c tbar                 (the line extrapolated to 0 K)
+ *   resid [M]        the largest |u_tc - (centre_c + slope_c (T_t - tbar))| over all t and all seven columns; a NaN is kept
+ *   drops [M] int32  the number of t with u_eq[t+1] < u_eq[t] (strict; a NaN is no drop)
+ * Per crystal (one wave each, rows in order, from the values as stored):
+ *   crystal_stats [B,4] fp64 (or NULL) = (sum of slope[:,6], rows whose slope[:,6] is not > 0 -- a NaN counts --, rows
+ *   with drops > 0, maximum of resid with a NaN kept); without rows (0, 0, 0, 0).
+ * T < 2 is an error.  M == 0 or B == 0: returns 0 without a launch and writes nothing.  No output may alias an input.  No
+ * atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_temp_series(const float* u_cif, const float* u_eq, const float* temps, int32_t T, const int64_t* row_ptr,
+                            int32_t B, int64_t M, float* slope, float* intercept, float* resid, int32_t* drops,
+                            double* crystal_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Training loss (reference: train/metrics.py:15-28, called from train/train.py:173-178): L1Loss and MSELoss with mean
  * reduction over the n = M*9 (or Bg) elements of pred / truth, both from one pair of small launches (slices, then
  * their sum), and their gradient from one more:

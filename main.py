@@ -21,7 +21,9 @@ frames (the stored one and K - 1 random rotations), bring the predictions back a
 deviation of a frame from it per atom.  ``--rigid_bond`` adds Hirshfeld's rigid-bond test to ``--predict`` and
 ``--inference``: a plausibility figure per bonded pair of atoms that needs no truth (cartnet_amd/bonds.py,
 ``metrics.bond_test``).  ``--riding_h`` gives every hydrogen of a ``--predict`` pass an isotropic U by the riding model, a
-multiple of its parent's predicted U_eq (``metrics.riding_h``).  There is no CPU path: the model runs on an AMD GPU only.
+multiple of its parent's predicted U_eq (``metrics.riding_h``).  ``--predict_temperatures SPEC`` predicts every crystal of a
+``--predict`` pass at a series of temperatures in one forward per batch and fits a line per atom through them
+(``metrics.temp_series``).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -118,6 +120,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="what --predict reads: a shard file (FILE.cnshard), a CIF file (FILE.cif) or a directory of CIF files")
     p.add_argument("--predict_temperature", type=float, default=None,
                    help="--predict from CIF files: the temperature in Kelvin of a crystal whose file gives none")
+    p.add_argument("--predict_temperatures", type=str, default=None, metavar="SPEC",
+                   help="--predict: predict every crystal at these temperatures (Kelvin) instead of its stored one, in one "
+                        "pass: a list 100,150,200 or a range A:B:STEP (100:300:50 is five values; B is included when STEP "
+                        "reaches it).  One forward then holds --eval_batch * T (* --rotations) crystals, the output has one "
+                        "entry and one CIF per crystal and temperature (NAME_150K), and with two or more temperatures a "
+                        "least-squares line per atom through them (series).  Not with --disable_temp, and with --predict "
+                        "only")
     p.add_argument("--predict_output", type=str, default="./predictions.pkl")
     p.add_argument("--predict_cif_dir", type=str, default=None, help="--predict: also write one CIF per crystal here (a shard's crystals in P1, a CIF's in its own setting)")
     p.add_argument("--rotations", type=int, default=1,
@@ -497,8 +506,49 @@ def montecarlo_batched(model, loader, device, output_path: str, rounds: int = 10
     return {"rounds": rounds, **_summary(iou, mae, sim)}
 
 
+def parse_temperatures(spec: str) -> list:
+    """``--predict_temperatures SPEC`` as a list of Kelvin values: ``100,150,200``, or ``A:B:STEP`` = A, A + STEP, ... up
+    to and including B when STEP reaches it (``100:300:50`` is five values, ``100:290:50`` four).  Raises ``SystemExit``
+    with a message for an empty spec, a value that is no number, one that is not finite or not > 0, a list that is not
+    strictly increasing and a STEP that is not > 0.  On the host: no device is touched."""
+    import math
+    flag = "--predict_temperatures"
+
+    def number(text: str) -> float:
+        try:
+            v = float(text)
+        except ValueError:
+            raise SystemExit(f"{flag}: {text.strip()!r} is no number") from None
+        if not math.isfinite(v):
+            raise SystemExit(f"{flag}: {text.strip()!r} is not finite")
+        return v
+    spec = (spec or "").strip()
+    if not spec:
+        raise SystemExit(f"{flag}: empty (a list 100,150,200 or a range A:B:STEP)")
+    if ":" in spec:
+        parts = spec.split(":")
+        if len(parts) != 3:
+            raise SystemExit(f"{flag}: a range is A:B:STEP, got {spec!r}")
+        a, b, step = (number(p) for p in parts)
+        if step <= 0:
+            raise SystemExit(f"{flag}: STEP must be > 0, got {step:g}")
+        count = math.floor((b - a) / step + 1e-9) + 1                        # B itself when STEP reaches it
+        if count < 1:
+            raise SystemExit(f"{flag}: the range {spec!r} is empty")
+        values = [a + k * step for k in range(count)]
+    else:
+        values = [number(p) for p in spec.split(",")]
+    if any(v <= 0 for v in values):
+        raise SystemExit(f"{flag}: temperatures are Kelvin values > 0")
+    if any(q <= p for p, q in zip(values, values[1:])):
+        raise SystemExit(f"{flag}: the temperatures must be strictly increasing")
+    return values
+
+
 def check_predict_args(args) -> None:
     """``--predict``'s requirements, checked before anything touches the device."""
+    if not args.predict:
+        raise SystemExit("--predict_temperatures serves --predict only")
     if cfg.dataset.name != "ADP":
         raise SystemExit("--predict: ADPs are predicted for the ADP dataset only")
     if args.checkpoint_path is None:
@@ -511,6 +561,11 @@ def check_predict_args(args) -> None:
                          "ecomformer)")
     if args.riding_h and not cfg.use_H:
         raise SystemExit("--riding_h with --disable_H: the hydrogens are gone, so there is nothing to ride")
+    if args.predict_temperatures is not None:
+        if not cfg.use_temp:
+            raise SystemExit("--predict_temperatures with --disable_temp: the model has no temperature input, so the "
+                             "series would be flat by construction")
+        parse_temperatures(args.predict_temperatures)
 
 
 def predict(model, args) -> dict:
@@ -541,11 +596,13 @@ def predict(model, args) -> dict:
     bond = {"rigid_bond": (args.bond_tolerance, args.rigid_bond_threshold)} if args.rigid_bond else {}
     ride = ({"riding_h": (args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating)}
             if args.riding_h else {})
+    temps = parse_temperatures(args.predict_temperatures) if args.predict_temperatures is not None else None
+    series = {"temperatures": temps} if temps is not None else {}
     out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
-                       rotations=cfg.rotations, seed=cfg.seed, **bond, **ride)
+                       rotations=cfg.rotations, seed=cfg.seed, **bond, **ride, **series)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
-    n = len(out["name"])
+    n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
     if args.predict_cif_dir:
         os.makedirs(args.predict_cif_dir, exist_ok=True)
         for k in range(n):
@@ -553,13 +610,20 @@ def predict(model, args) -> dict:
                 os.path.join(args.predict_cif_dir, f"{out['name'][k]}.cif"), entry(out, k))
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
 
-    def stacked(key: str, width: int) -> torch.Tensor:     # [n, width] fp64: the per-crystal figures of one kernel
-        return torch.stack(out[key]) if n else torch.zeros(0, width, dtype=torch.float64)
+    def stacked(key: str, width: int, of: dict = out) -> torch.Tensor:   # [n, width] fp64: one kernel's per-crystal figures
+        return torch.stack(of[key]) if of[key] else torch.zeros(0, width, dtype=torch.float64)
     stats = stacked("stats", 3)
-    res = {"crystals": n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
+    res = {"crystals": n // len(temps) if temps else n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
            "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
     if rejected is not None:
         res["rejected"] = len(rejected)
+    if temps is not None:
+        res.update(entries=n, temperatures=temps)
+    if "series" in out:                               # from the fp64 per-crystal stats of the lines; rows of ONE temperature
+        ts = stacked("t_stats", 4, out["series"])
+        res.update(ueq_slope_mean=float(ts[:, 0].sum()) / max(rows // len(temps), 1),
+                   non_increasing_rows=int(ts[:, 1].sum()), rows_with_drops=int(ts[:, 2].sum()),
+                   series_resid_max=float(ts[:, 3].max()) if len(ts) else 0.0)
     if cfg.rotations > 1:                             # per row, from the fp64 per-crystal (sum, maximum) of rot_spread
         rot = stacked("rot_stats", 2)
         res.update(rotations=cfg.rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
@@ -581,7 +645,7 @@ def predict(model, args) -> dict:
 def main(argv=None) -> dict:
     args = build_parser().parse_args(argv)
     fill_cfg(args)
-    if args.predict:
+    if args.predict or args.predict_temperatures is not None:
         check_predict_args(args)
     torch.set_num_threads(args.threads)
     rank, world, local = cdist.init_from_env()

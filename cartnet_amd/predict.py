@@ -1,6 +1,6 @@
 """ADPs for crystals that have no targets, in the convention crystallographic tools read.
 
-``predict_adps`` is the prediction-side counterpart of ``main.inference_batched``: per batch of a resident shard (labeled or
+``predict_adps`` is the prediction-side counterpart of ``evaluate.inference``: per batch of a resident shard (labeled or
 not) one forward, one ``adp_export`` (csrc/export_ops.hip: the predictions on the unit reciprocal axes -- the inverse of the
 transform the reference applied to the dataset's targets, dataset/extract_csd_data.py:115-123 -- with U_eq and the
 principal values / axes), the fractional coordinates, ONE device-to-host copy (``metrics.to_host``) and a split by row
@@ -13,6 +13,9 @@ With ``riding_h`` it brings an isotropic U for every hydrogen, a multiple of its
 With ``temperatures`` every batch is predicted at T temperatures by one forward over a replica batch, the result has one
 entry per crystal and temperature, and the copy also brings a least-squares line per row through the T exports
 (``metrics.temp_series``, csrc/series_ops.hip).
+Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in memory),
+``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the forward in K
+frames that this pass and ``evaluate.inference`` share.
 """
 from __future__ import annotations
 
@@ -96,6 +99,61 @@ def replicate(batch, K: int, R: Optional[torch.Tensor]):
             setattr(out, name, t.repeat(K, *([1] * (t.dim() - 1))))
     out.num_graphs = K * B
     return out
+
+
+def frame_stage(model, batch, row_ptr: torch.Tensor, rotations: int, gen, stats: bool):
+    """The prediction of ``batch`` (on the device, atomic numbers in ``x``) in ``rotations`` = K frames: K = 1 is the plain
+    forward; K > 1 is ONE forward of ``replicate(batch, K, R)`` with ``R = frames(B, K, gen, device)`` and the members'
+    ``metrics.frame_mean`` (``stats``: its per-crystal figures as well).  Returns ``(pred, R, FrameMean)``, the last two
+    ``None`` for K = 1; ``batch`` comes back with its atomic numbers in ``x`` (a forward puts the features there: it
+    replaces the tensor and writes into nothing, so no copy is taken)."""
+    if rotations == 1:
+        atoms = batch.x
+        pred, _ = model(batch)
+        batch.x = atoms
+        return pred, None, None
+    R = frames(int(batch.num_graphs), rotations, gen, batch.x.device)
+    members, _ = model(replicate(batch, rotations, R))                        # batch.x stays: the replica's is overwritten
+    fm = frame_mean(members, R, row_ptr, stats=stats)
+    return fm.mean, R, fm
+
+
+def parse_temperatures(spec: str) -> list:
+    """``--predict_temperatures SPEC`` as a list of Kelvin values: ``100,150,200``, or ``A:B:STEP`` = A, A + STEP, ... up
+    to and including B when STEP reaches it (``100:300:50`` is five values, ``100:290:50`` four).  Raises ``SystemExit``
+    with a message for an empty spec, a value that is no number, one that is not finite or not > 0, a list that is not
+    strictly increasing and a STEP that is not > 0.  On the host: no device is touched."""
+    flag = "--predict_temperatures"
+
+    def number(text: str) -> float:
+        try:
+            v = float(text)
+        except ValueError:
+            raise SystemExit(f"{flag}: {text.strip()!r} is no number") from None
+        if not math.isfinite(v):
+            raise SystemExit(f"{flag}: {text.strip()!r} is not finite")
+        return v
+    spec = (spec or "").strip()
+    if not spec:
+        raise SystemExit(f"{flag}: empty (a list 100,150,200 or a range A:B:STEP)")
+    if ":" in spec:
+        parts = spec.split(":")
+        if len(parts) != 3:
+            raise SystemExit(f"{flag}: a range is A:B:STEP, got {spec!r}")
+        a, b, step = (number(p) for p in parts)
+        if step <= 0:
+            raise SystemExit(f"{flag}: STEP must be > 0, got {step:g}")
+        count = math.floor((b - a) / step + 1e-9) + 1                        # B itself when STEP reaches it
+        if count < 1:
+            raise SystemExit(f"{flag}: the range {spec!r} is empty")
+        values = [a + k * step for k in range(count)]
+    else:
+        values = [number(p) for p in spec.split(",")]
+    if any(v <= 0 for v in values):
+        raise SystemExit(f"{flag}: temperatures are Kelvin values > 0")
+    if any(q <= p for p, q in zip(values, values[1:])):
+        raise SystemExit(f"{flag}: the temperatures must be strictly increasing")
+    return values
 
 
 def standardised(temperatures, temp_mean: float, temp_std: float, device) -> torch.Tensor:
@@ -238,21 +296,13 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
     one ``to_host``: tensors under their key of ``SPLIT``, and under names with a leading underscore what ``_host_stage``
     needs to cut and check them."""
-    device = batch.x.device
-    B = int(batch.num_graphs)
     row_ptr = target_row_ptr(batch)
     dev = _of_the_batch(batch, row_ptr)
     if "temperature" in shard.t:
         dev["_temp"] = shard.t["temperature"][dev["_sel"]]                    # the collated one is standardised
-    if rotations == 1:
-        pred, _ = model(batch)
-    else:
-        R = frames(B, rotations, gen, device)
-        members, _ = model(replicate(batch, rotations, R))
-        fm = frame_mean(members, R, row_ptr, stats=True)
-        pred = fm.mean
+    pred, R, fm = frame_stage(model, batch, row_ptr, rotations, gen, stats=True)
+    if fm is not None:
         dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
-    batch.x = dev["z"]                                                        # the graph and the atomic numbers again
     dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h))
     return dev
 
@@ -444,6 +494,74 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     if kelvin is not None and len(kelvin) >= 2:
         out["series"] = series
     return out
+
+
+def load_input(path: str, device, temperature: Optional[float] = None):
+    """What ``--predict_input`` names, as ``(shard, sym, rejected)``.  A shard file: the ``DeviceShard`` of it, ``None``,
+    ``None``.  A CIF file or a directory of them: the crystals the reference's filters accept, expanded to their unit cells
+    on the GPU in memory (``symmetry.expand``; no shard file is written), their ``CifSymmetry`` and the list of
+    ``(name, reason)`` of the crystals that were not accepted, which also go to stderr one per line; ``temperature`` is
+    the Kelvin value of a crystal whose file gives none.  No usable crystal raises ``SystemExit``."""
+    import os
+    from .shard import DeviceShard
+    if not (os.path.isdir(path) or path.lower().endswith(".cif")):
+        return DeviceShard.from_file(path, device), None, None
+    import sys
+    from .cif import load_crystals
+    from .symmetry import expand
+    crystals, rejected = load_crystals(path, False, temperature)
+    for name, why in rejected:
+        print(f"rejected\t{name}\t{why}", file=sys.stderr)
+    if not crystals:
+        raise SystemExit(f"--predict: no usable crystal in {path}")
+    arrays, sym = expand(crystals, device, labeled=False, temperature=temperature)
+    return DeviceShard(arrays, device, labeled=False, names=sym.names), sym, rejected
+
+
+def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir: Optional[str] = None, rejected=None,
+                    rotations: int = 1, temperatures: Optional[list] = None) -> dict:
+    """The result line of a whole ``predict_adps`` pass from its result ``out`` (``rotations`` and ``temperatures`` as the
+    pass was given them), summed from the kernels' fp64 per-crystal statistics: ``crystals``, ``rows``, ``u_eq_mean`` and
+    ``non_positive_rows``, then ``output`` and ``cif_dir`` as given and the number of ``rejected`` crystals if there is
+    such a list (``load_input``); with ``temperatures`` ``entries`` and ``temperatures``, and from a ``series``
+    ``ueq_slope_mean``, ``non_increasing_rows``, ``rows_with_drops`` and ``series_resid_max``; with frames ``rotations``,
+    ``rot_spread_max`` and ``rot_spread_mean``; with the rigid-bond test ``bonds``, ``rigid_bond_mean`` / ``_max`` /
+    ``_over``; with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
+    ``h_non_positive``.  A pass without crystals gives zeros."""
+    n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
+    rows = sum(int(t.shape[0]) for t in out["u_eq"])
+
+    def stacked(key: str, width: int, of: dict = out) -> torch.Tensor:   # [n, width] fp64: one kernel's per-crystal figures
+        return torch.stack(of[key]) if of[key] else torch.zeros(0, width, dtype=torch.float64)
+    stats = stacked("stats", 3)
+    res = {"crystals": n // len(temperatures) if temperatures else n, "rows": rows,
+           "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1), "non_positive_rows": int(stats[:, 2].sum()),
+           "output": output, "cif_dir": cif_dir}
+    if rejected is not None:
+        res["rejected"] = len(rejected)
+    if temperatures is not None:
+        res.update(entries=n, temperatures=temperatures)
+    if "series" in out:                               # from the fp64 per-crystal stats of the lines; rows of ONE temperature
+        ts = stacked("t_stats", 4, out["series"])
+        res.update(ueq_slope_mean=float(ts[:, 0].sum()) / max(rows // len(temperatures), 1),
+                   non_increasing_rows=int(ts[:, 1].sum()), rows_with_drops=int(ts[:, 2].sum()),
+                   series_resid_max=float(ts[:, 3].max()) if len(ts) else 0.0)
+    if rotations > 1:                                 # per row, from the fp64 per-crystal (sum, maximum) of rot_spread
+        rot = stacked("rot_stats", 2)
+        res.update(rotations=rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
+                   rot_spread_mean=float(rot[:, 0].sum()) / max(rows, 1))
+    if "bond_stats" in out:                           # over the directed bonds of the pass, from the fp64 per-crystal stats
+        bs = stacked("bond_stats", 4)
+        count = int(bs[:, 0].sum())
+        res.update(bonds=count, rigid_bond_mean=float(bs[:, 1].sum()) / count if count else 0.0,
+                   rigid_bond_max=float(bs[:, 2].max()) if n else 0.0, rigid_bond_over=int(bs[:, 3].sum()))
+    if "h_stats" in out:                              # from the fp64 per-crystal stats; the mean is over the non-orphans
+        hs = stacked("h_stats", 4)
+        hydrogens, orphans = int(hs[:, 0].sum()), int(hs[:, 1].sum())
+        res.update(hydrogens=hydrogens, h_orphans=orphans,
+                   h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,
+                   h_non_positive=int(hs[:, 3].sum()))
+    return res
 
 
 def entry(result: Dict[str, List], k: int) -> dict:

@@ -5,7 +5,8 @@ What is kept: the argparse flags and their defaults (main.py:123-154), the copy 
 (:156-188), seed -> loaders -> ``create_model()`` -> Adam -> ``train`` (:196-227), OneCycleLR, gradient accumulation
 with the last-iteration flush, best-validation checkpoint ``{"model_state", "optimizer_state"}`` under
 ``results/<name>/<seed>/ckpt/best.ckpt`` (train/train.py:91-102) and its reload for the test pass (:114-115),
-``--inference`` / ``--montecarlo`` on a checkpoint (main.py:21-119, 212-225).
+``--inference`` / ``--montecarlo`` on a checkpoint (main.py:21-119, 212-225; the passes are in cartnet_amd/evaluate.py).
+This file holds the parser, ``fill_cfg``, the dataset recipe and the loaders, the argument checks and the dispatch.
 What differs: the datasets (CSD / Jarvis need licences or the network) are replaced by synthetic ADP-shaped crystals
 (``--synthetic N`` graphs, ``--atoms lo hi``), wandb / GraphGym logging are dropped, ``--device`` replaces the hard-coded
 "cuda:0", and under ``torch.distributed.run`` the crystals are sharded across ranks with one gradient all-reduce per
@@ -36,12 +37,13 @@ from typing import Optional, Tuple
 import torch
 
 from cartnet_amd import distributed as cdist
+from cartnet_amd import evaluate
 from cartnet_amd.bonds import BOND_TOLERANCE, RIDING_FACTOR, RIDING_FACTOR_ROTATING, RIGID_BOND_THRESHOLD
 from cartnet_amd.config import cfg, set_cfg
 from cartnet_amd.data import DataLoader, optimize_cell, remove_hydrogens
 from cartnet_amd.master import create_model
-from cartnet_amd.metrics import to_host as _to_host
 from cartnet_amd.optim import FlatAdam, one_cycle_lr, one_cycle_momentum
+from cartnet_amd.predict import parse_temperatures
 from cartnet_amd.synthetic import augment_data, make_crystal
 from cartnet_amd.train import eval_epoch, train_epoch
 
@@ -110,7 +112,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "--atoms; the radius graph is rebuilt on the GPU where the reference would rebuild it")
     p.add_argument("--eval_batch", type=int, default=1,
                    help="ADP: crystals per batch of the test pass, --inference and --montecarlo.  The reference tests at "
-                        "batch size 1 (the default, and that code path); N > 1 runs N crystals per forward and still "
+                        "batch size 1 (the default); N > 1 runs N crystals per forward and still "
                         "reports batch size 1's results: per-crystal means, one rotation per crystal, one pickle entry "
                         "per crystal.  Other datasets ignore it (they test at --batch)")
     p.add_argument("--predict", action="store_true",
@@ -229,11 +231,19 @@ def shard_recipe(shards: list):
         req = graph_request(cfg, s.graph, s.has_graph)
         if req is not None:
             shards[i] = s.with_radius_graph(*req)
+    return hydrogen_and_cell_steps(shards), ((TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0))
+
+
+def hydrogen_and_cell_steps(shards: list) -> list:
+    """The steps of the recipe that follow the graph, on resident shards: hydrogen removal under ``--disable_H``
+    (loader/loader.py:29-32: DatasetADP(hydrogens=cfg.use_H), whatever the model), then the canonical lattice frame of
+    iComformer on ADP (loader/loader.py:24-32: DatasetADP(optimize_cell=True))."""
+    adp = cfg.dataset.name == "ADP"
     if adp and not cfg.use_H:
         shards = [s.without_hydrogens() for s in shards]
     if adp and cfg.model == "icomformer":
         shards = [s.with_optimized_cell() for s in shards]
-    return shards, ((TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0))
+    return shards
 
 
 def shard_loaders(rank: int, world: int):
@@ -262,287 +272,21 @@ def create_loaders(args, rank: int, world: int):
     tr = [graphs[i] for i in perm[:n_tr]]
     va = [graphs[i] for i in perm[n_tr:n_tr + n_va]] or tr[:1]
     te = [graphs[i] for i in perm[n_tr + n_va:]] or tr[:1]
-    no_h = adp and not cfg.use_H            # loader/loader.py:29-32: DatasetADP(hydrogens=cfg.use_H), whatever the model
-    # loader/loader.py:24-32: iComformer on ADP reads DatasetADP(optimize_cell=True); as in DatasetADP.get the order is
-    # cap on the full crystal, hydrogen removal, canonical lattice frame
-    canonical = adp and cfg.model == "icomformer"
+    # as in DatasetADP.get the order is: cap on the full crystal, hydrogen removal, canonical lattice frame
     if args.resident_dataset:                                             # cartnet_amd/shard.py
         from cartnet_amd.shard import DeviceShard, ShardLoader
-        shards = [DeviceShard.from_data_list(part, cfg.device) for part in (tr, va, te)]
-        if no_h:
-            shards = [s.without_hydrogens() for s in shards]
-        if canonical:
-            shards = [s.with_optimized_cell() for s in shards]
+        shards = hydrogen_and_cell_steps([DeviceShard.from_data_list(part, cfg.device) for part in (tr, va, te)])
         return [ShardLoader(shards[0], cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world,
                             augment=cfg.augment),
                 ShardLoader(shards[1], cfg.batch), ShardLoader(shards[2], cfg.eval_batch if adp else cfg.batch)]
-    if no_h:
+    if adp and not cfg.use_H:                                             # the host form of hydrogen_and_cell_steps
         tr, va, te = ([remove_hydrogens(d) for d in part] for part in (tr, va, te))
-    if canonical:
+    if adp and cfg.model == "icomformer":
         tr, va, te = ([optimize_cell(d) for d in part] for part in (tr, va, te))
     gen = torch.Generator().manual_seed(cfg.seed + 1000 * rank)
     aug = (lambda d: augment_data(d, gen)) if cfg.augment else None
     return [DataLoader(tr, cfg.batch, shuffle=True, seed=cfg.seed, rank=rank, world_size=world, transform=aug),
             DataLoader(va, cfg.batch), DataLoader(te, cfg.eval_batch if adp else cfg.batch)]
-
-
-def _summary(iou: torch.Tensor, mae: torch.Tensor, sim: torch.Tensor) -> dict:
-    """Mean and standard deviation over all atoms of a pass (main.py:52-60, 112-119)."""
-    return {"iou_mean": float(iou.mean()), "iou_std": float(iou.std()), "mae_mean": float(mae.mean()),
-            "mae_std": float(mae.std()), "similarity_index_mean": float(sim.mean()),
-            "similarity_index_std": float(sim.std())}
-
-
-def _pickle_lists(montecarlo: bool = False) -> dict:
-    """The empty lists of a batched pass's pickle: the keys of the batch-size-1 loop it stands in for, in that loop's
-    order (``inference``; ``montecarlo``, whose rounds store no temperature)."""
-    if montecarlo:
-        return {k: [] for k in ("pred", "true", "cell", "refcode", "pos", "atoms", "mae", "iou", "similarity_index")}
-    return {k: [] for k in ("pred", "true", "temp", "cell", "refcode", "pos", "atoms", "iou", "mae", "similarity_index")}
-
-
-def inference(model, loader, device, output_path: str) -> dict:
-    """main.py:21-60: eval mode, per test batch (batch size 1 on ADP, loader/loader.py:121) the prediction, the target
-    and the per-atom IoU / MAE / similarity index (train/metrics.py, here on the GPU); everything is pickled to
-    ``output_path``.  The synthetic crystals carry no refcode / original temperature: those two lists stay empty."""
-    import pickle
-    from cartnet_amd.metrics import compute_3D_IoU, get_similarity_index
-    model.eval()
-    out = {"pred": [], "true": [], "temp": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "iou": [], "mae": [],
-           "similarity_index": []}
-    with torch.no_grad():
-        for batch in loader:
-            if batch is None:
-                continue
-            batch.to(device)
-            out["cell"].append(batch.cell.detach().to("cpu"))
-            out["atoms"].append(batch.x[batch.non_H_mask].detach().to("cpu"))     # read BEFORE forward overwrites x (main.py:40)
-            if hasattr(batch, "pos"):
-                out["pos"].append(batch.pos[batch.non_H_mask].detach().to("cpu"))
-            pred, true = model(batch)
-            out["pred"].append(pred.detach().to("cpu"))
-            out["true"].append(true.detach().to("cpu"))
-            out["iou"].append(compute_3D_IoU(pred, true).detach().to("cpu"))
-            out["mae"].append((pred - true).abs().detach().to("cpu"))
-            out["similarity_index"].append(get_similarity_index(pred, true).detach().to("cpu"))
-    if hasattr(model, "flush_graph_checks"):
-        model.flush_graph_checks()
-    iou, mae, sim = (torch.cat(out[k]) for k in ("iou", "mae", "similarity_index"))
-    with open(output_path, "wb") as f:
-        pickle.dump(out, f)
-    return {**_summary(iou, mae, sim), "output": output_path}
-
-
-def montecarlo(model, loader, device, output_path: str, rounds: int = 100, seed: int = 0) -> dict:
-    """main.py:62-119: for ``rounds`` passes over the test loader, predict, rotate ``cart_dir`` by a uniform random
-    rotation R, predict again and compare with the rotated first prediction R^T pred R (IoU, MAE, similarity index): how
-    equivariant the trained network has become.  One pickle per round, as the reference writes them."""
-    import pickle
-    from cartnet_amd.metrics import compute_3D_IoU, get_similarity_index
-    from cartnet_amd.shard import random_rotations
-    model.eval()
-    gen = torch.Generator(device=device).manual_seed(seed)
-    iou_all, mae_all, sim_all = [], [], []
-    with torch.no_grad():
-        for i in range(rounds):
-            out = {"pred": [], "true": [], "cell": [], "refcode": [], "pos": [], "atoms": [], "mae": [], "iou": [],
-                   "similarity_index": []}
-            for batch in loader:
-                if batch is None:
-                    continue
-                batch_copy = batch.clone()                                   # forward overwrites batch.x (main.py:87)
-                batch_copy.num_graphs = batch.num_graphs
-                batch.to(device)
-                out["cell"].append(batch.cell.detach().to("cpu"))
-                out["atoms"].append(batch.x[batch.non_H_mask].detach().to("cpu"))
-                pseudo_true, _ = model(batch)
-                R = random_rotations(1, gen, device)[0]
-                batch_copy.to(device)
-                batch_copy.cart_dir = batch_copy.cart_dir @ R
-                pseudo_true = R.transpose(-1, -2) @ pseudo_true @ R
-                pred, _ = model(batch_copy)
-                out["pred"].append(pred.detach().to("cpu"))
-                out["true"].append(pseudo_true.detach().to("cpu"))
-                out["iou"].append(compute_3D_IoU(pred, pseudo_true).detach().to("cpu"))
-                out["similarity_index"].append(get_similarity_index(pred, pseudo_true).detach().to("cpu"))
-                out["mae"].append((pred - pseudo_true).abs().detach().to("cpu"))
-            with open(output_path.replace(".pkl", f"_montecarlo_{i}.pkl"), "wb") as f:
-                pickle.dump(out, f)
-            iou_all += out["iou"]
-            mae_all += out["mae"]
-            sim_all += out["similarity_index"]
-    iou, mae, sim = torch.cat(iou_all), torch.cat(mae_all), torch.cat(sim_all)
-    return {"rounds": rounds, **_summary(iou, mae, sim)}
-
-
-def _batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> None:
-    """Appends one list entry per crystal to ``out``: the tensors of ``per_row`` (dim 0 runs over the batch's non-hydrogen
-    atoms, in crystal order), ``cell``, ``atoms`` and, if asked for, ``pos``.  One transfer brings everything to the host,
-    the crystals' row counts included; the split by those counts happens there -- the lists the batch-size-1 loop writes
-    (main.py:38-49).  ``batch.x`` must hold the atomic numbers."""
-    from cartnet_amd.metrics import split_rows
-    dev = dict(per_row)
-    dev["atoms"] = batch.x[batch.non_H_mask]
-    dev["cell"] = batch.cell
-    if with_pos and hasattr(batch, "pos"):
-        dev["pos"] = batch.pos[batch.non_H_mask]
-    dev["_row_ptr"] = row_ptr
-    host = _to_host(dev)
-    rp = host.pop("_row_ptr")
-    rows = (rp[1:] - rp[:-1]).tolist()
-    out["cell"] += [c.unsqueeze(0) for c in host.pop("cell").unbind(0)]
-    for k, t in host.items():
-        out[k] += split_rows(t, rows)
-
-
-def inference_batched(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0, rigid_bond=None
-                      ) -> dict:
-    """``inference`` at any batch size (``--eval_batch N``): one forward and one ``adp_eval`` per batch; the pickle keeps
-    the layout of batch size 1, one list entry per crystal, and the result keys are the same.  ``rotations`` = K > 1: the
-    prediction that is evaluated against the truth is the mean over K frames (cartnet_amd.predict: ``frames``,
-    ``replicate``, one forward of ``N * K`` crystals, ``metrics.frame_mean``; one generator seeded with ``seed`` for the
-    whole pass); the pickle then also has ``rot_spread`` per crystal, the result ``rotations`` and ``rot_spread_max``.
-    ``rigid_bond`` = ``(tol, threshold)``: ``metrics.bond_test`` on the prediction and on the truth of every batch; the
-    pickle then also has ``bond_delta_max`` and ``bond_delta_max_true`` per crystal (one value per row), the result
-    ``rigid_bond_mean`` and ``rigid_bond_mean_true`` (the mean ``|D|`` over the directed bonds of the pass, 0 without
-    bonds): the truth's figure is the baseline the prediction's is to be compared with."""
-    import pickle
-    from cartnet_amd.metrics import adp_eval, bond_test, frame_mean, target_row_ptr
-    from cartnet_amd.predict import frames, replicate
-    model.eval()
-    out = _pickle_lists()
-    gen = None
-    if rotations > 1:
-        out["rot_spread"] = []
-        gen = torch.Generator(device=device).manual_seed(seed)
-    bond_sums = None                                      # [2,4] fp64 on the device: crystal_stats summed, prediction / truth
-    if rigid_bond is not None:
-        out["bond_delta_max"], out["bond_delta_max_true"] = [], []
-        bond_sums = torch.zeros((2, 4), dtype=torch.float64, device=device)
-    with torch.no_grad():
-        for batch in loader:
-            if batch is None:
-                continue
-            batch.to(device)
-            row_ptr = target_row_ptr(batch)
-            if rotations == 1:
-                atoms = batch.x.clone()                                       # forward overwrites x (main.py:40)
-                pred, true = model(batch)
-                extra = {}
-                batch.x = atoms
-            else:                                                             # the forward runs on the replica batch
-                R = frames(int(batch.num_graphs), rotations, gen, device)
-                members, _ = model(replicate(batch, rotations, R))
-                fm = frame_mean(members, R, row_ptr, stats=False)
-                pred, true, extra = fm.mean, batch.y, {"rot_spread": fm.spread}
-            if rigid_bond is not None:                                        # batch.x holds the atomic numbers again
-                for k, (name, u) in enumerate((("bond_delta_max", pred), ("bond_delta_max_true", true))):
-                    bt = bond_test(u, batch, row_ptr, *rigid_bond)
-                    extra[name] = bt.delta_max
-                    bond_sums[k] += bt.crystal_stats.sum(0)
-            res = adp_eval(pred, true, row_ptr, None, volume=False)
-            _batch_entries(out, batch, row_ptr, {"pred": pred, "true": true, "mae": res.abs_err, "iou": res.iou,
-                                                 "similarity_index": res.similarity_index, **extra}, with_pos=True)
-    if hasattr(model, "flush_graph_checks"):
-        model.flush_graph_checks()
-    iou, mae, sim = (torch.cat(out[k]) for k in ("iou", "mae", "similarity_index"))
-    with open(output_path, "wb") as f:
-        pickle.dump(out, f)
-    result = {**_summary(iou, mae, sim), "output": output_path}
-    if rotations > 1:
-        spread = torch.cat(out["rot_spread"])
-        result.update(rotations=rotations, rot_spread_max=float(spread.max()) if spread.numel() else 0.0)
-    if rigid_bond is not None:
-        (n_p, s_p, _, _), (n_t, s_t, _, _) = bond_sums.tolist()
-        result.update(rigid_bond_mean=s_p / n_p if n_p else 0.0, rigid_bond_mean_true=s_t / n_t if n_t else 0.0)
-    return result
-
-
-def montecarlo_batch(model, batch, R: torch.Tensor):
-    """One Monte-Carlo step (main.py:85-103) for a whole batch on the device, crystal g rotated by ``R[g]`` [B,3,3]:
-    clone, forward, rotate the clone's ``cart_dir`` per crystal (``cell`` is not rotated, as in the reference), forward
-    again, and one ``adp_eval`` that forms the pseudo-truth ``R_g^T pred_1 R_g`` and compares.  Returns
-    ``(pred, AdpEval, row_ptr)``; ``batch`` comes back with its atomic numbers in ``x``."""
-    from cartnet_amd.metrics import adp_eval, edge_row_ptr, rotate_rows, target_row_ptr
-    row_ptr = target_row_ptr(batch)
-    copy = batch.clone()                                                      # forward overwrites batch.x (main.py:87)
-    copy.num_graphs = batch.num_graphs
-    atoms = batch.x.clone()
-    first, _ = model(batch)
-    batch.x = atoms
-    copy.cart_dir = rotate_rows(copy.cart_dir.contiguous(), edge_row_ptr(copy), R)
-    pred, _ = model(copy)
-    return pred, adp_eval(pred, first, row_ptr, rot=R, volume=False), row_ptr
-
-
-def montecarlo_batched(model, loader, device, output_path: str, rounds: int = 100, seed: int = 0) -> dict:
-    """``montecarlo`` at any batch size (``--eval_batch N``): ``montecarlo_batch`` per batch with one fresh rotation per
-    crystal; the pickles keep the layout of batch size 1, one list entry per crystal, and the result keys are the same."""
-    import pickle
-    from cartnet_amd.shard import random_rotations
-    model.eval()
-    gen = torch.Generator(device=device).manual_seed(seed)
-    iou_all, mae_all, sim_all = [], [], []
-    with torch.no_grad():
-        for i in range(rounds):
-            out = _pickle_lists(montecarlo=True)
-            for batch in loader:
-                if batch is None:
-                    continue
-                batch.to(device)
-                R = random_rotations(int(batch.num_graphs), gen, device)
-                pred, res, row_ptr = montecarlo_batch(model, batch, R)
-                per_row = {"pred": pred, "true": res.true, "mae": res.abs_err, "iou": res.iou,
-                           "similarity_index": res.similarity_index}
-                _batch_entries(out, batch, row_ptr, per_row, with_pos=False)    # (main.py:62-119 stores no pos)
-            with open(output_path.replace(".pkl", f"_montecarlo_{i}.pkl"), "wb") as f:
-                pickle.dump(out, f)
-            iou_all += out["iou"]
-            mae_all += out["mae"]
-            sim_all += out["similarity_index"]
-    if hasattr(model, "flush_graph_checks"):
-        model.flush_graph_checks()
-    iou, mae, sim = torch.cat(iou_all), torch.cat(mae_all), torch.cat(sim_all)
-    return {"rounds": rounds, **_summary(iou, mae, sim)}
-
-
-def parse_temperatures(spec: str) -> list:
-    """``--predict_temperatures SPEC`` as a list of Kelvin values: ``100,150,200``, or ``A:B:STEP`` = A, A + STEP, ... up
-    to and including B when STEP reaches it (``100:300:50`` is five values, ``100:290:50`` four).  Raises ``SystemExit``
-    with a message for an empty spec, a value that is no number, one that is not finite or not > 0, a list that is not
-    strictly increasing and a STEP that is not > 0.  On the host: no device is touched."""
-    import math
-    flag = "--predict_temperatures"
-
-    def number(text: str) -> float:
-        try:
-            v = float(text)
-        except ValueError:
-            raise SystemExit(f"{flag}: {text.strip()!r} is no number") from None
-        if not math.isfinite(v):
-            raise SystemExit(f"{flag}: {text.strip()!r} is not finite")
-        return v
-    spec = (spec or "").strip()
-    if not spec:
-        raise SystemExit(f"{flag}: empty (a list 100,150,200 or a range A:B:STEP)")
-    if ":" in spec:
-        parts = spec.split(":")
-        if len(parts) != 3:
-            raise SystemExit(f"{flag}: a range is A:B:STEP, got {spec!r}")
-        a, b, step = (number(p) for p in parts)
-        if step <= 0:
-            raise SystemExit(f"{flag}: STEP must be > 0, got {step:g}")
-        count = math.floor((b - a) / step + 1e-9) + 1                        # B itself when STEP reaches it
-        if count < 1:
-            raise SystemExit(f"{flag}: the range {spec!r} is empty")
-        values = [a + k * step for k in range(count)]
-    else:
-        values = [number(p) for p in spec.split(",")]
-    if any(v <= 0 for v in values):
-        raise SystemExit(f"{flag}: temperatures are Kelvin values > 0")
-    if any(q <= p for p, q in zip(values, values[1:])):
-        raise SystemExit(f"{flag}: the temperatures must be strictly increasing")
-    return values
 
 
 def check_predict_args(args) -> None:
@@ -575,71 +319,24 @@ def predict(model, args) -> dict:
     cells on the GPU and take the same path; the pickle and the CIFs then carry one site-averaged ADP per atom of the
     asymmetric unit, and the result counts the ``rejected`` crystals (names and reasons go to stderr)."""
     import pickle
-    from cartnet_amd.predict import entry, predict_adps, write_cif, write_cif_symmetric
-    from cartnet_amd.shard import DeviceShard, ShardLoader
-    sym, rejected = None, None
-    if os.path.isdir(args.predict_input) or args.predict_input.lower().endswith(".cif"):
-        # CIF files: expanded in memory (no shard file is written), then through the recipe exactly as a shard
-        import sys
-        from cartnet_amd.cif import load_crystals
-        from cartnet_amd.symmetry import expand
-        crystals, rejected = load_crystals(args.predict_input, False, args.predict_temperature)
-        for name, why in rejected:
-            print(f"rejected\t{name}\t{why}", file=sys.stderr)
-        if not crystals:
-            raise SystemExit(f"--predict: no usable crystal in {args.predict_input}")
-        arrays, sym = expand(crystals, cfg.device, labeled=False, temperature=args.predict_temperature)
-        source = DeviceShard(arrays, cfg.device, labeled=False, names=sym.names)
-    else:
-        source = DeviceShard.from_file(args.predict_input, cfg.device)
-    shards, (mean, std) = shard_recipe([source])
-    bond = {"rigid_bond": (args.bond_tolerance, args.rigid_bond_threshold)} if args.rigid_bond else {}
-    ride = ({"riding_h": (args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating)}
-            if args.riding_h else {})
+    from cartnet_amd import predict as pr
+    from cartnet_amd.shard import ShardLoader
+    source, sym, rejected = pr.load_input(args.predict_input, cfg.device, args.predict_temperature)
+    (shard,), (mean, std) = shard_recipe([source])
     temps = parse_temperatures(args.predict_temperatures) if args.predict_temperatures is not None else None
-    series = {"temperatures": temps} if temps is not None else {}
-    out = predict_adps(model, ShardLoader(shards[0], cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
-                       rotations=cfg.rotations, seed=cfg.seed, **bond, **ride, **series)
+    out = pr.predict_adps(
+        model, ShardLoader(shard, cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
+        rotations=cfg.rotations, seed=cfg.seed, temperatures=temps,
+        rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None,
+        riding_h=(args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating) if args.riding_h else None)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
-    n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
     if args.predict_cif_dir:
         os.makedirs(args.predict_cif_dir, exist_ok=True)
-        for k in range(n):
-            (write_cif if sym is None else write_cif_symmetric)(
-                os.path.join(args.predict_cif_dir, f"{out['name'][k]}.cif"), entry(out, k))
-    rows = sum(int(t.shape[0]) for t in out["u_eq"])
-
-    def stacked(key: str, width: int, of: dict = out) -> torch.Tensor:   # [n, width] fp64: one kernel's per-crystal figures
-        return torch.stack(of[key]) if of[key] else torch.zeros(0, width, dtype=torch.float64)
-    stats = stacked("stats", 3)
-    res = {"crystals": n // len(temps) if temps else n, "rows": rows, "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1),
-           "non_positive_rows": int(stats[:, 2].sum()), "output": args.predict_output, "cif_dir": args.predict_cif_dir}
-    if rejected is not None:
-        res["rejected"] = len(rejected)
-    if temps is not None:
-        res.update(entries=n, temperatures=temps)
-    if "series" in out:                               # from the fp64 per-crystal stats of the lines; rows of ONE temperature
-        ts = stacked("t_stats", 4, out["series"])
-        res.update(ueq_slope_mean=float(ts[:, 0].sum()) / max(rows // len(temps), 1),
-                   non_increasing_rows=int(ts[:, 1].sum()), rows_with_drops=int(ts[:, 2].sum()),
-                   series_resid_max=float(ts[:, 3].max()) if len(ts) else 0.0)
-    if cfg.rotations > 1:                             # per row, from the fp64 per-crystal (sum, maximum) of rot_spread
-        rot = stacked("rot_stats", 2)
-        res.update(rotations=cfg.rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
-                   rot_spread_mean=float(rot[:, 0].sum()) / max(rows, 1))
-    if args.rigid_bond:                               # over the directed bonds of the pass, from the fp64 per-crystal stats
-        bs = stacked("bond_stats", 4)
-        count = int(bs[:, 0].sum())
-        res.update(bonds=count, rigid_bond_mean=float(bs[:, 1].sum()) / count if count else 0.0,
-                   rigid_bond_max=float(bs[:, 2].max()) if n else 0.0, rigid_bond_over=int(bs[:, 3].sum()))
-    if args.riding_h:                                 # from the fp64 per-crystal stats; the mean is over the non-orphans
-        hs = stacked("h_stats", 4)
-        hydrogens, orphans = int(hs[:, 0].sum()), int(hs[:, 1].sum())
-        res.update(hydrogens=hydrogens, h_orphans=orphans,
-                   h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,
-                   h_non_positive=int(hs[:, 3].sum()))
-    return res
+        for k, name in enumerate(out["name"]):            # entries: one per crystal, or per crystal and temperature
+            (pr.write_cif if sym is None else pr.write_cif_symmetric)(
+                os.path.join(args.predict_cif_dir, f"{name}.cif"), pr.entry(out, k))
+    return pr.pass_statistics(out, args.predict_output, args.predict_cif_dir, rejected, cfg.rotations, temps)
 
 
 def main(argv=None) -> dict:
@@ -669,18 +366,13 @@ def main(argv=None) -> dict:
         assert args.checkpoint_path is not None, "Weights not provided."
         ck = torch.load(args.checkpoint_path, map_location=cfg.device)
         model.load_state_dict(ck["model_state"])
-        batched = cfg.eval_batch > 1                                       # 1: the reference's loop, as it was
-        if args.inference and args.rigid_bond:                             # the rigid-bond test is a batched pass too
-            res = inference_batched(model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations,
-                                    seed=cfg.seed, rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold))
-        elif args.inference and cfg.rotations > 1:                         # the frame mean is a batched pass at any size
-            res = inference_batched(model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations,
-                                    seed=cfg.seed)
-        elif args.inference:
-            res = (inference_batched if batched else inference)(model, loaders[-1], cfg.device, args.inference_output)
+        if args.inference:
+            res = evaluate.inference(
+                model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations, seed=cfg.seed,
+                rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None)
         else:
-            res = (montecarlo_batched if batched else montecarlo)(model, loaders[-1], cfg.device, args.inference_output,
-                                                                  rounds=args.montecarlo_rounds, seed=cfg.seed)
+            res = evaluate.montecarlo(model, loaders[-1], cfg.device, args.inference_output,
+                                      rounds=args.montecarlo_rounds, seed=cfg.seed)
         if rank == 0:
             print(json.dumps(res), flush=True)
         return res

@@ -83,7 +83,7 @@ def test_row_offsets_of_a_hand_made_batch():
 
 
 def test_per_crystal_split_of_a_batch_on_the_host():
-    import main as entry
+    from cartnet_amd import evaluate
     from cartnet_amd.metrics import split_rows, target_row_ptr
     pieces = split_rows(torch.arange(12.).reshape(6, 2), [2, 0, 1, 3])
     assert [tuple(p.shape) for p in pieces] == [(2, 2), (0, 2), (1, 2), (3, 2)]
@@ -94,7 +94,7 @@ def test_per_crystal_split_of_a_batch_on_the_host():
     pred = torch.arange(6 * 9, dtype=torch.float32).reshape(6, 3, 3)
     iou = torch.arange(6, dtype=torch.float32)
     out = {"pred": [], "iou": [], "cell": [], "atoms": [], "pos": []}
-    entry._batch_entries(out, b, rp, {"pred": pred, "iou": iou}, with_pos=True)
+    evaluate.batch_entries(out, b, rp, {"pred": pred, "iou": iou}, with_pos=True)
     assert all(len(out[k]) == 4 for k in out)                                                 # one entry per crystal
     assert [tuple(p.shape) for p in out["pred"]] == [(2, 3, 3), (0, 3, 3), (1, 3, 3), (3, 3, 3)]
     assert torch.equal(torch.cat(out["pred"]), pred) and torch.equal(torch.cat(out["iou"]), iou)
@@ -102,5 +102,5 @@ def test_per_crystal_split_of_a_batch_on_the_host():
     assert [tuple(c.shape) for c in out["cell"]] == [(1, 3, 3)] * 4 and out["cell"][3][0, 0, 0].item() == 5.0
     assert out["pos"][3].tolist() == [[0., 1., 2.], [3., 4., 5.], [9., 10., 11.]]
     out = {"pred": [], "cell": [], "atoms": [], "pos": []}
-    entry._batch_entries(out, b, rp, {"pred": pred}, with_pos=False)                          # the Monte-Carlo pickles: no pos
+    evaluate.batch_entries(out, b, rp, {"pred": pred}, with_pos=False)                          # the Monte-Carlo pickles: no pos
     assert out["pos"] == [] and len(out["pred"]) == 4

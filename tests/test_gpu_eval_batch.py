@@ -1,6 +1,7 @@
 """Evaluation at any batch size with the results of batch size 1 (--eval_batch): the two kernels of csrc/eval_ops.hip
 against the existing metrics kernel, the collation kernel and fp64; eval_epoch(per_crystal=True), montecarlo_batch and
-main.py's batched --inference / --montecarlo against their batch-size-1 forms."""
+main.py's batched --inference / --montecarlo against their batch-size-1 forms; cartnet_amd.evaluate's two passes at batch
+size 1 against the reference's loops (main.py:21-119), written out here statement by statement."""
 import os
 import pickle
 
@@ -228,7 +229,7 @@ def test_eval_epoch_per_crystal_at_batch_4(crystals, dim, rbf, layers):
 
 
 def test_montecarlo_batch_against_the_batch_1_steps(crystals):
-    import main as entry
+    from cartnet_amd import evaluate as entry
     from cartnet_amd.data import Batch
     from cartnet_amd.shard import random_rotations
     m, _, _ = _cartnet(64, 16, 2, seed=12)
@@ -251,6 +252,86 @@ def test_montecarlo_batch_against_the_batch_1_steps(crystals):
             assert rel_err(p, second) < 2 * PRED_TOL, g
             bound = 2 * PRED_TOL * pseudo.abs().max().item() + ROT_TOL * first.abs().max().item()
             assert (t - pseudo).abs().max().item() <= bound, g
+
+
+# ------------------------------------------------------------------------- batch size 1 is the reference's loop
+
+def _loader_of_one(crystals, kind):
+    """The three smallest crystals (1, 2 and 23 atoms), one per batch, from the host loader or from a resident shard."""
+    from cartnet_amd.data import DataLoader
+    from cartnet_amd.shard import DeviceShard, ShardLoader
+    three = crystals[:3]
+    return DataLoader(three, 1) if kind == "host" else ShardLoader(DeviceShard.from_data_list(three, "cuda:0"), 1)
+
+
+@pytest.mark.parametrize("kind", ["host", "shard"])
+def test_inference_at_batch_1_is_the_reference_loop(crystals, tmp_path, kind):
+    from cartnet_amd import evaluate
+    from cartnet_amd.metrics import compute_3D_IoU, get_similarity_index
+    m, _, _ = _cartnet(64, 16, 2, seed=13)
+    path = str(tmp_path / "inf.pkl")
+    res = evaluate.inference(m, _loader_of_one(crystals, kind), "cuda:0", path)
+    out = pickle.load(open(path, "rb"))
+    assert tuple(out) == ("pred", "true", "temp", "cell", "refcode", "pos", "atoms", "iou", "mae", "similarity_index")
+    assert out["temp"] == [] and out["refcode"] == []
+    assert all(len(out[k]) == 3 for k in out if k not in ("temp", "refcode"))
+    ious, maes, sims = [], [], []
+    with torch.no_grad():
+        for g, batch in enumerate(_loader_of_one(crystals, kind)):            # main.py:33-49, statement by statement
+            batch.to("cuda:0")
+            cell = batch.cell.detach().to("cpu")
+            atoms = batch.x[batch.non_H_mask].detach().to("cpu")
+            pos = batch.pos[batch.non_H_mask].detach().to("cpu")
+            pred, true = m(batch)
+            ious.append(compute_3D_IoU(pred, true).detach().to("cpu"))
+            maes.append((pred - true).abs().detach().to("cpu"))
+            sims.append(get_similarity_index(pred, true).detach().to("cpu"))
+            assert torch.equal(out["pred"][g], pred.detach().to("cpu")), g
+            assert torch.equal(out["true"][g], true.detach().to("cpu")), g
+            assert torch.equal(out["iou"][g], ious[g]) and torch.equal(out["mae"][g], maes[g]), g
+            assert torch.equal(out["similarity_index"][g], sims[g]), g
+            assert torch.equal(out["atoms"][g], atoms) and torch.equal(out["pos"][g], pos), g
+            assert tuple(out["cell"][g].shape) == (1, 3, 3) and torch.equal(out["cell"][g], cell), g
+    assert g == 2
+    assert res == {**evaluate.summary(torch.cat(ious), torch.cat(maes), torch.cat(sims)), "output": path}
+
+
+@pytest.mark.parametrize("kind", ["host", "shard"])
+def test_montecarlo_at_batch_1_is_the_reference_loop(crystals, tmp_path, kind):
+    from cartnet_amd import evaluate
+    from cartnet_amd.metrics import compute_3D_IoU, get_similarity_index
+    from cartnet_amd.shard import random_rotations
+    m, _, _ = _cartnet(64, 16, 2, seed=14)
+    res = evaluate.montecarlo(m, _loader_of_one(crystals, kind), "cuda:0", str(tmp_path / "mc.pkl"), rounds=2, seed=5)
+    gen = torch.Generator(device="cuda:0").manual_seed(5)
+    ious, maes, sims = [], [], []
+    with torch.no_grad():
+        for i in range(2):
+            out = pickle.load(open(tmp_path / f"mc_montecarlo_{i}.pkl", "rb"))
+            assert tuple(out) == ("pred", "true", "cell", "refcode", "pos", "atoms", "mae", "iou", "similarity_index")
+            assert out["refcode"] == [] and out["pos"] == []
+            assert all(len(out[k]) == 3 for k in out if k not in ("refcode", "pos"))
+            for g, batch in enumerate(_loader_of_one(crystals, kind)):        # main.py:85-103, statement by statement
+                batch_copy = gu.clone_batch(batch)
+                batch.to("cuda:0")
+                cell = batch.cell.detach().to("cpu")
+                atoms = batch.x[batch.non_H_mask].detach().to("cpu")
+                pseudo_true, _ = m(batch)
+                R = random_rotations(1, gen, "cuda:0")[0]
+                batch_copy.to("cuda:0")
+                batch_copy.cart_dir = batch_copy.cart_dir @ R
+                pseudo_true = R.transpose(-1, -2) @ pseudo_true @ R
+                pred, _ = m(batch_copy)
+                ious.append(compute_3D_IoU(pred, pseudo_true).detach().to("cpu"))
+                sims.append(get_similarity_index(pred, pseudo_true).detach().to("cpu"))
+                maes.append((pred - pseudo_true).abs().detach().to("cpu"))
+                assert torch.equal(out["pred"][g], pred.detach().to("cpu")), (i, g)
+                assert torch.equal(out["true"][g], pseudo_true.detach().to("cpu")), (i, g)
+                assert torch.equal(out["iou"][g], ious[-1]) and torch.equal(out["mae"][g], maes[-1]), (i, g)
+                assert torch.equal(out["similarity_index"][g], sims[-1]), (i, g)
+                assert torch.equal(out["atoms"][g], atoms) and torch.equal(out["cell"][g], cell), (i, g)
+    assert len(ious) == 6
+    assert res == {"rounds": 2, **evaluate.summary(torch.cat(ious), torch.cat(maes), torch.cat(sims))}
 
 
 # ------------------------------------------------------------------------------------------------ through main.py

@@ -124,17 +124,22 @@ def test_predict_carries_the_direct_result_and_changes_nothing_else(work, monkey
 @pytest.mark.parametrize("eval_batch", [1, 4])
 def test_inference_tests_prediction_and_truth_on_the_batched_path(work, monkeypatch, capsys, eval_batch):
     import main as entry
+    from cartnet_amd import evaluate
     d, ckpt, _, splits = work
     monkeypatch.chdir(d)
     common = ["--inference", "--shard_dir", splits, "--checkpoint_path", ckpt, "--eval_batch", str(eval_batch)] + MODEL
     plain = entry.main(common + ["--inference_output", "inf_plain.pkl"])
+    calls = []
+    one_loop = evaluate.inference                                             # there is no other pass to take
 
-    def loop(*a, **k):
-        raise AssertionError("--inference --rigid_bond took the loop of batch size 1")
-    monkeypatch.setattr(entry, "inference", loop)
+    def spy(*a, **k):
+        calls.append(k)
+        return one_loop(*a, **k)
+    monkeypatch.setattr(evaluate, "inference", spy)
     capsys.readouterr()
     res = entry.main(common + ["--inference_output", "inf_bond.pkl", "--rigid_bond"])
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == [{"rotations": 1, "seed": 0, "rigid_bond": (TOL, THRESHOLD)}]
     assert line == res and set(res) == set(plain) | {"rigid_bond_mean", "rigid_bond_mean_true"}
     old, out = _load("inf_plain.pkl"), _load("inf_bond.pkl")
     assert set(out) == set(old) | {"bond_delta_max", "bond_delta_max_true"}
@@ -160,6 +165,7 @@ def test_inference_tests_prediction_and_truth_on_the_batched_path(work, monkeypa
 def test_without_the_flag_everything_is_as_it_was(work, monkeypatch, capsys):
     """The two figures alone switch nothing on: the key sets of both passes are the ones they have always had."""
     import main as entry
+    from cartnet_amd import evaluate
     from cartnet_amd.predict import KEYS
     d, ckpt, src, splits = work
     monkeypatch.chdir(d)
@@ -168,13 +174,13 @@ def test_without_the_flag_everything_is_as_it_was(work, monkeypatch, capsys):
                       "--predict_output", "quiet.pkl"] + MODEL + quiet)
     assert set(res) == PREDICT_JSON and tuple(_load("quiet.pkl")) == KEYS
     calls = []
-    batched = entry.inference_batched
+    one_loop = evaluate.inference
 
     def spy(*a, **k):
         calls.append(k)
-        return batched(*a, **k)
-    monkeypatch.setattr(entry, "inference_batched", spy)
+        return one_loop(*a, **k)
+    monkeypatch.setattr(evaluate, "inference", spy)
     res = entry.main(["--inference", "--shard_dir", splits, "--checkpoint_path", ckpt, "--eval_batch", "4",
                       "--inference_output", "inf_quiet.pkl"] + MODEL + quiet)
-    assert calls == [{}]                                                      # the call of every earlier version
+    assert calls == [{"rotations": 1, "seed": 0, "rigid_bond": None}]         # every option at its default: nothing switched on
     assert set(res) == INFERENCE_JSON and set(_load("inf_quiet.pkl")) == INFERENCE_PICKLE

@@ -93,25 +93,22 @@ def test_no_flag_is_rotations_one(trained, monkeypatch, capsys):
 @pytest.mark.parametrize("extra", [[], ["--resident_dataset"]])
 def test_inference_in_two_frames_takes_the_batched_path(trained, monkeypatch, capsys, extra):
     import main as entry
+    from cartnet_amd import evaluate
     work, ckpt, _ = trained
     monkeypatch.chdir(work)
     common = DATA + ["--inference", "--checkpoint_path", ckpt, "--eval_batch", "1"] + MODEL + extra
     plain = entry.main(common + ["--inference_output", "inf_plain.pkl"])
     calls = []
-    batched = entry.inference_batched
+    one_loop = evaluate.inference                                             # there is no other pass to take
 
     def spy(*a, **k):
         calls.append(k)
-        return batched(*a, **k)
-
-    def loop(*a, **k):
-        raise AssertionError("--inference --rotations 2 took the loop of batch size 1")
-    monkeypatch.setattr(entry, "inference_batched", spy)
-    monkeypatch.setattr(entry, "inference", loop)
+        return one_loop(*a, **k)
+    monkeypatch.setattr(evaluate, "inference", spy)
     capsys.readouterr()
     res = entry.main(common + ["--inference_output", "inf_rot.pkl", "--rotations", "2", "--seed", "4"])
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
-    assert line == res and calls == [{"rotations": 2, "seed": 4}]
+    assert line == res and calls == [{"rotations": 2, "seed": 4, "rigid_bond": None}]
     assert set(res) == set(plain) | {"rotations", "rot_spread_max"} and res["rotations"] == 2
     assert all(math.isfinite(v) for k, v in res.items() if k != "output") and res["rot_spread_max"] >= 0
     out, ref = _load("inf_rot.pkl"), _load("inf_plain.pkl")

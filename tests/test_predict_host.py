@@ -165,9 +165,8 @@ def test_export_entry_point_is_declared_bound_and_launches_nothing_without_rows(
 
 
 def test_to_host_is_shared_not_copied():
-    import main as entry
-    from cartnet_amd import metrics, predict
-    assert entry._to_host is metrics.to_host is predict.to_host
+    from cartnet_amd import evaluate, metrics, predict
+    assert evaluate.to_host is metrics.to_host is predict.to_host
     out = metrics.to_host({"a": torch.arange(6, dtype=torch.int64).reshape(2, 3), "b": torch.zeros(0, 3),
                            "c": torch.tensor([1.5, 2.5], dtype=torch.float64), "d": torch.tensor([True, False])})
     assert out["a"].tolist() == [[0, 1, 2], [3, 4, 5]] and tuple(out["b"].shape) == (0, 3)

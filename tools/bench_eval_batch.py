@@ -5,9 +5,10 @@ D = 256, L = 4 (fresh weights, eval mode) on two synthetic test splits held as r
     small   512 crystals of 30-70 atoms
     large   128 crystals of 194 atoms
 
-``eval_batch`` 1 is the batch-size-1 code path as it was before the flag existed (``eval_epoch`` per batch, ``inference``,
-``montecarlo``): the baseline.  16 and 64 are the batched forms (``per_crystal=True``, ``inference_batched``,
-``montecarlo_batched``).  The settings are taken alternately (1 16 64 1 16 64 ...) in one process after a warm-up round;
+``eval_batch`` 1 is the reference's batch size, the baseline: ``eval_epoch`` per batch, and ``evaluate.inference`` /
+``evaluate.montecarlo`` on a loader of batch size 1 (the latter then takes the reference's step, ``montecarlo_reference``).
+16 and 64 are the batched forms (``per_crystal=True``, and the same two passes on a larger loader; ``montecarlo_batch``
+is then the step).  The settings are taken alternately (1 16 64 1 16 64 ...) in one process after a warm-up round;
 a time is the host clock between two device synchronisations around the whole workload, pickles included, and the figure
 kept is the median of ``--rounds`` (3).  One more batched Monte-Carlo round runs with a HIP event pair around every
 ``adp_eval`` call: the share of the round spent in ``cartnet_adp_eval``'s two launches.
@@ -37,7 +38,7 @@ def run_split(name: str, rounds: int, mc_rounds: int) -> dict:
     import torch
 
     import main as entry
-    from cartnet_amd import metrics as gm
+    from cartnet_amd import evaluate
     from cartnet_amd.config import cfg
     from cartnet_amd.master import create_model
     from cartnet_amd.shard import DeviceShard, ShardLoader
@@ -57,14 +58,10 @@ def run_split(name: str, rounds: int, mc_rounds: int) -> dict:
 
     def workloads(n):
         loader = ShardLoader(shard, n)
-        if n == 1:
-            return {"test_pass": lambda: eval_epoch(loader, model, cfg.device, adp_metrics=True, test_metrics=True),
-                    "inference": lambda: entry.inference(model, loader, cfg.device, pkl),
-                    "montecarlo": lambda: entry.montecarlo(model, loader, cfg.device, pkl, rounds=mc_rounds)}
         return {"test_pass": lambda: eval_epoch(loader, model, cfg.device, adp_metrics=True, test_metrics=True,
-                                                per_crystal=True),
-                "inference": lambda: entry.inference_batched(model, loader, cfg.device, pkl),
-                "montecarlo": lambda: entry.montecarlo_batched(model, loader, cfg.device, pkl, rounds=mc_rounds)}
+                                                per_crystal=n > 1),
+                "inference": lambda: evaluate.inference(model, loader, cfg.device, pkl),
+                "montecarlo": lambda: evaluate.montecarlo(model, loader, cfg.device, pkl, rounds=mc_rounds)}
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -85,7 +82,7 @@ def run_split(name: str, rounds: int, mc_rounds: int) -> dict:
     med = {w: {n: statistics.median(v) for n, v in per.items()} for w, per in ms.items()}
 
     # the share of a batched Monte-Carlo round inside cartnet_adp_eval: an event pair around every call
-    pairs, plain = [], gm.adp_eval
+    pairs, plain = [], evaluate.adp_eval
 
     def stamped(*a, **k):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -94,11 +91,11 @@ def run_split(name: str, rounds: int, mc_rounds: int) -> dict:
         e1.record()
         pairs.append((e0, e1))
         return out
-    gm.adp_eval = stamped
+    evaluate.adp_eval = stamped
     try:
-        wall, _ = timed(lambda: entry.montecarlo_batched(model, ShardLoader(shard, 64), cfg.device, pkl, rounds=1))
+        wall, _ = timed(lambda: evaluate.montecarlo(model, ShardLoader(shard, 64), cfg.device, pkl, rounds=1))
     finally:
-        gm.adp_eval = plain
+        evaluate.adp_eval = plain
     in_eval = sum(a.elapsed_time(b) for a, b in pairs)
 
     import shutil

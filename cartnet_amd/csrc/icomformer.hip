@@ -24,8 +24,6 @@
 namespace {
 using namespace cn_model;
 
-thread_local EventPool g_icf_events;
-
 // ---- small index kernel: rows r = 3 e + i of the edge layer -------------------------------------------------------------
 // idx_edge[r] = e, idx_gl[r] = 3 * crystal(source of e) + i, ptr3[e] = 3 e, gedge_ptr[g] = rowptr[graph_ptr[g]]
 __global__ void cn_icf_index_kernel(const int* __restrict__ src32, const int64_t* __restrict__ batch, long long E,
@@ -103,6 +101,10 @@ __global__ __launch_bounds__(256) void cn_icf_rowvec2_kernel(float* __restrict__
   }
 }
 
+// CartnetGemmArgs.tile_policy of this file's row-sized products: grouped C x C products on the 128-wide fp32 kernel (round 3:
+// -1.8 %).  The C x C x C products of the folded lin_edge (gemm_args(0, ...)) keep the default policy 0.
+constexpr int TILE128 = 1;
+
 // ---- weight forms of one step -----------------------------------------------------------------------------------------
 // forward operand forms (transposed copy [in, out] + LDS image of W^T) and backward images (W as [K = out, N = in])
 enum { F_Q, F_K, F_V, F_EDGE, F_K1I, F_M1I, F_K1J, F_M1J, F_K1E, F_M1E, F_K2, F_M2, F_CAT, F_COUNT };
@@ -116,14 +118,6 @@ struct ConvW {
   char* F[F_COUNT];          // forward images
   char* B[B_COUNT];          // backward images
 };
-
-struct Jobs {                // batched image / transpose requests of a step
-  std::vector<const float*> psrc; std::vector<void*> pdst; std::vector<int32_t> pK, pN, psk, psn;
-  std::vector<const float*> tsrc; std::vector<float*> tdst; std::vector<int32_t> trows, tcols, tlds, tldd;
-  void clear() { psrc.clear(); pdst.clear(); pK.clear(); pN.clear(); psk.clear(); psn.clear();
-                 tsrc.clear(); tdst.clear(); trows.clear(); tcols.clear(); tlds.clear(); tldd.clear(); }
-};
-thread_local Jobs g_jobs;
 
 // Round 5: alpha = q_i * key / sqrt(C) is never written -- the second Linear leaves the key rows in gs[:, :C], the
 // statistics pass only reads them, and the gate kernels of both directions recompute the product (cartnet_att_gate_fwd,
@@ -170,10 +164,6 @@ struct IWork {
   const CartnetGroups *groups, *groups_e;      // &grp / &grp_e, or nullptr for one group (set by the entry points)
 };
 
-size_t img_bytes(int prec, int K, int N) {
-  return prec == 0 ? cartnet_gemm_pack_b_bytes(K, N) : cartnet_gemm_split_b_bytes(K, N);
-}
-
 IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* base, size_t* total) {
   IWork w;
   memset(&w, 0, sizeof(w));
@@ -185,18 +175,13 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
   w.nparts_n = cartnet_node_nparts(N);
   w.gp_n = cartnet_gate_scatter_nparts(N); w.gp_e = cartnet_gate_scatter_nparts((int)E);
   w.sp_n = cartnet_segment_nparts(N); w.sp_e = cartnet_segment_nparts((int)E); w.sp_3e = cartnet_segment_nparts((int)(3 * E));
-  // groups as model.hip's carve deals them: ceil(segments / G / segments-per-workgroup) workgroups per group (the edge
-  // layer's 3-row segments: at most 256, G x 256 workgroups cover the chip several times over)
-  w.G = (m.bn_group_size > 0 && Bg > m.bn_group_size) ? (Bg + m.bn_group_size - 1) / m.bn_group_size : 1;
+  // (the edge layer's 3-row segments: at most 256 partial rows per group, G x 256 workgroups cover the chip several times over)
+  w.G = group_count(Bg, m.bn_group_size);
   size_t grows = 0;      // partial rows of the grouped kernels
   if (w.G > 1) {
-    auto parts = [&](size_t segs, int cap) {
-      const size_t per = (segs + (size_t)4 * w.G - 1) / ((size_t)4 * w.G);
-      return (int)(per < 1 ? 1 : (per > (size_t)cap ? cap : per));
-    };
     w.grp.G = w.grp_e.G = w.G;
-    w.grp.edge_parts = parts(Nn, 1024); w.grp.node_parts = parts(Nn, 256);
-    w.grp_e.edge_parts = w.grp_e.node_parts = parts(En, 256);
+    w.grp.edge_parts = group_parts(Nn, w.G, 1024); w.grp.node_parts = group_parts(Nn, w.G, 256);
+    w.grp_e.edge_parts = w.grp_e.node_parts = group_parts(En, w.G, 256);
     grows = (size_t)w.G * std::max(w.grp.edge_parts, w.grp_e.edge_parts);
   }
   const size_t Gn = (size_t)w.G;
@@ -294,40 +279,6 @@ IWork icarve(const CartnetIcfModel& m, int N, long long E, int Bg, int M, char* 
   return w;
 }
 
-inline CartnetGemmArgs gargs(int prec, int M, int N, int K, int lda, int ldb, int ldc) {
-  CartnetGemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.precision = prec;
-  a.tile_policy = 1;      // grouped C x C products on the 128-wide fp32 kernel (CartnetGemmArgs.tile_policy; round 3: -1.8 %)
-  a.M = M; a.N = N; a.K = K;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  a.ngroups = 1; a.nsegs = 1; a.splitk = 1;
-  return a;
-}
-
-// outs[g] = dY[g]^T @ (silu?)(X[g]) over K rows (split-K slabs summed in fixed order); K == 0 -> zeros
-int iwgrad(int prec, const float* const* dY, int ldy, const float* const* X, int ldx, float* const* outs, int ldo,
-           long long K, int M, int N, int groups, bool b_act, const IWork& w, void* st) {
-  if (K <= 0) {
-    for (int g = 0; g < groups; ++g)
-      for (int r = 0; r < M; ++r)
-        if (hipMemsetAsync(outs[g] + (size_t)r * ldo, 0, sizeof(float) * N, (hipStream_t)st) != hipSuccess) return 2;
-    return 0;
-  }
-  const int S = split_k(K, wgrad_tiles(groups, M, N));
-  CartnetGemmArgs a = gargs(prec, M, N, (int)K, ldy, ldx, S > 1 ? N : ldo);
-  a.ngroups = groups; a.a_kstrided = 1; a.b_kstrided = 1; a.b_act = b_act ? 1 : 0; a.splitk = S;
-  const float* slabp[CARTNET_MAX_GROUPS];
-  for (int g = 0; g < groups; ++g) {
-    a.A[g] = dY[g]; a.B[g] = X[g];
-    a.C[g] = S > 1 ? w.slabs + (size_t)g * S * M * N : outs[g];
-    slabp[g] = a.C[g];
-  }
-  RUN(cartnet_gemm(&a, st));
-  if (S > 1) RUN(cartnet_splitk_reduce(slabp, outs, groups, S, M, N, ldo, st));
-  return 0;
-}
-
 int check_icf(const CartnetIcfModel* m, const CartnetBatch* b, const char* who) {
   CN_CHECK(m && b, "%s: null model/batch", who);
   CN_CHECK(m->C >= 8 && m->C % 8 == 0 && m->C / 2 <= 512, "%s: dim_in=%d must be a multiple of 8, <= 1024", who, m->C);
@@ -352,47 +303,30 @@ int check_icf(const CartnetIcfModel* m, const CartnetBatch* b, const char* who) 
   return 0;
 }
 
-// the views of one conv's weights and, with images in use, the requests that build their forms
-void plan_conv(const CartnetIcfConv& q, const float* Fk, const float* Fm, int C, int prec, bool use_img, ConvW& cw, Jobs& J) {
+// the views of one conv's weights
+void conv_views(const CartnetIcfConv& q, const float* Fk, const float* Fm, int C, ConvW& cw) {
   // (F_EDGE keeps its slot -- lin_edge itself is no longer applied to rows -- so that the indices stay put; F_K1E / F_M1E
   //  are the folded matrices F = W1e We)
   const float* W[F_COUNT] = {q.query_w, q.key_w, q.value_w, q.edge_w, q.key0_w, q.msg0_w, q.key0_w + C, q.msg0_w + C,
                              Fk, Fm, q.key2_w, q.msg2_w, q.concate_w};
   const int ld[F_COUNT] = {C, C, C, C, 3 * C, 3 * C, 3 * C, 3 * C, C, C, C, C, C};
   for (int f = 0; f < F_COUNT; ++f) { cw.W[f] = W[f]; cw.ldw[f] = ld[f]; }
-  if (!use_img) return;
+}
+
+// ... and, with images in use, the requests that build their forms (after conv_views)
+void queue_conv_forms(const CartnetIcfConv& q, const float* Fk, const float* Fm, int C, int prec, const ConvW& cw, WeightForms& J) {
   const size_t ib = img_bytes(prec, C, C);
-  auto fwd_img = [&](const float* w_, int ldw, char* dst) {       // B[k, n] = W[n, k]
-    J.psrc.push_back(w_); J.pdst.push_back(dst); J.pK.push_back(C); J.pN.push_back(C); J.psk.push_back(1); J.psn.push_back(ldw);
-  };
-  auto k_img = [&](const float* w_, int ldw, char* dst) {         // B[k, n] = W[k, n]
-    J.psrc.push_back(w_); J.pdst.push_back(dst); J.pK.push_back(C); J.pN.push_back(C); J.psk.push_back(ldw); J.psn.push_back(1);
-  };
+  auto k_img = [&](const float* w_, int ldw, char* dst) { J.image(w_, dst, C, C, ldw, 1); };      // B[k, n] = W[k, n]
   for (int f = 0; f < F_COUNT; ++f) {
     if (f == F_EDGE) continue;
-    fwd_img(W[f], ld[f], cw.F[f]);
-    J.tsrc.push_back(W[f]); J.tdst.push_back(cw.T[f]); J.trows.push_back(C); J.tcols.push_back(C);
-    J.tlds.push_back(ld[f]); J.tldd.push_back(C);
+    J.image(cw.W[f], cw.F[f], C, C, 1, cw.ldw[f]);                                                 // B[k, n] = W[n, k]
+    J.transpose(cw.W[f], cw.T[f], C, C, cw.ldw[f], C);
   }
   k_img(q.query_w, C, cw.B[B_QKV]); k_img(q.key_w, C, cw.B[B_QKV] + ib); k_img(q.value_w, C, cw.B[B_QKV] + 2 * ib);
   k_img(Fk, C, cw.B[B_E1]); k_img(Fm, C, cw.B[B_E1] + ib);                  // d(rows) = [dpr_k | dpr_m] [Fk; Fm]
   k_img(q.key0_w, 3 * C, cw.B[B_K1I]); k_img(q.msg0_w, 3 * C, cw.B[B_M1I]);
   k_img(q.key0_w + C, 3 * C, cw.B[B_K1I] + ib); k_img(q.msg0_w + C, 3 * C, cw.B[B_M1I] + ib);
   k_img(q.key2_w, C, cw.B[B_K2]); k_img(q.msg2_w, C, cw.B[B_M2]); k_img(q.concate_w, C, cw.B[B_CAT]);
-}
-
-int flush_jobs(Jobs& J, int prec, void* st) {
-  if (!J.psrc.empty()) {
-    const int n = (int)J.psrc.size();
-    if (prec == 0) RUN(cartnet_gemm_pack_b(J.psrc.data(), J.pdst.data(), J.pK.data(), J.pN.data(), J.psk.data(), J.psn.data(), n, st));
-    else RUN(cartnet_gemm_split_b(J.psrc.data(), J.pdst.data(), J.pK.data(), J.pN.data(), J.psk.data(), J.psn.data(), n, st));
-  }
-  for (size_t j0 = 0; j0 < J.tsrc.size(); j0 += 40) {
-    const int n = (int)std::min<size_t>(40, J.tsrc.size() - j0);
-    RUN(cartnet_transpose(J.tsrc.data() + j0, J.tdst.data() + j0, J.trows.data() + j0, J.tcols.data() + j0,
-                          J.tlds.data() + j0, J.tldd.data() + j0, n, st));
-  }
-  return 0;
 }
 
 // group g of a forward product Y = X W^T: the DMA form (transposed copy + image) when images are in use, else W itself
@@ -443,7 +377,7 @@ int att_forward(const CartnetIcfModel& m, const CartnetIcfConv& P, const Cartnet
   const int C = m.C, prec = m.gemm_precision;
   const bool afree = icf_alpha_free(C);
   {  // pr = rows_in F^T + c + term_i[idx_i] + term_j[idx_j]      (key | msg; F = W1[:, 2C:] We: lin_edge folded in)
-    CartnetGemmArgs a = gargs(prec, t.R, C, C, C, C, 2 * C);
+    CartnetGemmArgs a = gemm_args(prec, t.R, C, C, C, C, 2 * C, TILE128);
     a.ngroups = 2; fwd_form(a, cw, F_K1E, C, w.use_img);
     a.A[0] = rows_in; a.A[1] = rows_in;
     if (P.edge_b) { a.bias[0] = w.ck[l]; a.bias[1] = w.cm[l]; }
@@ -454,7 +388,7 @@ int att_forward(const CartnetIcfModel& m, const CartnetIcfConv& P, const Cartnet
     RUN(cartnet_gemm(&a, st));
   }
   {  // key' = silu(pr_k) W2k^T + b  -> keyb[:, :C];  msg = silu(pr_m) W2m^T + b -> gs[:, C:]
-    CartnetGemmArgs a = gargs(prec, t.R, C, C, 2 * C, C, 2 * C);
+    CartnetGemmArgs a = gemm_args(prec, t.R, C, C, 2 * C, C, 2 * C, TILE128);
     a.ngroups = 2; a.a_act = 1; fwd_form(a, cw, F_K2, C, w.use_img);
     a.A[0] = w.pr[l]; a.A[1] = w.pr[l] + C;
     fwd_operand(a, 0, cw, F_K2, w.use_img); fwd_operand(a, 1, cw, F_M2, w.use_img);
@@ -495,44 +429,42 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
   CN_CHECK((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "cartnet_icomformer_forward: workspace must be 256-byte aligned");
   const int C = m.C, H = C / 2, N = b.N, Bg = b.Bg, prec = m.gemm_precision;
   const int E = (int)b.E;
-  g_icf_events.next = 0;
-  Streams S{(hipStream_t)st, aux_stream ? (hipStream_t)aux_stream : (hipStream_t)st, aux_stream != nullptr && aux_stream != st,
-            &g_icf_events};
+  Streams S("cartnet_icomformer_forward", st, aux_stream);
   void* sw = (void*)S.side;
-  if (S.fork() != 0) { cartnet_set_error("cartnet_icomformer_forward: stream fork failed"); return 2; }
+  RUN(S.fork());
 
   // ---- weight forms of the step: every transposed copy and every image, two batched launches (side stream)
-  Jobs& J = g_jobs;
+  WeightForms& J = weight_forms();
   J.clear();
   for (int l = 0; l < 5; ++l) {
     const CartnetIcfConv& q = l < 4 ? P.att[l] : P.edge;
     {  // F{k,m} = W1{k,m}[:, 2C:] We   (C x C x C each, two groups)
-      CartnetGemmArgs a = gargs(0, C, C, C, 3 * C, C, C);
-      a.ngroups = 2; a.b_kstrided = 1; a.tile_policy = 0;
+      CartnetGemmArgs a = gemm_args(0, C, C, C, 3 * C, C, C);
+      a.ngroups = 2; a.b_kstrided = 1;
       a.A[0] = q.key0_w + 2 * C; a.A[1] = q.msg0_w + 2 * C; a.B[0] = q.edge_w; a.B[1] = q.edge_w;
       a.C[0] = w.Fk[l]; a.C[1] = w.Fm[l];
       RUN(cartnet_gemm(&a, sw));
     }
     if (q.edge_b) {   // c{k,m} = W1{k,m}[:, 2C:] be   (one row times W^T)
-      CartnetGemmArgs a = gargs(0, 1, C, C, C, 3 * C, C);
-      a.ngroups = 2; a.tile_policy = 0;
+      CartnetGemmArgs a = gemm_args(0, 1, C, C, C, 3 * C, C);
+      a.ngroups = 2;
       a.A[0] = q.edge_b; a.A[1] = q.edge_b; a.B[0] = q.key0_w + 2 * C; a.B[1] = q.msg0_w + 2 * C;
       a.C[0] = w.ck[l]; a.C[1] = w.cm[l];
       RUN(cartnet_gemm(&a, sw));
     }
-    plan_conv(q, w.Fk[l], w.Fm[l], C, prec, w.use_img, w.cw[l], J);
+    conv_views(q, w.Fk[l], w.Fm[l], C, w.cw[l]);
+    if (w.use_img) queue_conv_forms(q, w.Fk[l], w.Fm[l], C, prec, w.cw[l], J);
   }
   if (w.use_img) {
     for (int i = 0; i < 2; ++i) {
       const float* W_ = i ? P.rbf_angle_w : P.rbf_w;
-      J.psrc.push_back(W_); J.pdst.push_back(i ? w.rbfaF : w.rbfF); J.pK.push_back(C); J.pN.push_back(C); J.psk.push_back(1); J.psn.push_back(C);
-      J.tsrc.push_back(W_); J.tdst.push_back(i ? w.rbfaT : w.rbfT); J.trows.push_back(C); J.tcols.push_back(C); J.tlds.push_back(C); J.tldd.push_back(C);
+      J.image(W_, i ? w.rbfaF : w.rbfF, C, C, 1, C);
+      J.transpose(W_, i ? w.rbfaT : w.rbfT, C, C, C, C);
     }
-    if (H % 16 == 0) {      // head0 [H, C] as the backward operand [K = H, N = C]
-      J.psrc.push_back(P.head0_w); J.pdst.push_back(w.head0B); J.pK.push_back(H); J.pN.push_back(C); J.psk.push_back(C); J.psn.push_back(1);
-    }
+    if (H % 16 == 0) J.image(P.head0_w, w.head0B, H, C, C, 1);      // head0 [H, C] as the backward operand [K = H, N = C]
   }
-  RUN(flush_jobs(J, prec, sw));
+  RUN(J.flush_images(prec, sw));
+  RUN(J.flush_transposes(sw));
   hipEvent_t forms_ready = S.mark_side();
 
   // ---- graph layout, embeddings, lattice features (comformer.py:116-124)
@@ -556,15 +488,15 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
                        (long long)b.E, b.graph_ptr, w.rowptr, Bg, w.idx_edge, w.idx_gl, w.ptr3, w.gedge_ptr);
     CN_LAUNCH_CHECK("cartnet_icomformer_forward (index kernel)");
   }
-  if (S.main_waits(forms_ready) != 0) { cartnet_set_error("cartnet_icomformer_forward: stream wait failed"); return 2; }
+  RUN(S.main_waits(forms_ready));
 
   // out = softplus(rbf(vals) W^T + b): keeps (r, pre) for backward
   auto rbf_branch = [&](const float* vals, long long n, const float* centers, float gamma, const float* W_, const float* T_,
                         const char* F_, const float* bias, float* r, float* pre, float* out) -> int {
     RUN(cartnet_rbf_expand(vals, n, centers, C, gamma, r, C, st));
-    CartnetGemmArgs a = gargs(prec, (int)n, C, C, C, C, C);
+    CartnetGemmArgs a = gemm_args(prec, (int)n, C, C, C, C, C, TILE128);
     const bool img = w.use_img && n >= 2048;      // a handful of rows (lattice lengths): the plain NT form
-    a.A[0] = r; a.C[0] = pre; a.bias[0] = bias;
+    a.A[0] = r; a.bias[0] = bias;
     if (img) { a.b_kstrided = 1; a.B[0] = T_; a.b_split[0] = F_; } else { a.B[0] = W_; }
     // pre and softplus(pre) from the product's epilogue (CartnetGemmArgs.dact_kind = 1 with cpre + out_act): the element-wise
     // pass read pre and wrote out, 0.25 ms per step over the E + 3E rows
@@ -581,14 +513,14 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
     const CartnetIcfConv& q = P.att[l];
     const ConvW& cw = w.cw[l];
     {  // q | k | v
-      CartnetGemmArgs a = gargs(prec, N, C, C, C, C, 3 * C);
+      CartnetGemmArgs a = gemm_args(prec, N, C, C, C, C, 3 * C, TILE128);
       a.ngroups = 3; fwd_form(a, cw, F_Q, C, w.use_img);
       for (int g = 0; g < 3; ++g) { a.A[g] = x; a.C[g] = w.QKV[l] + g * C; fwd_operand(a, g, cw, F_Q + g, w.use_img); }
       a.bias[0] = q.query_b; a.bias[1] = q.key_b; a.bias[2] = q.value_b;
       RUN(cartnet_gemm(&a, st));
     }
     {  // node terms of key_update.0 / lin_msg_update.0: KPi = [k W1k_i^T + b | v W1m_i^T + b], KPj = [k W1k_j^T | v W1m_j^T]
-      CartnetGemmArgs a = gargs(prec, N, C, C, 3 * C, C, 2 * C);
+      CartnetGemmArgs a = gemm_args(prec, N, C, C, 3 * C, C, 2 * C, TILE128);
       a.ngroups = 4; fwd_form(a, cw, F_K1I, C, w.use_img);
       const float* k = w.QKV[l] + C; const float* v = w.QKV[l] + 2 * C;
       a.A[0] = k; a.A[1] = v; a.A[2] = k; a.A[3] = v;
@@ -601,7 +533,7 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
     Att t{E, N, w.rowptr, w.tgt32, w.src32, w.KPi[l], w.KPj[l], w.QKV[l], 3 * C, (long long)b.E, w.gp_n, w.sp_n, N, w.groups};
     RUN(att_forward(m, q, m.att_bn_att[l], cw, t, l, e, w, training, st));
     {  // o = lin_concate(aggr) with the BatchNorm statistics over atoms
-      CartnetGemmArgs a = gargs(prec, N, C, C, C, C, C);
+      CartnetGemmArgs a = gemm_args(prec, N, C, C, C, C, C, TILE128);
       fwd_form(a, cw, F_CAT, C, w.use_img);
       a.A[0] = w.aggr[l]; a.C[0] = w.o[l]; a.bias[0] = q.concate_b; fwd_operand(a, 0, cw, F_CAT, w.use_img);
       if (!w.groups) { a.colsum[0] = w.cs; a.colsq[0] = w.cq; }
@@ -621,14 +553,14 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
     const CartnetIcfConv& q = P.edge;
     const ConvW& cw = w.cw[l];
     {
-      CartnetGemmArgs a = gargs(prec, E, C, C, C, C, 3 * C);
+      CartnetGemmArgs a = gemm_args(prec, E, C, C, C, C, 3 * C, TILE128);
       a.ngroups = 3; fwd_form(a, cw, F_Q, C, w.use_img);
       for (int g = 0; g < 3; ++g) { a.A[g] = e; a.C[g] = w.QKV[l] + g * C; fwd_operand(a, g, cw, F_Q + g, w.use_img); }
       a.bias[0] = q.query_b; a.bias[1] = q.key_b; a.bias[2] = q.value_b;
       RUN(cartnet_gemm(&a, st));
     }
     for (int kv = 0; kv < 2; ++kv) {   // lin_key_e{i} / lin_value_e{i} on the lattice-length features: [Bg, 3C] views
-      CartnetGemmArgs a = gargs(prec, Bg, C, C, 3 * C, C, 3 * C);
+      CartnetGemmArgs a = gemm_args(prec, Bg, C, C, 3 * C, C, 3 * C, TILE128);
       a.ngroups = 3;
       for (int i = 0; i < 3; ++i) {
         a.A[i] = w.NLt + i * C; a.B[i] = kv ? q.value_e_w[i] : q.key_e_w[i]; a.bias[i] = kv ? q.value_e_b[i] : q.key_e_b[i];
@@ -637,7 +569,7 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
       RUN(cartnet_gemm(&a, st));
     }
     {  // per-edge term
-      CartnetGemmArgs a = gargs(prec, E, C, C, 3 * C, C, 2 * C);
+      CartnetGemmArgs a = gemm_args(prec, E, C, C, 3 * C, C, 2 * C, TILE128);
       a.ngroups = 2; fwd_form(a, cw, F_K1I, C, w.use_img);
       a.A[0] = w.QKV[l] + C; a.A[1] = w.QKV[l] + 2 * C; a.C[0] = w.Ka; a.C[1] = w.Ka + C;
       fwd_operand(a, 0, cw, F_K1I, w.use_img); fwd_operand(a, 1, cw, F_M1I, w.use_img);
@@ -645,7 +577,7 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
       RUN(cartnet_gemm(&a, st));
     }
     {  // per (crystal, lattice vector) term: a handful of rows, the plain NT form
-      CartnetGemmArgs a = gargs(prec, Bg * 3, C, C, C, 3 * C, 2 * C);
+      CartnetGemmArgs a = gemm_args(prec, Bg * 3, C, C, C, 3 * C, 2 * C, TILE128);
       a.ngroups = 2;
       a.A[0] = w.KY; a.A[1] = w.VY; a.B[0] = q.key0_w + C; a.B[1] = q.msg0_w + C; a.C[0] = w.KYb; a.C[1] = w.KYb + C;
       RUN(cartnet_gemm(&a, st));
@@ -655,7 +587,7 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
     RUN(att_forward(m, q, m.edge_bn_att, cw, t, l, w.NA, w, training, st));
     RUN(cartnet_eltwise(3, q.concate_b, nullptr, w.bias3, 1, C, C, 0, C, 3.0f, st));
     {
-      CartnetGemmArgs a = gargs(prec, E, C, C, C, C, C);
+      CartnetGemmArgs a = gemm_args(prec, E, C, C, C, C, C, TILE128);
       fwd_form(a, cw, F_CAT, C, w.use_img);
       a.A[0] = w.aggr[l]; a.C[0] = w.o[l]; a.bias[0] = w.bias3; fwd_operand(a, 0, cw, F_CAT, w.use_img);
       if (!w.groups_e) { a.colsum[0] = w.cs; a.colsq[0] = w.cq; }
@@ -675,14 +607,14 @@ extern "C" int cartnet_icomformer_forward(const CartnetIcfModel* model, const Ca
 
   // ---- Cholesky head (shared with CartNet)
   {
-    CartnetGemmArgs a = gargs(prec, N, H, C, C, C, H);
+    CartnetGemmArgs a = gemm_args(prec, N, H, C, C, C, H, TILE128);
     a.A[0] = x_out; a.B[0] = P.head0_w; a.C[0] = w.hid; a.bias[0] = P.head0_b;
     RUN(cartnet_gemm(&a, st));
   }
   RUN(cartnet_mask_index(b.non_h_mask, N, w.idx, nullptr, st));
   RUN(cartnet_cholesky_head_fwd(w.hid, w.idx, P.head2_w, P.head2_b, N, H, w.p6, pred, st));
   // join (the side stream carried only the weight forms)
-  if (S.main_waits(S.mark_side()) != 0) { cartnet_set_error("cartnet_icomformer_forward: stream join failed"); return 2; }
+  RUN(S.join());
   return 0;
 }
 
@@ -703,27 +635,22 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   w.groups_e = w.groups ? &w.grp_e : nullptr;
   const int C = m.C, H = C / 2, N = b.N, Bg = b.Bg, prec = m.gemm_precision;
   const int E = (int)b.E;
-  for (int l = 0; l < 5; ++l) {        // the views (the forms themselves were built by forward and are still in the workspace)
-    Jobs dummy;
-    plan_conv(l < 4 ? P.att[l] : P.edge, w.Fk[l], w.Fm[l], C, prec, false, w.cw[l], dummy);
-  }
-  g_icf_events.next = 0;
-  Streams S{(hipStream_t)stream, aux_stream ? (hipStream_t)aux_stream : (hipStream_t)stream,
-            aux_stream != nullptr && aux_stream != stream, &g_icf_events};
+  // the views (the forms themselves were built by forward and are still in the workspace)
+  for (int l = 0; l < 5; ++l) conv_views(l < 4 ? P.att[l] : P.edge, w.Fk[l], w.Fm[l], C, w.cw[l]);
+  Streams S("cartnet_icomformer_backward", stream, aux_stream);
   void* st = stream;
   void* sw = (void*)S.side;
-#define FORK() do { if (S.fork() != 0) { cartnet_set_error("cartnet_icomformer_backward: stream fork failed"); return 2; } } while (0)
-#define JOIN() do { if (S.main_waits(S.mark_side()) != 0) { cartnet_set_error("cartnet_icomformer_backward: stream join failed"); return 2; } } while (0)
+  const WgradPlan wk{prec, TILE128, w.slabs, w.slab_floats};      // every weight gradient runs on the side stream
   // weight gradient on the side stream: everything it reads was queued on the main stream before this point
   auto wg = [&](std::initializer_list<const float*> dY, int ldy, std::initializer_list<const float*> X, int ldx,
                 std::initializer_list<float*> outs, int ldo, long long K, int M_, int N_, bool b_act = false) -> int {
-    FORK();
-    return iwgrad(prec, dY.begin(), ldy, X.begin(), ldx, outs.begin(), ldo, K, M_, N_, (int)dY.size(), b_act, w, sw);
+    RUN(S.fork());
+    return wgrad(wk, dY.begin(), ldy, X.begin(), ldx, outs.begin(), ldo, K, M_, N_, (int)dY.size(), b_act, sw);
   };
   // dX (+ resid) = dY W with W [K = out, N = in] (leading dimension ldw) and its backward image if there is one
   auto dgemm = [&](const float* dY, int ldy, const float* W_, int ldw, const char* img, float* dX, int ldx, long long rows,
                    int Kout, int Nin, const float* resid, int ldr, void* s_, double* colparts = nullptr) -> int {
-    CartnetGemmArgs a = gargs(prec, (int)rows, Nin, Kout, ldy, ldw, ldx);
+    CartnetGemmArgs a = gemm_args(prec, (int)rows, Nin, Kout, ldy, ldw, ldx, TILE128);
     a.b_kstrided = 1; a.A[0] = dY; a.B[0] = W_; a.C[0] = dX; a.resid[0] = resid; a.ldr = ldr;
     a.colsum[0] = colparts;                                   // [tiles_m(rows)][Nin] partial column sums of dX
     if (img && rows >= 2048) a.b_split[0] = img;
@@ -731,15 +658,8 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   };
 
   // ---- head
-  const int head_row = 7 * H + 8;
   RUN(cartnet_cholesky_head_bwd(w.hid, w.idx, P.head2_w, w.p6, dpred, N, H, w.dhid, w.head_parts, st));
-  RUN(cartnet_colsum_finalize_f32(w.head_parts, w.nparts_n, head_row, w.head_tot, st));
-  if (hipMemcpyAsync(G.head2_w, w.head_tot, sizeof(float) * 6 * H, hipMemcpyDeviceToDevice, (hipStream_t)st) != hipSuccess ||
-      hipMemcpyAsync(G.head2_b, w.head_tot + 6 * H, sizeof(float) * 6, hipMemcpyDeviceToDevice, (hipStream_t)st) != hipSuccess ||
-      hipMemcpyAsync(G.head0_b, w.head_tot + 6 * H + 8, sizeof(float) * H, hipMemcpyDeviceToDevice, (hipStream_t)st) != hipSuccess) {
-    cartnet_set_error("cartnet_icomformer_backward: head gradient copy failed");
-    return 2;
-  }
+  RUN(head_grad_tail(S.who, w.head_parts, w.nparts_n, w.head_tot, 6 * H, 6, H, G.head2_w, G.head2_b, G.head0_b, st));
   RUN(wg({w.dhid}, H, {x_out}, C, {G.head0_w}, C, N, H, C));
   RUN(dgemm(w.dhid, H, P.head0_w, C, (w.use_img && H % 16 == 0) ? w.head0B : nullptr, w.dx_head, C, N, H, C, nullptr, 0, st));
 
@@ -832,7 +752,7 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     if (w.act[l]) RUN(wg({gs, gs + C}, 2 * C, {w.act[l], w.act[l] + C}, 2 * C, {g.key2_w, g.msg2_w}, C, t.R, C, C, false));
     else RUN(wg({gs, gs + C}, 2 * C, {w.pr[l], w.pr[l] + C}, 2 * C, {g.key2_w, g.msg2_w}, C, t.R, C, C, true));
     {  // dpr = (gs W2) * silu'(pr), column sums = bias gradients of the first Linears
-      CartnetGemmArgs a = gargs(prec, t.R, C, C, 2 * C, C, 2 * C);
+      CartnetGemmArgs a = gemm_args(prec, t.R, C, C, 2 * C, C, 2 * C, TILE128);
       a.ngroups = 2; a.b_kstrided = 1;
       a.A[0] = gs; a.A[1] = gs + C; a.B[0] = q.key2_w; a.B[1] = q.msg2_w;
       a.C[0] = w.dpr[l]; a.C[1] = w.dpr[l] + C; a.dact[0] = w.pr[l]; a.dact[1] = w.pr[l] + C; a.ldd = 2 * C;
@@ -859,9 +779,9 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
                            float* d_rows, const float* resid, const float* sp_pre = nullptr, float* sp_bias = nullptr) -> int {
     const ConvW& cw = w.cw[l];
     float* dpr = w.dpr[l];
-    FORK();
+    RUN(S.fork());
     {
-      CartnetGemmArgs a = gargs(prec, (int)R, C, C, 2 * C, C, C);
+      CartnetGemmArgs a = gemm_args(prec, (int)R, C, C, 2 * C, C, C, TILE128);
       a.nsegs = 2; a.b_kstrided = 1;
       a.A[0] = dpr; a.A[1] = dpr + C; a.B[0] = w.Fk[l]; a.B[1] = w.Fm[l]; a.C[0] = d_rows; a.resid[0] = resid; a.ldr = C;
       if (w.use_img) a.b_split_folded = cw.B[B_E1];
@@ -880,11 +800,11 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
       const float* dY[2] = {dpr, dpr + C};
       const float* X[2] = {rows_in, rows_in};
       float* o[2] = {w.dFk[l], w.dFm[l]};
-      RUN(iwgrad(prec, dY, 2 * C, X, C, o, C, R, C, C, 2, false, w, sw));
+      RUN(wgrad(wk, dY, 2 * C, X, C, o, C, R, C, C, 2, false, sw));
     }
     {  // dW1{k,m}[:, 2C:] = dF We^T
-      CartnetGemmArgs a = gargs(0, C, C, C, C, C, 3 * C);
-      a.ngroups = 2; a.tile_policy = 0;
+      CartnetGemmArgs a = gemm_args(0, C, C, C, C, C, 3 * C);
+      a.ngroups = 2;
       a.A[0] = w.dFk[l]; a.A[1] = w.dFm[l]; a.B[0] = q.edge_w; a.B[1] = q.edge_w;
       a.C[0] = g.key0_w + 2 * C; a.C[1] = g.msg0_w + 2 * C;
       RUN(cartnet_gemm(&a, sw));
@@ -895,8 +815,8 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
       CN_LAUNCH_CHECK("cartnet_icomformer_backward (rank-1 update)");
     }
     {  // dWe = W1k[:, 2C:]^T dFk + W1m[:, 2C:]^T dFm
-      CartnetGemmArgs a = gargs(0, C, C, C, 3 * C, C, C);
-      a.nsegs = 2; a.a_kstrided = 1; a.b_kstrided = 1; a.tile_policy = 0;
+      CartnetGemmArgs a = gemm_args(0, C, C, C, 3 * C, C, C);
+      a.nsegs = 2; a.a_kstrided = 1; a.b_kstrided = 1;
       a.A[0] = q.key0_w + 2 * C; a.A[1] = q.msg0_w + 2 * C; a.B[0] = w.dFk[l]; a.B[1] = w.dFm[l]; a.C[0] = g.edge_w;
       RUN(cartnet_gemm(&a, sw));
     }
@@ -913,7 +833,7 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   auto linear3_bwd = [&](int l, const CartnetIcfConv& q, const CartnetIcfConv& g, const float* inp, int rows, float* d_in) -> int {
     float* dQ = w.dQKV[l];
     RUN(wg({dQ, dQ + C, dQ + 2 * C}, 3 * C, {inp, inp, inp}, C, {g.query_w, g.key_w, g.value_w}, C, rows, C, C));
-    CartnetGemmArgs a = gargs(prec, rows, C, C, 3 * C, C, C);
+    CartnetGemmArgs a = gemm_args(prec, rows, C, C, 3 * C, C, C, TILE128);
     a.nsegs = 3; a.b_kstrided = 1;
     a.A[0] = dQ; a.A[1] = dQ + C; a.A[2] = dQ + 2 * C; a.B[0] = q.query_w; a.B[1] = q.key_w; a.B[2] = q.value_w;
     a.C[0] = d_in; a.resid[0] = w.dres[l]; a.ldr = C;
@@ -958,7 +878,7 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     RUN(wg({dKP, dKP + 2 * C, dKP + C, dKP + 3 * C}, 4 * C, {k, v, k, v}, 3 * C,
            {g.key0_w, g.msg0_w, g.key0_w + C, g.msg0_w + C}, 3 * C, N, C, C));
     for (int km = 0; km < 2; ++km) {   // dk = dKPi_k W1k_i + dKPj_k W1k_j ; dv likewise
-      CartnetGemmArgs a = gargs(prec, N, C, C, 4 * C, 3 * C, 3 * C);
+      CartnetGemmArgs a = gemm_args(prec, N, C, C, 4 * C, 3 * C, 3 * C, TILE128);
       a.nsegs = 2; a.b_kstrided = 1;
       const float* W1 = km ? q.msg0_w : q.key0_w;
       a.A[0] = dKP + km * 2 * C; a.A[1] = a.A[0] + C; a.B[0] = W1; a.B[1] = W1 + C;
@@ -1025,7 +945,7 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
         RUN(colsum(dT, 3 * C, Bg, C, w.pa, kv ? g.value_e_b[i] : g.key_e_b[i], st));
         RUN(wg({dT}, 3 * C, {w.NLt + i * C}, 3 * C, {kv ? g.value_e_w[i] : g.key_e_w[i]}, C, Bg, C, C));
       }
-      CartnetGemmArgs a = gargs(prec, Bg, C, C, 3 * C, C, 3 * C);
+      CartnetGemmArgs a = gemm_args(prec, Bg, C, C, 3 * C, C, 3 * C, TILE128);
       a.nsegs = 2; a.b_kstrided = 1;
       a.A[0] = w.dKY + i * C; a.A[1] = w.dVY + i * C; a.B[0] = q.key_e_w[i]; a.B[1] = q.value_e_w[i]; a.C[0] = w.dNL3 + i * C;
       RUN(cartnet_gemm(&a, st));
@@ -1041,16 +961,14 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     dx = w.dx[l];
     de_new = w.de[l];
   }
-#define WAIT_ROWS(l) do { if (S.main_waits(rows_ready[l]) != 0) { cartnet_set_error("cartnet_icomformer_backward: stream wait failed"); return 2; } } while (0)
-  WAIT_ROWS(1);                                      // de_new = de[1] (accumulated from layers 3 and 2 on the side stream)
+  RUN(S.main_waits(rows_ready[1]));      // de_new = de[1] (accumulated from layers 3 and 2 on the side stream)
   RUN(conv_edge_bwd(de_new));
   RUN(conv_bwd(0, dx, w.de_old));
   dx = w.dx[0];
   if (!rbf_fuse) {
-    WAIT_ROWS(0);                                    // de[0]
-    WAIT_ROWS(4);                                    // dNA
+    RUN(S.main_waits(rows_ready[0]));      // de[0]
+    RUN(S.main_waits(rows_ready[4]));      // dNA
   }
-#undef WAIT_ROWS
 
   // ---- RBF branches: out = softplus(pre), pre = rbf W^T + b; rbf.1 is shared by the distance and the lattice-length
   //      features, so its gradients add up
@@ -1075,7 +993,7 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
     RUN(rbf_bwd(w.r_nl, w.pre_nl, w.dNL3, (long long)Bg * 3, w.dpre_nl, w.gw2, w.gb2));
     RUN(rbf_bwd(w.r_na, w.pre_na, w.dNA, 3LL * b.E, w.dpre_na, G.rbf_angle_w, G.rbf_angle_b));
   }
-  JOIN();                                            // gw1 / gw2 come from the side stream
+  RUN(S.join());      // gw1 / gw2 come from the side stream
   RUN(cartnet_eltwise(2, w.gw1, w.gw2, G.rbf_w, C, C, C, C, C, 1.0f, st));
   RUN(cartnet_eltwise(2, w.gb1, w.gb2, G.rbf_b, 1, C, C, C, C, 1.0f, st));
 
@@ -1088,8 +1006,6 @@ extern "C" int cartnet_icomformer_backward(const CartnetIcfModel* model, const C
   }
   RUN(cartnet_sort_by_key(b.z, N, m.n_types, w.zperm, w.zptr, w.zstatus, st));
   RUN(cartnet_segment_sum_long(dx, C, w.zptr, w.zperm, m.n_types, N, C, w.seg_tmp, G.embedding, C, st));
-  JOIN();
-#undef FORK
-#undef JOIN
+  RUN(S.join());
   return 0;
 }

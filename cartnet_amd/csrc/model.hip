@@ -43,7 +43,7 @@ struct Work {
   float *dhid, *head_parts, *head_tot, *dx[2], *de[2], *daggr, *sums1, *sums2, *dPn[2], *dpre[2], *dhe, *dx0, *seg_tmp,
       *slabs, *slabs2, *e0wT, *gate_bnd;
   double *pa, *pb, *pc[2], *pd[2], *cs_misc[4];
-  size_t slab_floats;
+  size_t slab_floats, slab2_floats;
   int gparts, nparts_n, tiles_e, tiles_n;
   // BatchNorm groups (CartnetModel.bn_group_size > 0 and more than one group in this batch): gparts / nrows_n are then
   // the TOTAL partial-sum rows of the per-edge / per-node statistics kernels (G x parts per group)
@@ -57,12 +57,11 @@ struct Work {
 // de_out (544 MB per layer at the benchmark batch): needs a kernel that carries the epilogue (cartnet_gemm_gate_stats_ok:
 // fp32 MFMA or bf16x3, D = 256 -- the two K-segments of dE fold into one product --, at least 64 / 96 row tiles), one
 // BatchNorm group and per-rank statistics.  Training-mode passes only (the callers check `training`).
-inline bool gate_sums_fused(const CartnetModel& m, int G, int tiles_e, long long E) {
+inline bool gate_sums_fused(const CartnetModel& m, int G, long long E) {
   if (!(m.gemm_precision <= 1 && G == 1 && m.half_storage == 0 && m.bn_allreduce == nullptr && E > 0)) return false;
   // ONE predicate for "the dE product takes the kernel with the epilogue" (ADVICE r5): the launch cartnet_model_backward
   // will build (same shapes, strides and flags; placeholder pointers with the alignment the workspace guarantees) is put
   // to gemm.hip's own cartnet_gemm_gate_stats_ok -- forward commits to the per-target sums here, backward checks again.
-  (void)tiles_e;
   const int D = m.D;
   float* const ph = reinterpret_cast<float*>(uintptr_t(1) << 20);
   CartnetGemmArgs a;
@@ -87,12 +86,11 @@ Work carve(const CartnetModel& m, int N, long long E, int Bg, int M, bool need_b
   w.gparts = cartnet_gate_scatter_nparts(N);
   w.nparts_n = cartnet_node_nparts(N);
   w.nrows_n = w.nparts_n;
-  w.G = (m.bn_group_size > 0 && Bg > m.bn_group_size) ? (Bg + m.bn_group_size - 1) / m.bn_group_size : 1;
+  w.G = group_count(Bg, m.bn_group_size);
   if (w.G > 1) {
-    const int per = (int)((Nn + (size_t)4 * w.G - 1) / ((size_t)4 * w.G));    // ceil(N / G / nodes-per-workgroup)
     w.grp.G = w.G;
-    w.grp.edge_parts = per < 1 ? 1 : (per > 1024 ? 1024 : per);
-    w.grp.node_parts = per < 1 ? 1 : (per > 256 ? 256 : per);
+    w.grp.edge_parts = group_parts(Nn, w.G, 1024);
+    w.grp.node_parts = group_parts(Nn, w.G, 256);
     w.gparts = w.G * w.grp.edge_parts;
     w.nrows_n = w.G * w.grp.node_parts;
   }
@@ -164,7 +162,7 @@ Work carve(const CartnetModel& m, int N, long long E, int Bg, int M, bool need_b
     for (int l = 0; l < L; ++l) w.act[l] = c.take<float>(En * 2 * D);
     w.he_act = c.take<float>(En * 2 * D);
   }
-  if (need_bwd && gate_sums_fused(m, w.G, w.tiles_e, E)) {
+  if (need_bwd && gate_sums_fused(m, w.G, E)) {
     for (int l = 0; l < L; ++l) w.bc[l] = c.take<float>(Nn * 2 * D);
     w.gpa = c.take<double>((size_t)(w.tiles_e + w.nparts_n) * D);
     w.gpb = c.take<double>((size_t)(w.tiles_e + w.nparts_n) * D);
@@ -252,27 +250,11 @@ Work carve(const CartnetModel& m, int N, long long E, int Bg, int M, bool need_b
     size_t sl2 = wgrad_slab_floats(1, E, 2 * D, w.kf);
     const size_t sl2b = wgrad_slab_floats(1, E, w.ldf, 2 * D);
     if (sl2b > sl2) sl2 = sl2b;
+    w.slab2_floats = sl2;
     w.slabs2 = c.take<float>(sl2 > 0 ? sl2 : 1);
   }
   *total = align_up(c.off);
   return w;
-}
-
-// bytes of one D x D weight image at the model's GEMM precision (images of a folded operand sit back to back)
-inline size_t img_blk(const CartnetModel& m) {
-  return m.gemm_precision == 0 ? cartnet_gemm_pack_b_bytes(m.D, m.D) : cartnet_gemm_split_b_bytes(m.D, m.D);
-}
-
-thread_local int g_precision = 0;   // set per call from CartnetModel.gemm_precision
-
-inline CartnetGemmArgs gemm_args(int M, int N, int K, int lda, int ldb, int ldc) {
-  CartnetGemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.precision = g_precision;
-  a.M = M; a.N = N; a.K = K;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  a.ngroups = 1; a.nsegs = 1; a.splitk = 1;
-  return a;
 }
 
 // the fp32 forms under the _h forms' signatures (void* for the tensor that changes its element type)
@@ -299,36 +281,6 @@ inline float* hcol(float* p, size_t elems, bool half) {
   return half ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(p) + elems) : p + elems;
 }
 inline const float* hcol(const float* p, size_t elems, bool half) { return hcol(const_cast<float*>(p), elems, half); }
-
-// outs[g] = dY[g]^T @ (silu?)(X[g]): reduction over `K` rows, split over workgroups, slabs summed in fixed order.
-int wgrad(const float* const* dY, int ldy, const float* const* X, int ldx, float* const* outs, int ldo, long long K,
-          int M, int N, int groups, bool b_act, const Work& w, void* st, bool dy_half = false, bool x_half = false) {
-  if (K <= 0) {   // no rows: the gradient is zero
-    for (int g = 0; g < groups; ++g)
-      for (int r = 0; r < M; ++r)
-        if (hipMemsetAsync(outs[g] + (size_t)r * ldo, 0, sizeof(float) * N, (hipStream_t)st) != hipSuccess) return 2;
-    return 0;
-  }
-  const int S = split_k(K, wgrad_tiles(groups, M, N));
-  CartnetGemmArgs a = gemm_args(M, N, (int)K, ldy, ldx, S > 1 ? N : ldo);
-  a.ngroups = groups;
-  a.a_kstrided = 1;
-  a.b_kstrided = 1;
-  a.b_act = b_act ? 1 : 0;
-  a.a_half = dy_half ? 1 : 0;
-  a.b_half = x_half ? 1 : 0;
-  a.splitk = S;
-  const float* slabp[CARTNET_MAX_GROUPS];
-  for (int g = 0; g < groups; ++g) {
-    a.A[g] = dY[g];
-    a.B[g] = X[g];
-    a.C[g] = S > 1 ? w.slabs + (size_t)g * S * M * N : outs[g];
-    slabp[g] = a.C[g];
-  }
-  RUN(cartnet_gemm(&a, st));
-  if (S > 1) RUN(cartnet_splitk_reduce(slabp, outs, groups, S, M, N, ldo, st));
-  return 0;
-}
 
 int check_model(const CartnetModel* m, const CartnetBatch* b, const char* who) {
   CN_CHECK(m && b, "%s: null model/batch", who);
@@ -366,10 +318,6 @@ int check_model(const CartnetModel* m, const CartnetBatch* b, const char* who) {
 
 }  // namespace
 
-namespace {
-thread_local EventPool g_events;
-}  // namespace
-
 extern "C" size_t cartnet_workspace_bytes(const CartnetModel* model, int32_t N, int64_t E, int32_t Bg, int32_t M,
                                           int32_t need_backward) {
   if (!model || model->L < 1 || model->L > CARTNET_MAX_LAYERS) return 0;
@@ -382,7 +330,6 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
                                      size_t workspace_bytes, int32_t training, int32_t need_backward, float* pred,
                                      float* x_out, float* e_out, int32_t* status, void* st, void* aux_stream) {
   RUN(check_model(model, batch, "cartnet_model_forward"));
-  g_precision = model->gemm_precision;
   const CartnetModel& m = *model;
   const CartnetBatch& b = *batch;
   const CartnetParams& P = m.p;
@@ -393,21 +340,18 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
   Work w = carve(m, b.N, b.E, b.Bg, b.M, need_backward != 0, static_cast<char*>(workspace), &need);
   CN_CHECK(workspace_bytes >= need, "cartnet_model_forward: workspace %zu < required %zu bytes", workspace_bytes, need);
   w.groups = w.G > 1 ? &w.grp : nullptr;
-  const int D = m.D, L = m.L, H = D / 2, N = b.N;
+  const int D = m.D, L = m.L, H = D / 2, N = b.N, prec = m.gemm_precision;
   const int E = (int)b.E;
+  const size_t blk = img_bytes(prec, D, D);      // one D x D weight image (images of a folded operand sit back to back)
   const bool plain = !m.use_temperature && !m.atom_types;
 
   // Second stream (optional): what does not depend on the graph -- the weight transposes and images -- and the atom
   // branch of the encoder with the first layer's node terms (few row tiles: they leave most of the chip idle) run on it
   // next to the layout build and the edge encoder; the main stream waits for them where it needs them and the two
   // streams are joined before the call returns.
-  g_events.next = 0;
-  Streams S{(hipStream_t)st, aux_stream ? (hipStream_t)aux_stream : (hipStream_t)st, aux_stream != nullptr && aux_stream != st,
-            &g_events};
+  Streams S("cartnet_model_forward", st, aux_stream);
   void* sw = (void*)S.side;
-#define FORK() do { if (S.fork() != 0) { cartnet_set_error("cartnet_model_forward: stream fork failed"); return 2; } } while (0)
-#define MAIN_WAITS(ev) do { if (S.main_waits(ev) != 0) { cartnet_set_error("cartnet_model_forward: stream wait failed"); return 2; } } while (0)
-  FORK();      // the side stream starts after whatever the caller queued (the optimiser step that wrote the weights)
+  RUN(S.fork());      // the side stream starts after whatever the caller queued (the optimiser step that wrote the weights)
   // (the CSC permutation -- one workgroup per crystal, only backward reads it -- goes to the second stream when there is one)
   // (an inference pass -- need_backward = 0 -- does not build it at all)
   const bool want_csc = need_backward != 0, csc_aside = S.dual && want_csc;
@@ -415,51 +359,31 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
                         (want_csc && !csc_aside) ? w.colptr : nullptr, (want_csc && !csc_aside) ? w.perm : nullptr, status, st));
   if (w.groups) RUN(cartnet_group_ptrs(b.graph_ptr, b.Bg, m.bn_group_size, w.rowptr, w.G, w.node_gptr, w.edge_gptr, st));
   // weights -> [in, out]   (side stream)
-  {
-    constexpr int TB = 40;   // cartnet_transpose takes up to 40 matrices per launch
-    const float* src[TB]; float* dst[TB]; int32_t rows[TB], cols[TB], lds[TB], ldd[TB];
-    int n = 0;
-    auto flush = [&]() -> int {
-      if (n == 0) return 0;
-      int rc = cartnet_transpose(src, dst, rows, cols, lds, ldd, n, sw);
-      n = 0;
-      return rc;
-    };
-    auto add = [&](const float* s, float* d, int r, int c) -> int {
-      src[n] = s; dst[n] = d; rows[n] = r; cols[n] = c; lds[n] = c; ldd[n] = r;
-      if (++n == TB) return flush();
-      return 0;
-    };
-    if (w.ldf > w.kf &&
-        hipMemsetAsync(w.edge0T + (size_t)w.kf * 2 * D, 0, sizeof(float) * (size_t)(w.ldf - w.kf) * 2 * D,
-                       S.side) != hipSuccess) {
-      cartnet_set_error("cartnet_model_forward: memset failed");
-      return 2;
-    }
-    RUN(add(P.edge0_w, w.edge0T, 2 * D, w.kf));
-    RUN(add(P.edge2_w, w.edge2T, D, 2 * D));
-    if (!plain) RUN(add(P.atom_w, w.atomT, D, 2 * D));
-    RUN(add(P.head0_w, w.head0T, H, D));
-    for (int l = 0; l < L; ++l) {
-      RUN(add(P.layer[l].gate0_w, w.gate0T[l], D, 3 * D));
-      RUN(add(P.layer[l].aggr0_w, w.aggr0T[l], D, 3 * D));
-      RUN(add(P.layer[l].gate2_w, w.gate2T[l], D, D));
-      RUN(add(P.layer[l].aggr2_w, w.aggr2T[l], D, D));
-    }
-    RUN(flush());
+  WeightForms& F = weight_forms();
+  F.clear();
+  if (w.ldf > w.kf &&
+      hipMemsetAsync(w.edge0T + (size_t)w.kf * 2 * D, 0, sizeof(float) * (size_t)(w.ldf - w.kf) * 2 * D, S.side) != hipSuccess) {
+    cartnet_set_error("cartnet_model_forward: memset failed");
+    return 2;
   }
+  auto add = [&](const float* W, float* T, int r, int c) { F.transpose(W, T, r, c, c, r); };
+  add(P.edge0_w, w.edge0T, 2 * D, w.kf);
+  add(P.edge2_w, w.edge2T, D, 2 * D);
+  if (!plain) add(P.atom_w, w.atomT, D, 2 * D);
+  add(P.head0_w, w.head0T, H, D);
+  for (int l = 0; l < L; ++l) {
+    add(P.layer[l].gate0_w, w.gate0T[l], D, 3 * D);
+    add(P.layer[l].aggr0_w, w.aggr0T[l], D, 3 * D);
+    add(P.layer[l].gate2_w, w.gate2T[l], D, D);
+    add(P.layer[l].aggr2_w, w.aggr2T[l], D, D);
+  }
+  RUN(F.flush_transposes(sw));
 
   // bf16x3: split every weight operand once (forward operands B = W^T: stride_k 1, stride_n ld; backward operands
   // B = W: stride_k ld, stride_n 1)
   if (w.i_edge2) {
-    std::vector<const float*> src; std::vector<void*> dst; std::vector<int32_t> Ks, Ns, sk, sn;
-    const size_t blk = img_blk(m);
-    auto fwd = [&](const float* W, int ld, int K_, int N_, char* img) {
-      src.push_back(W); dst.push_back(img); Ks.push_back(K_); Ns.push_back(N_); sk.push_back(1); sn.push_back(ld);
-    };
-    auto bwd = [&](const float* W, int ld, int K_, int N_, char* img) {
-      src.push_back(W); dst.push_back(img); Ks.push_back(K_); Ns.push_back(N_); sk.push_back(ld); sn.push_back(1);
-    };
+    auto fwd = [&](const float* W, int ld, int K_, int N_, char* img) { F.image(W, img, K_, N_, 1, ld); };
+    auto bwd = [&](const float* W, int ld, int K_, int N_, char* img) { F.image(W, img, K_, N_, ld, 1); };
     bwd(w.edge0T, 2 * D, w.ldf, 2 * D, w.i_edge0);     // the zero-padded transposed copy is already [K, N]
     fwd(P.edge2_w, 2 * D, 2 * D, D, w.i_edge2);
     if (!plain) fwd(P.atom_w, 2 * D, 2 * D, D, w.i_atom);
@@ -490,13 +414,10 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
         bwd(q.aggr0_w + D, 3 * D, D, D, w.i_dx[l] + 3 * blk);
       }
     }
-    if (m.gemm_precision == 0)
-      RUN(cartnet_gemm_pack_b(src.data(), dst.data(), Ks.data(), Ns.data(), sk.data(), sn.data(), (int32_t)src.size(), sw));
-    else
-      RUN(cartnet_gemm_split_b(src.data(), dst.data(), Ks.data(), Ns.data(), sk.data(), sn.data(), (int32_t)src.size(), sw));
+    RUN(F.flush_images(prec, sw));
   }
   hipEvent_t weights_ready = S.mark_side();
-  FORK();      // the atom branch and the CSC build below write status bits: after the layout build has reset the word
+  RUN(S.fork());      // the atom branch and the CSC build below write status bits: after the layout build has reset the word
   if (m.cholesky) RUN(cartnet_mask_index(b.non_h_mask, N, w.idx, nullptr, sw));   // graph-only: off the head's critical path
   if (csc_aside)
     RUN(cartnet_csc_build(w.src32, w.rowptr, b.graph_ptr, b.Bg, N, b.E, w.colptr, w.perm, status, sw));
@@ -507,15 +428,15 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
   // ---- encoder, edges (cartnet.py:159)
   RUN(cartnet_edge_features(b.cart_dist, b.cart_dir, m.rbf_means, m.rbf_betas, b.E, m.R, m.invariant, m.radius,
                             m.env_radius, w.feat, w.ldf, w.env, st));
-  MAIN_WAITS(weights_ready);
+  RUN(S.main_waits(weights_ready));
   {
-    CartnetGemmArgs a = gemm_args(E, 2 * D, w.ldf, w.ldf, 2 * D, 2 * D);
+    CartnetGemmArgs a = gemm_args(prec, E, 2 * D, w.ldf, w.ldf, 2 * D, 2 * D);
     a.A[0] = w.feat; a.B[0] = w.edge0T; a.C[0] = w.he_pre; a.bias[0] = P.edge0_b; a.b_kstrided = 1;
     a.b_split[0] = w.i_edge0; a.c_half = half;
     RUN(cartnet_gemm(&a, st));
   }
   {
-    CartnetGemmArgs a = gemm_args(E, D, 2 * D, 2 * D, D, D);
+    CartnetGemmArgs a = gemm_args(prec, E, D, 2 * D, 2 * D, D, D);
     a.A[0] = w.he_pre; a.B[0] = w.edge2T; a.C[0] = w.e0; a.cpre[0] = w.e0_pre; a.bias[0] = P.edge2_b;
     a.b_kstrided = 1; a.a_act = 1; a.out_act = 1; a.b_split[0] = w.i_edge2; a.a_half = half;
     if (w.he_act) a.a_act_out[0] = w.he_act;
@@ -531,7 +452,7 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
                            m.use_temperature ? b.temperature : nullptr, m.atom_types ? P.embedding : nullptr,
                            m.use_temperature ? P.temp_w : nullptr, m.use_temperature ? P.temp_b : nullptr,
                            m.use_temperature ? nullptr : P.enc_bias, N, 2 * D, m.n_types, b.Bg, status, w.x0, sw));
-    CartnetGemmArgs a = gemm_args(N, D, 2 * D, 2 * D, D, D);
+    CartnetGemmArgs a = gemm_args(prec, N, D, 2 * D, 2 * D, D, D);
     a.A[0] = w.x0; a.B[0] = w.atomT; a.C[0] = w.xenc; a.cpre[0] = w.xa_pre; a.bias[0] = P.atom_b;
     a.b_kstrided = 1; a.a_act = 1; a.out_act = 1; a.b_split[0] = w.i_atom;
     RUN(cartnet_gemm(&a, sw));
@@ -539,10 +460,9 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
   // node-side halves of a layer's first Linears: Pn = [gate_i | aggr_i | gate_j | aggr_j]
   auto node_terms = [&](int l, const float* x, void* s_) -> int {
     const CartnetLayerParams& q = P.layer[l];
-    CartnetGemmArgs a = gemm_args(N, D, D, D, D, 4 * D);
+    CartnetGemmArgs a = gemm_args(prec, N, D, D, D, D, 4 * D);
     a.ngroups = 4; a.b_kstrided = 1;
     const float* Bt[4] = {w.gate0T[l], w.aggr0T[l], w.gate0T[l] + (size_t)D * D, w.aggr0T[l] + (size_t)D * D};
-    const size_t blk = img_blk(m);
     for (int g = 0; g < 4; ++g) {
       a.A[g] = x; a.B[g] = Bt[g]; a.C[g] = w.Pn + (size_t)g * D;
       if (w.i_pn[l]) a.b_split[g] = w.i_pn[l] + g * blk;
@@ -574,17 +494,17 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
     const CartnetLayerParams& q = P.layer[l];
     float* x_next = (l == L - 1) ? x_out : w.xl[l];
     float* e_next = (l == L - 1) ? e_out : w.el[l];
-    if (l == 0) MAIN_WAITS(atoms_ready);      // x, Pn of layer 0 (and the status bits of the atom branch)
+    if (l == 0) RUN(S.main_waits(atoms_ready));      // x, Pn of layer 0 (and the status bits of the atom branch)
     else RUN(node_terms(l, x, st));
     {  // pre = e W1e^T + Pn_i[tgt] + Pn_j[src]
-      CartnetGemmArgs a = gemm_args(E, D, D, D, D, 2 * D);
+      CartnetGemmArgs a = gemm_args(prec, E, D, D, D, D, 2 * D);
       a.ngroups = 2; a.b_kstrided = 1;
       a.A[0] = e; a.A[1] = e;
       a.B[0] = w.gate0T[l] + (size_t)2 * D * D; a.B[1] = w.aggr0T[l] + (size_t)2 * D * D;
       a.C[0] = w.pre[l]; a.C[1] = hcol(w.pre[l], D, half); a.c_half = half;
       a.gather_i[0] = w.Pn; a.gather_i[1] = w.Pn + D; a.gather_j[0] = w.Pn + 2 * D; a.gather_j[1] = w.Pn + 3 * D;
       a.ldg = 4 * D; a.tgt = w.tgt32; a.src = w.src32; a.gather_rows = N;
-      if (w.i_pre[l]) { a.b_split[0] = w.i_pre[l]; a.b_split[1] = w.i_pre[l] + img_blk(m); }
+      if (w.i_pre[l]) { a.b_split[0] = w.i_pre[l]; a.b_split[1] = w.i_pre[l] + blk; }
       RUN(cartnet_gemm(&a, st));
     }
     // Inference (eval-mode BatchNorm, nothing kept for backward, fp32 MFMA): the second Linears, the gate, the per-target
@@ -596,7 +516,7 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
       CartnetGateGemmArgs ga;
       memset(&ga, 0, sizeof(ga));
       ga.pre = w.pre[l]; ga.ldp = 2 * D;
-      ga.img_gate = w.i_gs[l]; ga.img_aggr = w.i_gs[l] + img_blk(m);
+      ga.img_gate = w.i_gs[l]; ga.img_aggr = w.i_gs[l] + blk;
       ga.bias_gate = q.gate2_b; ga.bias_aggr = q.aggr2_b;
       ga.mean_rstd = w.mr1[l]; ga.gamma = q.norm_w; ga.beta = q.norm_b;
       ga.env = m.use_envelope[l] ? w.env : nullptr;
@@ -610,13 +530,13 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
       continue;
     }
     {  // gs = silu(pre) W2^T + b2, BatchNorm statistics of the gate half
-      CartnetGemmArgs a = gemm_args(E, D, D, 2 * D, D, 2 * D);
+      CartnetGemmArgs a = gemm_args(prec, E, D, D, 2 * D, D, 2 * D);
       a.ngroups = 2; a.b_kstrided = 1; a.a_act = 1;
       a.A[0] = w.pre[l]; a.A[1] = hcol(w.pre[l], D, half); a.B[0] = w.gate2T[l]; a.B[1] = w.aggr2T[l];
       a.C[0] = w.gs[l]; a.C[1] = hcol(w.gs[l], D, half); a.bias[0] = q.gate2_b; a.bias[1] = q.aggr2_b;
       a.a_half = half; a.c_half = half;
       if (!w.groups && training) { a.colsum[0] = w.cs; a.colsq[0] = w.cq; }   // eval mode normalises with the running statistics
-      if (w.i_gs[l]) { a.b_split[0] = w.i_gs[l]; a.b_split[1] = w.i_gs[l] + img_blk(m); }
+      if (w.i_gs[l]) { a.b_split[0] = w.i_gs[l]; a.b_split[1] = w.i_gs[l] + blk; }
       if (w.act[l]) { a.a_act_out[0] = w.act[l]; a.a_act_out[1] = w.act[l] + D; }
       RUN(cartnet_gemm(&a, st));
     }
@@ -643,7 +563,7 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
 
   // ---- head
   {
-    CartnetGemmArgs a = gemm_args(N, H, D, D, H, H);
+    CartnetGemmArgs a = gemm_args(prec, N, H, D, D, H, H);
     a.A[0] = x; a.B[0] = w.head0T; a.C[0] = w.hid; a.bias[0] = P.head0_b; a.b_kstrided = 1;
     RUN(cartnet_gemm(&a, st));
   }
@@ -652,8 +572,6 @@ extern "C" int cartnet_model_forward(const CartnetModel* model, const CartnetBat
   } else {
     RUN(cartnet_scalar_head_fwd(w.hid, P.head2_w, P.head2_b, b.graph_ptr, b.Bg, H, pred, st));
   }
-#undef FORK
-#undef MAIN_WAITS
   return 0;
 }
 
@@ -665,7 +583,6 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
                                       size_t workspace_bytes, int32_t training, const float* dpred, const float* x_out,
                                       const CartnetParams* grads, void* stream, void* aux_stream) {
   RUN(check_model(model, batch, "cartnet_model_backward"));
-  g_precision = model->gemm_precision;
   const CartnetModel& m = *model;
   const CartnetBatch& b = *batch;
   const CartnetParams& P = m.p;
@@ -680,35 +597,27 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
   Work w = carve(m, b.N, b.E, b.Bg, b.M, true, static_cast<char*>(workspace), &need);
   CN_CHECK(workspace_bytes >= need, "cartnet_model_backward: workspace %zu < required %zu bytes", workspace_bytes, need);
   w.groups = w.G > 1 ? &w.grp : nullptr;      // node_gptr / edge_gptr were filled by the forward call
-  const int D = m.D, L = m.L, H = D / 2, N = b.N;
+  const int D = m.D, L = m.L, H = D / 2, N = b.N, prec = m.gemm_precision;
   const int E = (int)b.E;
-  g_events.next = 0;
-  Streams S{(hipStream_t)stream, aux_stream ? (hipStream_t)aux_stream : (hipStream_t)stream,
-            aux_stream != nullptr && aux_stream != stream, &g_events};
+  const size_t blk = img_bytes(prec, D, D);      // one D x D weight image (images of a folded operand sit back to back)
+  Streams S("cartnet_model_backward", stream, aux_stream);
   void* st = stream;            // main: activation-gradient chain
   void* sw = (void*)S.side;     // side: parameter gradients
-#define FORK() do { if (S.fork() != 0) { cartnet_set_error("cartnet_model_backward: stream fork failed"); return 2; } } while (0)
+  // weight gradients: the side stream's split-K slabs, and the second region for the one product the main stream runs
+  const WgradPlan wk{prec, 0, w.slabs, w.slab_floats}, wk2{prec, 0, w.slabs2, w.slab2_floats};
 
   hipEvent_t sort_done = nullptr;
   // Two slow single-workgroup jobs nobody waits for until the very end (atoms grouped by element for the embedding
   // gradient; the head's second-Linear gradient sums): queued on the side stream behind the first layer's weight
   // gradients, where that stream idles while the main stream runs the next layer's gate kernels -- in front of them
   // they delayed every weight-gradient product of the step by ~0.4 ms.
-  const int head_row = m.cholesky ? 7 * H + 8 : 2 * H + 8;
   auto deferred_side_jobs = [&]() -> int {
     if (m.atom_types) {
       RUN(cartnet_sort_by_key(b.z, N, m.n_types, w.zperm, w.zptr, w.zstatus, sw));
       sort_done = S.mark_side();
     }
-    RUN(cartnet_colsum_finalize_f32(w.head_parts, w.nparts_n, head_row, w.head_tot, sw));
-    const int nw2 = m.cholesky ? 6 * H : H, nb2 = m.cholesky ? 6 : 1;
-    if (hipMemcpyAsync(G.head2_w, w.head_tot, sizeof(float) * nw2, hipMemcpyDeviceToDevice, S.side) != hipSuccess ||
-        hipMemcpyAsync(G.head2_b, w.head_tot + nw2, sizeof(float) * nb2, hipMemcpyDeviceToDevice, S.side) != hipSuccess ||
-        hipMemcpyAsync(G.head0_b, w.head_tot + nw2 + 8, sizeof(float) * H, hipMemcpyDeviceToDevice, S.side) != hipSuccess) {
-      cartnet_set_error("cartnet_model_backward: head gradient copy failed");
-      return 2;
-    }
-    return 0;
+    return head_grad_tail(S.who, w.head_parts, w.nparts_n, w.head_tot, m.cholesky ? 6 * H : H, m.cholesky ? 6 : 1, H, G.head2_w,
+                          G.head2_b, G.head0_b, sw);
   };
   // ---- head
   {
@@ -717,14 +626,14 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
     else
       RUN(cartnet_scalar_head_bwd(w.hid, P.head2_w, b.graph_ptr, b.batch, dpred, N, b.Bg, H, w.dhid, w.head_parts, st));
     hipEvent_t dhid_done = S.mark_main();
-    CartnetGemmArgs a = gemm_args(N, D, H, H, D, D);
+    CartnetGemmArgs a = gemm_args(prec, N, D, H, H, D, D);
     a.A[0] = w.dhid; a.B[0] = P.head0_w; a.C[0] = w.dx[0]; a.b_kstrided = 1; a.b_split[0] = w.i_head0_b;
     RUN(cartnet_gemm(&a, st));       // (main stream first: see the host-order note in the layer loop)
-    if (S.side_waits(dhid_done) != 0) { cartnet_set_error("cartnet_model_backward: stream fork failed"); return 2; }
+    RUN(S.side_waits(dhid_done));
     const float* dY[1] = {w.dhid};
     const float* X[1] = {x_out};
     float* o[1] = {G.head0_w};
-    RUN(wgrad(dY, H, X, D, o, D, N, H, D, 1, false, w, sw));
+    RUN(wgrad(wk, dY, H, X, D, o, D, N, H, D, 1, false, sw));
   }
   float* dx = w.dx[0];
   float* dx_other = w.dx[1];
@@ -754,7 +663,7 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
   // all-reduce there, under the next layer's kernels.  The head's bucket completes with the deferred side jobs.
   auto bucket_ready = [&](int l) -> int {
     if (!m.grad_ready) return 0;
-    FORK();
+    RUN(S.fork());
     if (l == L - 1)
       CN_CHECK(m.grad_ready(m.grad_ready_user, L, sw) == 0, "cartnet_model_backward: the grad_ready callback failed (head)");
     CN_CHECK(m.grad_ready(m.grad_ready_user, l, sw) == 0, "cartnet_model_backward: the grad_ready callback failed (layer %d)", l);
@@ -777,7 +686,7 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
     float* dpre = w.dpre[par];
     float* dPn = w.dPn[par];
     // the side stream must be done with this parity's buffers (used two layers ago)
-    if (l + 2 < L && S.main_waits(side_done[l + 2]) != 0) { cartnet_set_error("cartnet_model_backward: wait failed"); return 2; }
+    if (l + 2 < L) RUN(S.main_waits(side_done[l + 2]));
     // node update: x_out = silu(bn2(aggr)) + x_in
     RUN(cartnet_node_update_bwd_stats(w.aggr[l], dx, w.mr2[l], q.norm2_w, q.norm2_b, N, D, w.pa, w.pb, w.groups, st));
     if (sync_bn) {
@@ -832,27 +741,27 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       const bool kept = w.act[l] != nullptr;            // silu(pre) kept by the forward pass: plain operand (precision 0)
       const float* X[2] = {kept ? w.act[l] : pre, hcol(kept ? w.act[l] : pre, D, half && !kept)};
       float* o[2] = {gq.gate2_w, gq.aggr2_w};
-      return wgrad(dY, 2 * D, X, 2 * D, o, D, b.E, D, D, 2, !kept, w, sw, half, half && !kept);
+      return wgrad(wk, dY, 2 * D, X, 2 * D, o, D, b.E, D, D, 2, !kept, sw, half, half && !kept);
     };
     auto main_dpre = [&]() -> int {   // dpre = (dgs @ W2) * silu'(pre), into this parity's buffer
-      CartnetGemmArgs a = gemm_args(E, D, D, 2 * D, D, 2 * D);
+      CartnetGemmArgs a = gemm_args(prec, E, D, D, 2 * D, D, 2 * D);
       a.ngroups = 2; a.b_kstrided = 1;
       a.A[0] = gs; a.A[1] = hcol(gs, D, half); a.B[0] = q.gate2_w; a.B[1] = q.aggr2_w;
       a.C[0] = dpre; a.C[1] = hcol(dpre, D, half); a.dact[0] = pre; a.dact[1] = hcol(pre, D, half); a.ldd = 2 * D;
       a.a_half = half; a.c_half = half; a.dact_half = half;
       // (no column sums here: the bias gradients of the first Linears are the column sums of dpre over all edges =
       //  the column sums over atoms of its by-target segment sums, 14x fewer rows -- taken from dPn below)
-      if (w.i_dpre[l]) { a.b_split[0] = w.i_dpre[l]; a.b_split[1] = w.i_dpre[l] + img_blk(m); }
+      if (w.i_dpre[l]) { a.b_split[0] = w.i_dpre[l]; a.b_split[1] = w.i_dpre[l] + blk; }
       return cartnet_gemm(&a, st);
     };
     auto side_w1e = [&]() -> int {   // edge-block weight gradients of the first Linears
       const float* dY[2] = {dpre, hcol(dpre, D, half)};
       const float* X[2] = {e_in, e_in};
       float* o[2] = {gq.gate0_w + 2 * D, gq.aggr0_w + 2 * D};
-      return wgrad(dY, 2 * D, X, D, o, 3 * D, b.E, D, D, 2, false, w, sw, half, false);
+      return wgrad(wk, dY, 2 * D, X, D, o, 3 * D, b.E, D, D, 2, false, sw, half, false);
     };
     auto main_de_in = [&]() -> int {   // de_in = de_out + dpre @ W1[:, 2D:]  (layer 0: continue through the encoder's last SiLU)
-      CartnetGemmArgs a = gemm_args(E, D, D, 2 * D, 3 * D, D);
+      CartnetGemmArgs a = gemm_args(prec, E, D, D, 2 * D, 3 * D, D);
       a.nsegs = 2; a.b_kstrided = 1;
       a.A[0] = dpre; a.A[1] = hcol(dpre, D, half); a.B[0] = q.gate0_w + 2 * D; a.B[1] = q.aggr0_w + 2 * D;
       a.a_half = half;
@@ -874,14 +783,14 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
         // the two K-segments only fold into one product at N = 256 (gemm.hip: segments_adjacent), and no kernel reads bf16
         // K-segments: two single-segment products instead, the second adding onto the first in place (every output
         // element is read and written by the same thread); the layer-0 epilogue goes on the second
-        CartnetGemmArgs a1 = gemm_args(E, D, D, 2 * D, 3 * D, D);
+        CartnetGemmArgs a1 = gemm_args(prec, E, D, D, 2 * D, 3 * D, D);
         a1.b_kstrided = 1; a1.a_half = 1;
         a1.A[0] = dpre; a1.B[0] = q.gate0_w + 2 * D; a1.C[0] = de_in; a1.resid[0] = de; a1.ldr = D;
         a1.b_split[0] = w.i_de[l];
         RUN(cartnet_gemm(&a1, st));
         CartnetGemmArgs a2 = a1;
         a2.A[0] = hcol(dpre, D, true); a2.B[0] = q.aggr0_w + 2 * D; a2.resid[0] = de_in;
-        a2.b_split[0] = w.i_de[l] + img_blk(m);
+        a2.b_split[0] = w.i_de[l] + blk;
         if (l == 0) { a2.dact[0] = w.e0_pre; a2.ldd = D; a2.colsum[0] = w.cs_misc[0]; }
         RUN(cartnet_gemm(&a2, st));
       } else {
@@ -908,10 +817,10 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       const float* dY[4] = {dPn, dPn + D, dPn + 2 * D, dPn + 3 * D};
       const float* X[4] = {x_in, x_in, x_in, x_in};
       float* o[4] = {gq.gate0_w, gq.aggr0_w, gq.gate0_w + D, gq.aggr0_w + D};
-      return wgrad(dY, 4 * D, X, D, o, 3 * D, N, D, D, 4, false, w, sw);
+      return wgrad(wk, dY, 4 * D, X, D, o, 3 * D, N, D, D, 4, false, sw);
     };
     auto main_dx = [&]() -> int {
-      CartnetGemmArgs a = gemm_args(N, D, D, 4 * D, 3 * D, D);
+      CartnetGemmArgs a = gemm_args(prec, N, D, D, 4 * D, 3 * D, D);
       a.nsegs = 4; a.b_kstrided = 1;
       a.A[0] = dPn; a.A[1] = dPn + D; a.A[2] = dPn + 2 * D; a.A[3] = dPn + 3 * D;
       a.B[0] = q.gate0_w; a.B[1] = q.aggr0_w; a.B[2] = q.gate0_w + D; a.B[3] = q.aggr0_w + D;
@@ -944,10 +853,10 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       hipEvent_t dpre_done = S.mark_main();
       RUN(main_de_in());
       if (!seg_first) {
-        if (S.side_waits(apply_done) != 0) { cartnet_set_error("cartnet_model_backward: stream fork failed"); return 2; }
+        RUN(S.side_waits(apply_done));
         RUN(side_w2());
       }
-      if (S.side_waits(dpre_done) != 0) { cartnet_set_error("cartnet_model_backward: stream fork failed"); return 2; }
+      RUN(S.side_waits(dpre_done));
       RUN(segsums(sw));
       hipEvent_t seg_done = S.mark_side();
       if (seg_first) RUN(side_w2());
@@ -956,7 +865,7 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       side_done[l] = S.mark_side();
       if (l == L - 1) RUN(deferred_side_jobs());
       RUN(bucket_ready(l));
-      if (S.main_waits(seg_done) != 0) { cartnet_set_error("cartnet_model_backward: wait failed"); return 2; }
+      RUN(S.main_waits(seg_done));
       RUN(main_dx());
     } else {
       // (Round 6, with dpre and dE as persistent launches that own every CU: queueing the layer's weight gradients BEHIND dE
@@ -964,14 +873,14 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       //  node update and the next gate kernels -- measured 13.29-13.32 against 13.14-13.21 ms for this order: dX, a 88 us
       //  product on the critical chain, then waits 400 us for a CU slot beside a weight-gradient launch and the node kernels
       //  run 3x slower beside one; profiles/HISTORY.md, "backward order")
-      FORK();
+      RUN(S.fork());
       RUN(side_w2());
       RUN(main_dpre());
-      FORK();
+      RUN(S.fork());
       RUN(side_w1e());
       RUN(main_de_in());
       RUN(segsums(st));
-      FORK();
+      RUN(S.fork());
       RUN(side_wn());
       side_done[l] = S.mark_side();
       if (l == L - 1) RUN(deferred_side_jobs());
@@ -986,18 +895,18 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
   // ---- encoder: de = d(e0_pre), dx = d(xa_pre)
   {
     hipEvent_t de_done = S.mark_main();
-    CartnetGemmArgs a = gemm_args(E, 2 * D, D, D, 2 * D, 2 * D);
+    CartnetGemmArgs a = gemm_args(prec, E, 2 * D, D, D, 2 * D, 2 * D);
     a.A[0] = de; a.B[0] = P.edge2_w; a.C[0] = w.dhe; a.dact[0] = w.he_pre; a.ldd = 2 * D; a.b_kstrided = 1;
     a.dact_half = half;
     a.b_split[0] = w.i_edge2_b;
     a.colsum[0] = w.cs_misc[2];
     RUN(cartnet_gemm(&a, st));       // dhe = d(he_pre)
-    if (S.side_waits(de_done) != 0) { cartnet_set_error("cartnet_model_backward: stream fork failed"); return 2; }
+    RUN(S.side_waits(de_done));
     const float* dY[1] = {de};
     const bool kept = w.he_act != nullptr;
     const float* X[1] = {kept ? w.he_act : w.he_pre};
     float* o[1] = {G.edge2_w};
-    RUN(wgrad(dY, D, X, 2 * D, o, 2 * D, b.E, D, 2 * D, 1, !kept, w, sw, false, half && !kept));
+    RUN(wgrad(wk, dY, D, X, 2 * D, o, 2 * D, b.E, D, 2 * D, 1, !kept, sw, false, half && !kept));
     // The first edge Linear's gradients stay on the MAIN stream (they need dhe, and the main stream has nothing else of
     // weight left): the weight-gradient stream still holds layer 0's products and dW2 of the encoder at this point, and
     // queueing these behind them left the main stream idle for the last ~0.8 ms of the step (r03 timeline).
@@ -1007,9 +916,7 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
     const float* dY2[1] = {w.dhe};
     const float* X2[1] = {w.feat};
     float* o2[1] = {G.edge0_w};
-    // (the split-K slabs of this product must not be the ones the weight-gradient stream is using: w.slabs2)
-    Work w2 = w;
-    w2.slabs = w.slabs2;
+    // (the split-K slabs of this product must not be the ones the weight-gradient stream is using: wk2 = w.slabs2)
     if (w.i_edge0) {
       // the DMA-fed weight-gradient kernels want 256-wide column tiles: compute the transpose, featT . dhe = dW0^T [ldf, 2D]
       // (rows kf.. are the zero pad columns of feat; one ragged row tile), and write its first kf rows transposed into the
@@ -1018,13 +925,13 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       const float* fT[1] = {w.feat};
       const float* dh[1] = {w.dhe};
       float* oT[1] = {w.e0wT};
-      RUN(wgrad(fT, w.ldf, dh, 2 * D, oT, 2 * D, b.E, w.ldf, 2 * D, 1, false, w2, st));
+      RUN(wgrad(wk2, fT, w.ldf, dh, 2 * D, oT, 2 * D, b.E, w.ldf, 2 * D, 1, false, st));
       const float* tsrc[1] = {w.e0wT};
       float* tdst[1] = {G.edge0_w};
       const int32_t trows[1] = {w.kf}, tcols[1] = {2 * D}, tlds[1] = {2 * D}, tldd[1] = {w.kf};
       RUN(cartnet_transpose(tsrc, tdst, trows, tcols, tlds, tldd, 1, st));
     } else {
-      RUN(wgrad(dY2, 2 * D, X2, w.ldf, o2, w.kf, b.E, 2 * D, w.kf, 1, false, w2, st));
+      RUN(wgrad(wk2, dY2, 2 * D, X2, w.ldf, o2, w.kf, b.E, 2 * D, w.kf, 1, false, st));
     }
   }
   if (plain) {   // every atom read the same learned row: its gradient is the column sum of dx over the atoms
@@ -1036,8 +943,8 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
     const float* dY[1] = {dx};
     const float* X[1] = {w.x0};
     float* o[1] = {G.atom_w};
-    RUN(wgrad(dY, D, X, 2 * D, o, 2 * D, N, D, 2 * D, 1, true, w, sw));
-    CartnetGemmArgs a = gemm_args(N, 2 * D, D, D, 2 * D, 2 * D);
+    RUN(wgrad(wk, dY, D, X, 2 * D, o, 2 * D, N, D, 2 * D, 1, true, sw));
+    CartnetGemmArgs a = gemm_args(prec, N, 2 * D, D, D, 2 * D, 2 * D);
     a.A[0] = dx; a.B[0] = P.atom_w; a.C[0] = w.dx0; a.dact[0] = w.x0; a.ldd = 2 * D; a.b_kstrided = 1;
     a.b_split[0] = w.i_atom_b;
     RUN(cartnet_gemm(&a, st));
@@ -1052,16 +959,15 @@ extern "C" int cartnet_model_backward(const CartnetModel* model, const CartnetBa
       float* outs[1] = {G.enc_bias};
       RUN(cartnet_colsum_finalize(parts, outs, 1, w.nparts_n, 2 * D, st));
     }
-    if (m.atom_types && S.main_waits(sort_done) != 0) { cartnet_set_error("cartnet_model_backward: wait failed"); return 2; }
-    if (m.atom_types)
-      RUN(cartnet_segment_sum_long(w.dx0, 2 * D, w.zptr, w.zperm, m.n_types, N, 2 * D, w.seg_tmp, G.embedding, 2 * D,
-                                   st));
+    if (m.atom_types) {
+      RUN(S.main_waits(sort_done));
+      RUN(cartnet_segment_sum_long(w.dx0, 2 * D, w.zptr, w.zperm, m.n_types, N, 2 * D, w.seg_tmp, G.embedding, 2 * D, st));
+    }
   }
   // join: everything queued on the side stream precedes whatever the caller enqueues next on the main stream
-  if (S.main_waits(S.mark_side()) != 0) { cartnet_set_error("cartnet_model_backward: stream join failed"); return 2; }
+  RUN(S.join());
   if (m.grad_ready)
     CN_CHECK(m.grad_ready(m.grad_ready_user, L + 1, st) == 0, "cartnet_model_backward: the grad_ready callback failed (encoder)");
-#undef FORK
   return 0;
 }
 

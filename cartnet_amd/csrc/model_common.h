@@ -1,5 +1,6 @@
-// Helpers shared by the translation units that sequence a whole network (model.hip: CartNet; icomformer.hip): workspace
-// carving, the split-K rule of the weight-gradient products, the two-stream event plumbing.  Host code only.
+// The host kit of the two step drivers (model.hip: CartNet; icomformer.hip): workspace carving, the BatchNorm-group rule,
+// GEMM argument blocks, the split-K weight-gradient product with its slab check, the batcher of a step's weight forms, the
+// two-stream event plumbing and the head-gradient tail.  Host code only; whatever both drivers need lives here, once.
 #pragma once
 #include "common.h"
 #include <vector>
@@ -22,6 +23,16 @@ struct Carver {
     return p;
   }
 };
+
+// BatchNorm groups inside one batch: group_count crystals-per-group blocks (1 = no grouping), and for the grouped
+// statistics kernels ceil(segments / G / 4 segments-per-workgroup) partial rows per group, at most `cap`
+inline int group_count(int Bg, int bn_group_size) {
+  return (bn_group_size > 0 && Bg > bn_group_size) ? (Bg + bn_group_size - 1) / bn_group_size : 1;
+}
+inline int group_parts(size_t segments, int G, int cap) {
+  const size_t per = (segments + (size_t)4 * G - 1) / ((size_t)4 * G);
+  return (int)(per < 1 ? 1 : (per > (size_t)cap ? (size_t)cap : per));
+}
 
 // Split-K of the weight-gradient products: ONE workgroup per CU (256), not two.  Round 4, same-box A B A B: the step
 // 14.63 / 14.92 -> 14.08 / 14.14 ms (fp32), 10.68 -> 10.59 (bf16x3), 6.55 -> 6.32 (bf16 + bf16 storage).  These launches
@@ -98,46 +109,167 @@ struct HostProfScope {
 #else
 #define CN_PROF_SCOPE(slot, what)
 #endif
+inline EventPool& event_pool() { thread_local EventPool p; return p; }      // one per thread, for both drivers
 
+// The two streams of one entry-point call: `main` is the caller's, `side` the optional second one (the same stream, and
+// every operation a no-op, when there is none).  Operations return 0, or 2 with the error text set.  The two mark_*
+// return nullptr both for "one stream: nothing to order" and for a failed record; a failure is remembered, and the next
+// fork / *_waits / join returns it -- a null event alone means "nothing was queued, nothing to wait for".
 struct Streams {
+  const char* who;      // the entry point, for the error text
   hipStream_t main, side;
-  bool dual;
-  EventPool* pool;      // the calling thread's pool (thread_local in the translation unit that sequences the call)
-  // after(main) -> side waits; returns 0 on success
+  bool dual, record_failed = false;
+  EventPool* pool;
+  Streams(const char* who_, void* stream, void* aux_stream)
+      : who(who_), main((hipStream_t)stream), side(aux_stream ? (hipStream_t)aux_stream : (hipStream_t)stream),
+        dual(aux_stream != nullptr && aux_stream != stream), pool(&event_pool()) {
+    pool->next = 0;
+  }
+  int fail(const char* what) { cartnet_set_error("%s: stream %s failed", who, what); return 2; }
+  hipEvent_t mark(hipStream_t s) {
+    hipEvent_t e = pool->get();
+    if (e && hipEventRecord(e, s) == hipSuccess) return e;
+    record_failed = true;
+    return nullptr;
+  }
+  int waits(hipStream_t s, hipEvent_t e, const char* what) {
+    if (record_failed) return fail("event record");
+    return hipStreamWaitEvent(s, e, 0) == hipSuccess ? 0 : fail(what);
+  }
+  // after(main) -> side waits
   int fork() {
     CN_PROF_SCOPE(4001, "Streams::fork (record + wait)");
-    if (!dual) return 0;
-    hipEvent_t e = pool->get();
-    if (!e || hipEventRecord(e, main) != hipSuccess || hipStreamWaitEvent(side, e, 0) != hipSuccess) return 2;
-    return 0;
+    return dual ? waits(side, mark(main), "fork") : 0;
   }
   // the two halves of fork(), for call sites that put the main stream's next kernels in the queue BEFORE spending host
   // time on the side stream's launches (a batch of tiny crystals is host-paced: what is enqueued first starts first)
   hipEvent_t mark_main() {
     CN_PROF_SCOPE(4002, "Streams::mark_main (record)");
-    if (!dual) return nullptr;
-    hipEvent_t e = pool->get();
-    if (!e || hipEventRecord(e, main) != hipSuccess) return nullptr;
-    return e;
+    return dual ? mark(main) : nullptr;
   }
-  int side_waits(hipEvent_t e) {
+  int side_waits(hipEvent_t e) {      // e comes from mark_main: null in dual mode is a failed record
     CN_PROF_SCOPE(4003, "Streams::side_waits (wait)");
     if (!dual) return 0;
-    if (!e) return 2;
-    return hipStreamWaitEvent(side, e, 0) == hipSuccess ? 0 : 2;
+    return e ? waits(side, e, "fork") : fail("fork");
   }
   hipEvent_t mark_side() {
     CN_PROF_SCOPE(4004, "Streams::mark_side (record)");
-    if (!dual) return nullptr;
-    hipEvent_t e = pool->get();
-    if (!e || hipEventRecord(e, side) != hipSuccess) return nullptr;
-    return e;
+    return dual ? mark(side) : nullptr;
   }
-  int main_waits(hipEvent_t e) {
+  int main_waits(hipEvent_t e) {      // e == nullptr: nothing was queued on the side stream for this dependency
     CN_PROF_SCOPE(4005, "Streams::main_waits (wait)");
-    if (!dual || !e) return 0;
-    return hipStreamWaitEvent(main, e, 0) == hipSuccess ? 0 : 2;
+    if (!dual || (!e && !record_failed)) return 0;
+    return waits(main, e, "wait");
   }
+  // everything queued on the side stream precedes whatever is enqueued next on the main stream
+  int join() { return main_waits(mark_side()); }
 };
 
+// ---- GEMM argument blocks ------------------------------------------------------------------------------------------------
+inline CartnetGemmArgs gemm_args(int prec, int M, int N, int K, int lda, int ldb, int ldc, int tile_policy = 0) {
+  CartnetGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.precision = prec;
+  a.tile_policy = tile_policy;      // 1: grouped C x C products on the 128-wide fp32 kernel (CartnetGemmArgs.tile_policy)
+  a.M = M; a.N = N; a.K = K;
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.ngroups = 1; a.nsegs = 1; a.splitk = 1;
+  return a;
+}
+
+// bytes of one [K, N] weight image at GEMM precision `prec` (images of a folded operand sit back to back)
+inline size_t img_bytes(int prec, int K, int N) {
+  return prec == 0 ? cartnet_gemm_pack_b_bytes(K, N) : cartnet_gemm_split_b_bytes(K, N);
+}
+
+// ---- weight gradients ----------------------------------------------------------------------------------------------------
+// How a driver's weight-gradient products run: precision, tile policy and the split-K slab region of the stream they are
+// queued on (`capacity` floats: the maximum of wgrad_slab_floats over the shapes the driver's carve lists).
+struct WgradPlan {
+  int prec, tile_policy;
+  float* slabs;
+  size_t capacity;
+};
+// outs[g] = dY[g]^T @ (silu?)(X[g]): reduction over `K` rows, split over workgroups, slabs summed in fixed order.
+// dy_half / x_half: the operand is stored as bf16 (half storage).
+inline int wgrad(const WgradPlan& p, const float* const* dY, int ldy, const float* const* X, int ldx, float* const* outs,
+                 int ldo, long long K, int M, int N, int groups, bool b_act, void* st, bool dy_half = false,
+                 bool x_half = false) {
+  if (K <= 0) {   // no rows: the gradient is zero
+    for (int g = 0; g < groups; ++g)
+      for (int r = 0; r < M; ++r)
+        if (hipMemsetAsync(outs[g] + (size_t)r * ldo, 0, sizeof(float) * N, (hipStream_t)st) != hipSuccess) return 2;
+    return 0;
+  }
+  const int S = split_k(K, wgrad_tiles(groups, M, N));
+  const size_t need = wgrad_slab_floats(groups, K, M, N);
+  CN_CHECK(need <= p.capacity,
+           "wgrad: %d x [%d, %d] over K = %lld needs %zu slab floats, %zu were carved (the shape is missing from the carve list)",
+           groups, M, N, K, need, p.capacity);
+  CartnetGemmArgs a = gemm_args(p.prec, M, N, (int)K, ldy, ldx, S > 1 ? N : ldo, p.tile_policy);
+  a.ngroups = groups; a.a_kstrided = 1; a.b_kstrided = 1; a.splitk = S;
+  a.b_act = b_act ? 1 : 0; a.a_half = dy_half ? 1 : 0; a.b_half = x_half ? 1 : 0;
+  const float* slabp[CARTNET_MAX_GROUPS];
+  for (int g = 0; g < groups; ++g) {
+    a.A[g] = dY[g];
+    a.B[g] = X[g];
+    a.C[g] = S > 1 ? p.slabs + (size_t)g * S * M * N : outs[g];
+    slabp[g] = a.C[g];
+  }
+  RUN(cartnet_gemm(&a, st));
+  if (S > 1) RUN(cartnet_splitk_reduce(slabp, outs, groups, S, M, N, ldo, st));
+  return 0;
+}
+
+// ---- weight forms of a step ----------------------------------------------------------------------------------------------
+// The transposed copies and pre-arranged images of a step's weights, collected and launched in batches.  One per thread
+// (weight_forms()); the vectors keep their capacity, so after a thread's first call nothing here touches the heap.
+struct WeightForms {
+  std::vector<const float*> isrc, tsrc;
+  std::vector<void*> idst;
+  std::vector<float*> tdst;
+  std::vector<int32_t> iK, iN, isk, isn, trows, tcols, tlds, tldd;
+  void clear() {
+    isrc.clear(); idst.clear(); iK.clear(); iN.clear(); isk.clear(); isn.clear();
+    tsrc.clear(); tdst.clear(); trows.clear(); tcols.clear(); tlds.clear(); tldd.clear();
+  }
+  // image of the operand B[k, n] = src[k * stride_k + n * stride_n]  (W^T of a row-major W: strides 1, ld; W itself: ld, 1)
+  void image(const float* src, void* dst, int K, int N, int stride_k, int stride_n) {
+    isrc.push_back(src); idst.push_back(dst); iK.push_back(K); iN.push_back(N); isk.push_back(stride_k); isn.push_back(stride_n);
+  }
+  void transpose(const float* src, float* dst, int rows, int cols, int lds, int ldd) {
+    tsrc.push_back(src); tdst.push_back(dst); trows.push_back(rows); tcols.push_back(cols); tlds.push_back(lds); tldd.push_back(ldd);
+  }
+  int flush_transposes(void* st) {
+    constexpr size_t TB = 40;   // cartnet_transpose takes up to 40 matrices per launch
+    for (size_t j = 0; j < tsrc.size(); j += TB)
+      RUN(cartnet_transpose(tsrc.data() + j, tdst.data() + j, trows.data() + j, tcols.data() + j, tlds.data() + j,
+                            tldd.data() + j, (int)(tsrc.size() - j < TB ? tsrc.size() - j : TB), st));
+    return 0;
+  }
+  int flush_images(int prec, void* st) {      // fp32 rows at precision 0, bf16 planes at precision 1 / 2
+    if (isrc.empty()) return 0;
+    return (prec == 0 ? cartnet_gemm_pack_b : cartnet_gemm_split_b)(isrc.data(), idst.data(), iK.data(), iN.data(), isk.data(),
+                                                                   isn.data(), (int32_t)isrc.size(), st);
+  }
+};
+inline WeightForms& weight_forms() { thread_local WeightForms f; return f; }
+
+// ---- head gradient -------------------------------------------------------------------------------------------------------
+// The head's backward kernel leaves partial rows [nw2 | nb2, padded to 8 | H]: dW of the second Linear, its bias gradient,
+// the bias gradient of the first.  Cholesky head: (6H, 6); scalar head: (H, 1).  Sums them and copies the three pieces out.
+inline int head_grad_tail(const char* who, const float* head_parts, int nparts, float* head_tot, int nw2, int nb2, int H,
+                          float* head2_w, float* head2_b, float* head0_b, void* st) {
+  RUN(cartnet_colsum_finalize_f32(head_parts, nparts, nw2 + 8 + H, head_tot, st));
+  hipStream_t s = (hipStream_t)st;
+  if (hipMemcpyAsync(head2_w, head_tot, sizeof(float) * nw2, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(head2_b, head_tot + nw2, sizeof(float) * nb2, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(head0_b, head_tot + nw2 + 8, sizeof(float) * H, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    cartnet_set_error("%s: head gradient copy failed", who);
+    return 2;
+  }
+  return 0;
+}
+
 }  // namespace cn_model
+

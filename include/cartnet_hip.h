@@ -861,7 +861,8 @@ int cartnet_group_sums_finalize(double* parts_a, double* parts_b, int32_t D, con
 /* groups != NULL: parts are [G][parts][C] with parts = edge_parts if parts_over_edges (rows written by a per-edge kernel)
  * else node_parts; the row counts are the groups' edge counts if count_over_edges else their node counts (nparts and
  * count are ignored); mean_rstd is [G][2C]; the running statistics receive G updates in group order and
- * num_batches_tracked += G. */
+ * num_batches_tracked += G.  A group of 0 rows or of 1 row (nn.BatchNorm1d refuses both in training mode) gets mean 0
+ * (1 row: the row itself), variance 0 and rstd = 1/sqrt(eps), and the running statistics still take that update. */
 int cartnet_bn_finalize(double* parts_sum, double* parts_sq, int32_t nparts, int64_t count, int32_t C,
                         float eps, float momentum, int32_t training, float* running_mean, float* running_var,
                         int64_t* num_batches_tracked, float* mean_rstd, const CartnetGroups* groups,

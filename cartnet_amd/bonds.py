@@ -35,6 +35,33 @@ isotropic U of the atom it is bonded to (SHELXL: 1.5 for methyl, hydroxyl and wa
 
 Only edges the graph holds are seen, as with the rigid-bond test.  In a cell so small that one hydrogen reaches its parent
 through two images inside the bond limit, both edges count: that hydrogen is counted twice.
+
+Molecules (``metrics.molecules``, csrc/molecule_ops.hip; ``molecules_host`` below restates it in numpy).  The bond graph
+has the directed edges of the rigid-bond test: ``e = (j -> i)`` is a bond when ``is_bond(cart_dist[e], z_i, z_j, tol,
+same_atom = i == j)`` holds and both ends have an ADP row.  An atom's own image is no bond, as in the rigid-bond test: a
+chain that bonds only to its own image (one atom per cell along the chain) is therefore seen as single atoms, not as a
+polymer.  A molecule is a component of that graph, defined as the fixpoint of a Jacobi propagation per crystal:
+
+  start       every atom with a row has ``label[i] = i`` and ``x[i] = 0`` (fp64, three components); an atom without a row
+              has label -1 and takes no part.
+  sweep       reads the previous sweep's values only.  Atom ``i`` takes the smallest label among the sources of its
+              incoming bonds; if it is below its own, ``i`` adopts it together with
+              ``x[i] = x[j] + fp64(cart_dist[e]) * fp64(cart_dir[e])`` along the edge that carries it -- the lowest edge
+              index when several do.  The stored direction is ``pos_target - pos_source_image`` (synthetic.py:50), so the
+              sum is the unwrapped position of ``i`` relative to the molecule's root, its lowest atom.
+  end         when no label changes; the number of sweeps is bounded by the atoms of the crystal.
+  status      one pass over all bonds ``j -> i`` after the fixpoint.  ``label[i] != label[j]``: the graph is asymmetric
+              there (a capped graph can be: ``--max_neighbours``, eComformer) and both molecules get bit 2, *open*.
+              Equal labels with ``|x[i] - (x[j] + v_e)|^2 > 0.25 A^2``: the molecule reaches its own image, as a polymer
+              or a framework does, and gets bit 1, *periodic*.  0.5 A is far above the rounding of ``x`` and far below any
+              lattice translation.  A molecule is *tested* when its status is 0 and it has two or more atoms.
+  numbering   ``mol[m]``: the index of the row's molecule inside its crystal, molecules numbered in the order of their
+              roots; ``mol_size[m]`` and ``mol_status[m]`` repeat the molecule's figures on each of its rows.
+
+The rigid-body test on top of it (``metrics.molecule_test``; Rosenfield, Trueblood & Dunitz, Acta Cryst. A34 (1978) 828)
+generalises Hirshfeld's test from bonds to all pairs of a tested molecule: for the row of atom ``i``, over the atoms
+``j != i`` of its molecule in atom order and in fp64, ``r = x_i - x_j`` and ``D = r^T (S_i - S_j) r / (r . r)`` with ``S``
+the symmetric part of ``U`` (the difference is taken first); a pair with ``r . r == 0`` is not counted.
 """
 from __future__ import annotations
 
@@ -110,3 +137,75 @@ def riding_hydrogens_host(z, edge_index, cart_dist, atom_row, u_eq, tol: float =
         mult[i] = np.float32(f_rot if z[p] == 8 or (z[p] == 6 and n >= 3) else f)
         u_iso[i] = np.float32(np.float64(mult[i]) * np.float64(u_eq[atom_row[p]]))
     return parent, count, mult, u_iso
+
+
+MOLECULE_PERIODIC, MOLECULE_OPEN = 1, 2        # the bits of a molecule's status
+MOLECULE_CLOSURE = 0.5                         # Angstrom: a bond that disagrees with x by more reaches an image
+
+
+def molecules_host(z, edge_index, cart_dist, cart_dir, atom_row, ptr=None, tol: float = BOND_TOLERANCE) -> dict:
+    """The molecule rule of the module docstring in plain numpy: a dict with ``label`` [N] int64, ``x`` [N,3] fp64,
+    ``mol`` / ``size`` / ``status`` [M] int32, ``crystal_counts`` [B,5] fp64 (molecules, tested, periodic, open, largest
+    size) and ``sweeps`` [B] int64, the sweeps each crystal took including the last one that changed nothing.  ``z`` [N];
+    ``edge_index`` [2,E] = (source, target); ``cart_dist`` [E] and ``cart_dir`` [E,3] fp32; ``atom_row`` [N]: an atom's row
+    or -1 (M is the largest row plus one); ``ptr`` [B+1]: the crystals' atom offsets (``None``: one crystal).  An edge
+    between atoms of different crystals is no bond."""
+    z = np.asarray(z, dtype=np.int64).reshape(-1)
+    src, tgt = (np.asarray(a, dtype=np.int64).reshape(-1) for a in np.asarray(edge_index).reshape(2, -1))
+    dist = np.asarray(cart_dist, dtype=np.float32).reshape(-1)
+    dirs = np.asarray(cart_dir, dtype=np.float32).reshape(-1, 3)
+    atom_row = np.asarray(atom_row, dtype=np.int64).reshape(-1)
+    N = z.shape[0]
+    M = int(atom_row.max()) + 1 if N else 0
+    ptr = np.asarray([0, N] if ptr is None else ptr, dtype=np.int64).reshape(-1)
+    B = len(ptr) - 1
+    crystal = np.searchsorted(ptr, np.arange(N), side="right") - 1
+    inside = (src >= 0) & (src < N) & (tgt >= 0) & (tgt < N)
+    s, t = np.where(inside, src, 0), np.where(inside, tgt, 0)
+    has_row = atom_row >= 0
+    bond = inside & (crystal[s] == crystal[t]) & has_row[s] & has_row[t] & is_bond(dist, z[t], z[s], tol, same_atom=s == t)
+    be = np.nonzero(bond)[0]                                      # the bond edges, in edge order
+    s, t = s[be], t[be]
+    v = dist[be].astype(np.float64)[:, None] * dirs[be].astype(np.float64)
+    label = np.where(has_row, np.arange(N, dtype=np.int64), -1)
+    x = np.zeros((N, 3), dtype=np.float64)
+    sweeps = np.ones(B, dtype=np.int64)
+    for _ in range(N + 1):
+        # per target the edge with the smallest source label, the lowest edge among equals
+        order = np.lexsort((np.arange(len(be)), label[s], t))
+        first = np.ones(len(order), dtype=bool)
+        first[1:] = t[order][1:] != t[order][:-1]
+        w = order[first]
+        w = w[label[s[w]] < label[t[w]]]
+        if not len(w):
+            break
+        new_label, new_x = label.copy(), x.copy()                # Jacobi: the sweep reads the previous values only
+        new_label[t[w]] = label[s[w]]
+        new_x[t[w]] = x[s[w]] + v[w]
+        label, x = new_label, new_x
+        sweeps[np.unique(crystal[t[w]])] += 1
+    root = np.nonzero(label == np.arange(N))[0]                   # ascending: the order of the molecules
+    open_, periodic = np.zeros(N, dtype=bool), np.zeros(N, dtype=bool)     # per root atom
+    differ = label[s] != label[t]
+    open_[label[s[differ]]] = True
+    open_[label[t[differ]]] = True
+    gap = x[t] - (x[s] + v)
+    far = ~differ & ((gap * gap).sum(1) > MOLECULE_CLOSURE ** 2)
+    periodic[label[t[far]]] = True
+    status_of = periodic * MOLECULE_PERIODIC + open_ * MOLECULE_OPEN
+    size_of = np.bincount(label[has_row], minlength=N) if N else np.zeros(0, dtype=np.int64)
+    number_of = np.zeros(N, dtype=np.int64)
+    number_of[root] = np.arange(len(root)) - np.searchsorted(root, ptr[crystal[root]])   # roots of the crystal below it
+    rows = np.nonzero(has_row)[0]
+    mol, size, status = (np.zeros(M, dtype=np.int32) for _ in range(3))
+    mol[atom_row[rows]] = number_of[label[rows]]
+    size[atom_row[rows]] = size_of[label[rows]]
+    status[atom_row[rows]] = status_of[label[rows]]
+    counts = np.zeros((B, 5), dtype=np.float64)
+    for g in range(B):
+        r = root[(root >= ptr[g]) & (root < ptr[g + 1])]
+        st, sz = status_of[r], size_of[r]
+        counts[g] = (len(r), ((st == 0) & (sz >= 2)).sum(), (st & MOLECULE_PERIODIC > 0).sum(),
+                     (st & MOLECULE_OPEN > 0).sum(), sz.max() if len(r) else 0)
+    return {"label": label, "x": x, "mol": mol, "size": size, "status": status, "crystal_counts": counts,
+            "sweeps": sweeps}

@@ -14,14 +14,17 @@ import pickle
 
 import torch
 
-from .metrics import (adp_eval, bond_test, compute_3D_IoU, edge_row_ptr, get_similarity_index, rotate_rows, split_rows,
-                      target_row_ptr, to_host)
+from .metrics import (adp_eval, bond_test, compute_3D_IoU, edge_row_ptr, get_similarity_index, molecule_test, molecules,
+                      rotate_rows, split_rows, target_row_ptr, to_host)
 from .predict import frame_stage
 from .shard import random_rotations
 
 # the keys of the two pickles in the order the reference's loops create them (a Monte-Carlo round stores no temperature)
 INFERENCE_KEYS = ("pred", "true", "temp", "cell", "refcode", "pos", "atoms", "iou", "mae", "similarity_index")
 MONTECARLO_KEYS = ("pred", "true", "cell", "refcode", "pos", "atoms", "mae", "iou", "similarity_index")
+# what --inference --rigid_molecule adds to its pickle: the molecules, then the test of the prediction and of the truth
+MOLECULE_KEYS = ("mol", "mol_size", "mol_status", "mol_pairs", "mol_delta_max", "mol_over", "mol_pairs_true",
+                 "mol_delta_max_true", "mol_over_true")
 
 
 def summary(iou: torch.Tensor, mae: torch.Tensor, sim: torch.Tensor) -> dict:
@@ -56,7 +59,8 @@ def batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> N
         out[k] += split_rows(t, rows)
 
 
-def inference(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0, rigid_bond=None) -> dict:
+def inference(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0, rigid_bond=None,
+              rigid_molecule=None) -> dict:
     """main.py:21-60 at any batch size: eval mode, per test batch one forward and one ``adp_eval`` -- the prediction, the
     target and the per-atom IoU / MAE / similarity index -- and everything pickled to ``output_path`` with one list entry
     per crystal (the reference's test loader has batch size 1, loader/loader.py:121).  The crystals carry no refcode /
@@ -66,7 +70,12 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
     ``(tol, threshold)``: ``metrics.bond_test`` on the prediction and on the truth of every batch; the pickle then also has
     ``bond_delta_max`` and ``bond_delta_max_true`` per crystal (one value per row), the result ``rigid_bond_mean`` and
     ``rigid_bond_mean_true`` (the mean ``|D|`` over the directed bonds of the pass, 0 without bonds): the truth's figure is
-    the baseline the prediction's is to be compared with."""
+    the baseline the prediction's is to be compared with.  ``rigid_molecule`` = ``(tol, threshold)``: the molecules of
+    every batch (``metrics.molecules``, found once) and ``metrics.molecule_test`` on the prediction and on the truth; the
+    pickle then also has ``mol``, ``mol_size`` and ``mol_status`` and, per test, ``mol_pairs`` / ``mol_delta_max`` /
+    ``mol_over`` and the same with the suffix ``_true`` (one value per row), the result ``molecules``,
+    ``molecules_tested``, ``rigid_molecule_pairs`` and ``rigid_molecule_mean`` / ``_max`` / ``_over`` and those three with
+    the suffix ``_true`` (over the directed pairs of the pass, 0 without pairs)."""
     model.eval()
     out = {k: [] for k in INFERENCE_KEYS}
     gen = None
@@ -77,6 +86,12 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
     if rigid_bond is not None:
         out["bond_delta_max"], out["bond_delta_max_true"] = [], []
         bond_sums = torch.zeros((2, 4), dtype=torch.float64, device=device)
+    mol_counts = mol_sums = mol_max = None                # on the device: crystal_counts summed; crystal_stats, as bond_sums
+    if rigid_molecule is not None:
+        out.update({k: [] for k in MOLECULE_KEYS})
+        mol_counts = torch.zeros(5, dtype=torch.float64, device=device)
+        mol_sums = torch.zeros((2, 4), dtype=torch.float64, device=device)
+        mol_max = torch.zeros(2, dtype=torch.float64, device=device)
     with torch.no_grad():
         for batch in loader:
             if batch is None:
@@ -91,6 +106,16 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
                     bt = bond_test(u, batch, row_ptr, *rigid_bond)
                     extra[name] = bt.delta_max
                     bond_sums[k] += bt.crystal_stats.sum(0)
+            if rigid_molecule is not None:                                    # found once, tested twice
+                mo = molecules(batch, row_ptr, rigid_molecule[0], rows=int(pred.shape[0]))
+                extra.update(mol=mo.mol, mol_size=mo.size, mol_status=mo.status)
+                mol_counts += mo.crystal_counts.sum(0)
+                for k, (suffix, u) in enumerate((("", pred), ("_true", true))):
+                    mt = molecule_test(u, batch, row_ptr, mo, rigid_molecule[1])
+                    extra.update({"mol_pairs" + suffix: mt.pairs, "mol_delta_max" + suffix: mt.delta_max,
+                                  "mol_over" + suffix: mt.over})
+                    mol_sums[k] += mt.crystal_stats.sum(0)
+                    mol_max[k] = torch.maximum(mol_max[k], mt.crystal_stats[:, 2].max())
             res = adp_eval(pred, true, row_ptr, None, volume=False)
             batch_entries(out, batch, row_ptr, {"pred": pred, "true": true, "mae": res.abs_err, "iou": res.iou,
                                                 "similarity_index": res.similarity_index, **extra}, with_pos=True)
@@ -105,6 +130,12 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
     if rigid_bond is not None:
         (n_p, s_p, _, _), (n_t, s_t, _, _) = bond_sums.tolist()
         result.update(rigid_bond_mean=s_p / n_p if n_p else 0.0, rigid_bond_mean_true=s_t / n_t if n_t else 0.0)
+    if rigid_molecule is not None:
+        counts, sums, highest = mol_counts.tolist(), mol_sums.tolist(), mol_max.tolist()
+        result.update(molecules=int(counts[0]), molecules_tested=int(counts[1]), rigid_molecule_pairs=int(sums[0][0]))
+        for suffix, (n_pairs, s, _, n_over), hi in zip(("", "_true"), sums, highest):
+            result.update({"rigid_molecule_mean" + suffix: s / n_pairs if n_pairs else 0.0,
+                           "rigid_molecule_max" + suffix: hi, "rigid_molecule_over" + suffix: int(n_over)})
     return result
 
 

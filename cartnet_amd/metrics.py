@@ -322,14 +322,18 @@ def _check_graph(batch, dev, M: int, who: str, rows: str, need_dir: bool):
     return z, N, ei, E, dist, dirs, mask
 
 
+def _atom_rows(mask, N: int, dev) -> torch.Tensor:
+    """[N] int64: an atom's row, -1 outside the mask; without a mask every atom has one."""
+    if mask is None:
+        return torch.arange(N, dtype=torch.int64, device=dev)
+    mask = mask.to(torch.bool)
+    return torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
+
+
 def _atom_lookups(mask, ei: torch.Tensor, N: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(atom_row [N], seg_ptr [N+1])`` int64: an atom's row (-1 outside the mask; without a mask every atom has one) and
     its edge segment, with static-shape device ops."""
-    if mask is None:
-        atom_row = torch.arange(N, dtype=torch.int64, device=dev)
-    else:
-        mask = mask.to(torch.bool)
-        atom_row = torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
+    atom_row = _atom_rows(mask, N, dev)
     # the edges are sorted by target: atom i owns the edges between the first target >= i and the first target >= i + 1
     seg_ptr = torch.searchsorted(ei[1].contiguous(), torch.arange(N + 1, dtype=torch.int64, device=dev))
     return atom_row, seg_ptr
@@ -419,6 +423,125 @@ def riding_h(u_eq: torch.Tensor, batch, tol: float = 0.4, f: float = 1.2, f_rot:
             float(f), float(f_rot), B, N, M, E, parent.data_ptr(), count.data_ptr(), mult.data_ptr(), u_iso.data_ptr(),
             stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_riding_h")
     return RidingH(parent, count, mult, u_iso, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Molecules and the rigid-body test (csrc/molecule_ops.hip): the components of the bond graph with every atom's unwrapped
+# position, and Hirshfeld's postulate for all pairs of atoms of a molecule (Rosenfield, Trueblood & Dunitz 1978).  Two
+# calls, because molecules do not depend on U: found once per batch, tested as often as there are predictions of it.
+# The rule: bonds.py.
+
+class Molecules(NamedTuple):
+    """What ``molecules`` returns, all on the device: ``label`` [N] int64, the batch's atom index of the root (the lowest
+    atom) of an atom's molecule, -1 for an atom without a row; ``x`` [N,3] fp64, the atom's position relative to that
+    root, unwrapped through the cell faces; per row ``mol`` [M] int32 (the molecule's number inside its crystal, in the
+    order of the roots), ``size`` [M] int32 (its atoms) and ``status`` [M] int32 (bit 1 periodic, bit 2 open; 0 and two or
+    more atoms: tested); ``crystal_counts`` [B,5] fp64: molecules, tested, periodic, open, largest size."""
+    label: torch.Tensor
+    x: torch.Tensor
+    mol: torch.Tensor
+    size: torch.Tensor
+    status: torch.Tensor
+    crystal_counts: torch.Tensor
+
+
+class MoleculeTest(NamedTuple):
+    """What ``molecule_test`` returns, all on the device, per row over the other atoms of its molecule: ``pairs`` [M]
+    int32; ``delta_sum`` [M] fp32, the sum of ``|D|`` with ``D = r^T (U_i - U_j) r / r.r``; ``delta_max`` [M] fp32;
+    ``worst`` [M] int64, the batch's atom index of the partner with the largest ``|D|``; ``over`` [M] int32, the pairs with
+    ``|D| > threshold``.  Rows of untested molecules hold 0, 0, 0, -1, 0.  ``crystal_stats`` [B,4] fp64: per crystal the
+    sum of ``pairs``, the sum of ``delta_sum``, the maximum of ``delta_max`` and the sum of ``over`` -- DIRECTED, as
+    ``BondTest``'s: every pair is seen from both of its ends."""
+    pairs: torch.Tensor
+    delta_sum: torch.Tensor
+    delta_max: torch.Tensor
+    worst: torch.Tensor
+    over: torch.Tensor
+    crystal_stats: torch.Tensor
+
+
+def _atom_ptr(batch, who: str, dev) -> Tuple[torch.Tensor, int]:
+    ptr = _batch_field(batch, "ptr")
+    if not torch.is_tensor(ptr):
+        raise ValueError(f"{who} needs the crystals' atom offsets in batch.ptr")
+    return _check_row_ptr(ptr.to(torch.int64), dev)
+
+
+def molecules(batch, row_ptr: torch.Tensor, tol: float = 0.4, rows: Optional[int] = None) -> Molecules:
+    """The molecules of ``batch``: one call of ``cartnet_molecules``, one workgroup per crystal, nothing read back.
+    ``batch``: as for ``bond_test`` -- ``x`` (or ``z``), ``edge_index`` sorted by target, ``cart_dist``, ``cart_dir``,
+    ``non_H_mask`` if some atoms have no row -- and ``ptr`` [B+1], the crystals' atom offsets.  ``row_ptr`` [B+1]:
+    ``target_row_ptr``.  ``rows``: the number M of rows, which the caller usually knows from the prediction's shape; without
+    it M is the batch's ``y``'s, N if there is no mask, and else counted from the mask (the one host read this can cost).
+    A bond is the rigid-bond test's (``cartnet_amd.bonds``); a molecule is a component of the bond graph."""
+    z = _batch_field(batch, "x", "z")
+    if not torch.is_tensor(z):
+        raise ValueError("molecules needs the atomic numbers in batch.x (a forward has overwritten them)")
+    dev = z.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    atom_ptr, B_atoms = _atom_ptr(batch, "molecules", dev)
+    if B_atoms != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {B_atoms}")
+    mask = _batch_field(batch, "non_H_mask")
+    if rows is None:
+        y = _batch_field(batch, "y")
+        rows = int(z.shape[0]) if mask is None else int(y.shape[0]) if torch.is_tensor(y) else int(mask.sum())
+    M = int(rows)
+    z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "molecules", "rows", True)
+    label = torch.empty(N, dtype=torch.int64, device=dev)
+    x = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    mol, size, status = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(3))
+    if M == 0 or N == 0:                         # the entry point launches nothing
+        return Molecules(label.fill_(-1), x.zero_(), mol, size, status, torch.zeros((B, 5), dtype=torch.float64, device=dev))
+    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
+    counts = torch.empty((B, 5), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        radii = covalent_radii(dev)
+        _l.check(_l.load().cartnet_molecules(
+            z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None, _l.ptr(dirs) if E else None,
+            atom_row.data_ptr(), seg_ptr.data_ptr(), atom_ptr.data_ptr(), row_ptr.data_ptr(), radii.data_ptr(),
+            int(radii.numel()), float(tol), B, N, M, E, label.data_ptr(), x.data_ptr(), mol.data_ptr(), size.data_ptr(),
+            status.data_ptr(), counts.data_ptr(), _l.stream_ptr()), "cartnet_molecules")
+    return Molecules(label, x, mol, size, status, counts)
+
+
+def molecule_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Molecules,
+                  threshold: float = 1e-3) -> MoleculeTest:
+    """The rigid-body test of the ADPs ``u`` [M,3,3] on the ``molecules`` of ``batch`` (``molecules(batch, row_ptr)``):
+    one call of ``cartnet_adp_molecule_test``.  For every row of a tested molecule (status 0, two or more atoms) the other
+    atoms of the molecule in atom order, ``D = r^T (U_i - U_j) r / r.r`` along ``r = x_i - x_j``.  ``batch`` gives
+    ``non_H_mask`` and ``ptr``; nothing is read back."""
+    _check_fp32("u", u)
+    u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    atom_ptr, B_atoms = _atom_ptr(batch, "molecule_test", dev)
+    mo = molecules
+    N = int(mo.label.shape[0])
+    if not (B_atoms == B and tuple(mo.x.shape) == (N, 3) and mo.x.dtype == torch.float64 and mo.label.dtype == torch.int64
+            and all(t.dtype == torch.int32 and tuple(t.shape) == (M,) for t in (mo.status, mo.size))
+            and all(t.device == dev for t in (mo.label, mo.x, mo.status, mo.size))):
+        raise ValueError(f"molecules does not belong to this batch and u ({B} crystals, {M} rows)")
+    mask = _batch_field(batch, "non_H_mask")
+    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
+        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
+    if mask is None and M != N:
+        raise ValueError(f"u holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    pairs = torch.empty(M, dtype=torch.int32, device=dev)
+    delta_sum = torch.empty(M, dtype=torch.float32, device=dev)
+    delta_max = torch.empty(M, dtype=torch.float32, device=dev)
+    worst = torch.empty(M, dtype=torch.int64, device=dev)
+    over = torch.empty(M, dtype=torch.int32, device=dev)
+    if M == 0 or N == 0:                         # the entry point launches nothing
+        return MoleculeTest(pairs, delta_sum, delta_max, worst, over, torch.zeros((B, 4), dtype=torch.float64, device=dev))
+    atom_row = _atom_rows(mask, N, dev)
+    label, x, status, size = (t.contiguous() for t in (mo.label, mo.x, mo.status, mo.size))
+    stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _l.check(_l.load().cartnet_adp_molecule_test(
+            u.data_ptr(), label.data_ptr(), x.data_ptr(), atom_row.data_ptr(), atom_ptr.data_ptr(), row_ptr.data_ptr(),
+            status.data_ptr(), size.data_ptr(), float(threshold), B, N, M, pairs.data_ptr(), delta_sum.data_ptr(), delta_max.data_ptr(), worst.data_ptr(),
+            over.data_ptr(), stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_molecule_test")
+    return MoleculeTest(pairs, delta_sum, delta_max, worst, over, stats)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,9 @@ With ``riding_h`` it brings an isotropic U for every hydrogen, a multiple of its
 With ``temperatures`` every batch is predicted at T temperatures by one forward over a replica batch, the result has one
 entry per crystal and temperature, and the copy also brings a least-squares line per row through the T exports
 (``metrics.temp_series``, csrc/series_ops.hip).
+With ``rigid_molecule`` the copy also brings the molecules of every crystal -- the components of its bond graph, found on
+the GPU, with every atom's unwrapped position -- and the rigid-body test of the exported ADPs over all pairs of atoms of a
+molecule (``metrics.molecules``, ``metrics.molecule_test``, csrc/molecule_ops.hip).
 Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in memory),
 ``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the forward in K
 frames that this pass and ``evaluate.inference`` share.
@@ -25,7 +28,8 @@ from typing import Dict, List, Optional
 import torch
 
 from .metrics import (adp_export, bond_test, check_export_status, check_temperatures, edge_row_ptr, frame_mean,
-                      riding_h as riding_h_call, rotate_rows, split_rows, target_row_ptr, temp_series, to_host)
+                      molecule_test, molecules as find_molecules, riding_h as riding_h_call, rotate_rows, split_rows,
+                      target_row_ptr, temp_series, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
@@ -34,6 +38,8 @@ BOND_KEYS = ("bond_count", "bond_delta_mean", "bond_delta_max", "bond_worst", "b
              "bond_stats")                                                                # with rigid_bond only
 H_KEYS = ("u_iso", "h_parent", "h_count", "h_mult", "h_stats")                            # with riding_h only
 H_SYM_KEYS = ("u_iso_asym", "h_parent_asym")                                              # ... and a CifSymmetry
+MOL_KEYS = ("mol", "mol_size", "mol_status", "mol_pos", "mol_pairs", "mol_delta_mean", "mol_delta_max", "mol_worst",
+            "mol_over", "mol_stats")                                                      # with rigid_molecule only
 SERIES_KEYS = ("t_slope", "t_intercept", "t_ueq_slope", "t_ueq_intercept", "t_resid", "t_drops", "t_stats")
 # with two or more temperatures the result has one more key, "series": a dict of lists, one entry per input crystal, with
 # "name", "temps" and SERIES_KEYS
@@ -203,6 +209,20 @@ def riding_entries(rh, batch) -> dict:
             "h_stats": rh.crystal_stats}
 
 
+def molecule_entries(mo, mt, batch) -> dict:
+    """The keys of ``MOL_KEYS`` from the ``metrics.Molecules`` of ``batch`` and a ``metrics.MoleculeTest`` on them, on the
+    device: ``mol_pos`` = ``fp32(x)`` of the row's atom, NaN where the molecule's status is not 0; ``mol_delta_mean`` =
+    ``delta_sum / pairs`` (0 without pairs); ``mol_worst`` as an atom index inside its crystal (-1 without pairs);
+    ``mol_stats`` [B,9] = the five counts of the molecules, then the four figures of the test.  Static-shape device ops:
+    nothing is read back."""
+    pos = mo.x[batch.non_H_mask].to(torch.float32)
+    return {"mol": mo.mol, "mol_size": mo.size, "mol_status": mo.status,
+            "mol_pos": torch.where((mo.status == 0).unsqueeze(1), pos, torch.full_like(pos, float("nan"))),
+            "mol_pairs": mt.pairs, "mol_delta_mean": mt.delta_sum / mt.pairs.clamp(min=1).to(torch.float32),
+            "mol_delta_max": mt.delta_max, "mol_worst": _in_crystal(mt.worst, batch), "mol_over": mt.over,
+            "mol_stats": torch.cat([mo.crystal_counts, mt.crystal_stats], dim=1)}
+
+
 def u_eq_of_cif(u_cif: torch.Tensor, cell: torch.Tensor) -> torch.Tensor:
     """[n] fp64: the equivalent isotropic U of ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12 on the unit reciprocal axes) in
     ``cell`` ([3,3], or [n,3,3] with one cell per row; rows = lattice vectors):
@@ -255,6 +275,9 @@ SPLIT = {"atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "u_cart
 # exactly the tensor keys of an entry (tests/test_cif_writers_golden.py holds it to that).
 SERIES_SPLIT = {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t_ueq_intercept": "row", "t_resid": "row",
                 "t_drops": "row", "t_stats": "crystal"}
+# ... and for MOL_KEYS: only "row" and "crystal" keys
+MOL_SPLIT = {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "row", "mol_pairs": "row",
+             "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"}
 
 
 def _check_pass(loader, rotations: int):
@@ -292,10 +315,10 @@ def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
             "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
 
 
-def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h) -> dict:
+def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h, rigid_molecule=None) -> dict:
     """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
-    one ``to_host``: tensors under their key of ``SPLIT``, and under names with a leading underscore what ``_host_stage``
-    needs to cut and check them."""
+    one ``to_host``: tensors under their key of ``SPLIT`` (``MOL_SPLIT``), and under names with a leading underscore what
+    ``_host_stage`` needs to cut and check them."""
     row_ptr = target_row_ptr(batch)
     dev = _of_the_batch(batch, row_ptr)
     if "temperature" in shard.t:
@@ -303,13 +326,24 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     pred, R, fm = frame_stage(model, batch, row_ptr, rotations, gen, stats=True)
     if fm is not None:
         dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
-    dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h))
+    dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h,
+                         _found_molecules(batch, row_ptr, int(pred.shape[0]), rigid_molecule)))
     return dev
 
 
-def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h) -> dict:
+def _found_molecules(batch, row_ptr: torch.Tensor, rows: int, rigid_molecule):
+    """``(metrics.Molecules of the batch, threshold)`` for ``rigid_molecule`` = ``(tol, threshold)``, or ``None``: found
+    once per batch (they do not depend on U), tested once per prediction of it (``_exported``)."""
+    if rigid_molecule is None:
+        return None
+    tol, threshold = rigid_molecule
+    return find_molecules(batch, row_ptr, tol, rows=rows), threshold
+
+
+def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, found=None) -> dict:
     """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch`` (its atomic numbers in ``x``):
-    the export and, as asked for, the rigid-bond test, the riding hydrogens and the site average."""
+    the export and, as asked for, the rigid-bond test, the rigid-body test on the molecules ``found``
+    (``_found_molecules``), the riding hydrogens and the site average."""
     device = batch.x.device
     B = int(batch.num_graphs)
     sel = batch._meta[:B]
@@ -318,6 +352,9 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
                stats=ex.crystal_stats, _status=ex.status)
     if rigid_bond is not None:
         dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
+    if found is not None:
+        mo, threshold = found
+        dev.update(molecule_entries(mo, molecule_test(pred, batch, row_ptr, mo, threshold), batch))
     if riding_h is not None:
         rh = riding_h_call(ex.u_eq, batch, *riding_h)
         dev.update(riding_entries(rh, batch))
@@ -334,7 +371,7 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
 
 
 def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, riding_h, kelvin: list,
-                         temps: torch.Tensor) -> dict:
+                         temps: torch.Tensor, rigid_molecule=None) -> dict:
     """One batch (on the device) at the T temperatures ``kelvin`` (``temps``: their model-side values, ``standardised``)
     through ONE forward of ``replicate_temperatures`` and the kernels that follow it, those once per temperature on that
     temperature's rows.  Returns what travels to the host in one ``to_host``: what does not depend on the temperature
@@ -348,6 +385,7 @@ def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, rid
     if R is not None:
         dev["frames"] = R.transpose(0, 1)
     rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
+    found = _found_molecules(batch, row_ptr, rows // rotations, rigid_molecule)   # once for the T temperatures
     per = []
     for t in range(T):
         pred, d = members[t * rows:(t + 1) * rows], {}
@@ -355,7 +393,7 @@ def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, rid
             fm = frame_mean(pred, R, row_ptr, stats=True)
             pred = fm.mean
             d.update(rot_spread=fm.spread, rot_stats=fm.crystal_spread)
-        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h))
+        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, found))
         per.append(d)
         dev.update({f"{k}@{t}": v for k, v in d.items()})
     if T >= 2:
@@ -409,6 +447,7 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
     riding = "_ueq_asym" in host                                              # what riding_asym takes, per site and per atom
     ueq_sites = split_rows(host.pop("_ueq_asym"), counts["site"]) if riding else None
     parents = split_rows(host.pop("_parent_asym"), counts["atom"]) if riding else None
+    _split(out, {k: host.pop(k) for k in MOL_KEYS if k in host}, counts, MOL_SPLIT)
     _split(out, host, counts)
     if sym is not None:
         out["asym_labels"] += [sym.labels[i] for i in ids]
@@ -426,7 +465,7 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
 
 
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
-                 temperatures=None) -> Dict[str, List]:
+                 temperatures=None, rigid_molecule=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
@@ -464,7 +503,16 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     one ``metrics.temp_series`` per batch on the exported ``u_cif`` / ``u_eq`` (with rotations the frame means'),
     ``t_slope`` [n,6] (A^2/K) and ``t_intercept`` [n,6] of ``u_cif``, ``t_ueq_slope`` [n], ``t_ueq_intercept`` [n],
     ``t_resid`` [n], ``t_drops`` [n] int32 and ``t_stats`` [4] fp64 (sum of ``t_ueq_slope``, rows whose U_eq slope is not
-    > 0, rows with a drop, largest ``t_resid``).  ``None`` is the pass as it always was."""
+    > 0, rows with a drop, largest ``t_resid``).  ``None`` is the pass as it always was.  ``rigid_molecule`` =
+    ``(tol, threshold)``: per batch one ``metrics.molecules`` (the components of the bond graph; they do not depend on U,
+    so with temperatures they are found once for all T) and one ``metrics.molecule_test`` per exported ``u_cart`` (with
+    rotations the frame mean, with the stored ``cart_dir``; with CIF input the rows of the expanded cell, before site
+    averaging), travelling in the same copy.  The result then also has, per crystal, ``mol`` [n] (the row's molecule,
+    numbered inside the crystal), ``mol_size`` [n], ``mol_status`` [n] (bit 1 periodic, bit 2 open), ``mol_pos`` [n,3] fp32
+    (the atom's unwrapped position relative to its molecule's lowest atom; NaN where the status is not 0), ``mol_pairs``
+    [n], ``mol_delta_mean`` [n], ``mol_delta_max`` [n], ``mol_worst`` [n] (an atom index inside the crystal, -1 without
+    pairs), ``mol_over`` [n] and ``mol_stats`` [9] fp64 (molecules, tested, periodic, open, largest size; directed pairs,
+    sum of ``|D|``, largest ``|D|``, pairs over the threshold).  ``None`` is the pass as it always was."""
     rotations = int(rotations)
     shard = _check_pass(loader, rotations)
     kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
@@ -472,7 +520,8 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
                             + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())
                             + (H_KEYS if riding_h is not None else ())
-                            + (H_SYM_KEYS if riding_h is not None and sym is not None else ())}
+                            + (H_SYM_KEYS if riding_h is not None and sym is not None else ())
+                            + (MOL_KEYS if rigid_molecule is not None else ())}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     if kelvin is not None:
         temps = standardised(kelvin, loader.temp_mean, loader.temp_std, device)
@@ -483,11 +532,11 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
                 continue
             batch.to(device)
             if kelvin is None:
-                _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h)),
-                            shard, sym)
+                _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h,
+                                                       rigid_molecule)), shard, sym)
             else:
                 _host_stage_series(out, series, to_host(_device_stage_series(model, batch, sym, rotations, gen, rigid_bond,
-                                                                             riding_h, kelvin, temps)),
+                                                                             riding_h, kelvin, temps, rigid_molecule)),
                                    shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
@@ -526,7 +575,9 @@ def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir:
     such a list (``load_input``); with ``temperatures`` ``entries`` and ``temperatures``, and from a ``series``
     ``ueq_slope_mean``, ``non_increasing_rows``, ``rows_with_drops`` and ``series_resid_max``; with frames ``rotations``,
     ``rot_spread_max`` and ``rot_spread_mean``; with the rigid-bond test ``bonds``, ``rigid_bond_mean`` / ``_max`` /
-    ``_over``; with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
+    ``_over``; with the rigid-body test ``molecules``, ``molecules_tested`` / ``_periodic`` / ``_open``,
+    ``molecule_atoms_max`` and ``rigid_molecule_pairs`` / ``_mean`` / ``_max`` / ``_over`` (over the entries: with
+    temperatures every crystal counts once per temperature); with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
     ``h_non_positive``.  A pass without crystals gives zeros."""
     n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
@@ -561,13 +612,22 @@ def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir:
         res.update(hydrogens=hydrogens, h_orphans=orphans,
                    h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,
                    h_non_positive=int(hs[:, 3].sum()))
+    if "mol_stats" in out:                            # the sums over the entries, from the fp64 per-crystal figures
+        ms = stacked("mol_stats", 9)
+        count = int(ms[:, 5].sum())
+        res.update(molecules=int(ms[:, 0].sum()), molecules_tested=int(ms[:, 1].sum()),
+                   molecules_periodic=int(ms[:, 2].sum()), molecules_open=int(ms[:, 3].sum()),
+                   molecule_atoms_max=int(ms[:, 4].max()) if n else 0, rigid_molecule_pairs=count,
+                   rigid_molecule_mean=float(ms[:, 6].sum()) / count if count else 0.0,
+                   rigid_molecule_max=float(ms[:, 7].max()) if n else 0.0, rigid_molecule_over=int(ms[:, 8].sum()))
     return res
 
 
 def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
-    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS + H_KEYS + H_SYM_KEYS if key in result}
+    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS + H_KEYS + H_SYM_KEYS + MOL_KEYS
+            if key in result}
 
 
 def cell_parameters(cell) -> tuple:

@@ -504,6 +504,64 @@ int cartnet_adp_riding_h(const float* u_eq, const int64_t* z, const int64_t* edg
                          int64_t* parent, int32_t* count, float* mult, float* u_iso, double* crystal_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Molecules: the components of the bond graph of every crystal of one batch, with each atom's unwrapped position
+ * relative to its molecule's root.  The reference has no counterpart: it has no notion of a bond, and its only
+ * statements about a prediction need the truth (main.py:47-49).
+ *   z, edge_index, cart_dist, cart_dir, atom_row, seg_ptr, radii, n_radii, tol as for cartnet_adp_bond_test; ptr [B+1]
+ *   int64: crystal g owns the atoms [ptr[g], ptr[g+1]); row_ptr [B+1] int64: its rows (the rows of a crystal's atoms come
+ *   from atom_row; row_ptr is the pair test's and is only checked here).
+ * An edge e = (j -> i) is a bond by the rule of cartnet_adp_bond_test (i != j, both Z non-hydrogen and inside the
+ * table, both ends with a row, cart_dist[e] <= (radii[z_i] + radii[z_j]) + tol in fp32 in that order); an edge whose
+ * source is no atom of the target's crystal is none.  The definition is a Jacobi propagation (cartnet_amd/bonds.py,
+ * molecules_host): label[i] = i and x[i] = 0 at the start; in a sweep, which reads the previous sweep's values only, atom
+ * i takes the smallest label among the sources of its incoming bonds and, if that is below its own, adopts it with
+ * x[i] = x[j] + fp64(cart_dist[e]) * fp64(cart_dir[e]) along the lowest edge that carries it; until no label changes,
+ * and never more than (atoms of the crystal + 1) sweeps.  One workgroup per crystal; nothing is read back.
+ *   label [N] int64       the batch's atom index of the molecule's root, its lowest atom; -1 for an atom without a row
+ *   x [N,3] fp64          the position relative to the root, unwrapped through the cell faces; 0 without a row
+ *   mol [M] int32         the number of the row's molecule inside its crystal, in the order of the roots
+ *   mol_size [M] int32    the atoms of the row's molecule
+ *   mol_status [M] int32  of the row's molecule: bit 1 (value 1) periodic -- some bond inside it disagrees with x by
+ *                         more than 0.5 A, the molecule reaches its own image; bit 2 (value 2) open -- some bond has
+ *                         different labels at its ends (a capped, asymmetric graph): both molecules get it
+ *   crystal_counts [B,5] fp64 = (molecules, tested -- status 0 and two or more atoms --, periodic, open, largest size)
+ * mol, mol_size and mol_status hold intermediate values while the kernel runs.  E == 0 needs no edge arrays.  M == 0,
+ * N == 0 or B == 0: returns 0 without a launch and writes nothing.  No atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_molecules(const int64_t* z, const int64_t* edge_index, const float* cart_dist, const float* cart_dir,
+                      const int64_t* atom_row, const int64_t* seg_ptr, const int64_t* ptr, const int64_t* row_ptr,
+                      const float* radii, int32_t n_radii, float tol, int32_t B, int64_t N, int64_t M, int64_t E,
+                      int64_t* label, double* x, int32_t* mol, int32_t* mol_size, int32_t* mol_status,
+                      double* crystal_counts, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
+ * The rigid-body test of Rosenfield, Trueblood & Dunitz (Acta Cryst. A34 (1978) 828) on the ADPs of one batch:
+ * Hirshfeld's postulate for all pairs of atoms of a molecule.  The reference has no counterpart: its only statements
+ * about a prediction need the truth (main.py:47-49).
+ *   u [M,3,3] fp32; label, x, mol_status, mol_size: cartnet_molecules' results for the same batch; atom_row, ptr,
+ *   row_ptr as there.
+ * A molecule is tested when its status is 0 and it has two or more atoms.  For the row m of atom i in a tested molecule,
+ * over the atoms j != i with label[j] == label[i] in atom order, in fp64:
+ *   r = x_i - x_j,  D = r^T (S_i - S_j) r / (r.r)  with S = (U + U^T) / 2 (the difference is taken first); a pair with
+ *   r.r == 0 is not counted.
+ *   pairs [M] int32       the counted pairs
+ *   delta_sum [M] fp32    sum of |D|, summed in fp64 in atom order
+ *   delta_max [M] fp32    the largest |D|; 0 without pairs
+ *   worst [M] int64       the batch's atom index of the partner with the largest |D| (a tie: the lower atom; a NaN is
+ *                         kept); -1 without pairs
+ *   over [M] int32        the pairs with |D| > threshold, compared in fp64
+ * Rows of untested molecules get 0, 0, 0, -1, 0.  Per crystal (one wave each, rows in order, from the values as stored):
+ *   crystal_stats [B,4] fp64 (or NULL) = (sum of pairs, sum of delta_sum, maximum of delta_max, sum of over).  Every
+ *   pair is seen from both of its ends: these are directed counts.
+ * M == 0, N == 0 or B == 0: returns 0 without a launch and writes nothing.  No atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_molecule_test(const float* u, const int64_t* label, const double* x, const int64_t* atom_row,
+                              const int64_t* ptr, const int64_t* row_ptr, const int32_t* mol_status,
+                              const int32_t* mol_size, double threshold, int32_t B, int64_t N, int64_t M, int32_t* pairs,
+                              float* delta_sum, float* delta_max, int64_t* worst, int32_t* over, double* crystal_stats,
+                              void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * A least-squares line per row and component through the exported ADPs of one batch over T temperatures.  The reference
  * predicts every crystal at the one temperature it is stored with (main.py:21-60); the model reads the temperature, so
  * one batch replicated T times answers how the ellipsoids grow.

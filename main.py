@@ -24,7 +24,9 @@ deviation of a frame from it per atom.  ``--rigid_bond`` adds Hirshfeld's rigid-
 ``metrics.bond_test``).  ``--riding_h`` gives every hydrogen of a ``--predict`` pass an isotropic U by the riding model, a
 multiple of its parent's predicted U_eq (``metrics.riding_h``).  ``--predict_temperatures SPEC`` predicts every crystal of a
 ``--predict`` pass at a series of temperatures in one forward per batch and fits a line per atom through them
-(``metrics.temp_series``).  There is no CPU path: the model runs on an AMD GPU only.
+(``metrics.temp_series``).  ``--rigid_molecule`` finds the molecules of every crystal of a ``--predict`` or ``--inference``
+pass on the GPU and tests the ADPs for rigid-body motion over all pairs of atoms of a molecule (``metrics.molecules``,
+``metrics.molecule_test``).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -147,6 +149,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--rigid_bond: an edge is a bond up to the sum of the covalent radii plus this many Angstrom")
     p.add_argument("--rigid_bond_threshold", type=float, default=RIGID_BOND_THRESHOLD,
                    help="--rigid_bond: bonds whose amplitudes differ by more than this (A^2) are counted as over")
+    p.add_argument("--rigid_molecule", action="store_true",
+                   help="--predict / --inference: find the molecules of every crystal (the components of the bond graph, "
+                        "bonds as for --rigid_bond with --bond_tolerance) and run the rigid-body test of Rosenfield, "
+                        "Trueblood & Dunitz on the ADPs (and, with --inference, on the truth): Hirshfeld's test over ALL "
+                        "pairs of atoms of a molecule, along the unwrapped interatomic vectors.  Molecules that reach their "
+                        "own image (polymers, frameworks) or whose graph is capped are reported and not tested.  Not "
+                        "without --predict or --inference; --montecarlo and training ignore it")
+    p.add_argument("--rigid_molecule_threshold", type=float, default=RIGID_BOND_THRESHOLD,
+                   help="--rigid_molecule: pairs whose amplitudes differ by more than this (A^2) are counted as over")
     p.add_argument("--riding_h", action="store_true",
                    help="--predict: give every hydrogen an isotropic U by the riding model, a multiple of the predicted U_eq "
                         "of the atom it is bonded to (the nearest non-hydrogen atom within r_H + r + --bond_tolerance among "
@@ -312,6 +323,12 @@ def check_predict_args(args) -> None:
         parse_temperatures(args.predict_temperatures)
 
 
+def rigid_molecule_option(args) -> dict:
+    """``--rigid_molecule`` as the keyword of ``predict_adps`` / ``evaluate.inference``; without the flag no keyword at
+    all: the passes are called as they always were."""
+    return {"rigid_molecule": (args.bond_tolerance, args.rigid_molecule_threshold)} if args.rigid_molecule else {}
+
+
 def predict(model, args) -> dict:
     """``--predict``: the one shard of ``--predict_input`` through ``shard_recipe`` as the test split goes through it, in
     batches of ``--eval_batch``; the pickle of ``cartnet_amd.predict.predict_adps`` and, if asked for, one CIF per
@@ -328,7 +345,8 @@ def predict(model, args) -> dict:
         model, ShardLoader(shard, cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
         rotations=cfg.rotations, seed=cfg.seed, temperatures=temps,
         rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None,
-        riding_h=(args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating) if args.riding_h else None)
+        riding_h=(args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating) if args.riding_h else None,
+        **rigid_molecule_option(args))
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     if args.predict_cif_dir:
@@ -344,6 +362,8 @@ def main(argv=None) -> dict:
     fill_cfg(args)
     if args.predict or args.predict_temperatures is not None:
         check_predict_args(args)
+    if args.rigid_molecule and not (args.predict or args.inference):
+        raise SystemExit("--rigid_molecule serves --predict and --inference only")
     torch.set_num_threads(args.threads)
     rank, world, local = cdist.init_from_env()
     if world > 1:
@@ -369,7 +389,8 @@ def main(argv=None) -> dict:
         if args.inference:
             res = evaluate.inference(
                 model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations, seed=cfg.seed,
-                rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None)
+                rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None,
+                **rigid_molecule_option(args))
         else:
             res = evaluate.montecarlo(model, loaders[-1], cfg.device, args.inference_output,
                                       rounds=args.montecarlo_rounds, seed=cfg.seed)

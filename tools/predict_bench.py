@@ -1,5 +1,5 @@
-"""What the four ``predict_adps`` benchmarks share (bench_predict.py, bench_predict_rotations.py, bench_bond_test.py,
-bench_riding_h.py): the model and the shard, the timed pass, the alternating rounds, the event-stamping wrapper and the
+"""What the ``predict_adps`` benchmarks share (bench_predict.py, bench_predict_rotations.py, bench_bond_test.py,
+bench_riding_h.py, bench_rigid_molecule.py): the model and the shard, the timed pass, the alternating rounds, the event-stamping wrapper and the
 time-limited child process.  A tool states its variants and builds its JSON; everything else is here.
 
 The model is CartNet D = 256, L = 4 (fresh weights, eval mode); the shard 512 synthetic crystals of 30-70 atoms, packed
@@ -25,7 +25,8 @@ SHARD = f"{CRYSTALS} synthetic crystals of {ATOMS[0]}-{ATOMS[1]} atoms, unlabele
 class Bench:
     """The model and the shard on the device; ``tool`` names the caller in the message of a machine without a GPU."""
 
-    def __init__(self, tool: str):
+    def __init__(self, tool: str, crystals=None):
+        """``crystals``: geometry-only ``Data`` objects to pack instead of the synthetic ones (bench_rigid_molecule.py)."""
         import torch
 
         import main as entry
@@ -40,16 +41,18 @@ class Bench:
         torch.manual_seed(0)
         self.torch, self.predict, self.device = torch, predict, cfg.device
         self.model = create_model()
-        crystals = [make_geometry(50000 + g, None, ATOMS) for g in range(CRYSTALS)]
-        for d in crystals:
-            del d.y
+        if crystals is None:
+            crystals = [make_geometry(50000 + g, None, ATOMS) for g in range(CRYSTALS)]
+            for d in crystals:
+                del d.y
+        self.crystals = len(crystals)
         (self.shard,), _ = entry.shard_recipe([DeviceShard.from_data_list(crystals, cfg.device)])
         assert not self.shard.labeled and self.shard.has_graph
 
     def sizes(self, rounds: int) -> dict:
         """The keys every tool's JSON starts with."""
         s = self.shard
-        return {"device": self.torch.cuda.get_device_name(0), "crystals": CRYSTALS, "atoms": int(s.atom_ptr[-1]),
+        return {"device": self.torch.cuda.get_device_name(0), "crystals": self.crystals, "atoms": int(s.atom_ptr[-1]),
                 "edges": int(s.edge_ptr[-1]), "rows": int(s.y_ptr[-1]), "rounds": rounds}
 
     def timed(self, eval_batch: int, passes: int = 1, **kw):

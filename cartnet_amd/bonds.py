@@ -62,6 +62,40 @@ The rigid-body test on top of it (``metrics.molecule_test``; Rosenfield, Trueblo
 generalises Hirshfeld's test from bonds to all pairs of a tested molecule: for the row of atom ``i``, over the atoms
 ``j != i`` of its molecule in atom order and in fp64, ``r = x_i - x_j`` and ``D = r^T (S_i - S_j) r / (r . r)`` with ``S``
 the symmetric part of ``U`` (the difference is taken first); a pair with ``r . r == 0`` is not counted.
+
+The TLS fit (``metrics.tls_fit``, csrc/tls_ops.hip; ``tls_fit_host`` below restates it in numpy; Schomaker & Trueblood,
+Acta Cryst. B24 (1968) 63): how much of a molecule's ADPs is rigid-body motion, which motion, and what is left per atom.
+
+  fitted      a molecule whose status is 0 and that has at least ``TLS_MIN_ATOMS`` = 5 rows (the design matrix of any
+              four points has rank <= 18); rows of other molecules get the neutral values ``u_tls`` / ``params`` /
+              ``eig`` NaN, ``resid`` 0, ``rank`` 0, ``rfac`` 0.
+  geometry    ``c``: the fp64 mean of ``x`` over the molecule's atoms, summed in atom order; ``r_i = x_i - c``;
+              ``rho = sqrt(mean |r_i|^2)``, summed in atom order.  ``rho == 0``: not fitted, neutral rows.
+  model       ``U(r) = T + A L A^T + A S + S^T A^T`` with ``A(r) = [[0, z, -y], [-z, 0, x], [y, -x, 0]]`` (``u = t +
+              lambda x r``), ``T`` and ``L`` symmetric, ``S = <lambda t^T>`` a general 3x3 matrix with ``tr S = 0`` (the
+              trace cannot be determined: ``A + A^T = 0``).  20 parameters: T (6) and L (6) in the order 11, 22, 33,
+              23, 13, 12 (``u_cif``'s), then S (8) in the order 11, 22, 12, 13, 21, 23, 31, 32 with ``S33 = -(S11 +
+              S22)``.  The fit is done in scaled units ``r / rho``, ``L rho^2``, ``S rho``: all columns are O(1).
+  objective   minimise ``sum_i |Sym(U_i) - U(r_i)|_F^2``; ``Sym(U_i)`` in fp64 from the fp32 entries.  Six observations
+              per atom in the order of T's parameters, the off-diagonal ones weighted sqrt(2): the row of ``J_i`` for the
+              observation (p, q) holds ``w_pq dU_pq / dparam`` (``tls_design``).
+  solve       ``N = J^T J`` (20 x 20) and ``b = J^T y``, fp64, summed over the atoms in atom order.  The eigenvalues of
+              ``N`` by cyclic Jacobi (``jacobi_eigh``): a sweep is the 19 rounds of the round-robin ordering, ten
+              disjoint rotations a round, all of a round taken from the matrix as the round found it.  Before every
+              sweep: done when ``sum_{i != j} N_ij^2 <= TLS_JACOBI_TOL^2 sum_i N_ii^2`` with ``TLS_JACOBI_TOL`` = 1e-15;
+              never more than ``TLS_MAX_SWEEPS`` = 30 sweeps.  The eigenvalues ``l_k > TLS_RANK_EPS l_max``
+              (``TLS_RANK_EPS`` = 1e-10) are kept, ``rank`` is their number and
+              ``p = V_kept diag(1 / l) V_kept^T b``: the minimum-norm solution in the scaled parameters.  A rank below
+              20 is no error: a planar or a linear molecule has one.  The fitted ``U(r_i)`` and the residuals are
+              unique all the same; T, L and S are then the minimum-norm representative.  Sweeps used up: ``rank = -1``
+              and every other output NaN.
+  molecule    ``T``, ``L``, ``S`` about ``c`` (unscaled: ``L / rho^2``, ``S / rho``); ``origin = c``, relative to the
+              root atom as ``x`` is; ``rfac = sqrt(sum |resid_i|^2 / sum |Sym U_i|_F^2)`` (0 if the denominator is);
+              the principal values of ``T`` and of ``L`` ascending, by the same Jacobi routine at n = 3.
+  row         ``u_tls = U(r_i)`` and ``resid = |Sym U_i - u_tls|_F``.  fp64 throughout, one rounding to fp32 on store.
+  crystal     fitted molecules (``rank != 0``, counted at their roots), those of them with ``rank < 20``, those whose
+              smallest principal value of ``T`` or of ``L`` is negative, and over the rows of the fitted molecules the
+              sum of ``resid^2`` as stored, the sum of ``|Sym U|_F^2`` and the largest ``resid`` (a NaN is kept).
 """
 from __future__ import annotations
 
@@ -209,3 +243,198 @@ def molecules_host(z, edge_index, cart_dist, cart_dir, atom_row, ptr=None, tol: 
                      (st & MOLECULE_OPEN > 0).sum(), sz.max() if len(r) else 0)
     return {"label": label, "x": x, "mol": mol, "size": size, "status": status, "crystal_counts": counts,
             "sweeps": sweeps}
+
+
+TLS_MIN_ATOMS = 5              # four points never determine the model: their design matrix has rank <= 18
+TLS_PARAMS = 20                # T (6), L (6), S (8: the trace is fixed at 0)
+TLS_RANK_EPS = 1e-10           # eigenvalues of the normal matrix above this fraction of the largest are kept
+TLS_JACOBI_TOL = 1e-15         # done when |off-diagonal|_F <= this * |diagonal|_F, looked at before every sweep
+TLS_MAX_SWEEPS = 30            # the hard bound; the test molecules take 6 to 11
+TLS_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))                  # 11 22 33 23 13 12: T, L and the observations
+TLS_S_ENTRIES = ((0, 0), (1, 1), (0, 1), (0, 2), (1, 0), (1, 2), (2, 0), (2, 1))   # S's parameters; S33 = -(S11 + S22)
+
+
+def tls_cross(r) -> np.ndarray:
+    """``A(r)`` [n,3,3] for ``r`` [n,3]: ``A w = w x r``, so a libration ``lambda`` displaces the atom by ``A lambda``."""
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    A = np.zeros((len(r), 3, 3))
+    A[:, 0, 1], A[:, 0, 2], A[:, 1, 2] = r[:, 2], -r[:, 1], r[:, 0]
+    return A - A.transpose(0, 2, 1)
+
+
+def tls_model(r, T, L, S) -> np.ndarray:
+    """``U(r) = T + A L A^T + A S + S^T A^T`` [n,3,3] in fp64."""
+    A = tls_cross(r)
+    AS = A @ S
+    return T + A @ L @ A.transpose(0, 2, 1) + AS + AS.transpose(0, 2, 1)
+
+
+def tls_design(r) -> np.ndarray:
+    """``J`` [n,6,20] for (scaled) positions ``r`` [n,3]: row o is the observation ``TLS_PAIRS[o]``, weighted sqrt(2) off
+    the diagonal; the columns are T, L and S in the module docstring's order."""
+    A = tls_cross(r)
+    n = len(A)
+    w = np.array([1.0, 1.0, 1.0] + [np.sqrt(2.0)] * 3)
+    cols = []
+    for m, k in TLS_PAIRS:                                                     # T: the observation itself
+        E = np.zeros((3, 3))
+        E[m, k] = E[k, m] = 1.0
+        cols.append(np.broadcast_to(E, (n, 3, 3)))
+    for m, k in TLS_PAIRS:                                                     # L: A E A^T
+        E = np.zeros((3, 3))
+        E[m, k] = E[k, m] = 1.0
+        cols.append(A @ E @ A.transpose(0, 2, 1))
+    for m, k in TLS_S_ENTRIES:                                                 # S: A E + (A E)^T, traceless
+        E = np.zeros((3, 3))
+        E[m, k] = 1.0
+        if m == k:
+            E[2, 2] = -1.0
+        AE = A @ E
+        cols.append(AE + AE.transpose(0, 2, 1))
+    J = np.empty((n, 6, TLS_PARAMS))
+    for o, (p, q) in enumerate(TLS_PAIRS):
+        for a, Ua in enumerate(cols):
+            J[:, o, a] = w[o] * Ua[:, p, q]
+    return J
+
+
+def jacobi_eigh(N, tol: float = TLS_JACOBI_TOL, max_sweeps: int = TLS_MAX_SWEEPS):
+    """Eigenvalues and eigenvectors of the symmetric ``N`` [n,n] by cyclic Jacobi in the round-robin ordering, as the
+    kernel runs it: ``(w [n] unsorted, V [n,n] with N V = V diag(w), sweeps)``; ``w`` is ``None`` when ``max_sweeps``
+    sweeps did not reach ``|off-diagonal|_F <= tol |diagonal|_F``.  An odd n plays with a bye.  All rotations of a round are
+    taken from the matrix as the round found it and applied together: ``N' = G^T N G``."""
+    A = np.array(N, dtype=np.float64)
+    n = A.shape[0]
+    V = np.eye(n)
+    even = n + (n & 1)
+    m = even - 1
+    idx = np.arange(n)
+    for sweep in range(max_sweeps + 1):
+        d = np.diag(A)
+        off = A - np.diag(d)
+        if (off * off).sum() <= tol * tol * (d * d).sum():
+            return d.copy(), V, sweep
+        if sweep == max_sweeps:
+            break
+        for r in range(m):
+            partner = np.where(idx == r, m, np.where(idx == m, r, (2 * r - idx) % m))
+            partner = np.where(partner >= n, idx, partner)                    # the bye
+            p, q = np.minimum(idx, partner), np.maximum(idx, partner)
+            app, aqq, apq = A[p, p], A[q, q], A[p, q]
+            turn = (p != q) & (apq != 0.0)
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                theta = (aqq - app) / (2.0 * np.where(turn, apq, 1.0))
+                t = np.where(theta < 0.0, -1.0, 1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+            c = np.where(turn, 1.0 / np.sqrt(t * t + 1.0), 1.0)
+            s = np.where(turn, t * c, 0.0)
+            s = np.where(idx == p, -s, s)                                     # column j of N G: c N_j + s_j N_j'
+            B = A * c[None, :] + A[:, partner] * s[None, :]
+            A = B * c[:, None] + B[partner, :] * s[:, None]
+            A[idx[turn], partner[turn]] = 0.0                                 # the entry the rotation annihilates
+            V = V * c[None, :] + V[:, partner] * s[None, :]
+    return None, V, max_sweeps
+
+
+def _in_order(a) -> np.ndarray:
+    """The sum over dim 0, one addition after the other in index order."""
+    return np.cumsum(a, axis=0)[-1]
+
+
+def tls_solve_host(x, u) -> dict:
+    """The TLS fit of ONE molecule whatever its size: ``x`` [n,3] fp64 and ``u`` [n,3,3] in atom order.  A dict with
+    ``T``, ``L``, ``S`` [3,3], ``origin`` [3], ``rank``, ``eigenvalues`` [20] (of the normal matrix, ascending, relative
+    to the largest), ``sweeps``, ``u_tls`` [n,3,3], ``resid`` [n], ``rfac``, ``T_principal`` / ``L_principal`` [3]
+    ascending, ``sym2`` (the sum of ``|Sym U_i|_F^2``) -- fp64 all.  ``rank`` 0: ``rho == 0``; -1: the sweep bound."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    U = np.asarray(u).astype(np.float64).reshape(-1, 3, 3)
+    sym = 0.5 * (U + U.transpose(0, 2, 1))
+    n = len(x)
+    nan3 = np.full((3, 3), np.nan)
+    out = {"T": nan3, "L": nan3, "S": nan3, "origin": np.full(3, np.nan), "rank": 0, "eigenvalues": np.zeros(TLS_PARAMS),
+           "sweeps": 0, "u_tls": np.full((n, 3, 3), np.nan), "resid": np.zeros(n), "rfac": 0.0,
+           "T_principal": np.full(3, np.nan), "L_principal": np.full(3, np.nan), "sym2": 0.0}
+    c = _in_order(x) / n
+    r = x - c
+    rho = np.sqrt(_in_order((r * r).sum(1)) / n)
+    if not rho > 0.0:
+        return out
+    w = np.array([1.0, 1.0, 1.0] + [np.sqrt(2.0)] * 3)
+    J = tls_design(r / rho)
+    y = np.stack([w[o] * sym[:, p, q] for o, (p, q) in enumerate(TLS_PAIRS)], axis=1)
+    N = _in_order(np.einsum("ioa,iob->iab", J, J))
+    b = _in_order(np.einsum("ioa,io->ia", J, y))
+    out["sym2"] = float(_in_order((y * y).sum(1)))
+    lam, V, out["sweeps"] = jacobi_eigh(N)
+    if lam is None:
+        out.update(rank=-1, resid=np.full(n, np.nan), rfac=np.nan)
+        return out
+    top = lam.max()
+    keep = lam > TLS_RANK_EPS * top
+    out["rank"], out["eigenvalues"] = int(keep.sum()), np.sort(lam) / top
+    coef = np.where(keep, (V.T @ b) / np.where(keep, lam, 1.0), 0.0)
+    p = V @ coef
+
+    def full(v):
+        return np.array([[v[0], v[5], v[4]], [v[5], v[1], v[3]], [v[4], v[3], v[2]]])
+    T, L = full(p[0:6]), full(p[6:12]) / (rho * rho)
+    S = np.zeros((3, 3))
+    for (a, k), v in zip(TLS_S_ENTRIES, p[12:20]):
+        S[a, k] = v
+    S[2, 2] = -(S[0, 0] + S[1, 1])
+    S = S / rho
+    fit = tls_model(r, T, L, S)
+    d = sym - fit
+    resid = np.sqrt((d * d).sum((1, 2)))
+    out.update(T=T, L=L, S=S, origin=c, u_tls=fit, resid=resid,
+               rfac=float(np.sqrt(_in_order(resid * resid) / out["sym2"])) if out["sym2"] > 0.0 else 0.0)
+    for key, mat in (("T_principal", T), ("L_principal", L)):
+        vals, _, _ = jacobi_eigh(mat)
+        out[key] = np.sort(vals) if vals is not None else np.full(3, np.nan)
+    return out
+
+
+def tls_fit_host(u, label, x, atom_row, status, size, ptr=None) -> dict:
+    """The TLS rule of the module docstring in plain numpy, on what ``molecules_host`` (or ``metrics.molecules``) gives:
+    ``u`` [M,3,3] fp32; ``label`` [N] and ``x`` [N,3] per atom; ``atom_row`` [N]; ``status`` and ``size`` [M] per row;
+    ``ptr`` [B+1] (``None``: one crystal).  A dict with, per row and rounded once to fp32, ``u_tls`` [M,3,3], ``resid`` [M],
+    ``params`` [M,24] (T6, L6, S9 row-major, origin3), ``eig`` [M,6] (the principal values of T, then of L) and ``rfac``
+    [M]; ``rank`` [M] int32; ``crystal_stats`` [B,6] fp64; and ``molecules``: ``{root atom: tls_solve_host's dict}`` of
+    the molecules that were fitted."""
+    u = np.asarray(u, dtype=np.float32).reshape(-1, 3, 3)
+    label = np.asarray(label, dtype=np.int64).reshape(-1)
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+    atom_row = np.asarray(atom_row, dtype=np.int64).reshape(-1)
+    status, size = np.asarray(status).reshape(-1), np.asarray(size).reshape(-1)
+    N, M = len(label), len(u)
+    ptr = np.asarray([0, N] if ptr is None else ptr, dtype=np.int64).reshape(-1)
+    B = len(ptr) - 1
+    u_tls = np.full((M, 3, 3), np.nan, dtype=np.float32)
+    params = np.full((M, 24), np.nan, dtype=np.float32)
+    eig = np.full((M, 6), np.nan, dtype=np.float32)
+    resid, rfac = np.zeros(M, dtype=np.float32), np.zeros(M, dtype=np.float32)
+    rank = np.zeros(M, dtype=np.int32)
+    stats = np.zeros((B, 6), dtype=np.float64)
+    fitted = {}
+    pick = [0, 4, 8, 5, 2, 1]                                                 # 11 22 33 23 13 12 of a row-major 3x3
+    for root in np.nonzero(label == np.arange(N))[0]:
+        mr = atom_row[root]
+        if status[mr] != 0 or size[mr] < TLS_MIN_ATOMS:
+            continue
+        atoms = np.nonzero(label == root)[0]
+        rows = atom_row[atoms]
+        fit = tls_solve_host(x[atoms], u[rows])
+        if fit["rank"] == 0:
+            continue
+        fitted[int(root)] = fit
+        u_tls[rows], resid[rows] = fit["u_tls"], fit["resid"]
+        params[rows] = np.concatenate([fit["T"].reshape(-1)[pick], fit["L"].reshape(-1)[pick], fit["S"].reshape(-1),
+                                       fit["origin"]])
+        eig[rows] = np.concatenate([fit["T_principal"], fit["L_principal"]])
+        rank[rows], rfac[rows] = fit["rank"], fit["rfac"]
+        g = int(np.searchsorted(ptr, root, side="right") - 1)
+        low = min(fit["T_principal"][0], fit["L_principal"][0])
+        stored = resid[rows].astype(np.float64)
+        stats[g, :5] += (1, fit["rank"] < TLS_PARAMS, low < 0.0, (stored * stored).sum(), fit["sym2"])
+        stats[g, 5] = np.nan if np.isnan(stored).any() or np.isnan(stats[g, 5]) else max(stats[g, 5], stored.max())
+    return {"u_tls": u_tls, "resid": resid, "params": params, "eig": eig, "rank": rank, "rfac": rfac,
+            "crystal_stats": stats, "molecules": fitted}

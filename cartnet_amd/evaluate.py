@@ -15,8 +15,8 @@ import pickle
 import torch
 
 from .metrics import (adp_eval, bond_test, compute_3D_IoU, edge_row_ptr, get_similarity_index, molecule_test, molecules,
-                      rotate_rows, split_rows, target_row_ptr, to_host)
-from .predict import frame_stage
+                      rotate_rows, split_rows, target_row_ptr, tls_fit as tls_fit_call, to_host)
+from .predict import TLS_KEYS, frame_stage, tls_entries
 from .shard import random_rotations
 
 # the keys of the two pickles in the order the reference's loops create them (a Monte-Carlo round stores no temperature)
@@ -25,6 +25,9 @@ MONTECARLO_KEYS = ("pred", "true", "cell", "refcode", "pos", "atoms", "mae", "io
 # what --inference --rigid_molecule adds to its pickle: the molecules, then the test of the prediction and of the truth
 MOLECULE_KEYS = ("mol", "mol_size", "mol_status", "mol_pairs", "mol_delta_max", "mol_over", "mol_pairs_true",
                  "mol_delta_max_true", "mol_over_true")
+# what --inference --tls_fit adds on top of that: predict.TLS_KEYS but the per-crystal figures, for the prediction and,
+# with the suffix _true, for the truth
+TLS_ROW_KEYS = tuple(k for k in TLS_KEYS if k != "tls_stats")
 
 
 def summary(iou: torch.Tensor, mae: torch.Tensor, sim: torch.Tensor) -> dict:
@@ -60,7 +63,7 @@ def batch_entries(out: dict, batch, row_ptr, per_row: dict, with_pos: bool) -> N
 
 
 def inference(model, loader, device, output_path: str, rotations: int = 1, seed: int = 0, rigid_bond=None,
-              rigid_molecule=None) -> dict:
+              rigid_molecule=None, tls_fit=None) -> dict:
     """main.py:21-60 at any batch size: eval mode, per test batch one forward and one ``adp_eval`` -- the prediction, the
     target and the per-atom IoU / MAE / similarity index -- and everything pickled to ``output_path`` with one list entry
     per crystal (the reference's test loader has batch size 1, loader/loader.py:121).  The crystals carry no refcode /
@@ -75,7 +78,14 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
     pickle then also has ``mol``, ``mol_size`` and ``mol_status`` and, per test, ``mol_pairs`` / ``mol_delta_max`` /
     ``mol_over`` and the same with the suffix ``_true`` (one value per row), the result ``molecules``,
     ``molecules_tested``, ``rigid_molecule_pairs`` and ``rigid_molecule_mean`` / ``_max`` / ``_over`` and those three with
-    the suffix ``_true`` (over the directed pairs of the pass, 0 without pairs)."""
+    the suffix ``_true`` (over the directed pairs of the pass, 0 without pairs).  ``tls_fit`` = ``True`` (with
+    ``rigid_molecule`` only; otherwise ``ValueError``): ``metrics.tls_fit`` on the prediction and on the truth, on the same
+    molecules; the pickle then also has the per-row keys of ``predict.TLS_KEYS`` (``tls_u``, ``tls_resid``, ``tls_T``, ...)
+    and the same with the suffix ``_true``, the result ``tls_molecules``, ``tls_rank_deficient``, ``tls_nonphysical``,
+    ``tls_r`` (over all fitted rows of the pass) and ``tls_resid_max``, the last four also with the suffix ``_true``: the
+    truth's ``tls_r_true`` is the baseline the prediction's is to be compared with."""
+    if tls_fit and rigid_molecule is None:
+        raise ValueError("tls_fit fits the molecules of rigid_molecule: it needs that keyword")
     model.eval()
     out = {k: [] for k in INFERENCE_KEYS}
     gen = None
@@ -92,6 +102,11 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
         mol_counts = torch.zeros(5, dtype=torch.float64, device=device)
         mol_sums = torch.zeros((2, 4), dtype=torch.float64, device=device)
         mol_max = torch.zeros(2, dtype=torch.float64, device=device)
+    tls_sums = tls_max = None                             # the same for the TLS fit's crystal_stats
+    if tls_fit:
+        out.update({k + suffix: [] for suffix in ("", "_true") for k in TLS_ROW_KEYS})
+        tls_sums = torch.zeros((2, 5), dtype=torch.float64, device=device)
+        tls_max = torch.zeros(2, dtype=torch.float64, device=device)
     with torch.no_grad():
         for batch in loader:
             if batch is None:
@@ -116,6 +131,11 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
                                   "mol_over" + suffix: mt.over})
                     mol_sums[k] += mt.crystal_stats.sum(0)
                     mol_max[k] = torch.maximum(mol_max[k], mt.crystal_stats[:, 2].max())
+                    if tls_fit:
+                        entries = tls_entries(tls_fit_call(u, batch, row_ptr, mo))
+                        extra.update({key + suffix: entries[key] for key in TLS_ROW_KEYS})
+                        tls_sums[k] += entries["tls_stats"][:, :5].sum(0)
+                        tls_max[k] = torch.maximum(tls_max[k], entries["tls_stats"][:, 5].max())
             res = adp_eval(pred, true, row_ptr, None, volume=False)
             batch_entries(out, batch, row_ptr, {"pred": pred, "true": true, "mae": res.abs_err, "iou": res.iou,
                                                 "similarity_index": res.similarity_index, **extra}, with_pos=True)
@@ -136,6 +156,12 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
         for suffix, (n_pairs, s, _, n_over), hi in zip(("", "_true"), sums, highest):
             result.update({"rigid_molecule_mean" + suffix: s / n_pairs if n_pairs else 0.0,
                            "rigid_molecule_max" + suffix: hi, "rigid_molecule_over" + suffix: int(n_over)})
+    if tls_fit:
+        sums, highest = tls_sums.tolist(), tls_max.tolist()
+        result.update(tls_molecules=int(sums[0][0]))
+        for suffix, (_, deficient, negative, r2, s2), hi in zip(("", "_true"), sums, highest):
+            result.update({"tls_rank_deficient" + suffix: int(deficient), "tls_nonphysical" + suffix: int(negative),
+                           "tls_r" + suffix: (r2 / s2) ** 0.5 if s2 > 0 else 0.0, "tls_resid_max" + suffix: hi})
     return result
 
 

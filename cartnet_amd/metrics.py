@@ -544,6 +544,63 @@ def molecule_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Mole
     return MoleculeTest(pairs, delta_sum, delta_max, worst, over, stats)
 
 
+class TlsFit(NamedTuple):
+    """What ``tls_fit`` returns, all on the device, per row: ``u_tls`` [M,3,3] fp32, the ADP the fitted rigid body gives
+    the row's atom; ``resid`` [M] fp32, ``|Sym U - u_tls|_F``; and the figures of the row's molecule, repeated on each of
+    its rows: ``params`` [M,24] fp32 (T as 11 22 33 23 13 12, L the same, S row-major, the origin relative to the
+    molecule's root atom), ``eig`` [M,6] fp32 (the principal values of T, then of L, ascending), ``rank`` [M] int32 (20: all
+    parameters determined; less: the minimum-norm representative; -1: the iteration's sweeps ran out) and ``rfac`` [M]
+    fp32.  Rows of unfitted molecules hold NaN, 0, NaN, NaN, 0, 0.  ``crystal_stats`` [B,6] fp64: fitted molecules, those
+    with ``rank < 20``, those with a negative principal value of T or L, the sum of ``resid^2``, the sum of
+    ``|Sym U|_F^2`` over the fitted rows and the largest ``resid``."""
+    u_tls: torch.Tensor
+    resid: torch.Tensor
+    params: torch.Tensor
+    eig: torch.Tensor
+    rank: torch.Tensor
+    rfac: torch.Tensor
+    crystal_stats: torch.Tensor
+
+
+def tls_fit(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Molecules) -> TlsFit:
+    """The TLS fit of the ADPs ``u`` [M,3,3] on the ``molecules`` of ``batch`` (``molecules(batch, row_ptr)``): one call of
+    ``cartnet_adp_tls_fit``.  Every molecule with status 0 and five or more atoms gets the rigid-body tensors T, L and S
+    that explain its ADPs best (Schomaker & Trueblood 1968; the rule: ``cartnet_amd.bonds``).  ``batch`` gives
+    ``non_H_mask`` and ``ptr``; nothing is read back."""
+    _check_fp32("u", u)
+    u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    atom_ptr, B_atoms = _atom_ptr(batch, "tls_fit", dev)
+    mo = molecules
+    N = int(mo.label.shape[0])
+    if not (B_atoms == B and tuple(mo.x.shape) == (N, 3) and mo.x.dtype == torch.float64 and mo.label.dtype == torch.int64
+            and all(t.dtype == torch.int32 and tuple(t.shape) == (M,) for t in (mo.status, mo.size))
+            and all(t.device == dev for t in (mo.label, mo.x, mo.status, mo.size))):
+        raise ValueError(f"molecules does not belong to this batch and u ({B} crystals, {M} rows)")
+    mask = _batch_field(batch, "non_H_mask")
+    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
+        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
+    if mask is None and M != N:
+        raise ValueError(f"u holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    u_tls = torch.empty((M, 3, 3), dtype=torch.float32, device=dev)
+    resid = torch.empty(M, dtype=torch.float32, device=dev)
+    params = torch.empty((M, 24), dtype=torch.float32, device=dev)
+    eig = torch.empty((M, 6), dtype=torch.float32, device=dev)
+    rank = torch.empty(M, dtype=torch.int32, device=dev)
+    rfac = torch.empty(M, dtype=torch.float32, device=dev)
+    if M == 0 or N == 0:                         # the entry point launches nothing
+        return TlsFit(u_tls, resid, params, eig, rank, rfac, torch.zeros((B, 6), dtype=torch.float64, device=dev))
+    atom_row = _atom_rows(mask, N, dev)
+    label, x, status, size = (t.contiguous() for t in (mo.label, mo.x, mo.status, mo.size))
+    stats = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _l.check(_l.load().cartnet_adp_tls_fit(
+            u.data_ptr(), label.data_ptr(), x.data_ptr(), atom_row.data_ptr(), atom_ptr.data_ptr(), row_ptr.data_ptr(),
+            status.data_ptr(), size.data_ptr(), B, N, M, u_tls.data_ptr(), resid.data_ptr(), params.data_ptr(),
+            eig.data_ptr(), rank.data_ptr(), rfac.data_ptr(), stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_tls_fit")
+    return TlsFit(u_tls, resid, params, eig, rank, rfac, stats)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Temperature series (csrc/series_ops.hip): the exported ADPs of one batch predicted at T temperatures, as a least-squares
 # line per row and component -- how fast the ellipsoids grow, and whether they grow at all.

@@ -16,6 +16,9 @@ entry per crystal and temperature, and the copy also brings a least-squares line
 With ``rigid_molecule`` the copy also brings the molecules of every crystal -- the components of its bond graph, found on
 the GPU, with every atom's unwrapped position -- and the rigid-body test of the exported ADPs over all pairs of atoms of a
 molecule (``metrics.molecules``, ``metrics.molecule_test``, csrc/molecule_ops.hip).
+With ``tls_fit`` on top of that it brings the TLS fit of every molecule of five or more atoms: the rigid-body tensors T, L
+and S that explain the molecule's exported ADPs best, the ADP that rigid body gives every atom and what is left over
+(``metrics.tls_fit``, csrc/tls_ops.hip).
 Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in memory),
 ``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the forward in K
 frames that this pass and ``evaluate.inference`` share.
@@ -29,7 +32,7 @@ import torch
 
 from .metrics import (adp_export, bond_test, check_export_status, check_temperatures, edge_row_ptr, frame_mean,
                       molecule_test, molecules as find_molecules, riding_h as riding_h_call, rotate_rows, split_rows,
-                      target_row_ptr, temp_series, to_host)
+                      target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
@@ -40,6 +43,8 @@ H_KEYS = ("u_iso", "h_parent", "h_count", "h_mult", "h_stats")                  
 H_SYM_KEYS = ("u_iso_asym", "h_parent_asym")                                              # ... and a CifSymmetry
 MOL_KEYS = ("mol", "mol_size", "mol_status", "mol_pos", "mol_pairs", "mol_delta_mean", "mol_delta_max", "mol_worst",
             "mol_over", "mol_stats")                                                      # with rigid_molecule only
+TLS_KEYS = ("tls_u", "tls_resid", "tls_T", "tls_L", "tls_S", "tls_origin", "tls_T_principal", "tls_L_principal",
+            "tls_rank", "tls_r", "tls_stats")                                            # with tls_fit only
 SERIES_KEYS = ("t_slope", "t_intercept", "t_ueq_slope", "t_ueq_intercept", "t_resid", "t_drops", "t_stats")
 # with two or more temperatures the result has one more key, "series": a dict of lists, one entry per input crystal, with
 # "name", "temps" and SERIES_KEYS
@@ -223,6 +228,20 @@ def molecule_entries(mo, mt, batch) -> dict:
             "mol_stats": torch.cat([mo.crystal_counts, mt.crystal_stats], dim=1)}
 
 
+_SYM6 = (0, 5, 4, 5, 1, 3, 4, 3, 2)               # a row-major symmetric 3x3 from its 11 22 33 23 13 12
+
+
+def tls_entries(tf) -> dict:
+    """The keys of ``TLS_KEYS`` from a ``metrics.TlsFit``, on the device: ``params`` cut into ``tls_T`` / ``tls_L`` /
+    ``tls_S`` [M,3,3] and ``tls_origin`` [M,3], ``eig`` into the two triples of principal values.  Static-shape device ops:
+    nothing is read back."""
+    M = int(tf.params.shape[0])
+    return {"tls_u": tf.u_tls, "tls_resid": tf.resid, "tls_T": tf.params[:, 0:6][:, _SYM6].reshape(M, 3, 3),
+            "tls_L": tf.params[:, 6:12][:, _SYM6].reshape(M, 3, 3), "tls_S": tf.params[:, 12:21].reshape(M, 3, 3),
+            "tls_origin": tf.params[:, 21:24], "tls_T_principal": tf.eig[:, 0:3], "tls_L_principal": tf.eig[:, 3:6],
+            "tls_rank": tf.rank, "tls_r": tf.rfac, "tls_stats": tf.crystal_stats}
+
+
 def u_eq_of_cif(u_cif: torch.Tensor, cell: torch.Tensor) -> torch.Tensor:
     """[n] fp64: the equivalent isotropic U of ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12 on the unit reciprocal axes) in
     ``cell`` ([3,3], or [n,3,3] with one cell per row; rows = lattice vectors):
@@ -278,6 +297,8 @@ SERIES_SPLIT = {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t
 # ... and for MOL_KEYS: only "row" and "crystal" keys
 MOL_SPLIT = {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "row", "mol_pairs": "row",
              "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"}
+# ... and for TLS_KEYS
+TLS_SPLIT = {**{k: "row" for k in TLS_KEYS}, "tls_stats": "crystal"}
 
 
 def _check_pass(loader, rotations: int):
@@ -315,7 +336,8 @@ def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
             "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
 
 
-def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h, rigid_molecule=None) -> dict:
+def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h, rigid_molecule=None,
+                  tls_fit=None) -> dict:
     """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
     one ``to_host``: tensors under their key of ``SPLIT`` (``MOL_SPLIT``), and under names with a leading underscore what
     ``_host_stage`` needs to cut and check them."""
@@ -327,22 +349,23 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     if fm is not None:
         dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
     dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h,
-                         _found_molecules(batch, row_ptr, int(pred.shape[0]), rigid_molecule)))
+                         _found_molecules(batch, row_ptr, int(pred.shape[0]), rigid_molecule, tls_fit)))
     return dev
 
 
-def _found_molecules(batch, row_ptr: torch.Tensor, rows: int, rigid_molecule):
-    """``(metrics.Molecules of the batch, threshold)`` for ``rigid_molecule`` = ``(tol, threshold)``, or ``None``: found
-    once per batch (they do not depend on U), tested once per prediction of it (``_exported``)."""
+def _found_molecules(batch, row_ptr: torch.Tensor, rows: int, rigid_molecule, tls_fit=None):
+    """``(metrics.Molecules of the batch, threshold, whether they are also fitted)`` for ``rigid_molecule`` =
+    ``(tol, threshold)``, or ``None``: found once per batch (they do not depend on U), tested -- and with ``tls_fit``
+    fitted -- once per prediction of it (``_exported``)."""
     if rigid_molecule is None:
         return None
     tol, threshold = rigid_molecule
-    return find_molecules(batch, row_ptr, tol, rows=rows), threshold
+    return find_molecules(batch, row_ptr, tol, rows=rows), threshold, bool(tls_fit)
 
 
 def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, found=None) -> dict:
     """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch`` (its atomic numbers in ``x``):
-    the export and, as asked for, the rigid-bond test, the rigid-body test on the molecules ``found``
+    the export and, as asked for, the rigid-bond test, the rigid-body test (and the TLS fit) on the molecules ``found``
     (``_found_molecules``), the riding hydrogens and the site average."""
     device = batch.x.device
     B = int(batch.num_graphs)
@@ -353,8 +376,10 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
     if rigid_bond is not None:
         dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
     if found is not None:
-        mo, threshold = found
+        mo, threshold, fit = found
         dev.update(molecule_entries(mo, molecule_test(pred, batch, row_ptr, mo, threshold), batch))
+        if fit:
+            dev.update(tls_entries(tls_fit_call(pred, batch, row_ptr, mo)))
     if riding_h is not None:
         rh = riding_h_call(ex.u_eq, batch, *riding_h)
         dev.update(riding_entries(rh, batch))
@@ -371,7 +396,7 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
 
 
 def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, riding_h, kelvin: list,
-                         temps: torch.Tensor, rigid_molecule=None) -> dict:
+                         temps: torch.Tensor, rigid_molecule=None, tls_fit=None) -> dict:
     """One batch (on the device) at the T temperatures ``kelvin`` (``temps``: their model-side values, ``standardised``)
     through ONE forward of ``replicate_temperatures`` and the kernels that follow it, those once per temperature on that
     temperature's rows.  Returns what travels to the host in one ``to_host``: what does not depend on the temperature
@@ -385,7 +410,7 @@ def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, rid
     if R is not None:
         dev["frames"] = R.transpose(0, 1)
     rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
-    found = _found_molecules(batch, row_ptr, rows // rotations, rigid_molecule)   # once for the T temperatures
+    found = _found_molecules(batch, row_ptr, rows // rotations, rigid_molecule, tls_fit)   # once for the T temperatures
     per = []
     for t in range(T):
         pred, d = members[t * rows:(t + 1) * rows], {}
@@ -448,6 +473,7 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
     ueq_sites = split_rows(host.pop("_ueq_asym"), counts["site"]) if riding else None
     parents = split_rows(host.pop("_parent_asym"), counts["atom"]) if riding else None
     _split(out, {k: host.pop(k) for k in MOL_KEYS if k in host}, counts, MOL_SPLIT)
+    _split(out, {k: host.pop(k) for k in TLS_KEYS if k in host}, counts, TLS_SPLIT)
     _split(out, host, counts)
     if sym is not None:
         out["asym_labels"] += [sym.labels[i] for i in ids]
@@ -465,7 +491,7 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
 
 
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
-                 temperatures=None, rigid_molecule=None) -> Dict[str, List]:
+                 temperatures=None, rigid_molecule=None, tls_fit=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
@@ -512,8 +538,20 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     (the atom's unwrapped position relative to its molecule's lowest atom; NaN where the status is not 0), ``mol_pairs``
     [n], ``mol_delta_mean`` [n], ``mol_delta_max`` [n], ``mol_worst`` [n] (an atom index inside the crystal, -1 without
     pairs), ``mol_over`` [n] and ``mol_stats`` [9] fp64 (molecules, tested, periodic, open, largest size; directed pairs,
-    sum of ``|D|``, largest ``|D|``, pairs over the threshold).  ``None`` is the pass as it always was."""
+    sum of ``|D|``, largest ``|D|``, pairs over the threshold).  ``None`` is the pass as it always was.  ``tls_fit`` = ``True``
+    (with ``rigid_molecule`` only; otherwise ``ValueError``): one ``metrics.tls_fit`` wherever ``molecule_test`` runs, on the
+    same ``u_cart`` and the same molecules, travelling in the same copy.  The result then also has, per crystal, ``tls_u``
+    [n,3,3] (the ADP the fitted rigid body gives the atom), ``tls_resid`` [n] (``|Sym u_cart - tls_u|_F``) and, repeated on
+    every row of a molecule, ``tls_T`` / ``tls_L`` / ``tls_S`` [n,3,3] (A^2, rad^2, rad A, about ``tls_origin``),
+    ``tls_origin`` [n,3] (the centroid in the frame of ``mol_pos``), ``tls_T_principal`` / ``tls_L_principal`` [n,3]
+    ascending, ``tls_rank`` [n] (20: all parameters determined; less: the minimum-norm representative; 0: not fitted;
+    -1: no convergence) and ``tls_r`` [n] (the molecule's ``sqrt(sum resid^2 / sum |Sym U|^2)``), and ``tls_stats`` [6] fp64
+    (fitted molecules, rank-deficient ones, ones with a negative principal value, sum of ``resid^2``, sum of
+    ``|Sym U|^2`` over the fitted rows, largest ``resid``).  Rows of molecules that are not fitted (status not 0, fewer
+    than five atoms) hold NaN, ``tls_resid`` / ``tls_rank`` / ``tls_r`` 0.  ``None`` is the pass as it always was."""
     rotations = int(rotations)
+    if tls_fit and rigid_molecule is None:
+        raise ValueError("tls_fit fits the molecules of rigid_molecule: it needs that keyword")
     shard = _check_pass(loader, rotations)
     kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
     model.eval()
@@ -521,7 +559,8 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
                             + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())
                             + (H_KEYS if riding_h is not None else ())
                             + (H_SYM_KEYS if riding_h is not None and sym is not None else ())
-                            + (MOL_KEYS if rigid_molecule is not None else ())}
+                            + (MOL_KEYS if rigid_molecule is not None else ())
+                            + (TLS_KEYS if tls_fit else ())}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     if kelvin is not None:
         temps = standardised(kelvin, loader.temp_mean, loader.temp_std, device)
@@ -533,10 +572,11 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             batch.to(device)
             if kelvin is None:
                 _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h,
-                                                       rigid_molecule)), shard, sym)
+                                                       rigid_molecule, tls_fit)), shard, sym)
             else:
                 _host_stage_series(out, series, to_host(_device_stage_series(model, batch, sym, rotations, gen, rigid_bond,
-                                                                             riding_h, kelvin, temps, rigid_molecule)),
+                                                                             riding_h, kelvin, temps, rigid_molecule,
+                                                                             tls_fit)),
                                    shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
@@ -577,7 +617,8 @@ def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir:
     ``rot_spread_max`` and ``rot_spread_mean``; with the rigid-bond test ``bonds``, ``rigid_bond_mean`` / ``_max`` /
     ``_over``; with the rigid-body test ``molecules``, ``molecules_tested`` / ``_periodic`` / ``_open``,
     ``molecule_atoms_max`` and ``rigid_molecule_pairs`` / ``_mean`` / ``_max`` / ``_over`` (over the entries: with
-    temperatures every crystal counts once per temperature); with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
+    temperatures every crystal counts once per temperature); with the TLS fit ``tls_molecules``, ``tls_rank_deficient``,
+    ``tls_nonphysical``, ``tls_r`` (over all fitted rows) and ``tls_resid_max``; with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
     ``h_non_positive``.  A pass without crystals gives zeros."""
     n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
@@ -620,6 +661,12 @@ def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir:
                    molecule_atoms_max=int(ms[:, 4].max()) if n else 0, rigid_molecule_pairs=count,
                    rigid_molecule_mean=float(ms[:, 6].sum()) / count if count else 0.0,
                    rigid_molecule_max=float(ms[:, 7].max()) if n else 0.0, rigid_molecule_over=int(ms[:, 8].sum()))
+    if "tls_stats" in out:                            # the same; tls_r over all fitted rows of the pass
+        ts = stacked("tls_stats", 6)
+        r2, s2 = float(ts[:, 3].sum()), float(ts[:, 4].sum())
+        res.update(tls_molecules=int(ts[:, 0].sum()), tls_rank_deficient=int(ts[:, 1].sum()),
+                   tls_nonphysical=int(ts[:, 2].sum()), tls_r=math.sqrt(r2 / s2) if s2 > 0 else 0.0,
+                   tls_resid_max=float(ts[:, 5].max()) if n else 0.0)
     return res
 
 
@@ -627,7 +674,7 @@ def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
     return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS + H_KEYS + H_SYM_KEYS + MOL_KEYS
-            if key in result}
+            + TLS_KEYS if key in result}
 
 
 def cell_parameters(cell) -> tuple:

@@ -562,6 +562,41 @@ int cartnet_adp_molecule_test(const float* u, const int64_t* label, const double
                               void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * The TLS fit of Schomaker & Trueblood (Acta Cryst. B24 (1968) 63) per molecule of one batch: the rigid-body tensors
+ * T, L and S that explain the molecule's ADPs best, and what is left per atom.  The reference has no counterpart: its
+ * only statements about a prediction need the truth (main.py:47-49).
+ *   u [M,3,3] fp32; label, x, mol_status, mol_size: cartnet_molecules' results for the same batch; atom_row, ptr,
+ *   row_ptr as there.
+ * A molecule is fitted when its status is 0 and it has five or more atoms (cartnet_amd/bonds.py states the rule,
+ * tls_fit_host restates it).  c = the mean of x over its atoms in atom order, r_i = x_i - c, rho^2 = mean |r_i|^2 (rho == 0:
+ * not fitted).  Model U(r) = T + A L A^T + A S + S^T A^T with A(r) = [[0, z, -y], [-z, 0, x], [y, -x, 0]], T and L
+ * symmetric, tr S = 0: 20 parameters (T and L as 11 22 33 23 13 12, S as 11 22 12 13 21 23 31 32), fitted in the scaled
+ * units r / rho, L rho^2, S rho to sum_i |Sym(U_i) - U(r_i)|_F^2 through the normal matrix N = J^T J, whose eigenvalues come
+ * from a cyclic Jacobi iteration (round-robin ordering, at most 30 sweeps, done at |off-diagonal|_F <= 1e-15
+ * |diagonal|_F); eigenvalues above 1e-10 of the largest are kept and give the minimum-norm solution.  fp64 throughout,
+ * one rounding to fp32 per stored value.
+ *   u_tls [M,3,3] fp32    U(r_i) of the fit
+ *   resid [M] fp32        |Sym U_i - u_tls|_F
+ *   params [M,24] fp32    T (11 22 33 23 13 12), L (the same), S (3x3 row-major), origin c (relative to the root atom, as
+ *                         x is); the molecule's values on each of its rows
+ *   eig [M,6] fp32        the principal values of T, then of L, ascending
+ *   rank [M] int32        the eigenvalues kept (20: the molecule determines every parameter; less: T, L, S are the
+ *                         minimum-norm representative, u_tls and resid are unique all the same); -1: the sweeps ran out,
+ *                         and every other output of the molecule is NaN
+ *   rfac [M] fp32         sqrt(sum resid^2 / sum |Sym U_i|_F^2) over the molecule (0 if the denominator is)
+ * Rows of unfitted molecules get u_tls, params and eig NaN, resid 0, rank 0, rfac 0.  Per crystal (one wave each):
+ *   crystal_stats [B,6] fp64 (or NULL) = (fitted molecules -- rank != 0, counted at roots --, those with rank < 20,
+ *   those whose smallest principal value of T or L is negative, sum of resid^2 as stored, sum of |Sym U|_F^2 over the rows
+ *   of fitted molecules, largest resid with a NaN kept).
+ * Grid (B, 8): workgroup (g, s) fits the molecules of crystal g whose number is s modulo 8.  M == 0, N == 0 or B == 0:
+ * returns 0 without a launch and writes nothing.  No atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_tls_fit(const float* u, const int64_t* label, const double* x, const int64_t* atom_row,
+                        const int64_t* ptr, const int64_t* row_ptr, const int32_t* mol_status, const int32_t* mol_size,
+                        int32_t B, int64_t N, int64_t M, float* u_tls, float* resid, float* params, float* eig,
+                        int32_t* rank, float* rfac, double* crystal_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * A least-squares line per row and component through the exported ADPs of one batch over T temperatures.  The reference
  * predicts every crystal at the one temperature it is stored with (main.py:21-60); the model reads the temperature, so
  * one batch replicated T times answers how the ellipsoids grow.

@@ -26,7 +26,8 @@ multiple of its parent's predicted U_eq (``metrics.riding_h``).  ``--predict_tem
 ``--predict`` pass at a series of temperatures in one forward per batch and fits a line per atom through them
 (``metrics.temp_series``).  ``--rigid_molecule`` finds the molecules of every crystal of a ``--predict`` or ``--inference``
 pass on the GPU and tests the ADPs for rigid-body motion over all pairs of atoms of a molecule (``metrics.molecules``,
-``metrics.molecule_test``).  There is no CPU path: the model runs on an AMD GPU only.
+``metrics.molecule_test``).  ``--tls_fit`` (with ``--rigid_molecule``) fits the rigid-body tensors T, L and S of
+Schomaker & Trueblood to the ADPs of every such molecule (``metrics.tls_fit``).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -158,6 +159,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "without --predict or --inference; --montecarlo and training ignore it")
     p.add_argument("--rigid_molecule_threshold", type=float, default=RIGID_BOND_THRESHOLD,
                    help="--rigid_molecule: pairs whose amplitudes differ by more than this (A^2) are counted as over")
+    p.add_argument("--tls_fit", action="store_true",
+                   help="--rigid_molecule: also fit the TLS model of Schomaker & Trueblood to the ADPs of every molecule of "
+                        "five or more atoms (and, with --inference, to the truth as the baseline): the translation, "
+                        "libration and screw tensors of the rigid body that explains them best, the ADP that body gives "
+                        "every atom (tls_u) and what is left over (tls_resid, and tls_r per molecule).  It uses "
+                        "--rigid_molecule's molecules and --bond_tolerance, and is refused without that flag; --montecarlo "
+                        "and training ignore it")
     p.add_argument("--riding_h", action="store_true",
                    help="--predict: give every hydrogen an isotropic U by the riding model, a multiple of the predicted U_eq "
                         "of the atom it is bonded to (the nearest non-hydrogen atom within r_H + r + --bond_tolerance among "
@@ -324,9 +332,14 @@ def check_predict_args(args) -> None:
 
 
 def rigid_molecule_option(args) -> dict:
-    """``--rigid_molecule`` as the keyword of ``predict_adps`` / ``evaluate.inference``; without the flag no keyword at
-    all: the passes are called as they always were."""
-    return {"rigid_molecule": (args.bond_tolerance, args.rigid_molecule_threshold)} if args.rigid_molecule else {}
+    """``--rigid_molecule`` (and ``--tls_fit`` on top of it) as the keywords of ``predict_adps`` /
+    ``evaluate.inference``; without a flag no keyword for it at all: the passes are called as they always were."""
+    if not args.rigid_molecule:
+        return {}
+    option = {"rigid_molecule": (args.bond_tolerance, args.rigid_molecule_threshold)}
+    if args.tls_fit:
+        option["tls_fit"] = True
+    return option
 
 
 def predict(model, args) -> dict:
@@ -364,6 +377,8 @@ def main(argv=None) -> dict:
         check_predict_args(args)
     if args.rigid_molecule and not (args.predict or args.inference):
         raise SystemExit("--rigid_molecule serves --predict and --inference only")
+    if args.tls_fit and not args.rigid_molecule:
+        raise SystemExit("--tls_fit fits the molecules of --rigid_molecule: give that flag as well")
     torch.set_num_threads(args.threads)
     rank, world, local = cdist.init_from_env()
     if world > 1:

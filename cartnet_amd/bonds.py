@@ -96,6 +96,45 @@ Acta Cryst. B24 (1968) 63): how much of a molecule's ADPs is rigid-body motion, 
   crystal     fitted molecules (``rank != 0``, counted at their roots), those of them with ``rank < 20``, those whose
               smallest principal value of ``T`` or of ``L`` is negative, and over the rows of the fitted molecules the
               sum of ``resid^2`` as stored, the sum of ``|Sym U|_F^2`` and the largest ``resid`` (a NaN is kept).
+
+Anisotropic hydrogens (``metrics.aniso_h``, csrc/aniso_h_ops.hip; ``aniso_hydrogens_host`` below restates it in numpy):
+a full tensor for every hydrogen from what the three rules above give -- the decomposition of SHADE (Madsen, J. Appl.
+Cryst. 39 (2006) 757) and of ADPH (Roversi & Destro, Chem. Phys. Lett. 386 (2004) 472): rigid-body motion plus internal
+X-H motion.  Per atom ``i`` of a batch, ``u_h[i]`` [3,3] fp32 and ``source[i]`` int32:
+
+  heavy       a non-hydrogen atom with a row: ``u_h[i] = u[atom_row[i]]`` copied bit for bit, ``source = 1``; without a
+              row NaN, ``source = 0``.
+  orphan      a hydrogen with ``parent[i] < 0`` (riding's orphans; also a parent out of range or without a row): NaN,
+              ``source = 0``.
+  edge        for a hydrogen with parent ``p``: among the edges ``p -> i`` of ``i``'s segment the one with the smallest
+              ``cart_dist``, a tie going to the lowest edge index (a NaN distance is never taken) -- the edge the riding
+              rule chose.  ``v = fp64(cart_dist[e]) * fp64(cart_dir[e])`` is the vector from the parent's image to the
+              hydrogen: from the edge, never from ``pos``, so cell faces do not matter.  No such edge, or ``|v|^2`` not
+              ``> 0``: NaN, ``source = 0``.  Otherwise ``d = v / |v|``.
+  tensor      ``u_h[i] = Sym(U_p) + D_lib + U_int`` in fp64 with one rounding to fp32; the six components of the upper
+              triangle are computed and stored on both sides of the diagonal, so the stored tensor is exactly symmetric.
+  internal    ``U_int = stretch * d d^T + bend * (I - d d^T)``: ``stretch`` along the bond, ``bend`` in both directions
+              across it.  ``ANISO_H_STRETCH`` = 0.005 A^2 and ``ANISO_H_BEND`` = 0.020 A^2, independent of the
+              temperature, are this project's NOMINAL figures: of the order of the internal X-H mean-square displacements
+              that neutron studies report, written from memory of that literature and not checked against a table;
+              nothing here can verify them.  They are arguments so that a user can put in values of their choice.
+  libration   ``D_lib = U_LS(r_p + v) - U_LS(r_p)`` with ``U_LS(r) = A(r) L A(r)^T + A(r) S + S^T A(r)^T`` and ``A`` =
+              ``tls_cross``'s: how the fitted rigid-body motion of the parent's molecule grows from the parent's position
+              to the hydrogen's (``T`` cancels).  ``L``, ``S`` and the origin ``c`` are read from the parent's row of
+              ``tls_fit``'s ``params`` AS STORED in fp32, converted to fp64; ``r_p = x[p] - c`` with ``x`` the fp64
+              positions of ``molecules``.  The term exists only when TLS results are passed and
+              ``rank[atom_row[p]] > 0``: then ``source = 3`` for rank 20 and ``source = 4`` for a lower rank, where ``L``
+              and ``S`` are the minimum-norm representative -- for a planar molecule the out-of-plane part of a
+              hydrogen's libration is then the representative's, not a determined quantity.  Otherwise (no TLS passed, a
+              molecule not fitted, rank 0 and rank -1) ``D_lib = 0`` and ``source = 2``.
+  crystal     over the crystal's atoms in order, from the values as stored: the hydrogens with a tensor (``source >= 2``),
+              those of them with ``source >= 3``, the sum of their ``trace / 3`` (fp64), and those whose tensor is not
+              positive definite by Sylvester's criterion -- the three leading minors ``> 0`` in fp64 on the stored
+              values; a NaN counts as not positive.
+
+Using the parent's own tensor plus the CHANGE of the fitted motion keeps a hydrogen consistent with its parent even where
+the fit is poor; SHADE uses the fitted tensor at the hydrogen instead.  For exactly rigid rows (``U_p = U_TLS(r_p)``) the
+two coincide: ``u_h = U_TLS(r_p + v) + U_int``.
 """
 from __future__ import annotations
 
@@ -438,3 +477,95 @@ def tls_fit_host(u, label, x, atom_row, status, size, ptr=None) -> dict:
         stats[g, 5] = np.nan if np.isnan(stored).any() or np.isnan(stats[g, 5]) else max(stats[g, 5], stored.max())
     return {"u_tls": u_tls, "resid": resid, "params": params, "eig": eig, "rank": rank, "rfac": rfac,
             "crystal_stats": stats, "molecules": fitted}
+
+
+ANISO_H_STRETCH = 0.005        # A^2 along X-H: a NOMINAL figure (see the module docstring), not a checked literature value
+ANISO_H_BEND = 0.020           # A^2 across X-H, both directions alike: nominal as well
+ANISO_H_NONE, ANISO_H_COPY, ANISO_H_PARENT, ANISO_H_TLS, ANISO_H_TLS_DEFICIENT = 0, 1, 2, 3, 4     # ``source``
+
+
+def tls_libration(r, L, S) -> np.ndarray:
+    """``U_LS(r) = A L A^T + A S + S^T A^T`` [3,3] in fp64 for one position ``r`` [3]: ``tls_model`` without ``T``."""
+    A = tls_cross(r)[0]
+    AS = A @ S
+    return A @ L @ A.T + AS + AS.T
+
+
+def positive_definite(u) -> np.ndarray:
+    """Sylvester's criterion for ``u`` [n,3,3]: the three leading minors ``> 0``, in fp64; a NaN is not positive."""
+    t = np.asarray(u).astype(np.float64).reshape(-1, 9).T
+    m2 = t[0] * t[4] - t[1] * t[3]
+    m3 = (t[0] * (t[4] * t[8] - t[5] * t[7]) - t[1] * (t[3] * t[8] - t[5] * t[6])) + t[2] * (t[3] * t[7] - t[4] * t[6])
+    with np.errstate(invalid="ignore"):
+        return (t[0] > 0.0) & (m2 > 0.0) & (m3 > 0.0)
+
+
+def aniso_hydrogens_host(u, z, edge_index, cart_dist, cart_dir, atom_row, parent, x=None, params=None, rank=None,
+                         stretch: float = ANISO_H_STRETCH, bend: float = ANISO_H_BEND, ptr=None) -> dict:
+    """The anisotropic-hydrogen rule of the module docstring in plain numpy: a dict with ``u_h`` [N,3,3] fp32, ``source``
+    [N] int32 and ``crystal_stats`` [B,4] fp64 and, for whoever wants the terms apart, ``bond`` [N,3] (``v``) and ``lib``
+    [N,3,3] (``D_lib``) in fp64, NaN / 0 where there is none.  ``u`` [M,3,3] fp32; ``z``, ``edge_index``, ``cart_dist``,
+    ``cart_dir``, ``atom_row`` as for ``molecules_host``; ``parent`` [N]: ``riding_hydrogens_host``'s; ``x`` [N,3] fp64
+    (``molecules_host``), ``params`` [M,24] fp32 and ``rank`` [M] (``tls_fit_host``): all three or none; ``ptr`` [B+1]
+    (``None``: one crystal)."""
+    u = np.asarray(u, dtype=np.float32).reshape(-1, 3, 3)
+    z = np.asarray(z, dtype=np.int64).reshape(-1)
+    src, tgt = (np.asarray(a, dtype=np.int64).reshape(-1) for a in np.asarray(edge_index).reshape(2, -1))
+    dist = np.asarray(cart_dist, dtype=np.float32).reshape(-1)
+    dirs = np.asarray(cart_dir, dtype=np.float32).reshape(-1, 3)
+    atom_row = np.asarray(atom_row, dtype=np.int64).reshape(-1)
+    parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+    N, M = len(z), len(u)
+    if (x is None) != (params is None) or (x is None) != (rank is None):
+        raise ValueError("x, params and rank come together or not at all")
+    if x is not None:
+        x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+        params = np.asarray(params, dtype=np.float32).reshape(-1, 24).astype(np.float64)
+        rank = np.asarray(rank).reshape(-1)
+    ptr = np.asarray([0, N] if ptr is None else ptr, dtype=np.int64).reshape(-1)
+    has_row = (atom_row >= 0) & (atom_row < M)
+    u_h = np.full((N, 3, 3), np.nan, dtype=np.float32)
+    source = np.zeros(N, dtype=np.int32)
+    bond = np.full((N, 3), np.nan)
+    lib = np.zeros((N, 3, 3))
+    heavy = (z != 1) & has_row
+    u_h[heavy], source[heavy] = u[atom_row[heavy]], ANISO_H_COPY
+    upper = np.triu(np.ones((3, 3), dtype=bool))
+    for i in np.nonzero((z == 1) & (parent >= 0) & (parent < N))[0]:
+        p = parent[i]
+        if not has_row[p]:
+            continue
+        best, at = np.float32(np.inf), -1
+        for e in np.nonzero((tgt == i) & (src == p))[0]:                      # edge order: a tie keeps the lowest edge
+            if dist[e] < best:
+                best, at = dist[e], e
+        if at < 0:
+            continue
+        v = np.float64(dist[at]) * dirs[at].astype(np.float64)
+        n2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+        if not n2 > 0.0:
+            continue
+        d = v / np.sqrt(n2)
+        mp = atom_row[p]
+        Up = u[mp].astype(np.float64)
+        source[i] = ANISO_H_PARENT
+        if x is not None and rank[mp] > 0:
+            L = params[mp, 6:12][[0, 5, 4, 5, 1, 3, 4, 3, 2]].reshape(3, 3)
+            S = params[mp, 12:21].reshape(3, 3)
+            rp = x[p] - params[mp, 21:24]
+            lib[i] = tls_libration(rp + v, L, S) - tls_libration(rp, L, S)
+            source[i] = ANISO_H_TLS if rank[mp] == TLS_PARAMS else ANISO_H_TLS_DEFICIENT
+        dd = np.outer(d, d)
+        full = (0.5 * (Up + Up.T) + lib[i]) + (stretch * dd + bend * (np.eye(3) - dd))
+        tri = np.where(upper, full, 0.0).astype(np.float32)                  # the upper triangle, rounded once ...
+        u_h[i] = tri + np.triu(tri, 1).T                                      # ... and stored on both sides
+        bond[i] = v
+    stats = np.zeros((len(ptr) - 1, 4), dtype=np.float64)
+    stored = u_h.astype(np.float64)
+    good = positive_definite(u_h)
+    for g in range(len(ptr) - 1):
+        a = np.arange(ptr[g], ptr[g + 1])
+        a = a[source[a] >= ANISO_H_PARENT]
+        tr = ((stored[a, 0, 0] + stored[a, 1, 1]) + stored[a, 2, 2]) / 3.0
+        stats[g] = (len(a), (source[a] >= ANISO_H_TLS).sum(), tr.sum(), (~good[a]).sum())
+    return {"u_h": u_h, "source": source, "crystal_stats": stats, "bond": bond, "lib": lib}

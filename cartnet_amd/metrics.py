@@ -602,6 +602,70 @@ def tls_fit(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Molecules)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Anisotropic hydrogens (csrc/aniso_h_ops.hip): where the riding model gives a hydrogen one number, this gives it a tensor
+# -- its parent's, plus the change of the molecule's fitted rigid-body motion from the parent to the hydrogen, plus a
+# nominal internal X-H motion in the bond frame (SHADE, ADPH).  The rule: bonds.py.
+
+class AnisoH(NamedTuple):
+    """What ``aniso_h`` returns, all on the device, per atom of the batch: ``u_h`` [N,3,3] fp32, a non-hydrogen atom's own
+    row (bit for bit; NaN without a row) and a hydrogen's tensor (exactly symmetric; NaN for an orphan); ``source`` [N]
+    int32: 0 no tensor, 1 the atom's own row, 2 the parent's tensor plus the internal motion, 3 that plus the libration
+    of a fully determined TLS fit, 4 the same from a rank-deficient fit (its minimum-norm representative);
+    ``crystal_stats`` [B,4] fp64: per crystal the hydrogens with a tensor, those with ``source >= 3``, the sum of their
+    ``trace / 3`` and those whose tensor is not positive definite."""
+    u_h: torch.Tensor
+    source: torch.Tensor
+    crystal_stats: torch.Tensor
+
+
+def aniso_h(u: torch.Tensor, batch, row_ptr: torch.Tensor, riding: RidingH, molecules: Optional[Molecules] = None,
+            tls: Optional[TlsFit] = None, stretch: float = 0.005, bend: float = 0.020) -> AnisoH:
+    """A displacement tensor for every hydrogen of ``batch`` from the ADPs ``u`` [M,3,3] of the non-hydrogen atoms: one
+    call of ``cartnet_adp_aniso_h``.  ``batch``: as for ``bond_test`` (a batch of either loader, or a dict of its arrays)
+    with ``ptr`` [B+1]; ``row_ptr`` [B+1]: ``target_row_ptr``; ``riding``: ``riding_h`` of the same batch (its ``parent``
+    is read).  ``molecules`` and ``tls`` (``molecules(batch, row_ptr)`` and ``tls_fit`` on them): both or neither; with
+    them a hydrogen whose parent's molecule was fitted also gets the change of that rigid-body motion from the parent's
+    position to its own, without them every hydrogen with a parent has ``source = 2``.  ``stretch`` / ``bend`` (A^2): the
+    internal mean-square displacement along and across the X-H bond; the defaults are nominal figures
+    (``cartnet_amd.bonds``).  Nothing is read back."""
+    _check_fp32("u", u)
+    u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    atom_ptr, B_atoms = _atom_ptr(batch, "aniso_h", dev)
+    if B_atoms != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {B_atoms}")
+    z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "aniso_h", "u", True)
+    parent = riding.parent
+    if not (parent.dtype == torch.int64 and tuple(parent.shape) == (N,) and parent.device == dev):
+        raise ValueError(f"riding does not belong to this batch ({N} atoms)")
+    if (molecules is None) != (tls is None):
+        raise ValueError("molecules and tls come together or not at all")
+    x = params = rank = None
+    if tls is not None:
+        x, params, rank = molecules.x, tls.params, tls.rank
+        if not (tuple(x.shape) == (N, 3) and x.dtype == torch.float64 and tuple(params.shape) == (M, 24)
+                and params.dtype == torch.float32 and tuple(rank.shape) == (M,) and rank.dtype == torch.int32
+                and all(t.device == dev for t in (x, params, rank))):
+            raise ValueError(f"molecules and tls do not belong to this batch and u ({N} atoms, {M} rows)")
+        x, params, rank = x.contiguous(), params.contiguous(), rank.contiguous()
+    u_h = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
+    source = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:                                   # the entry point launches nothing
+        return AnisoH(u_h, source, torch.zeros((B, 4), dtype=torch.float64, device=dev))
+    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
+    parent = parent.contiguous()
+    stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _l.check(_l.load().cartnet_adp_aniso_h(
+            _l.ptr(u) if M else None, z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None,
+            _l.ptr(dirs) if E else None, atom_row.data_ptr(), seg_ptr.data_ptr(), atom_ptr.data_ptr(), parent.data_ptr(),
+            _l.ptr(x) if M else None, _l.ptr(params) if M else None, _l.ptr(rank) if M else None, float(stretch),
+            float(bend), B, N, M, E, u_h.data_ptr(), source.data_ptr(), stats.data_ptr(), _l.stream_ptr()),
+            "cartnet_adp_aniso_h")
+    return AnisoH(u_h, source, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Temperature series (csrc/series_ops.hip): the exported ADPs of one batch predicted at T temperatures, as a least-squares
 # line per row and component -- how fast the ellipsoids grow, and whether they grow at all.
 

@@ -19,6 +19,9 @@ molecule (``metrics.molecules``, ``metrics.molecule_test``, csrc/molecule_ops.hi
 With ``tls_fit`` on top of that it brings the TLS fit of every molecule of five or more atoms: the rigid-body tensors T, L
 and S that explain the molecule's exported ADPs best, the ADP that rigid body gives every atom and what is left over
 (``metrics.tls_fit``, csrc/tls_ops.hip).
+With ``aniso_h`` on top of ``riding_h`` it brings a full tensor for every hydrogen -- its parent's exported tensor, the change
+of the molecule's fitted rigid-body motion from the parent to the hydrogen where ``tls_fit`` gave one, and a nominal internal
+X-H motion (``metrics.aniso_h``, csrc/aniso_h_ops.hip) -- and both writers give such a hydrogen an anisotropic row.
 Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in memory),
 ``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the forward in K
 frames that this pass and ``evaluate.inference`` share.
@@ -30,9 +33,9 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .metrics import (adp_export, bond_test, check_export_status, check_temperatures, edge_row_ptr, frame_mean,
-                      molecule_test, molecules as find_molecules, riding_h as riding_h_call, rotate_rows, split_rows,
-                      target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
+from .metrics import (adp_export, aniso_h as aniso_h_call, bond_test, check_export_status, check_temperatures,
+                      edge_row_ptr, frame_mean, molecule_test, molecules as find_molecules, riding_h as riding_h_call,
+                      rotate_rows, split_rows, target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
 SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
@@ -45,6 +48,8 @@ MOL_KEYS = ("mol", "mol_size", "mol_status", "mol_pos", "mol_pairs", "mol_delta_
             "mol_over", "mol_stats")                                                      # with rigid_molecule only
 TLS_KEYS = ("tls_u", "tls_resid", "tls_T", "tls_L", "tls_S", "tls_origin", "tls_T_principal", "tls_L_principal",
             "tls_rank", "tls_r", "tls_stats")                                            # with tls_fit only
+AH_KEYS = ("h_u_cart", "h_u_cif", "h_u_eq", "h_source", "h_aniso_stats")               # with aniso_h only
+AH_SYM_KEYS = ("h_u_cif_asym",)                                                           # ... and a CifSymmetry
 SERIES_KEYS = ("t_slope", "t_intercept", "t_ueq_slope", "t_ueq_intercept", "t_resid", "t_drops", "t_stats")
 # with two or more temperatures the result has one more key, "series": a dict of lists, one entry per input crystal, with
 # "name", "temps" and SERIES_KEYS
@@ -242,6 +247,28 @@ def tls_entries(tf) -> dict:
             "tls_rank": tf.rank, "tls_r": tf.rfac, "tls_stats": tf.crystal_stats}
 
 
+def aniso_entries(ah, batch) -> dict:
+    """The keys of ``AH_KEYS`` from a ``metrics.AnisoH`` of ``batch``, on the device: one ``adp_export`` over ATOMS as rows
+    (``batch.ptr`` as the row offsets) brings ``u_h`` into CIF convention with its equivalent isotropic value.  Rows without
+    a tensor are NaN and stay NaN: the export's Jacobi has a fixed number of sweeps.  Nothing is read back."""
+    ex = adp_export(ah.u_h, batch.ptr.to(torch.int64), batch.cell, axes=False, stats=False, check=False)
+    return {"h_u_cart": ah.u_h, "h_u_cif": ex.u_cif, "h_u_eq": ex.u_eq, "h_source": ah.source,
+            "h_aniso_stats": ah.crystal_stats}
+
+
+def aniso_asym(asym_z, u_cif_asym, h_u_cif) -> torch.Tensor:
+    """[a,6] fp32: the tensors of one crystal from a CIF per atom of its asymmetric unit, on the host.  A non-hydrogen atom
+    gets its site's ``u_cif_asym`` (the orbit mean); hydrogen ``k`` gets expanded atom ``k``'s ``h_u_cif`` -- the first
+    ``a`` expanded atoms are the asymmetric unit under the identity, which ``riding_asym`` has verified.  A hydrogen's
+    tensor is NOT averaged over its orbit: it is the one of the image the file lists."""
+    asym_z = torch.as_tensor(asym_z).to(torch.int64)
+    heavy = asym_z != 1
+    site = (torch.cumsum(heavy, 0) - 1).clamp(min=0)
+    n = int(asym_z.shape[0])
+    own = u_cif_asym[site] if int(u_cif_asym.shape[0]) else torch.full((n, 6), float("nan"))
+    return torch.where(heavy.unsqueeze(1), own, h_u_cif[:n]).to(torch.float32)
+
+
 def u_eq_of_cif(u_cif: torch.Tensor, cell: torch.Tensor) -> torch.Tensor:
     """[n] fp64: the equivalent isotropic U of ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12 on the unit reciprocal axes) in
     ``cell`` ([3,3], or [n,3,3] with one cell per row; rows = lattice vectors):
@@ -299,6 +326,8 @@ MOL_SPLIT = {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "r
              "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"}
 # ... and for TLS_KEYS
 TLS_SPLIT = {**{k: "row" for k in TLS_KEYS}, "tls_stats": "crystal"}
+# ... and for AH_KEYS: per atom, not per row
+AH_SPLIT = {**{k: "atom" for k in AH_KEYS}, "h_aniso_stats": "crystal"}
 
 
 def _check_pass(loader, rotations: int):
@@ -337,7 +366,7 @@ def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
 
 
 def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h, rigid_molecule=None,
-                  tls_fit=None) -> dict:
+                  tls_fit=None, aniso_h=None) -> dict:
     """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
     one ``to_host``: tensors under their key of ``SPLIT`` (``MOL_SPLIT``), and under names with a leading underscore what
     ``_host_stage`` needs to cut and check them."""
@@ -349,7 +378,7 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     if fm is not None:
         dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
     dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h,
-                         _found_molecules(batch, row_ptr, int(pred.shape[0]), rigid_molecule, tls_fit)))
+                         _found_molecules(batch, row_ptr, int(pred.shape[0]), rigid_molecule, tls_fit), aniso_h))
     return dev
 
 
@@ -363,10 +392,12 @@ def _found_molecules(batch, row_ptr: torch.Tensor, rows: int, rigid_molecule, tl
     return find_molecules(batch, row_ptr, tol, rows=rows), threshold, bool(tls_fit)
 
 
-def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, found=None) -> dict:
+def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, found=None,
+              aniso_h=None) -> dict:
     """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch`` (its atomic numbers in ``x``):
     the export and, as asked for, the rigid-bond test, the rigid-body test (and the TLS fit) on the molecules ``found``
-    (``_found_molecules``), the riding hydrogens and the site average."""
+    (``_found_molecules``), the riding hydrogens (and their tensors, with the TLS fit if there is one) and the site
+    average."""
     device = batch.x.device
     B = int(batch.num_graphs)
     sel = batch._meta[:B]
@@ -375,14 +406,19 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
                stats=ex.crystal_stats, _status=ex.status)
     if rigid_bond is not None:
         dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
+    mo = tf = None
     if found is not None:
         mo, threshold, fit = found
         dev.update(molecule_entries(mo, molecule_test(pred, batch, row_ptr, mo, threshold), batch))
         if fit:
-            dev.update(tls_entries(tls_fit_call(pred, batch, row_ptr, mo)))
+            tf = tls_fit_call(pred, batch, row_ptr, mo)
+            dev.update(tls_entries(tf))
     if riding_h is not None:
         rh = riding_h_call(ex.u_eq, batch, *riding_h)
         dev.update(riding_entries(rh, batch))
+        if aniso_h is not None:
+            ah = aniso_h_call(pred, batch, row_ptr, rh, mo if tf is not None else None, tf, *aniso_h)
+            dev.update(aniso_entries(ah, batch))
     if sym is not None:
         from .symmetry import site_average
         dev["u_cif_asym"], dev["spread"] = site_average(pred, row_ptr, batch._sel, sym)
@@ -396,7 +432,7 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
 
 
 def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, riding_h, kelvin: list,
-                         temps: torch.Tensor, rigid_molecule=None, tls_fit=None) -> dict:
+                         temps: torch.Tensor, rigid_molecule=None, tls_fit=None, aniso_h=None) -> dict:
     """One batch (on the device) at the T temperatures ``kelvin`` (``temps``: their model-side values, ``standardised``)
     through ONE forward of ``replicate_temperatures`` and the kernels that follow it, those once per temperature on that
     temperature's rows.  Returns what travels to the host in one ``to_host``: what does not depend on the temperature
@@ -418,7 +454,7 @@ def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, rid
             fm = frame_mean(pred, R, row_ptr, stats=True)
             pred = fm.mean
             d.update(rot_spread=fm.spread, rot_stats=fm.crystal_spread)
-        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, found))
+        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, found, aniso_h))
         per.append(d)
         dev.update({f"{k}@{t}": v for k, v in d.items()})
     if T >= 2:
@@ -474,6 +510,7 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
     parents = split_rows(host.pop("_parent_asym"), counts["atom"]) if riding else None
     _split(out, {k: host.pop(k) for k in MOL_KEYS if k in host}, counts, MOL_SPLIT)
     _split(out, {k: host.pop(k) for k in TLS_KEYS if k in host}, counts, TLS_SPLIT)
+    _split(out, {k: host.pop(k) for k in AH_KEYS if k in host}, counts, AH_SPLIT)
     _split(out, host, counts)
     if sym is not None:
         out["asym_labels"] += [sym.labels[i] for i in ids]
@@ -487,11 +524,13 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
                                 ueq_sites[g])
             out["u_iso_asym"].append(u)
             out["h_parent_asym"].append(pa)
+            if "h_u_cif_asym" in out:
+                out["h_u_cif_asym"].append(aniso_asym(sym.z[i], out["u_cif_asym"][k], out["h_u_cif"][k]))
     return names, counts
 
 
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
-                 temperatures=None, rigid_molecule=None, tls_fit=None) -> Dict[str, List]:
+                 temperatures=None, rigid_molecule=None, tls_fit=None, aniso_h=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
     the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
@@ -548,10 +587,23 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     -1: no convergence) and ``tls_r`` [n] (the molecule's ``sqrt(sum resid^2 / sum |Sym U|^2)``), and ``tls_stats`` [6] fp64
     (fitted molecules, rank-deficient ones, ones with a negative principal value, sum of ``resid^2``, sum of
     ``|Sym U|^2`` over the fitted rows, largest ``resid``).  Rows of molecules that are not fitted (status not 0, fewer
-    than five atoms) hold NaN, ``tls_resid`` / ``tls_rank`` / ``tls_r`` 0.  ``None`` is the pass as it always was."""
+    than five atoms) hold NaN, ``tls_resid`` / ``tls_rank`` / ``tls_r`` 0.  ``None`` is the pass as it always was.
+    ``aniso_h`` = ``(stretch, bend)`` (with ``riding_h`` only; otherwise ``ValueError``): one ``metrics.aniso_h`` wherever
+    ``riding_h`` runs -- on the frame mean with rotations, once per temperature, on the rows of the expanded cell with CIF
+    input -- with the TLS fit of the same ``u_cart`` when ``tls_fit`` is on (without it every hydrogen with a parent has
+    source 2), then one ``adp_export`` over atoms as rows, travelling in the same copy.  The result then also has, per
+    crystal and per ATOM, ``h_u_cart`` [N,3,3] (a non-hydrogen atom's own row; a hydrogen's tensor: its parent's plus the
+    change of the fitted rigid-body motion from the parent to the hydrogen plus ``stretch`` along and ``bend`` across the
+    X-H bond; NaN without one), ``h_u_cif`` [N,6], ``h_u_eq`` [N], ``h_source`` [N] (0 none, 1 own row, 2 parent, 3 parent
+    and TLS, 4 parent and a rank-deficient TLS) and ``h_aniso_stats`` [4] fp64 (hydrogens with a tensor, those with source
+    >= 3, the sum of their ``trace / 3``, those not positive definite); with ``sym`` also ``h_u_cif_asym`` [a,6] per atom
+    of the asymmetric unit (``aniso_asym``: a hydrogen's is the listed image's, not an orbit mean).  ``None`` is the pass
+    as it always was."""
     rotations = int(rotations)
     if tls_fit and rigid_molecule is None:
         raise ValueError("tls_fit fits the molecules of rigid_molecule: it needs that keyword")
+    if aniso_h is not None and riding_h is None:
+        raise ValueError("aniso_h builds on the parents of riding_h: it needs that keyword")
     shard = _check_pass(loader, rotations)
     kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
     model.eval()
@@ -560,7 +612,9 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
                             + (H_KEYS if riding_h is not None else ())
                             + (H_SYM_KEYS if riding_h is not None and sym is not None else ())
                             + (MOL_KEYS if rigid_molecule is not None else ())
-                            + (TLS_KEYS if tls_fit else ())}
+                            + (TLS_KEYS if tls_fit else ())
+                            + (AH_KEYS if aniso_h is not None else ())
+                            + (AH_SYM_KEYS if aniso_h is not None and sym is not None else ())}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     if kelvin is not None:
         temps = standardised(kelvin, loader.temp_mean, loader.temp_std, device)
@@ -572,11 +626,11 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             batch.to(device)
             if kelvin is None:
                 _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h,
-                                                       rigid_molecule, tls_fit)), shard, sym)
+                                                       rigid_molecule, tls_fit, aniso_h)), shard, sym)
             else:
                 _host_stage_series(out, series, to_host(_device_stage_series(model, batch, sym, rotations, gen, rigid_bond,
                                                                              riding_h, kelvin, temps, rigid_molecule,
-                                                                             tls_fit)),
+                                                                             tls_fit, aniso_h)),
                                    shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
@@ -619,7 +673,9 @@ def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir:
     ``molecule_atoms_max`` and ``rigid_molecule_pairs`` / ``_mean`` / ``_max`` / ``_over`` (over the entries: with
     temperatures every crystal counts once per temperature); with the TLS fit ``tls_molecules``, ``tls_rank_deficient``,
     ``tls_nonphysical``, ``tls_r`` (over all fitted rows) and ``tls_resid_max``; with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
-    ``h_non_positive``.  A pass without crystals gives zeros."""
+    ``h_non_positive``; with anisotropic hydrogens ``h_aniso`` (hydrogens with a tensor), ``h_aniso_tls`` (those with a
+    libration term), ``h_aniso_ueq_mean`` (over ``h_aniso``) and ``h_aniso_non_positive``.  A pass without crystals gives
+    zeros."""
     n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
 
@@ -653,6 +709,11 @@ def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir:
         res.update(hydrogens=hydrogens, h_orphans=orphans,
                    h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,
                    h_non_positive=int(hs[:, 3].sum()))
+    if "h_aniso_stats" in out:
+        ah = stacked("h_aniso_stats", 4)
+        count = int(ah[:, 0].sum())
+        res.update(h_aniso=count, h_aniso_tls=int(ah[:, 1].sum()),
+                   h_aniso_ueq_mean=float(ah[:, 2].sum()) / count if count else 0.0, h_aniso_non_positive=int(ah[:, 3].sum()))
     if "mol_stats" in out:                            # the sums over the entries, from the fp64 per-crystal figures
         ms = stacked("mol_stats", 9)
         count = int(ms[:, 5].sum())
@@ -674,7 +735,7 @@ def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
     return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS + H_KEYS + H_SYM_KEYS + MOL_KEYS
-            + TLS_KEYS if key in result}
+            + TLS_KEYS + AH_KEYS + AH_SYM_KEYS if key in result}
 
 
 def cell_parameters(cell) -> tuple:
@@ -699,14 +760,30 @@ def _iso_columns(u_iso, z):
     return [f" {'?' if math.isnan(x) else format(x, '.6f')} {'Uani' if v != 1 else 'Uiso'}" for x, v in zip(u, z)]
 
 
-def _write(path: str, entry: dict, z, labels, frac, u, whose: str, symmetry: list, iso, type_column: bool) -> None:
+def _hydrogen_tensors(h_cif, h_eq, z) -> dict:
+    """``{atom: (U_eq, [U_11 U_22 U_33 U_23 U_13 U_12])}`` of the hydrogens of ``z`` whose tensor in ``h_cif`` [>= n,6]
+    (with ``h_eq`` [>= n]) is finite; empty for an entry without anisotropic hydrogens (``h_cif`` is ``None``)."""
+    if h_cif is None:
+        return {}
+    rows, eq = h_cif.tolist(), h_eq.tolist()
+    if len(rows) < len(z) or len(eq) < len(z):
+        raise ValueError(f"{len(rows)} hydrogen tensors for {len(z)} atoms")
+    return {i: (float(eq[i]), rows[i]) for i, v in enumerate(z)
+            if v == 1 and all(math.isfinite(x) for x in rows[i]) and math.isfinite(eq[i])}
+
+
+def _write(path: str, entry: dict, z, labels, frac, u, whose: str, symmetry: list, iso, type_column: bool,
+           h_cif=None, h_eq=None) -> None:
     """What the two writers share: the cell, the temperature, ``symmetry`` (the lines that state the setting), the atom loop
     (``labels``, ``z``, ``frac``) and the anisotropic loop of the non-hydrogen atoms (``u``: one row each, ``U_11 U_22 U_33
     U_23 U_13 U_12``).  ``iso``: the entry's isotropic values or ``None``; without them the atom loop has no further column,
-    or with ``type_column`` the type alone (``Uani``, ``.`` for a hydrogen)."""
+    or with ``type_column`` the type alone (``Uani``, ``.`` for a hydrogen).  ``h_cif`` / ``h_eq``: per atom the tensors
+    and equivalent values of an entry with anisotropic hydrogens; a hydrogen with a finite one is typed ``Uani`` with its
+    own U_eq and gets a row of the anisotropic loop, which then runs in atom order over all atoms that have a tensor."""
     heavy = [i for i, v in enumerate(z) if v != 1]
     if len(heavy) != len(u):
         raise ValueError(f"{len(u)} ADP rows for {len(heavy)} non-hydrogen atoms{whose}")
+    hydrogens = _hydrogen_tensors(h_cif, h_eq, z)
     a, b, c, al, be, ga = cell_parameters(entry["cell"])
     name = "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in str(entry["name"])) or "crystal"
     lines = [f"data_{name}",
@@ -726,12 +803,17 @@ def _write(path: str, entry: dict, z, labels, frac, u, whose: str, symmetry: lis
         tails = [f" {'Uani' if v != 1 else '.'}" for v in z]
     else:
         tails = [""] * len(z)
+    if iso is not None:
+        for i, (eq, _) in hydrogens.items():
+            tails[i] = f" {eq:.6f} Uani"
     for lab, v, f, tail in zip(labels, z, frac, tails):
         lines.append(f"{lab} {SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'} {f[0]:.6f} {f[1]:.6f} {f[2]:.6f}" + tail)
     lines += ["loop_", "_atom_site_aniso_label", "_atom_site_aniso_U_11", "_atom_site_aniso_U_22", "_atom_site_aniso_U_33",
               "_atom_site_aniso_U_23", "_atom_site_aniso_U_13", "_atom_site_aniso_U_12"]
-    for i, row in zip(heavy, u):
-        lines.append(labels[i] + " " + " ".join(f"{x:.6f}" for x in row))
+    rows = dict(zip(heavy, u))
+    rows.update({i: row for i, (_, row) in hydrogens.items()})
+    for i in sorted(rows):
+        lines.append(labels[i] + " " + " ".join(f"{x:.6f}" for x in rows[i]))
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
 
@@ -740,21 +822,28 @@ def write_cif(path: str, entry: dict) -> None:
     """One crystal as a P1 CIF: the cell, the temperature, every atom (label = element symbol + running number) and the
     anisotropic displacement parameters of the non-hydrogen atoms, ``U_11 U_22 U_33 U_23 U_13 U_12``.  An entry with
     ``u_iso`` (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv`` and ``_atom_site_adp_type`` in the atom
-    loop: ``Uani`` with U_eq for a non-hydrogen atom, ``Uiso`` with the riding value for a hydrogen, ``?`` for an orphan."""
+    loop: ``Uani`` with U_eq for a non-hydrogen atom, ``Uiso`` with the riding value for a hydrogen, ``?`` for an orphan.
+    An entry with ``h_u_cif`` (``predict_adps(aniso_h=)``) gives every hydrogen with a finite tensor the type ``Uani``, its
+    ``h_u_eq`` and a row of the anisotropic loop; an orphan stays ``?`` / ``Uiso``."""
     z = [int(v) for v in entry["z"].tolist()]
     labels = [f"{SYMBOLS[v] if 0 <= v < len(SYMBOLS) else 'X'}{i + 1}" for i, v in enumerate(z)]
     p1 = ["_symmetry_space_group_name_H-M 'P 1'", "_symmetry_Int_Tables_number 1",
           "loop_", "_symmetry_equiv_pos_as_xyz", "'x, y, z'"]
-    _write(path, entry, z, labels, entry["frac"].tolist(), entry["u_cif"].tolist(), "", p1, entry.get("u_iso"), False)
+    _write(path, entry, z, labels, entry["frac"].tolist(), entry["u_cif"].tolist(), "", p1, entry.get("u_iso"), False,
+           entry.get("h_u_cif"), entry.get("h_u_eq"))
 
 
 def write_cif_symmetric(path: str, entry: dict) -> None:
     """One crystal in the setting of the file it came from: the cell, the temperature, the symmetry operators, the
     asymmetric unit with the input's labels and coordinates, and the site-averaged anisotropic displacement parameters of
     its non-hydrogen atoms (``u_cif_asym``: ``U_11 U_22 U_33 U_23 U_13 U_12``).  An entry with ``u_iso_asym``
-    (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv``, and its hydrogens the type ``Uiso``."""
+    (``predict_adps(riding_h=)``) also gets ``_atom_site_U_iso_or_equiv``, and its hydrogens the type ``Uiso``.  An entry
+    with ``h_u_cif_asym`` (``predict_adps(aniso_h=)``) gives every hydrogen with a finite tensor the type ``Uani``, the
+    ``h_u_eq`` of the expanded atom it is (the first atoms of the expanded cell are the asymmetric unit) and a row of the
+    anisotropic loop: the tensor of the listed image, not an orbit mean."""
     z = [int(v) for v in entry["asym_z"].tolist()]
     ops = ["loop_", "_space_group_symop_id", "_space_group_symop_operation_xyz"]
     ops += [f"{k + 1} '{op}'" for k, op in enumerate(entry["symops"])]
     _write(path, entry, z, list(entry["asym_labels"]), entry["asym_frac"].tolist(), entry["u_cif_asym"].tolist(),
-           " of the asymmetric unit", ops, entry.get("u_iso_asym"), True)
+           " of the asymmetric unit", ops, entry.get("u_iso_asym"), True, entry.get("h_u_cif_asym"),
+           entry.get("h_u_eq") if "h_u_cif_asym" in entry else None)

@@ -597,6 +597,42 @@ int cartnet_adp_tls_fit(const float* u, const int64_t* label, const double* x, c
                         int32_t* rank, float* rfac, double* crystal_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Anisotropic hydrogens: a displacement tensor for every hydrogen of one batch from its parent's tensor, the change of
+ * the fitted rigid-body motion of the parent's molecule from the parent's position to the hydrogen's, and a nominal
+ * internal X-H motion in the bond frame (the decomposition of SHADE, Madsen 2006, and ADPH, Roversi & Destro 2004).  The
+ * reference has no counterpart: a hydrogen never gets a displacement parameter there (dataset/datasetADP.py:49).
+ *   u [M,3,3] fp32; z, edge_index, cart_dist, cart_dir, atom_row, seg_ptr as for cartnet_adp_bond_test; atom_ptr as for
+ *   cartnet_adp_riding_h; parent [N] int64: cartnet_adp_riding_h's; x [N,3] fp64: cartnet_molecules'; params [M,24] fp32
+ *   and rank [M] int32: cartnet_adp_tls_fit's.  x, params and rank come together or are all NULL (no TLS results).
+ * Per atom i (cartnet_amd/bonds.py states the rule, aniso_hydrogens_host restates it):
+ *   z_i != 1              with a row: u_h[i] = u[atom_row[i]] bit for bit, source 1; without one: NaN, source 0
+ *   z_i == 1              p = parent[i]; p < 0 (or out of range, or without a row): NaN, source 0.  Otherwise e = the edge
+ *                         p -> i of i's segment with the smallest cart_dist (a tie: the lowest edge; a NaN distance is never
+ *                         taken), v = fp64(cart_dist[e]) * fp64(cart_dir[e]); no such edge or |v|^2 not > 0: NaN, source 0.
+ *                         Otherwise d = v / |v| and
+ *                           u_h[i] = Sym(u[atom_row[p]]) + D_lib + stretch d d^T + bend (I - d d^T)
+ *                         with D_lib = U_LS(r_p + v) - U_LS(r_p), U_LS(r) = A L A^T + A S + S^T A^T, A(r) as for
+ *                         cartnet_adp_tls_fit, L, S and the origin c the fp32 values of params[atom_row[p]] and
+ *                         r_p = x[p] - c, when x is given and rank[atom_row[p]] > 0: source 3 for rank 20, 4 below (the
+ *                         minimum-norm representative); D_lib = 0 and source 2 otherwise.
+ *   u_h [N,3,3] fp32      fp64 arithmetic, the six components of the upper triangle rounded once each and stored on both
+ *                         sides of the diagonal: exactly symmetric
+ *   source [N] int32      0 ... 4 as above
+ * Per crystal (one wave each, atoms in order, from the values as stored):
+ *   crystal_stats [B,4] fp64 (or NULL) = (hydrogens with a tensor, those of them with source >= 3, the sum of their
+ *   trace / 3, those of them whose tensor is not positive definite: one of the three leading minors not > 0, a NaN counting
+ *   as not positive); without atoms (0, 0, 0, 0).
+ * E == 0 needs no edge arrays, M == 0 no u (no atom has a tensor then).  N == 0 or B == 0: returns 0 without a launch
+ * and writes nothing.  Edge ends and rows out of range are skipped, never dereferenced.  No atomics, no LDS: two runs
+ * give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_aniso_h(const float* u, const int64_t* z, const int64_t* edge_index, const float* cart_dist,
+                        const float* cart_dir, const int64_t* atom_row, const int64_t* seg_ptr, const int64_t* atom_ptr,
+                        const int64_t* parent, const double* x, const float* params, const int32_t* rank, double stretch,
+                        double bend, int32_t B, int64_t N, int64_t M, int64_t E, float* u_h, int32_t* source,
+                        double* crystal_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * A least-squares line per row and component through the exported ADPs of one batch over T temperatures.  The reference
  * predicts every crystal at the one temperature it is stored with (main.py:21-60); the model reads the temperature, so
  * one batch replicated T times answers how the ellipsoids grow.

@@ -27,7 +27,9 @@ multiple of its parent's predicted U_eq (``metrics.riding_h``).  ``--predict_tem
 (``metrics.temp_series``).  ``--rigid_molecule`` finds the molecules of every crystal of a ``--predict`` or ``--inference``
 pass on the GPU and tests the ADPs for rigid-body motion over all pairs of atoms of a molecule (``metrics.molecules``,
 ``metrics.molecule_test``).  ``--tls_fit`` (with ``--rigid_molecule``) fits the rigid-body tensors T, L and S of
-Schomaker & Trueblood to the ADPs of every such molecule (``metrics.tls_fit``).  There is no CPU path: the model runs on an AMD GPU only.
+Schomaker & Trueblood to the ADPs of every such molecule (``metrics.tls_fit``).  ``--aniso_h`` (with ``--riding_h``) gives
+every hydrogen a full tensor from its parent's, that rigid-body motion and a nominal internal X-H motion
+(``metrics.aniso_h``).  There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -41,7 +43,7 @@ import torch
 
 from cartnet_amd import distributed as cdist
 from cartnet_amd import evaluate
-from cartnet_amd.bonds import BOND_TOLERANCE, RIDING_FACTOR, RIDING_FACTOR_ROTATING, RIGID_BOND_THRESHOLD
+from cartnet_amd.bonds import ANISO_H_BEND, ANISO_H_STRETCH, BOND_TOLERANCE, RIDING_FACTOR, RIDING_FACTOR_ROTATING, RIGID_BOND_THRESHOLD
 from cartnet_amd.config import cfg, set_cfg
 from cartnet_amd.data import DataLoader, optimize_cell, remove_hydrogens
 from cartnet_amd.master import create_model
@@ -177,6 +179,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--riding_h_factor_rotating", type=float, default=RIDING_FACTOR_ROTATING,
                    help="--riding_h: the same for hydrogens on oxygen (hydroxyl, water) and on a carbon that carries three "
                         "or more (methyl)")
+    p.add_argument("--aniso_h", action="store_true",
+                   help="--predict --riding_h: also give every hydrogen with a parent a full displacement tensor (SHADE / "
+                        "ADPH style): its parent's predicted tensor, plus -- with --rigid_molecule --tls_fit -- the change "
+                        "of the molecule's fitted rigid-body motion from the parent to the hydrogen, plus an internal X-H "
+                        "motion of --aniso_h_stretch along and --aniso_h_bend across the bond; the CIFs then list the "
+                        "hydrogens as Uani.  Refused without --predict and without --riding_h; --tls_fit is optional")
+    p.add_argument("--aniso_h_stretch", type=float, default=ANISO_H_STRETCH,
+                   help="--aniso_h: internal mean-square displacement along X-H (A^2).  The default is a nominal figure, "
+                        "not a checked literature value: put in your own")
+    p.add_argument("--aniso_h_bend", type=float, default=ANISO_H_BEND,
+                   help="--aniso_h: the same across X-H, in both directions alike (A^2); nominal as well")
     return p
 
 
@@ -342,6 +355,11 @@ def rigid_molecule_option(args) -> dict:
     return option
 
 
+def aniso_h_option(args) -> dict:
+    """``--aniso_h`` as the keyword of ``predict_adps``; without the flag no keyword at all."""
+    return {"aniso_h": (args.aniso_h_stretch, args.aniso_h_bend)} if args.aniso_h else {}
+
+
 def predict(model, args) -> dict:
     """``--predict``: the one shard of ``--predict_input`` through ``shard_recipe`` as the test split goes through it, in
     batches of ``--eval_batch``; the pickle of ``cartnet_amd.predict.predict_adps`` and, if asked for, one CIF per
@@ -359,7 +377,7 @@ def predict(model, args) -> dict:
         rotations=cfg.rotations, seed=cfg.seed, temperatures=temps,
         rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None,
         riding_h=(args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating) if args.riding_h else None,
-        **rigid_molecule_option(args))
+        **rigid_molecule_option(args), **aniso_h_option(args))
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     if args.predict_cif_dir:
@@ -373,6 +391,10 @@ def predict(model, args) -> dict:
 def main(argv=None) -> dict:
     args = build_parser().parse_args(argv)
     fill_cfg(args)
+    if args.aniso_h and not args.predict:
+        raise SystemExit("--aniso_h serves --predict only")
+    if args.aniso_h and not args.riding_h:
+        raise SystemExit("--aniso_h builds on the parents of --riding_h: give that flag as well")
     if args.predict or args.predict_temperatures is not None:
         check_predict_args(args)
     if args.rigid_molecule and not (args.predict or args.inference):

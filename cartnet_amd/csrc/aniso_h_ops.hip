@@ -5,11 +5,11 @@
 // has no counterpart: a hydrogen never gets a displacement parameter there (dataset/datasetADP.py:49).  The rule is stated
 // in cartnet_amd/bonds.py (aniso_hydrogens_host restates it in numpy).
 //
-//   cn_aniso_h_kernel          AH_LANES lanes per atom, the layout of riding_ops.hip.  The group of a hydrogen with a parent
-//                              p strides the hydrogen's edge segment, sixteen edges a pass, and keeps per lane the running
-//                              (dist, edge) minimum over the edges p -> i; the group folds the pairs by a butterfly,
-//                              compared lexicographically (smaller dist, then the lower edge): the edge the riding rule
-//                              chose.  Lane 0 of the group then does the 3x3 arithmetic in fp64: v = dist * dir, d = v / |v|,
+//   cn_aniso_h_kernel          BG_LANES lanes per atom, the group layout of bond_graph.h.  The group of a hydrogen with a
+//                              parent p strides the hydrogen's edge segment, sixteen edges a pass, and keeps per lane the
+//                              running (dist, edge) minimum over the edges p -> i; the group folds the pairs with
+//                              bg_argmin: the edge the riding rule chose.
+//                              Lane 0 of the group then does the 3x3 arithmetic in fp64: v = dist * dir, d = v / |v|,
 //                              Sym(U_p) + [U_LS(r_p + v) - U_LS(r_p)] + stretch d d^T + bend (I - d d^T), the six
 //                              components of the upper triangle, each rounded once to fp32 and stored on both sides of the
 //                              diagonal.  A non-hydrogen atom's lane 0 copies its own row bit for bit.
@@ -18,18 +18,12 @@
 //                              positive definite), the crystal's atoms taking the place of rows in crystal_reduce.h.
 //
 // This file is compiled with -ffp-contract=off: no multiply-add is fused, so |v|^2 and the minors of the crystal kernel are
-// the numpy rule's operation for operation, and their decisions (> 0) fall alike.  No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.
+// the numpy rule's operation for operation, and their decisions (> 0) fall alike; the helpers of bond_graph.h used here
+// hold no product.  No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.
 // 64-bit offsets throughout.  No kernel uses scratch or LDS.
-#include "common.h"
-#include "crystal_reduce.h"
-
-#include <math.h>
+#include "bond_graph.h"
 
 namespace {
-
-constexpr int AH_LANES = 16;                     // lanes per atom: an atom has ~100 incoming edges at radius 5
-constexpr int AH_THREADS = 256;
-constexpr int AH_ATOMS = AH_THREADS / AH_LANES;  // atoms per workgroup
 
 // the six components 00 01 02 11 12 22 of U_LS(r) = A L A^T + A S + S^T A^T, A = [[0, z, -y], [-z, 0, x], [y, -x, 0]];
 // L symmetric as 11 22 33 23 13 12, S row-major
@@ -54,15 +48,14 @@ __device__ __forceinline__ void ah_rigid(const double r[3], const double l6[6], 
     }
 }
 
-__global__ __launch_bounds__(AH_THREADS) void cn_aniso_h_kernel(
+__global__ __launch_bounds__(BG_THREADS) void cn_aniso_h_kernel(
     const float* __restrict__ u, const int64_t* __restrict__ z, const int64_t* __restrict__ src,
     const float* __restrict__ cart_dist, const float* __restrict__ cart_dir, const int64_t* __restrict__ atom_row,
     const int64_t* __restrict__ seg_ptr, const int64_t* __restrict__ parent, const double* __restrict__ x,
     const float* __restrict__ params, const int32_t* __restrict__ rank, double stretch, double bend, int64_t N, int64_t M,
     int64_t E, float* __restrict__ u_h, int32_t* __restrict__ source) {
-  const int sub = threadIdx.x & (AH_LANES - 1);
-  const int64_t i = (int64_t)blockIdx.x * AH_ATOMS + (threadIdx.x / AH_LANES);
-  // every lane of a group takes the same branch below: a group is never split, and a shuffle reads its own group only
+  const int sub = threadIdx.x & (BG_LANES - 1);
+  const int64_t i = (int64_t)blockIdx.x * BG_ATOMS + (threadIdx.x / BG_LANES);
   bool hydrogen = false;
   int64_t p = -1, mp = -1, e0 = 0, e1 = 0;
   if (i < N) {
@@ -71,21 +64,16 @@ __global__ __launch_bounds__(AH_THREADS) void cn_aniso_h_kernel(
       p = parent[i];
       if (p < 0 || p >= N) p = -1;
       if (p >= 0) {
-        mp = atom_row[p];
-        if (mp < 0 || mp >= M) p = mp = -1;
+        mp = bg_row(atom_row, p, M);
+        if (mp < 0) p = -1;
       }
     }
   }
-  if (p >= 0) {
-    e0 = seg_ptr[i];
-    e1 = seg_ptr[i + 1];
-    e0 = e0 < 0 ? 0 : (e0 > E ? E : e0);
-    e1 = e1 < e0 ? e0 : (e1 > E ? E : e1);
-  }
+  if (p >= 0) bg_segment(seg_ptr, i, E, e0, e1);
   float best = INFINITY;
   int64_t at = E;                                                  // E: no edge yet
 #pragma unroll 1
-  for (int64_t c = e0; c < e1; c += AH_LANES) {
+  for (int64_t c = e0; c < e1; c += BG_LANES) {
     const int64_t e = c + sub;
     if (e < e1 && src[e] == p) {
       const float dist = cart_dist[e];
@@ -95,21 +83,13 @@ __global__ __launch_bounds__(AH_THREADS) void cn_aniso_h_kernel(
       }
     }
   }
-#pragma unroll
-  for (int o = AH_LANES / 2; o > 0; o >>= 1) {
-    const float d = __shfl_xor(best, o);
-    const long long a = __shfl_xor((long long)at, o);
-    if (a < E && (at == E || d < best || (d == best && a < at))) {
-      best = d;
-      at = a;
-    }
-  }
+  bg_argmin(best, at, E);
   if (i >= N || sub != 0) return;
   float* __restrict__ out = u_h + (size_t)i * 9;
   int32_t code = 0;
   if (!hydrogen) {
-    const int64_t m = atom_row[i];
-    if (m >= 0 && m < M) {
+    const int64_t m = bg_row(atom_row, i, M);
+    if (m >= 0) {
       const float* __restrict__ row = u + (size_t)m * 9;
 #pragma unroll
       for (int k = 0; k < 9; ++k) out[k] = row[k];
@@ -212,7 +192,7 @@ extern "C" int cartnet_adp_aniso_h(const float* u, const int64_t* z, const int64
   CN_CHECK(B >= 0 && N >= 0 && M >= 0 && E >= 0, "cartnet_adp_aniso_h: bad sizes (B=%d, N=%lld, M=%lld, E=%lld)", B,
            (long long)N, (long long)M, (long long)E);
   CN_CHECK(stretch == stretch && bend == bend, "cartnet_adp_aniso_h: stretch and bend must be numbers");
-  CN_CHECK(N < (1LL << 31) * AH_ATOMS, "cartnet_adp_aniso_h: too many atoms for one launch");
+  CN_CHECK(N < (1LL << 31) * BG_ATOMS, "cartnet_adp_aniso_h: too many atoms for one launch");
   if (B == 0 || N == 0) return 0;
   CN_CHECK(z && atom_row && seg_ptr && parent && u_h && source, "cartnet_adp_aniso_h: null pointer");
   CN_CHECK(M == 0 || u, "cartnet_adp_aniso_h: null pointer");
@@ -221,9 +201,9 @@ extern "C" int cartnet_adp_aniso_h(const float* u, const int64_t* z, const int64
   CN_CHECK((x && params && rank) || (!x && !params && !rank),
            "cartnet_adp_aniso_h: x, params and rank come together or not at all");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((N + AH_ATOMS - 1) / AH_ATOMS));
+  const dim3 grid((unsigned)((N + BG_ATOMS - 1) / BG_ATOMS));
   // without edges every segment is empty, without rows no hydrogen has a parent: the same launch writes the neutral values
-  hipLaunchKernelGGL(cn_aniso_h_kernel, grid, dim3(AH_THREADS), 0, st, u, z, edge_index, cart_dist, cart_dir, atom_row,
+  hipLaunchKernelGGL(cn_aniso_h_kernel, grid, dim3(BG_THREADS), 0, st, u, z, edge_index, cart_dist, cart_dir, atom_row,
                      seg_ptr, parent, x, params, rank, stretch, bend, N, M, E, u_h, source);
   CN_LAUNCH_CHECK("cartnet_adp_aniso_h");
   if (crystal_stats) {

@@ -2,10 +2,8 @@
 // Cryst. A34 (1978) 828) on predicted ADPs: Hirshfeld's postulate for ALL pairs of atoms of a molecule,
 // D_ij = r^T U_i r / r.r - r^T U_j r / r.r ~ 0 along every interatomic vector r of a body that moves rigidly.  The
 // reference has no counterpart: its only statements about a prediction need the truth (main.py:47-49).  The bond rule is
-// that of bond_ops.hip (cartnet_amd/bonds.py): a directed edge e = (j -> i) is a bond when i != j, both atomic numbers are
-// non-hydrogen and inside the radii table, both ends have a row, and cart_dist[e] <= (r[z_i] + r[z_j]) + tol in fp32 in
-// exactly that order.  An edge whose source lies outside the target's crystal is none (a well-formed batch has no such
-// edge; one workgroup never reads what another writes).
+// that of bond_graph.h (bg_bond) with the target's crystal as the admissible range of sources: an edge whose source lies
+// outside it is no bond (a well-formed batch has no such edge; one workgroup never reads what another writes).
 //
 //   cn_molecules_kernel       one workgroup per crystal, everything between two workgroup barriers, in five steps.
 //     labels   Jacobi sweeps of "take the smallest label among the sources of my incoming bonds", the lowest edge among
@@ -24,23 +22,19 @@
 //              finished labels: a scan of the crystal per atom, as the pair test below does anyway.
 //     counts   crystal_counts[g] = (molecules, tested, periodic, open, largest size) over the roots, integer sums
 //              folded through LDS in a fixed order.
-//   cn_molecule_test_kernel   MT_LANES lanes per atom: they stride the atoms of its crystal, sixteen a pass, and keep
+//   cn_molecule_test_kernel   BG_LANES lanes per atom: they stride the atoms of its crystal, sixteen a pass, and keep
 //                             those with its label.  Per pair, in fp64: r = x_i - x_j, D = r^T (S_i - S_j) r / r.r with S
 //                             the symmetric part (the difference of the fp32 entries is taken first: exact in fp64); a
-//                             pair with r.r == 0 is not counted.  The pairs of a pass are folded in ATOM order with the
-//                             ballot-and-shuffle of cn_bond_test_kernel: sequential fp64 sums, a tie of |D| keeps the lower
-//                             atom, a NaN is kept.  Rows of untested molecules (status != 0 or a single atom) get the
-//                             neutral values without a pass.
-//   cn_molecule_test_crystal_kernel   one wave per crystal (crystal_reduce.h): (sum of pairs, sum of delta_sum, maximum of
-//                             delta_max, sum of over) of the values as stored.
+//                             pair with r.r == 0 is not counted.  The pairs of a pass are folded in ATOM order (bg_walk,
+//                             bg_fold): sequential fp64 sums, a tie of |D| keeps the lower atom, a NaN is kept.  Rows of
+//                             untested molecules (status != 0 or a single atom) get the neutral values without a pass.
+//   cn_molecule_test_crystal_kernel   one wave per crystal: bg_pair_stats over the rows' pairs.
 //
 // No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.  64-bit offsets throughout.
 // No scratch; LDS only for the changed-flags of the sweeps and the five counts.
-#include "common.h"
-#include "crystal_reduce.h"
+#include "bond_graph.h"
 
 #include <limits.h>
-#include <math.h>
 
 namespace {
 
@@ -48,49 +42,16 @@ constexpr int MOL_THREADS = 256;
 constexpr int MOL_WAVES = MOL_THREADS / WAVE;
 constexpr double MOL_CLOSURE2 = 0.25;            // (0.5 A)^2: far above the rounding of x, far below a lattice translation
 
-constexpr int MT_LANES = 16;                     // lanes per atom
-constexpr int MT_THREADS = 256;
-constexpr int MT_ATOMS = MT_THREADS / MT_LANES;  // atoms per workgroup and pass
-constexpr int MT_CHUNKS = 8;                     // workgroups per crystal: they stride its atoms, MT_ATOMS a pass
-
-struct MolGraph {
-  const int64_t* __restrict__ z;
-  const int64_t* __restrict__ src;
-  const float* __restrict__ cart_dist;
-  const int64_t* __restrict__ atom_row;
-  const int64_t* __restrict__ seg_ptr;
-  const float* __restrict__ radii;
-  int n_radii;
-  float tol;
-  int64_t N, M, E, a0, a1;                       // a0, a1: the crystal's atoms
-};
+constexpr int MT_CHUNKS = 8;                     // workgroups per crystal: they stride its atoms, BG_ATOMS a pass
 
 // the row of atom i, or -1
-__device__ __forceinline__ int64_t mol_row(const MolGraph& g, int64_t i) {
-  const int64_t m = g.atom_row[i];
-  return (m < 0 || m >= g.M) ? -1 : m;
-}
+__device__ __forceinline__ int64_t mol_row(const BondGraph& g, int64_t i) { return bg_row(g.atom_row, i, g.M); }
 
-// atom i's edge segment, clamped; empty for an atom that never bonds.  At most INT_MAX edges are looked at.
-__device__ __forceinline__ void mol_segment(const MolGraph& g, int64_t i, int64_t zi, int64_t& e0, int64_t& e1) {
-  e0 = g.seg_ptr[i];
-  e1 = g.seg_ptr[i + 1];
-  e0 = e0 < 0 ? 0 : (e0 > g.E ? g.E : e0);
-  e1 = e1 < e0 ? e0 : (e1 > g.E ? g.E : e1);
+// atom i's edge segment; empty for an atom that never bonds.  At most INT_MAX edges are looked at.
+__device__ __forceinline__ void mol_segment(const BondGraph& g, int64_t i, int64_t zi, int64_t& e0, int64_t& e1) {
+  bg_segment(g.seg_ptr, i, g.E, e0, e1);
   if (e1 - e0 > (int64_t)INT_MAX) e1 = e0 + INT_MAX;
   if (zi <= 1 || zi >= g.n_radii) e1 = e0;
-}
-
-// whether edge e into atom i (covalent radius ri) is a bond; its source and the source's row
-__device__ __forceinline__ bool mol_bond(const MolGraph& g, int64_t i, float ri, int64_t e, int64_t& j, int64_t& mj) {
-  const float dist = g.cart_dist[e];
-  j = g.src[e];
-  if (j == i || j < g.a0 || j >= g.a1) return false;
-  const int64_t zj = g.z[j];
-  if (zj <= 1 || zj >= g.n_radii) return false;
-  const float limit = (ri + g.radii[zj]) + g.tol;
-  mj = mol_row(g, j);
-  return dist <= limit && mj >= 0;
 }
 
 __global__ __launch_bounds__(MOL_THREADS) void cn_molecules_kernel(
@@ -101,10 +62,10 @@ __global__ __launch_bounds__(MOL_THREADS) void cn_molecules_kernel(
     double* __restrict__ crystal_counts) {
   __shared__ int fold[MOL_WAVES][5];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
-  MolGraph g = {z, src, cart_dist, atom_row, seg_ptr, radii, n_radii, tol, N, M, E, 0, 0};
-  cr_rows(ptr, blockIdx.x, N, g.a0, g.a1);
-  if (g.a1 - g.a0 > (int64_t)INT_MAX) g.a1 = g.a0 + INT_MAX;      // a label is an int32 index inside the crystal
-  const int64_t a0 = g.a0, a1 = g.a1;
+  const BondGraph g = {z, src, cart_dist, atom_row, seg_ptr, radii, n_radii, tol, N, M, E};
+  int64_t a0, a1;                                                 // the crystal's atoms
+  cr_rows(ptr, blockIdx.x, N, a0, a1);
+  if (a1 - a0 > (int64_t)INT_MAX) a1 = a0 + INT_MAX;              // a label is an int32 index inside the crystal
   const int64_t n = a1 > a0 ? a1 - a0 : 0;
 
   // ---- labels: every atom with a row starts as its own
@@ -135,7 +96,7 @@ __global__ __launch_bounds__(MOL_THREADS) void cn_molecules_kernel(
         const float ri = radii[zi];
         for (int64_t e = e0; e < e1; ++e) {
           int64_t j, mj;
-          if (!mol_bond(g, i, ri, e, j, mj)) continue;
+          if (!bg_bond(g, i, ri, e, a0, a1, j, mj)) continue;
           const int32_t lj = cur[mj];
           if (lj < best) {                                        // strictly: among equal labels the lowest edge stays
             best = lj;
@@ -219,7 +180,7 @@ __global__ __launch_bounds__(MOL_THREADS) void cn_molecules_kernel(
     const int64_t ri_row = mol_row(g, li);
     for (int64_t e = e0; e < e1; ++e) {
       int64_t j, mj;
-      if (!mol_bond(g, i, ri, e, j, mj)) continue;
+      if (!bg_bond(g, i, ri, e, a0, a1, j, mj)) continue;
       const int64_t lj = label[j];
       if (lj != li) {
         const int64_t rj_row = (lj >= a0 && lj < a1) ? mol_row(g, lj) : -1;
@@ -299,29 +260,24 @@ __device__ __forceinline__ double mt_delta(const double ui[9], const float* __re
   for (int q = 0; q < 9; ++q) w[q] = ui[q] - (double)uj[q];
   const double a = xi[0] - xj[0], b = xi[1] - xj[1], c = xi[2] - xj[2];
   rr = a * a + b * b + c * c;
-  const double form =
-      w[0] * a * a + w[4] * b * b + w[8] * c * c + (w[1] + w[3]) * a * b + (w[2] + w[6]) * a * c + (w[5] + w[7]) * b * c;
+  const double form = bg_form(w, a, b, c);
   return rr == 0.0 ? 0.0 : form / rr;
 }
 
-__global__ __launch_bounds__(MT_THREADS) void cn_molecule_test_kernel(
+__global__ __launch_bounds__(BG_THREADS) void cn_molecule_test_kernel(
     const float* __restrict__ u, const int64_t* __restrict__ label, const double* __restrict__ x,
     const int64_t* __restrict__ atom_row, const int64_t* __restrict__ ptr, const int32_t* __restrict__ mol_status,
     const int32_t* __restrict__ mol_size, double threshold, int64_t N, int64_t M, int32_t* __restrict__ pairs,
     float* __restrict__ delta_sum, float* __restrict__ delta_max, int64_t* __restrict__ worst,
     int32_t* __restrict__ over) {
-  const int lane = threadIdx.x & (WAVE - 1), sub = lane & (MT_LANES - 1), base = lane - sub;
+  const int lane = threadIdx.x & (WAVE - 1), sub = lane & (BG_LANES - 1), base = lane - sub;
   int64_t a0, a1;
   cr_rows(ptr, blockIdx.x, N, a0, a1);
-  // every lane of a group takes the same branch below: a group is never split, and a shuffle reads its own group only
 #pragma unroll 1
-  for (int64_t first = a0 + (int64_t)blockIdx.y * MT_ATOMS; first < a1; first += (int64_t)MT_CHUNKS * MT_ATOMS) {
-    const int64_t i = first + (threadIdx.x / MT_LANES);
+  for (int64_t first = a0 + (int64_t)blockIdx.y * BG_ATOMS; first < a1; first += (int64_t)MT_CHUNKS * BG_ATOMS) {
+    const int64_t i = first + (threadIdx.x / BG_LANES);
     int64_t m = -1, li = -1;
-    if (i < a1) {
-      m = atom_row[i];
-      if (m < 0 || m >= M) m = -1;                                // a hydrogen (or an index that is no row): nothing to write
-    }
+    if (i < a1) m = bg_row(atom_row, i, M);                        // -1: nothing to write
     bool tested = false;
     if (m >= 0) {
       li = label[i];
@@ -334,44 +290,30 @@ __global__ __launch_bounds__(MT_THREADS) void cn_molecule_test_kernel(
 #pragma unroll
       for (int q = 0; q < 3; ++q) xi[q] = x[i * 3 + q];
     }
-    int32_t n_pairs = 0, n_over = 0;
-    double sum = 0.0, hi = 0.0;
-    int64_t who = -1;
+    BgFold f;
     const int64_t c1 = tested ? a1 : a0;                          // an untested row makes no pass
 #pragma unroll 1
-    for (int64_t c = a0; c < c1; c += MT_LANES) {
+    for (int64_t c = a0; c < c1; c += BG_LANES) {
       const int64_t j = c + sub;
       bool pair = false;
       double a = 0.0;
       if (j < a1 && j != i && label[j] == li) {
-        const int64_t mj = atom_row[j];
-        if (mj >= 0 && mj < M) {
+        const int64_t mj = bg_row(atom_row, j, M);
+        if (mj >= 0) {
           double rr;
           a = fabs(mt_delta(ui, u + mj * 9, xi, x + j * 3, rr));
           pair = rr != 0.0;
         }
       }
-      unsigned int found = (unsigned int)((__ballot(pair) >> base) & ((1ull << MT_LANES) - 1));
-      while (found) {                                             // the pairs of this pass, lowest atom first
-        const int l = base + __builtin_ctz(found);
-        found &= found - 1;
-        const double av = __shfl(a, l);
-        const long long jv = __shfl((long long)j, l);
-        n_pairs += 1;
-        sum += av;
-        n_over += av > threshold ? 1 : 0;
-        if (av > hi || who < 0 || (av != av && hi == hi)) {       // a tie keeps the earlier atom; a NaN is kept
-          hi = av;
-          who = jv;
-        }
-      }
+      // the pairs of this pass, lowest atom first
+      bg_walk(pair, base, [&](int l) { bg_fold(f, __shfl(a, l), __shfl((long long)j, l), threshold); });
     }
     if (m >= 0 && sub == 0) {
-      pairs[m] = n_pairs;
-      delta_sum[m] = (float)sum;
-      delta_max[m] = (float)hi;
-      worst[m] = who;
-      over[m] = n_over;
+      pairs[m] = f.n;
+      delta_sum[m] = (float)f.sum;
+      delta_max[m] = (float)f.hi;
+      worst[m] = f.who;
+      over[m] = f.over;
     }
   }
 }
@@ -382,26 +324,7 @@ __global__ __launch_bounds__(WAVE) void cn_molecule_test_crystal_kernel(const in
                                                                         const float* __restrict__ delta_max,
                                                                         const int32_t* __restrict__ over,
                                                                         double* __restrict__ stats) {
-  const int g = blockIdx.x, lane = threadIdx.x;
-  int64_t r0, r1;
-  cr_rows(row_ptr, g, M, r0, r1);
-  double np = 0.0, sum = 0.0, hi = 0.0, no = 0.0;
-  for (int64_t r = r0 + lane; r < r1; r += WAVE) {
-    np += (double)pairs[r];
-    sum += (double)delta_sum[r];
-    hi = cr_max_nan(hi, (double)delta_max[r]);
-    no += (double)over[r];
-  }
-  np = cr_wave_sum(np);
-  sum = cr_wave_sum(sum);
-  hi = cr_wave_max_nan(hi);
-  no = cr_wave_sum(no);
-  if (lane == 0) {
-    stats[(size_t)g * 4 + 0] = np;
-    stats[(size_t)g * 4 + 1] = sum;
-    stats[(size_t)g * 4 + 2] = hi;
-    stats[(size_t)g * 4 + 3] = no;
-  }
+  bg_pair_stats(row_ptr, M, pairs, delta_sum, delta_max, over, stats);
 }
 
 }  // namespace
@@ -441,7 +364,7 @@ extern "C" int cartnet_adp_molecule_test(const float* u, const int64_t* label, c
                worst && over,
            "cartnet_adp_molecule_test: null pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(cn_molecule_test_kernel, dim3((unsigned)B, MT_CHUNKS), dim3(MT_THREADS), 0, st, u, label, x, atom_row,
+  hipLaunchKernelGGL(cn_molecule_test_kernel, dim3((unsigned)B, MT_CHUNKS), dim3(BG_THREADS), 0, st, u, label, x, atom_row,
                      ptr, mol_status, mol_size, threshold, N, M, pairs, delta_sum, delta_max, worst, over);
   CN_LAUNCH_CHECK("cartnet_adp_molecule_test");
   if (crystal_stats) {

@@ -1,19 +1,17 @@
 // Riding hydrogens: an isotropic U for every hydrogen from the predicted U_eq of the atom it is bonded to (the riding model
 // of crystallographic refinement; SHELXL's convention is 1.5 for methyl, hydroxyl and water hydrogens and 1.2 for all
 // others).  The reference has no counterpart: its dataset keeps only the rows of non_H_mask (dataset/datasetADP.py:49), so a
-// hydrogen never gets a displacement parameter.  Like the rigid-bond test (bond_ops.hip) this reads the batch's radius
-// graph, whose edges hold the periodic images solved (cart_dist) and are sorted by target atom.
+// hydrogen never gets a displacement parameter.  This reads the batch's bond graph (bond_graph.h: the group layout, the
+// segments and rows, the bond rule and the argmin of a group are that header's).
 //
-// An edge with a hydrogen at one end and the atom p at the other is an H bond when 1 < z_p < n_radii and
-// cart_dist[e] <= (r[1] + r[z_p]) + tol in fp32 in exactly that order (additions only: numpy fp32 gives the same bits).  A
-// NaN distance never qualifies.  The rule is stated in cartnet_amd/bonds.py (riding_hydrogens_host restates it in numpy).
+// An edge with a hydrogen at one end and the atom p at the other is an H bond when it is a bond by bg_bond with the
+// hydrogen's radius at the hydrogen's end: 1 < z_p < n_radii, p has a row and cart_dist[e] <= bg_h_limit(z_p).  A NaN
+// distance never qualifies.  The rule is stated in cartnet_amd/bonds.py (riding_hydrogens_host restates it in numpy).
 //
-//   cn_riding_parent_kernel   RH_LANES lanes per atom.  A hydrogen's group strides its edge segment, sixteen edges a pass,
+//   cn_riding_parent_kernel   BG_LANES lanes per atom.  A hydrogen's group strides its edge segment, sixteen edges a pass,
 //                             and filters on cart_dist and z[source] first; only then is the source's row looked up.  Each
-//                             lane keeps its running (dist, edge) minimum; the group folds the pairs by a butterfly,
-//                             compared lexicographically (smaller dist, then the lower edge), which is the sequential
-//                             minimum whatever the lane layout.  Lane 0 of the group writes parent[i] (-1: an orphan, or
-//                             no hydrogen).
+//                             lane keeps its running (dist, edge) minimum; the group folds the pairs with bg_argmin.  Lane
+//                             0 of the group writes parent[i] (-1: an orphan, or no hydrogen).
 //   cn_riding_value_kernel    after the parent kernel on the same stream.  The group of atom i strides the segment of
 //                             t = i (a non-hydrogen atom) or t = parent[i] (a hydrogen) and counts the edges s -> t with
 //                             z[s] == 1, parent[s] == t and an H bond: integers, so the butterfly sum has no order.  A
@@ -26,65 +24,35 @@
 //
 // No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.  64-bit offsets throughout.  No
 // kernel uses scratch or LDS.
-#include "common.h"
-#include "crystal_reduce.h"
-
-#include <math.h>
+#include "bond_graph.h"
 
 namespace {
 
-constexpr int RH_LANES = 16;                     // lanes per atom: an atom has ~100 incoming edges at radius 5
-constexpr int RH_THREADS = 256;
-constexpr int RH_ATOMS = RH_THREADS / RH_LANES;  // atoms per workgroup
-
-// the clamped edge segment of atom t
-__device__ __forceinline__ void rh_segment(const int64_t* __restrict__ seg_ptr, int64_t t, int64_t E, int64_t& e0,
-                                           int64_t& e1) {
-  e0 = seg_ptr[t];
-  e1 = seg_ptr[t + 1];
-  e0 = e0 < 0 ? 0 : (e0 > E ? E : e0);
-  e1 = e1 < e0 ? e0 : (e1 > E ? E : e1);
-}
-
-__global__ __launch_bounds__(RH_THREADS) void cn_riding_parent_kernel(
+__global__ __launch_bounds__(BG_THREADS) void cn_riding_parent_kernel(
     const int64_t* __restrict__ z, const int64_t* __restrict__ src, const float* __restrict__ cart_dist,
     const int64_t* __restrict__ atom_row, const int64_t* __restrict__ seg_ptr, const float* __restrict__ radii,
     int n_radii, float tol, int64_t N, int64_t M, int64_t E, int64_t* __restrict__ parent) {
-  const int sub = threadIdx.x & (RH_LANES - 1);
-  const int64_t i = (int64_t)blockIdx.x * RH_ATOMS + (threadIdx.x / RH_LANES);
-  // every lane of a group takes the same branch below: a group is never split, and a shuffle reads its own group only
+  const BondGraph g = {z, src, cart_dist, atom_row, seg_ptr, radii, n_radii, tol, N, M, E};
+  const int sub = threadIdx.x & (BG_LANES - 1);
+  const int64_t i = (int64_t)blockIdx.x * BG_ATOMS + (threadIdx.x / BG_LANES);
   int64_t e0 = 0, e1 = 0;
-  if (i < N && z[i] == 1) rh_segment(seg_ptr, i, E, e0, e1);
+  if (i < N && z[i] == 1) bg_segment(seg_ptr, i, E, e0, e1);
   const float rh = e1 > e0 && n_radii > 1 ? radii[1] : 0.f;
   float best = INFINITY;
   int64_t at = E;                                                  // E: no edge yet
 #pragma unroll 1
-  for (int64_t c = e0; c < e1; c += RH_LANES) {
+  for (int64_t c = e0; c < e1; c += BG_LANES) {
     const int64_t e = c + sub;
-    if (e < e1) {
+    int64_t j, mj;
+    if (e < e1 && bg_bond(g, i, rh, e, 0, N, j, mj)) {
       const float dist = cart_dist[e];
-      const int64_t j = src[e];
-      if (j != i && j >= 0 && j < N) {
-        const int64_t zj = z[j];
-        if (zj > 1 && zj < n_radii && dist <= (rh + radii[zj]) + tol) {      // false for a NaN distance
-          const int64_t mj = atom_row[j];
-          if (mj >= 0 && mj < M && (dist < best || at == E)) {              // a lane's edges ascend: a tie keeps the earlier
-            best = dist;
-            at = e;
-          }
-        }
+      if (dist < best || at == E) {                                // a lane's edges ascend: a tie keeps the earlier
+        best = dist;
+        at = e;
       }
     }
   }
-#pragma unroll
-  for (int o = RH_LANES / 2; o > 0; o >>= 1) {
-    const float d = __shfl_xor(best, o);
-    const long long a = __shfl_xor((long long)at, o);
-    if (a < E && (at == E || d < best || (d == best && a < at))) {
-      best = d;
-      at = a;
-    }
-  }
+  bg_argmin(best, at, E);
   if (i < N && sub == 0) {
     int64_t p = -1;
     if (at < E) p = src[at];
@@ -92,14 +60,15 @@ __global__ __launch_bounds__(RH_THREADS) void cn_riding_parent_kernel(
   }
 }
 
-__global__ __launch_bounds__(RH_THREADS) void cn_riding_value_kernel(
+__global__ __launch_bounds__(BG_THREADS) void cn_riding_value_kernel(
     const float* __restrict__ u_eq, const int64_t* __restrict__ z, const int64_t* __restrict__ src,
     const float* __restrict__ cart_dist, const int64_t* __restrict__ atom_row, const int64_t* __restrict__ seg_ptr,
     const float* __restrict__ radii, int n_radii, float tol, float f, float f_rot, int64_t N, int64_t M, int64_t E,
     const int64_t* __restrict__ parent, int32_t* __restrict__ count, float* __restrict__ mult,
     float* __restrict__ u_iso) {
-  const int sub = threadIdx.x & (RH_LANES - 1);
-  const int64_t i = (int64_t)blockIdx.x * RH_ATOMS + (threadIdx.x / RH_LANES);
+  const BondGraph g = {z, src, cart_dist, atom_row, seg_ptr, radii, n_radii, tol, N, M, E};
+  const int sub = threadIdx.x & (BG_LANES - 1);
+  const int64_t i = (int64_t)blockIdx.x * BG_ATOMS + (threadIdx.x / BG_LANES);
   bool hydrogen = false;
   int64_t t = -1, zt = 0, e0 = 0, e1 = 0;
   if (i < N) {
@@ -109,12 +78,12 @@ __global__ __launch_bounds__(RH_THREADS) void cn_riding_value_kernel(
   }
   if (t >= 0) {
     zt = z[t];
-    if (zt > 1 && zt < n_radii) rh_segment(seg_ptr, t, E, e0, e1);
+    if (zt > 1 && zt < n_radii) bg_segment(seg_ptr, t, E, e0, e1);
   }
-  const float limit = e1 > e0 ? (radii[1] + radii[zt]) + tol : 0.f;
+  const float limit = e1 > e0 ? bg_h_limit(g, zt) : 0.f;
   int32_t n = 0;
 #pragma unroll 1
-  for (int64_t c = e0; c < e1; c += RH_LANES) {
+  for (int64_t c = e0; c < e1; c += BG_LANES) {
     const int64_t e = c + sub;
     if (e < e1 && cart_dist[e] <= limit) {
       const int64_t s = src[e];
@@ -122,10 +91,9 @@ __global__ __launch_bounds__(RH_THREADS) void cn_riding_value_kernel(
     }
   }
 #pragma unroll
-  for (int o = RH_LANES / 2; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  for (int o = BG_LANES / 2; o > 0; o >>= 1) n += __shfl_xor(n, o);
   if (i < N && sub == 0) {
-    int64_t m = t >= 0 ? atom_row[t] : -1;
-    if (m < 0 || m >= M) m = -1;
+    const int64_t m = t >= 0 ? bg_row(atom_row, t, M) : -1;
     float k = 0.f, v = NAN;
     if (!hydrogen) {
       if (m >= 0) v = u_eq[m];
@@ -155,8 +123,8 @@ __global__ __launch_bounds__(WAVE) void cn_riding_crystal_kernel(const int64_t* 
     if (z[a] != 1) continue;
     nh += 1.0;
     const int64_t p = parent[a];
-    const int64_t m = p >= 0 && p < N ? atom_row[p] : -1;
-    if (m < 0 || m >= M) {
+    const int64_t m = p >= 0 && p < N ? bg_row(atom_row, p, M) : -1;
+    if (m < 0) {
       orphans += 1.0;
       continue;
     }
@@ -187,19 +155,19 @@ extern "C" int cartnet_adp_riding_h(const float* u_eq, const int64_t* z, const i
            "cartnet_adp_riding_h: bad sizes (B=%d, N=%lld, M=%lld, E=%lld, n_radii=%d)", B, (long long)N, (long long)M,
            (long long)E, n_radii);
   CN_CHECK(tol == tol && f == f && f_rot == f_rot, "cartnet_adp_riding_h: tol, f and f_rot must be numbers");
-  CN_CHECK(N < (1LL << 31) * RH_ATOMS, "cartnet_adp_riding_h: too many atoms for one launch");
+  CN_CHECK(N < (1LL << 31) * BG_ATOMS, "cartnet_adp_riding_h: too many atoms for one launch");
   if (B == 0 || N == 0) return 0;
   CN_CHECK(z && atom_row && seg_ptr && parent && count && mult && u_iso, "cartnet_adp_riding_h: null pointer");
   CN_CHECK(M == 0 || u_eq, "cartnet_adp_riding_h: null pointer");
   CN_CHECK(E == 0 || (edge_index && cart_dist && radii), "cartnet_adp_riding_h: null pointer");
   CN_CHECK(!crystal_stats || atom_ptr, "cartnet_adp_riding_h: null pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((N + RH_ATOMS - 1) / RH_ATOMS));
+  const dim3 grid((unsigned)((N + BG_ATOMS - 1) / BG_ATOMS));
   // without edges every segment is empty, without rows no atom is a parent: the same launches write the neutral values
-  hipLaunchKernelGGL(cn_riding_parent_kernel, grid, dim3(RH_THREADS), 0, st, z, edge_index, cart_dist, atom_row, seg_ptr,
+  hipLaunchKernelGGL(cn_riding_parent_kernel, grid, dim3(BG_THREADS), 0, st, z, edge_index, cart_dist, atom_row, seg_ptr,
                      radii, (int)n_radii, tol, N, M, E, parent);
   CN_LAUNCH_CHECK("cartnet_adp_riding_h");
-  hipLaunchKernelGGL(cn_riding_value_kernel, grid, dim3(RH_THREADS), 0, st, u_eq, z, edge_index, cart_dist, atom_row,
+  hipLaunchKernelGGL(cn_riding_value_kernel, grid, dim3(BG_THREADS), 0, st, u_eq, z, edge_index, cart_dist, atom_row,
                      seg_ptr, radii, (int)n_radii, tol, f, f_rot, N, M, E, parent, count, mult, u_iso);
   CN_LAUNCH_CHECK("cartnet_adp_riding_h");
   if (crystal_stats) {

@@ -30,10 +30,7 @@
 //
 // No atomics, no workgroup waits for another, fixed order: two runs give the same bytes.  64-bit offsets throughout.
 // Nothing that is indexed dynamically lives in registers: N, V, J_i, b and p are in LDS (about 12 KB); no scratch.
-#include "common.h"
-#include "crystal_reduce.h"
-
-#include <math.h>
+#include "bond_graph.h"
 
 namespace {
 
@@ -97,12 +94,6 @@ __device__ __forceinline__ double tls_design(int o, int a, double x, double y, d
   double v = (n == q ? tls_a(p, m, x, y, z) : 0.0) + (n == p ? tls_a(q, m, x, y, z) : 0.0);
   if (k < 2) v -= (q == 2 ? tls_a(p, 2, x, y, z) : 0.0) + (p == 2 ? tls_a(q, 2, x, y, z) : 0.0);
   return w * v;
-}
-
-// the row of atom i, or -1
-__device__ __forceinline__ int64_t tls_row(const int64_t* __restrict__ atom_row, int64_t i, int64_t M) {
-  const int64_t m = atom_row[i];
-  return (m < 0 || m >= M) ? -1 : m;
 }
 
 struct TlsOut {
@@ -226,7 +217,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
 
   // ---- the rows of unfitted molecules, strided over the slots
   for (int64_t i = a0 + (int64_t)slot * TLS_THREADS + tid; i < a1; i += (int64_t)TLS_SLOTS * TLS_THREADS) {
-    const int64_t m = tls_row(atom_row, i, M);
+    const int64_t m = bg_row(atom_row, i, M);
     if (m >= 0 && !(mol_status[m] == 0 && mol_size[m] >= TLS_MIN_ATOMS)) tls_blank(out, m, 0.0f, 0);
   }
 
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
 #pragma unroll 1
   for (int64_t walk = a0; walk < a1; walk += WAVE) {
     const int64_t cand = walk + lane;
-    unsigned long long roots = __ballot(cand < a1 && label[cand] == cand && tls_row(atom_row, cand, M) >= 0);
+    unsigned long long roots = __ballot(cand < a1 && label[cand] == cand && bg_row(atom_row, cand, M) >= 0);
 #pragma unroll 1
     while (roots) {
       const int64_t root = walk + __builtin_ctzll(roots);
@@ -243,7 +234,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
       const bool mine = number % TLS_SLOTS == slot;
       number += 1;
       if (!mine) continue;
-      const int64_t mr = tls_row(atom_row, root, M);
+      const int64_t mr = bg_row(atom_row, root, M);
       if (!(mol_status[mr] == 0 && mol_size[mr] >= TLS_MIN_ATOMS)) continue;
 
       // ---- geometry: c, then rho, the members folded in atom order
@@ -252,7 +243,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
 #pragma unroll 1
       for (int64_t base = a0; base < a1; base += WAVE) {
         const int64_t i = base + lane;
-        const bool member = i < a1 && label[i] == root && tls_row(atom_row, i, M) >= 0;
+        const bool member = i < a1 && label[i] == root && bg_row(atom_row, i, M) >= 0;
         double xi[3] = {0.0, 0.0, 0.0};
         if (member) {
 #pragma unroll
@@ -273,7 +264,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
 #pragma unroll 1
       for (int64_t base = a0; base < a1; base += WAVE) {
         const int64_t i = base + lane;
-        const bool member = i < a1 && label[i] == root && tls_row(atom_row, i, M) >= 0;
+        const bool member = i < a1 && label[i] == root && bg_row(atom_row, i, M) >= 0;
         double d2 = 0.0;
         if (member) {
 #pragma unroll
@@ -292,7 +283,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
       const double rho = sqrt(spread / (double)atoms);
       if (!(rho > 0.0)) {                                            // all atoms in one point (or a NaN): not fitted
         for (int64_t i = a0 + tid; i < a1; i += TLS_THREADS) {
-          const int64_t m = tls_row(atom_row, i, M);
+          const int64_t m = bg_row(atom_row, i, M);
           if (m >= 0 && label[i] == root) tls_blank(out, m, 0.0f, 0);
         }
         continue;
@@ -304,7 +295,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
       for (int64_t base = a0; base < a1; base += WAVE) {
         if (wid == 0) {
           const int64_t i = base + lane;
-          const bool member = i < a1 && label[i] == root && tls_row(atom_row, i, M) >= 0;
+          const bool member = i < a1 && label[i] == root && bg_row(atom_row, i, M) >= 0;
           const unsigned long long found = __ballot(member);
           if (member) sh.members[__popcll(found & ((1ull << lane) - 1ull))] = lane;
           if (lane == 0) sh.count = __popcll(found);
@@ -323,7 +314,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
                                           (x[i * 3 + 2] - c[2]) / rho);
             } else {
               const int o = e - 6 * TLS_P, p = tls_p(o), q = tls_q(o);
-              const int64_t m = tls_row(atom_row, i, M);
+              const int64_t m = bg_row(atom_row, i, M);
               const double s = 0.5 * ((double)u[m * 9 + p * 3 + q] + (double)u[m * 9 + q * 3 + p]);
               sh.y[at][o] = o < 3 ? s : TLS_SQRT2 * s;
             }
@@ -367,7 +358,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
       if (sweeps < 0) {
         const float nan = __builtin_nanf("");
         for (int64_t i = a0 + tid; i < a1; i += TLS_THREADS) {
-          const int64_t m = tls_row(atom_row, i, M);
+          const int64_t m = bg_row(atom_row, i, M);
           if (m >= 0 && label[i] == root) tls_blank(out, m, nan, -1);
         }
         __syncthreads();
@@ -419,7 +410,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
         }
 #pragma unroll 1
         for (int64_t i = a0 + tid; i < a1; i += TLS_THREADS) {
-          const int64_t m = tls_row(atom_row, i, M);
+          const int64_t m = bg_row(atom_row, i, M);
           if (m < 0 || label[i] != root) continue;
           const double rx = x[i * 3 + 0] - c[0], ry = x[i * 3 + 1] - c[1], rz = x[i * 3 + 2] - c[2];
           const double A[9] = {0.0, rz, -ry, -rz, 0.0, rx, ry, -rx, 0.0};
@@ -462,7 +453,7 @@ __global__ __launch_bounds__(TLS_THREADS) void cn_tls_fit_kernel(
       // ---- the molecule's figures on every one of its rows
 #pragma unroll 1
       for (int64_t i = a0 + tid; i < a1; i += TLS_THREADS) {
-        const int64_t m = tls_row(atom_row, i, M);
+        const int64_t m = bg_row(atom_row, i, M);
         if (m < 0 || label[i] != root) continue;
         float* __restrict__ pr = out.params + m * 24;
         pr[0] = (float)sh.mol[0];  pr[1] = (float)sh.mol[4];   pr[2] = (float)sh.mol[8];
@@ -491,7 +482,7 @@ __global__ __launch_bounds__(WAVE) void cn_tls_crystal_kernel(const float* __res
   cr_rows(ptr, g, N, a0, a1);
   double fitted = 0.0, deficient = 0.0, negative = 0.0, r2 = 0.0, s2 = 0.0, hi = 0.0;
   for (int64_t i = a0 + lane; i < a1; i += WAVE) {
-    const int64_t m = tls_row(atom_row, i, M);
+    const int64_t m = bg_row(atom_row, i, M);
     if (m < 0) continue;
     const int32_t rk = rank[m];
     if (rk == 0) continue;

@@ -14,8 +14,8 @@ import pickle
 
 import torch
 
-from .metrics import (adp_eval, bond_test, compute_3D_IoU, edge_row_ptr, get_similarity_index, molecule_test, molecules,
-                      rotate_rows, split_rows, target_row_ptr, tls_fit as tls_fit_call, to_host)
+from .metrics import (adp_eval, batch_graph, bond_test, compute_3D_IoU, edge_row_ptr, get_similarity_index, molecule_test,
+                      molecules, rotate_rows, split_rows, target_row_ptr, tls_fit as tls_fit_call, to_host)
 from .predict import TLS_KEYS, frame_stage, tls_entries
 from .shard import random_rotations
 
@@ -116,23 +116,25 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
             true = batch.y
             pred, _, fm = frame_stage(model, batch, row_ptr, rotations, gen, stats=False)
             extra = {} if fm is None else {"rot_spread": fm.spread}
-            if rigid_bond is not None:                                        # batch.x holds the atomic numbers again
+            if rigid_bond is not None or rigid_molecule is not None:          # batch.x holds the atomic numbers again
+                graph = batch_graph(batch, int(pred.shape[0]), "inference")   # checked and looked up once per batch
+            if rigid_bond is not None:
                 for k, (name, u) in enumerate((("bond_delta_max", pred), ("bond_delta_max_true", true))):
-                    bt = bond_test(u, batch, row_ptr, *rigid_bond)
+                    bt = bond_test(u, graph, row_ptr, *rigid_bond)
                     extra[name] = bt.delta_max
                     bond_sums[k] += bt.crystal_stats.sum(0)
             if rigid_molecule is not None:                                    # found once, tested twice
-                mo = molecules(batch, row_ptr, rigid_molecule[0], rows=int(pred.shape[0]))
+                mo = molecules(graph, row_ptr, rigid_molecule[0])
                 extra.update(mol=mo.mol, mol_size=mo.size, mol_status=mo.status)
                 mol_counts += mo.crystal_counts.sum(0)
                 for k, (suffix, u) in enumerate((("", pred), ("_true", true))):
-                    mt = molecule_test(u, batch, row_ptr, mo, rigid_molecule[1])
+                    mt = molecule_test(u, graph, row_ptr, mo, rigid_molecule[1])
                     extra.update({"mol_pairs" + suffix: mt.pairs, "mol_delta_max" + suffix: mt.delta_max,
                                   "mol_over" + suffix: mt.over})
                     mol_sums[k] += mt.crystal_stats.sum(0)
                     mol_max[k] = torch.maximum(mol_max[k], mt.crystal_stats[:, 2].max())
                     if tls_fit:
-                        entries = tls_entries(tls_fit_call(u, batch, row_ptr, mo))
+                        entries = tls_entries(tls_fit_call(u, graph, row_ptr, mo))
                         extra.update({key + suffix: entries[key] for key in TLS_ROW_KEYS})
                         tls_sums[k] += entries["tls_stats"][:, :5].sum(0)
                         tls_max[k] = torch.maximum(tls_max[k], entries["tls_stats"][:, 5].max())

@@ -296,62 +296,108 @@ def _batch_field(batch, *names):
     return None
 
 
-def _check_graph(batch, dev, M: int, who: str, rows: str, need_dir: bool):
-    """The arrays ``bond_test`` and ``riding_h`` read from a batch (or a dict of its arrays), checked: ``(z, N, edge_index,
-    E, cart_dist, cart_dir or None, non_H_mask or None)``."""
-    z = _batch_field(batch, "x", "z")
-    if not (torch.is_tensor(z) and z.dtype == torch.int64 and z.dim() == 1 and z.device == dev):
-        raise ValueError(f"{who} needs the atomic numbers in batch.x (a forward has overwritten them)")
-    z, N = z.contiguous(), int(z.shape[0])
-    ei, dist = (_batch_field(batch, k) for k in ("edge_index", "cart_dist"))
-    dirs = _batch_field(batch, "cart_dir") if need_dir else None
-    if not (torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.shape[0] == 2 and ei.device == dev):
-        raise ValueError("edge_index must be an int64 tensor [2,E] on the data's device")
-    ei, E = ei.contiguous(), int(ei.shape[1])
-    if not (torch.is_tensor(dist) and dist.dtype == torch.float32 and tuple(dist.shape) == (E,) and dist.device == dev
-            and (not need_dir or (torch.is_tensor(dirs) and dirs.dtype == torch.float32 and tuple(dirs.shape) == (E, 3)
-                                  and dirs.device == dev))):
-        raise ValueError("cart_dist [E] and cart_dir [E,3] must be fp32 tensors on the data's device" if need_dir else
-                         "cart_dist [E] must be an fp32 tensor on the data's device")
-    dist, dirs = dist.detach().contiguous(), dirs.detach().contiguous() if need_dir else None
-    mask = _batch_field(batch, "non_H_mask")
-    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
-        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
-    if mask is None and M != N:
-        raise ValueError(f"{rows} holds {M} rows for {N} atoms and the batch has no non_H_mask")
-    return z, N, ei, E, dist, dirs, mask
-
-
-def _atom_rows(mask, N: int, dev) -> torch.Tensor:
-    """[N] int64: an atom's row, -1 outside the mask; without a mask every atom has one."""
-    if mask is None:
-        return torch.arange(N, dtype=torch.int64, device=dev)
-    mask = mask.to(torch.bool)
-    return torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
+class BatchGraph(NamedTuple):
+    """Everything the bond-graph analyses (``bond_test``, ``riding_h``, ``molecules``, ``molecule_test``, ``tls_fit``,
+    ``aniso_h``) take from a batch, checked once by ``batch_graph`` and good for every prediction of that batch: ``z`` [N]
+    int64; ``edge_index`` [2,E] sorted by target; ``cart_dist`` [E]; ``cart_dir`` [E,3] (``None`` if not asked for);
+    ``mask`` = ``non_H_mask`` [N] (``None``: every atom has a row); ``M``, the rows; the two lookups of the kernels,
+    ``atom_row`` [N] int64 (an atom's row, -1 outside the mask) and ``seg_ptr`` [N+1] int64 (atom i owns the edges
+    ``[seg_ptr[i], seg_ptr[i+1])``); ``atom_ptr`` [B+1] int64 with ``B``, the crystals' atom offsets (both ``None`` for a
+    batch without ``ptr``); ``radii``, ``covalent_radii`` on the batch's device."""
+    z: torch.Tensor
+    N: int
+    edge_index: torch.Tensor
+    E: int
+    cart_dist: torch.Tensor
+    cart_dir: Optional[torch.Tensor]
+    mask: Optional[torch.Tensor]
+    M: int
+    atom_row: torch.Tensor
+    seg_ptr: torch.Tensor
+    atom_ptr: Optional[torch.Tensor]
+    B: Optional[int]
+    radii: torch.Tensor
 
 
 def _atom_lookups(mask, ei: torch.Tensor, N: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(atom_row [N], seg_ptr [N+1])`` int64: an atom's row (-1 outside the mask; without a mask every atom has one) and
     its edge segment, with static-shape device ops."""
-    atom_row = _atom_rows(mask, N, dev)
+    if mask is None:
+        atom_row = torch.arange(N, dtype=torch.int64, device=dev)
+    else:
+        mask = mask.to(torch.bool)
+        atom_row = torch.where(mask, torch.cumsum(mask, 0, dtype=torch.int64) - 1, -1)
     # the edges are sorted by target: atom i owns the edges between the first target >= i and the first target >= i + 1
     seg_ptr = torch.searchsorted(ei[1].contiguous(), torch.arange(N + 1, dtype=torch.int64, device=dev))
     return atom_row, seg_ptr
 
 
+def batch_graph(batch, rows: Optional[int] = None, who: str = "batch_graph", what: str = "rows", need_dir: bool = True,
+                need_ptr: bool = True, dev=None) -> BatchGraph:
+    """The ``BatchGraph`` of ``batch``: a batch of either loader, or a dict of its arrays -- ``x`` (or ``z``) [N] int64
+    atomic numbers, ``edge_index`` [2,E] int64 sorted by target (every loader's order), ``cart_dist`` [E], ``cart_dir``
+    [E,3], ``ptr`` [B+1] and, if some atoms have no row, ``non_H_mask`` [N] (without it every atom has a row, as
+    ``target_row_ptr`` assumes).  ``rows``: the number M of rows, which the caller usually knows from the prediction's
+    shape; without it M is the batch's ``y``'s, N if there is no mask, and else counted from the mask (the one host read
+    this can cost).  The two lookups are built here, once, with static-shape device ops; nothing else is read back.  A
+    ``BatchGraph`` comes back as it is, after the check that it has ``rows`` rows and what the caller needs.  ``who`` and
+    ``what`` name the caller and its per-row argument in the messages; ``dev``: the device the arrays must be on (default:
+    that of the atomic numbers)."""
+    if isinstance(batch, BatchGraph):
+        g = batch
+        if rows is not None and int(rows) != g.M:
+            raise ValueError(f"{what} holds {int(rows)} rows, the batch graph was built for {g.M}")
+        if dev is not None and g.z.device != dev:
+            raise ValueError(f"{what} and the batch graph are on different devices")
+    else:
+        z = _batch_field(batch, "x", "z")
+        if dev is None and torch.is_tensor(z):
+            dev = z.device
+        if not (torch.is_tensor(z) and z.dtype == torch.int64 and z.dim() == 1 and z.device == dev):
+            raise ValueError(f"{who} needs the atomic numbers in batch.x (a forward has overwritten them)")
+        z, N = z.contiguous(), int(z.shape[0])
+        ei, dist = (_batch_field(batch, k) for k in ("edge_index", "cart_dist"))
+        dirs = _batch_field(batch, "cart_dir") if need_dir else None
+        if not (torch.is_tensor(ei) and ei.dtype == torch.int64 and ei.dim() == 2 and ei.shape[0] == 2 and ei.device == dev):
+            raise ValueError("edge_index must be an int64 tensor [2,E] on the data's device")
+        ei, E = ei.contiguous(), int(ei.shape[1])
+        if not (torch.is_tensor(dist) and dist.dtype == torch.float32 and tuple(dist.shape) == (E,) and dist.device == dev
+                and (not need_dir or (torch.is_tensor(dirs) and dirs.dtype == torch.float32
+                                      and tuple(dirs.shape) == (E, 3) and dirs.device == dev))):
+            raise ValueError("cart_dist [E] and cart_dir [E,3] must be fp32 tensors on the data's device" if need_dir else
+                             "cart_dist [E] must be an fp32 tensor on the data's device")
+        dist, dirs = dist.detach().contiguous(), dirs.detach().contiguous() if need_dir else None
+        mask = _batch_field(batch, "non_H_mask")
+        if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
+            raise ValueError("non_H_mask must be a tensor [N] on the data's device")
+        if rows is None:
+            y = _batch_field(batch, "y")
+            rows = N if mask is None else int(y.shape[0]) if torch.is_tensor(y) else int(mask.sum())
+        M = int(rows)
+        if mask is None and M != N:
+            raise ValueError(f"{what} holds {M} rows for {N} atoms and the batch has no non_H_mask")
+        ptr = _batch_field(batch, "ptr")
+        atom_ptr, B = _check_row_ptr(ptr.to(torch.int64), dev) if torch.is_tensor(ptr) else (None, None)
+        g = BatchGraph(z, N, ei, E, dist, dirs, mask, M, *_atom_lookups(mask, ei, N, dev), atom_ptr, B,
+                       covalent_radii(dev))
+    if need_dir and g.cart_dir is None:
+        raise ValueError("cart_dist [E] and cart_dir [E,3] must be fp32 tensors on the data's device")
+    if need_ptr and g.atom_ptr is None:
+        raise ValueError(f"{who} needs the crystals' atom offsets in batch.ptr")
+    return g
+
+
 def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, threshold: float = 1e-3) -> BondTest:
     """Hirshfeld's rigid-bond test of the ADPs ``u`` [M,3,3] on the bonds of ``batch``: one call of
-    ``cartnet_adp_bond_test``.  ``batch``: a batch of either loader, or a dict of its arrays -- ``x`` (or ``z``) [N] int64
-    atomic numbers, ``edge_index`` [2,E] int64 sorted by target (every loader's order), ``cart_dist`` [E], ``cart_dir``
-    [E,3] and, if some atoms have no row, ``non_H_mask`` [N] (without it every atom has a row, as ``target_row_ptr``
-    assumes) -- with ``u`` holding one row per atom of the mask, in atom order.  ``row_ptr`` [B+1]: ``target_row_ptr``.
-    An edge ``j -> i`` is a bond by the rule of ``cartnet_amd.bonds`` (``r_i + r_j + tol``, both ends non-hydrogen, no
-    self image); only edges the graph holds are seen.  The two lookups the kernel needs -- an atom's row and its edge
-    segment -- are built here with static-shape device ops; nothing is read back."""
+    ``cartnet_adp_bond_test``.  ``batch``: what ``batch_graph`` takes (``ptr`` is not needed) or its ``BatchGraph``, with
+    ``u`` holding one row per atom of the mask, in atom order.  ``row_ptr`` [B+1]: ``target_row_ptr``.  An edge ``j -> i``
+    is a bond by the rule of ``cartnet_amd.bonds`` (``r_i + r_j + tol``, both ends non-hydrogen, no self image); only edges
+    the graph holds are seen.  Nothing is read back."""
     _check_fp32("u", u)
     u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
-    z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "bond_test", "u", True)
+    g = batch_graph(batch, M, "bond_test", "u", need_ptr=False, dev=dev)
+    z, N, ei, E, dist, dirs = g.z, g.N, g.edge_index, g.E, g.cart_dist, g.cart_dir
     bonds = torch.empty(M, dtype=torch.int32, device=dev)
     delta_sum = torch.empty(M, dtype=torch.float32, device=dev)
     delta_max = torch.empty(M, dtype=torch.float32, device=dev)
@@ -361,13 +407,12 @@ def bond_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, tol: float = 0.4, t
     if M == 0 or N == 0:                         # the entry point launches nothing
         return BondTest(bonds, delta_sum, delta_max, worst, over, ratio,
                         torch.zeros((B, 4), dtype=torch.float64, device=dev))
-    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
     stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        radii = covalent_radii(dev)
         _l.check(_l.load().cartnet_adp_bond_test(
-            u.data_ptr(), z.data_ptr(), ei.data_ptr(), dist.data_ptr(), dirs.data_ptr(), atom_row.data_ptr(), seg_ptr.data_ptr(), row_ptr.data_ptr(), radii.data_ptr(),
-            int(radii.numel()), float(tol), float(threshold), B, N, M, E, bonds.data_ptr(), delta_sum.data_ptr(),
+            u.data_ptr(), z.data_ptr(), ei.data_ptr(), dist.data_ptr(), dirs.data_ptr(), g.atom_row.data_ptr(),
+            g.seg_ptr.data_ptr(), row_ptr.data_ptr(), g.radii.data_ptr(),
+            int(g.radii.numel()), float(tol), float(threshold), B, N, M, E, bonds.data_ptr(), delta_sum.data_ptr(),
             delta_max.data_ptr(), worst.data_ptr(), over.data_ptr(), ratio.data_ptr(), stats.data_ptr(),
             _l.stream_ptr()), "cartnet_adp_bond_test")
     return BondTest(bonds, delta_sum, delta_max, worst, over, ratio, stats)
@@ -394,32 +439,26 @@ class RidingH(NamedTuple):
 
 def riding_h(u_eq: torch.Tensor, batch, tol: float = 0.4, f: float = 1.2, f_rot: float = 1.5) -> RidingH:
     """An isotropic U for every hydrogen of ``batch`` from ``u_eq`` [M] (``AdpExport.u_eq``: one row per atom of the mask,
-    in atom order): one call of ``cartnet_adp_riding_h``.  ``batch``: as for ``bond_test`` -- ``x`` (or ``z``),
-    ``edge_index`` sorted by target, ``cart_dist``, ``non_H_mask`` if some atoms have no row -- and ``ptr`` [B+1], the
-    crystals' atom offsets.  A hydrogen's parent is the nearest non-hydrogen atom with a row within
+    in atom order): one call of ``cartnet_adp_riding_h``.  ``batch``: what ``batch_graph`` takes (``cart_dir`` is not
+    needed) or its ``BatchGraph``.  A hydrogen's parent is the nearest non-hydrogen atom with a row within
     ``r_H + r_parent + tol`` among the edges the graph holds; the multiplier is ``f_rot`` on oxygen and on a carbon that
-    carries three or more hydrogens, ``f`` otherwise (the rule: ``cartnet_amd.bonds``).  The two lookups are built as in
-    ``bond_test``; nothing is read back."""
+    carries three or more hydrogens, ``f`` otherwise (the rule: ``cartnet_amd.bonds``).  Nothing is read back."""
     _check_fp32("u_eq", u_eq, (), "[M]")
     u_eq, M, dev = u_eq.detach().contiguous(), int(u_eq.shape[0]), u_eq.device
-    ptr = _batch_field(batch, "ptr")
-    if not torch.is_tensor(ptr):
-        raise ValueError("riding_h needs the crystals' atom offsets in batch.ptr")
-    atom_ptr, B = _check_row_ptr(ptr.to(torch.int64), dev)
-    z, N, ei, E, dist, _, mask = _check_graph(batch, dev, M, "riding_h", "u_eq", False)
+    g = batch_graph(batch, M, "riding_h", "u_eq", need_dir=False, dev=dev)
+    z, N, ei, E, dist, B = g.z, g.N, g.edge_index, g.E, g.cart_dist, g.B
     parent = torch.empty(N, dtype=torch.int64, device=dev)
     count = torch.empty(N, dtype=torch.int32, device=dev)
     mult = torch.empty(N, dtype=torch.float32, device=dev)
     u_iso = torch.empty(N, dtype=torch.float32, device=dev)
     if N == 0:                                   # the entry point launches nothing
         return RidingH(parent, count, mult, u_iso, torch.zeros((B, 4), dtype=torch.float64, device=dev))
-    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
     stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        radii = covalent_radii(dev)
         _l.check(_l.load().cartnet_adp_riding_h(
             _l.ptr(u_eq) if M else None, z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None,
-            atom_row.data_ptr(), seg_ptr.data_ptr(), atom_ptr.data_ptr(), radii.data_ptr(), int(radii.numel()), float(tol),
+            g.atom_row.data_ptr(), g.seg_ptr.data_ptr(), g.atom_ptr.data_ptr(), g.radii.data_ptr(),
+            int(g.radii.numel()), float(tol),
             float(f), float(f_rot), B, N, M, E, parent.data_ptr(), count.data_ptr(), mult.data_ptr(), u_iso.data_ptr(),
             stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_riding_h")
     return RidingH(parent, count, mult, u_iso, stats)
@@ -460,47 +499,38 @@ class MoleculeTest(NamedTuple):
     crystal_stats: torch.Tensor
 
 
-def _atom_ptr(batch, who: str, dev) -> Tuple[torch.Tensor, int]:
-    ptr = _batch_field(batch, "ptr")
-    if not torch.is_tensor(ptr):
-        raise ValueError(f"{who} needs the crystals' atom offsets in batch.ptr")
-    return _check_row_ptr(ptr.to(torch.int64), dev)
+def _check_molecules(mo: "Molecules", g: BatchGraph, B: int, M: int, dev) -> tuple:
+    """``(label, x, status, size)`` of ``mo``, contiguous, after the check that they are the molecules of the batch of
+    ``g`` and of a prediction of ``M`` rows in ``B`` crystals on ``dev``."""
+    N = g.N
+    if not (g.B == B and tuple(mo.label.shape) == (N,) and tuple(mo.x.shape) == (N, 3) and mo.x.dtype == torch.float64
+            and mo.label.dtype == torch.int64
+            and all(t.dtype == torch.int32 and tuple(t.shape) == (M,) for t in (mo.status, mo.size))
+            and all(t.device == dev for t in (mo.label, mo.x, mo.status, mo.size))):
+        raise ValueError(f"molecules does not belong to this batch and u ({B} crystals, {M} rows)")
+    return tuple(t.contiguous() for t in (mo.label, mo.x, mo.status, mo.size))
 
 
 def molecules(batch, row_ptr: torch.Tensor, tol: float = 0.4, rows: Optional[int] = None) -> Molecules:
     """The molecules of ``batch``: one call of ``cartnet_molecules``, one workgroup per crystal, nothing read back.
-    ``batch``: as for ``bond_test`` -- ``x`` (or ``z``), ``edge_index`` sorted by target, ``cart_dist``, ``cart_dir``,
-    ``non_H_mask`` if some atoms have no row -- and ``ptr`` [B+1], the crystals' atom offsets.  ``row_ptr`` [B+1]:
-    ``target_row_ptr``.  ``rows``: the number M of rows, which the caller usually knows from the prediction's shape; without
-    it M is the batch's ``y``'s, N if there is no mask, and else counted from the mask (the one host read this can cost).
+    ``batch`` and ``rows``: what ``batch_graph`` takes, or its ``BatchGraph``.  ``row_ptr`` [B+1]: ``target_row_ptr``.
     A bond is the rigid-bond test's (``cartnet_amd.bonds``); a molecule is a component of the bond graph."""
-    z = _batch_field(batch, "x", "z")
-    if not torch.is_tensor(z):
-        raise ValueError("molecules needs the atomic numbers in batch.x (a forward has overwritten them)")
-    dev = z.device
+    g = batch_graph(batch, rows, "molecules")
+    z, N, ei, E, dist, dirs, M, dev = g.z, g.N, g.edge_index, g.E, g.cart_dist, g.cart_dir, g.M, g.z.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
-    atom_ptr, B_atoms = _atom_ptr(batch, "molecules", dev)
-    if B_atoms != B:
-        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {B_atoms}")
-    mask = _batch_field(batch, "non_H_mask")
-    if rows is None:
-        y = _batch_field(batch, "y")
-        rows = int(z.shape[0]) if mask is None else int(y.shape[0]) if torch.is_tensor(y) else int(mask.sum())
-    M = int(rows)
-    z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "molecules", "rows", True)
+    if g.B != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {g.B}")
     label = torch.empty(N, dtype=torch.int64, device=dev)
     x = torch.empty((N, 3), dtype=torch.float64, device=dev)
     mol, size, status = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(3))
     if M == 0 or N == 0:                         # the entry point launches nothing
         return Molecules(label.fill_(-1), x.zero_(), mol, size, status, torch.zeros((B, 5), dtype=torch.float64, device=dev))
-    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
     counts = torch.empty((B, 5), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        radii = covalent_radii(dev)
         _l.check(_l.load().cartnet_molecules(
             z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None, _l.ptr(dirs) if E else None,
-            atom_row.data_ptr(), seg_ptr.data_ptr(), atom_ptr.data_ptr(), row_ptr.data_ptr(), radii.data_ptr(),
-            int(radii.numel()), float(tol), B, N, M, E, label.data_ptr(), x.data_ptr(), mol.data_ptr(), size.data_ptr(),
+            g.atom_row.data_ptr(), g.seg_ptr.data_ptr(), g.atom_ptr.data_ptr(), row_ptr.data_ptr(), g.radii.data_ptr(),
+            int(g.radii.numel()), float(tol), B, N, M, E, label.data_ptr(), x.data_ptr(), mol.data_ptr(), size.data_ptr(),
             status.data_ptr(), counts.data_ptr(), _l.stream_ptr()), "cartnet_molecules")
     return Molecules(label, x, mol, size, status, counts)
 
@@ -509,23 +539,14 @@ def molecule_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Mole
                   threshold: float = 1e-3) -> MoleculeTest:
     """The rigid-body test of the ADPs ``u`` [M,3,3] on the ``molecules`` of ``batch`` (``molecules(batch, row_ptr)``):
     one call of ``cartnet_adp_molecule_test``.  For every row of a tested molecule (status 0, two or more atoms) the other
-    atoms of the molecule in atom order, ``D = r^T (U_i - U_j) r / r.r`` along ``r = x_i - x_j``.  ``batch`` gives
-    ``non_H_mask`` and ``ptr``; nothing is read back."""
+    atoms of the molecule in atom order, ``D = r^T (U_i - U_j) r / r.r`` along ``r = x_i - x_j``.  ``batch``: the one the
+    molecules were found in, or its ``BatchGraph``; nothing is read back."""
     _check_fp32("u", u)
     u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
-    atom_ptr, B_atoms = _atom_ptr(batch, "molecule_test", dev)
-    mo = molecules
-    N = int(mo.label.shape[0])
-    if not (B_atoms == B and tuple(mo.x.shape) == (N, 3) and mo.x.dtype == torch.float64 and mo.label.dtype == torch.int64
-            and all(t.dtype == torch.int32 and tuple(t.shape) == (M,) for t in (mo.status, mo.size))
-            and all(t.device == dev for t in (mo.label, mo.x, mo.status, mo.size))):
-        raise ValueError(f"molecules does not belong to this batch and u ({B} crystals, {M} rows)")
-    mask = _batch_field(batch, "non_H_mask")
-    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
-        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
-    if mask is None and M != N:
-        raise ValueError(f"u holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    g = batch_graph(batch, M, "molecule_test", "u", need_dir=False, dev=dev)
+    N = g.N
+    label, x, status, size = _check_molecules(molecules, g, B, M, dev)
     pairs = torch.empty(M, dtype=torch.int32, device=dev)
     delta_sum = torch.empty(M, dtype=torch.float32, device=dev)
     delta_max = torch.empty(M, dtype=torch.float32, device=dev)
@@ -533,14 +554,13 @@ def molecule_test(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Mole
     over = torch.empty(M, dtype=torch.int32, device=dev)
     if M == 0 or N == 0:                         # the entry point launches nothing
         return MoleculeTest(pairs, delta_sum, delta_max, worst, over, torch.zeros((B, 4), dtype=torch.float64, device=dev))
-    atom_row = _atom_rows(mask, N, dev)
-    label, x, status, size = (t.contiguous() for t in (mo.label, mo.x, mo.status, mo.size))
     stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _l.check(_l.load().cartnet_adp_molecule_test(
-            u.data_ptr(), label.data_ptr(), x.data_ptr(), atom_row.data_ptr(), atom_ptr.data_ptr(), row_ptr.data_ptr(),
-            status.data_ptr(), size.data_ptr(), float(threshold), B, N, M, pairs.data_ptr(), delta_sum.data_ptr(), delta_max.data_ptr(), worst.data_ptr(),
-            over.data_ptr(), stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_molecule_test")
+            u.data_ptr(), label.data_ptr(), x.data_ptr(), g.atom_row.data_ptr(), g.atom_ptr.data_ptr(), row_ptr.data_ptr(),
+            status.data_ptr(), size.data_ptr(), float(threshold), B, N, M, pairs.data_ptr(), delta_sum.data_ptr(),
+            delta_max.data_ptr(), worst.data_ptr(), over.data_ptr(), stats.data_ptr(), _l.stream_ptr()),
+            "cartnet_adp_molecule_test")
     return MoleculeTest(pairs, delta_sum, delta_max, worst, over, stats)
 
 
@@ -565,23 +585,14 @@ class TlsFit(NamedTuple):
 def tls_fit(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Molecules) -> TlsFit:
     """The TLS fit of the ADPs ``u`` [M,3,3] on the ``molecules`` of ``batch`` (``molecules(batch, row_ptr)``): one call of
     ``cartnet_adp_tls_fit``.  Every molecule with status 0 and five or more atoms gets the rigid-body tensors T, L and S
-    that explain its ADPs best (Schomaker & Trueblood 1968; the rule: ``cartnet_amd.bonds``).  ``batch`` gives
-    ``non_H_mask`` and ``ptr``; nothing is read back."""
+    that explain its ADPs best (Schomaker & Trueblood 1968; the rule: ``cartnet_amd.bonds``).  ``batch``: the one the
+    molecules were found in, or its ``BatchGraph``; nothing is read back."""
     _check_fp32("u", u)
     u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
-    atom_ptr, B_atoms = _atom_ptr(batch, "tls_fit", dev)
-    mo = molecules
-    N = int(mo.label.shape[0])
-    if not (B_atoms == B and tuple(mo.x.shape) == (N, 3) and mo.x.dtype == torch.float64 and mo.label.dtype == torch.int64
-            and all(t.dtype == torch.int32 and tuple(t.shape) == (M,) for t in (mo.status, mo.size))
-            and all(t.device == dev for t in (mo.label, mo.x, mo.status, mo.size))):
-        raise ValueError(f"molecules does not belong to this batch and u ({B} crystals, {M} rows)")
-    mask = _batch_field(batch, "non_H_mask")
-    if mask is not None and not (tuple(mask.shape) == (N,) and mask.device == dev):
-        raise ValueError("non_H_mask must be a tensor [N] on the data's device")
-    if mask is None and M != N:
-        raise ValueError(f"u holds {M} rows for {N} atoms and the batch has no non_H_mask")
+    g = batch_graph(batch, M, "tls_fit", "u", need_dir=False, dev=dev)
+    N = g.N
+    label, x, status, size = _check_molecules(molecules, g, B, M, dev)
     u_tls = torch.empty((M, 3, 3), dtype=torch.float32, device=dev)
     resid = torch.empty(M, dtype=torch.float32, device=dev)
     params = torch.empty((M, 24), dtype=torch.float32, device=dev)
@@ -590,12 +601,10 @@ def tls_fit(u: torch.Tensor, batch, row_ptr: torch.Tensor, molecules: Molecules)
     rfac = torch.empty(M, dtype=torch.float32, device=dev)
     if M == 0 or N == 0:                         # the entry point launches nothing
         return TlsFit(u_tls, resid, params, eig, rank, rfac, torch.zeros((B, 6), dtype=torch.float64, device=dev))
-    atom_row = _atom_rows(mask, N, dev)
-    label, x, status, size = (t.contiguous() for t in (mo.label, mo.x, mo.status, mo.size))
     stats = torch.empty((B, 6), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _l.check(_l.load().cartnet_adp_tls_fit(
-            u.data_ptr(), label.data_ptr(), x.data_ptr(), atom_row.data_ptr(), atom_ptr.data_ptr(), row_ptr.data_ptr(),
+            u.data_ptr(), label.data_ptr(), x.data_ptr(), g.atom_row.data_ptr(), g.atom_ptr.data_ptr(), row_ptr.data_ptr(),
             status.data_ptr(), size.data_ptr(), B, N, M, u_tls.data_ptr(), resid.data_ptr(), params.data_ptr(),
             eig.data_ptr(), rank.data_ptr(), rfac.data_ptr(), stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_tls_fit")
     return TlsFit(u_tls, resid, params, eig, rank, rfac, stats)
@@ -621,8 +630,8 @@ class AnisoH(NamedTuple):
 def aniso_h(u: torch.Tensor, batch, row_ptr: torch.Tensor, riding: RidingH, molecules: Optional[Molecules] = None,
             tls: Optional[TlsFit] = None, stretch: float = 0.005, bend: float = 0.020) -> AnisoH:
     """A displacement tensor for every hydrogen of ``batch`` from the ADPs ``u`` [M,3,3] of the non-hydrogen atoms: one
-    call of ``cartnet_adp_aniso_h``.  ``batch``: as for ``bond_test`` (a batch of either loader, or a dict of its arrays)
-    with ``ptr`` [B+1]; ``row_ptr`` [B+1]: ``target_row_ptr``; ``riding``: ``riding_h`` of the same batch (its ``parent``
+    call of ``cartnet_adp_aniso_h``.  ``batch``: what ``batch_graph`` takes, or its ``BatchGraph``;
+    ``row_ptr`` [B+1]: ``target_row_ptr``; ``riding``: ``riding_h`` of the same batch (its ``parent``
     is read).  ``molecules`` and ``tls`` (``molecules(batch, row_ptr)`` and ``tls_fit`` on them): both or neither; with
     them a hydrogen whose parent's molecule was fitted also gets the change of that rigid-body motion from the parent's
     position to its own, without them every hydrogen with a parent has ``source = 2``.  ``stretch`` / ``bend`` (A^2): the
@@ -631,10 +640,10 @@ def aniso_h(u: torch.Tensor, batch, row_ptr: torch.Tensor, riding: RidingH, mole
     _check_fp32("u", u)
     u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
     row_ptr, B = _check_row_ptr(row_ptr, dev)
-    atom_ptr, B_atoms = _atom_ptr(batch, "aniso_h", dev)
-    if B_atoms != B:
-        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {B_atoms}")
-    z, N, ei, E, dist, dirs, mask = _check_graph(batch, dev, M, "aniso_h", "u", True)
+    g = batch_graph(batch, M, "aniso_h", "u", dev=dev)
+    if g.B != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {g.B}")
+    z, N, ei, E, dist, dirs = g.z, g.N, g.edge_index, g.E, g.cart_dist, g.cart_dir
     parent = riding.parent
     if not (parent.dtype == torch.int64 and tuple(parent.shape) == (N,) and parent.device == dev):
         raise ValueError(f"riding does not belong to this batch ({N} atoms)")
@@ -642,23 +651,21 @@ def aniso_h(u: torch.Tensor, batch, row_ptr: torch.Tensor, riding: RidingH, mole
         raise ValueError("molecules and tls come together or not at all")
     x = params = rank = None
     if tls is not None:
-        x, params, rank = molecules.x, tls.params, tls.rank
-        if not (tuple(x.shape) == (N, 3) and x.dtype == torch.float64 and tuple(params.shape) == (M, 24)
-                and params.dtype == torch.float32 and tuple(rank.shape) == (M,) and rank.dtype == torch.int32
-                and all(t.device == dev for t in (x, params, rank))):
+        x, params, rank = _check_molecules(molecules, g, B, M, dev)[1], tls.params, tls.rank
+        if not (tuple(params.shape) == (M, 24) and params.dtype == torch.float32 and tuple(rank.shape) == (M,)
+                and rank.dtype == torch.int32 and params.device == dev and rank.device == dev):
             raise ValueError(f"molecules and tls do not belong to this batch and u ({N} atoms, {M} rows)")
-        x, params, rank = x.contiguous(), params.contiguous(), rank.contiguous()
+        params, rank = params.contiguous(), rank.contiguous()
     u_h = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
     source = torch.empty(N, dtype=torch.int32, device=dev)
     if N == 0:                                   # the entry point launches nothing
         return AnisoH(u_h, source, torch.zeros((B, 4), dtype=torch.float64, device=dev))
-    atom_row, seg_ptr = _atom_lookups(mask, ei, N, dev)
     parent = parent.contiguous()
     stats = torch.empty((B, 4), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _l.check(_l.load().cartnet_adp_aniso_h(
             _l.ptr(u) if M else None, z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None,
-            _l.ptr(dirs) if E else None, atom_row.data_ptr(), seg_ptr.data_ptr(), atom_ptr.data_ptr(), parent.data_ptr(),
+            _l.ptr(dirs) if E else None, g.atom_row.data_ptr(), g.seg_ptr.data_ptr(), g.atom_ptr.data_ptr(), parent.data_ptr(),
             _l.ptr(x) if M else None, _l.ptr(params) if M else None, _l.ptr(rank) if M else None, float(stretch),
             float(bend), B, N, M, E, u_h.data_ptr(), source.data_ptr(), stats.data_ptr(), _l.stream_ptr()),
             "cartnet_adp_aniso_h")

@@ -33,8 +33,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .metrics import (adp_export, aniso_h as aniso_h_call, bond_test, check_export_status, check_temperatures,
-                      edge_row_ptr, frame_mean, molecule_test, molecules as find_molecules, riding_h as riding_h_call,
+from .metrics import (adp_export, aniso_h as aniso_h_call, batch_graph, bond_test, check_export_status,
+                      check_temperatures, edge_row_ptr, frame_mean, molecule_test, molecules as find_molecules, riding_h as riding_h_call,
                       rotate_rows, split_rows, target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
 
 KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
@@ -377,27 +377,26 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, rid
     pred, R, fm = frame_stage(model, batch, row_ptr, rotations, gen, stats=True)
     if fm is not None:
         dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
-    dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h,
-                         _found_molecules(batch, row_ptr, int(pred.shape[0]), rigid_molecule, tls_fit), aniso_h))
+    graph, mo = _of_the_graph(batch, row_ptr, int(pred.shape[0]), rigid_bond, riding_h, rigid_molecule)
+    dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, graph, mo, rigid_molecule, tls_fit, aniso_h))
     return dev
 
 
-def _found_molecules(batch, row_ptr: torch.Tensor, rows: int, rigid_molecule, tls_fit=None):
-    """``(metrics.Molecules of the batch, threshold, whether they are also fitted)`` for ``rigid_molecule`` =
-    ``(tol, threshold)``, or ``None``: found once per batch (they do not depend on U), tested -- and with ``tls_fit``
-    fitted -- once per prediction of it (``_exported``)."""
-    if rigid_molecule is None:
-        return None
-    tol, threshold = rigid_molecule
-    return find_molecules(batch, row_ptr, tol, rows=rows), threshold, bool(tls_fit)
+def _of_the_graph(batch, row_ptr: torch.Tensor, rows: int, rigid_bond, riding_h, rigid_molecule):
+    """``(metrics.BatchGraph of the batch, its metrics.Molecules)``, each ``None`` unless a flag needs it: what the analyses
+    of ``_exported`` share and what does not depend on U, so checked, built and found once per batch (its atomic numbers in
+    ``x``), however many predictions of it follow."""
+    if rigid_bond is None and riding_h is None and rigid_molecule is None:
+        return None, None
+    graph = batch_graph(batch, rows, "predict_adps")
+    return graph, None if rigid_molecule is None else find_molecules(graph, row_ptr, rigid_molecule[0])
 
 
-def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, found=None,
-              aniso_h=None) -> dict:
-    """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch`` (its atomic numbers in ``x``):
-    the export and, as asked for, the rigid-bond test, the rigid-body test (and the TLS fit) on the molecules ``found``
-    (``_found_molecules``), the riding hydrogens (and their tensors, with the TLS fit if there is one) and the site
-    average."""
+def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, graph=None, mo=None,
+              rigid_molecule=None, tls_fit=None, aniso_h=None) -> dict:
+    """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch``: the export and, as asked for
+    and on ``graph`` and ``mo`` (``_of_the_graph``), the rigid-bond test, the rigid-body test (and the TLS fit) on the
+    molecules, the riding hydrogens (and their tensors, with the TLS fit if there is one) and the site average."""
     device = batch.x.device
     B = int(batch.num_graphs)
     sel = batch._meta[:B]
@@ -405,19 +404,18 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
     dev = dict(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
                stats=ex.crystal_stats, _status=ex.status)
     if rigid_bond is not None:
-        dev.update(bond_entries(bond_test(pred, batch, row_ptr, *rigid_bond), batch))
-    mo = tf = None
-    if found is not None:
-        mo, threshold, fit = found
-        dev.update(molecule_entries(mo, molecule_test(pred, batch, row_ptr, mo, threshold), batch))
-        if fit:
-            tf = tls_fit_call(pred, batch, row_ptr, mo)
+        dev.update(bond_entries(bond_test(pred, graph, row_ptr, *rigid_bond), batch))
+    tf = None
+    if mo is not None:
+        dev.update(molecule_entries(mo, molecule_test(pred, graph, row_ptr, mo, rigid_molecule[1]), batch))
+        if tls_fit:
+            tf = tls_fit_call(pred, graph, row_ptr, mo)
             dev.update(tls_entries(tf))
     if riding_h is not None:
-        rh = riding_h_call(ex.u_eq, batch, *riding_h)
+        rh = riding_h_call(ex.u_eq, graph, *riding_h)
         dev.update(riding_entries(rh, batch))
         if aniso_h is not None:
-            ah = aniso_h_call(pred, batch, row_ptr, rh, mo if tf is not None else None, tf, *aniso_h)
+            ah = aniso_h_call(pred, graph, row_ptr, rh, mo if tf is not None else None, tf, *aniso_h)
             dev.update(aniso_entries(ah, batch))
     if sym is not None:
         from .symmetry import site_average
@@ -446,7 +444,7 @@ def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, rid
     if R is not None:
         dev["frames"] = R.transpose(0, 1)
     rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
-    found = _found_molecules(batch, row_ptr, rows // rotations, rigid_molecule, tls_fit)   # once for the T temperatures
+    graph, mo = _of_the_graph(batch, row_ptr, rows // rotations, rigid_bond, riding_h, rigid_molecule)   # once for all T
     per = []
     for t in range(T):
         pred, d = members[t * rows:(t + 1) * rows], {}
@@ -454,7 +452,7 @@ def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, rid
             fm = frame_mean(pred, R, row_ptr, stats=True)
             pred = fm.mean
             d.update(rot_spread=fm.spread, rot_stats=fm.crystal_spread)
-        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, found, aniso_h))
+        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, graph, mo, rigid_molecule, tls_fit, aniso_h))
         per.append(d)
         dev.update({f"{k}@{t}": v for k, v in d.items()})
     if T >= 2:

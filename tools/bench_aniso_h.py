@@ -7,7 +7,7 @@ not depend on the rank.
 
 The variants are taken alternately (off on off on ...) in one process after a warm-up round; a time is the host clock
 between two device synchronisations around the whole pass, and the figure kept is the median of ``--rounds`` (5).  Two more
-passes run with a HIP event pair around every ``aniso_h`` call (its two lookups and ``cartnet_adp_aniso_h``'s two launches)
+passes run with a HIP event pair around every ``aniso_h`` call (``cartnet_adp_aniso_h``'s two launches; the lookups are per batch)
 and around every ``aniso_entries`` call (the export over atoms as rows): the feature's own share.  The flag-off pass runs
 no line of the feature; the parent commit's figure for it (``off_parent_ms``) was taken once with the parent's tree on the
 same box and is a constant here, with its source.  There is no threshold: the tool reports.

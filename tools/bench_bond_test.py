@@ -6,7 +6,8 @@ tools/bench_predict.py.
 The two variants are taken alternately (off on off on ...) in one process after a warm-up round; a time is the host clock
 between two device synchronisations around the whole pass (forwards, exports, bond tests, transfers, the host-side split),
 and the figure kept is the median of ``--rounds`` (5).  One more pass runs with a HIP event pair around every ``bond_test``
-call (the two lookups built with torch and ``cartnet_adp_bond_test``'s two launches): the share of the pass spent there.
+call (``cartnet_adp_bond_test``'s two launches; the lookups are built per batch, outside the call): the share of the pass
+spent there.
 There is no threshold: the tool reports.
 
 The measurement runs in a child process under a time limit; the parent never touches the GPU.  One JSON object goes to

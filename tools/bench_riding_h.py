@@ -7,8 +7,9 @@ non-hydrogen atom within the bond limit; the tool reports how many do (``riders`
 The two variants are taken alternately (off on off on ...) in one process after a warm-up round; a time is the host clock
 between two device synchronisations around the whole pass (forwards, exports, riding calls, transfers, the host-side split),
 and the figure kept is the median of ``--rounds`` (5).  The pass without the flag is the code path of every earlier version:
-the baseline.  One more pass runs with a HIP event pair around every ``riding_h`` call (the two lookups built with torch and
-``cartnet_adp_riding_h``'s three launches): the share of the pass spent there.  There is no threshold: the tool reports.
+the baseline.  One more pass runs with a HIP event pair around every ``riding_h`` call (``cartnet_adp_riding_h``'s three
+launches; the lookups are built per batch, outside the call): the share of the pass spent there.  There is no threshold:
+the tool reports.
 
 The measurement runs in a child process under a time limit; the parent never touches the GPU.  One JSON object goes to
 stdout and, with ``--out``, to a file.

@@ -9,7 +9,7 @@ figure ``profiles/exp_bond_test.json`` holds for the parent commit.
 
 The variants are taken alternately (off on off on ...) in one process after a warm-up round; a time is the host clock
 between two device synchronisations around the whole pass, and the figure kept is the median of ``--rounds`` (5).  Two more
-passes run with a HIP event pair around every ``molecules`` call (its two lookups and ``cartnet_molecules``' launch) and
+passes run with a HIP event pair around every ``molecules`` call (``cartnet_molecules``' launch on the batch's graph) and
 around every ``molecule_test`` call: the two entry points' own share.  The sweeps per crystal are those of
 ``bonds.molecules_host`` on the same batches.  There is no threshold: the tool reports.
 

@@ -6,8 +6,8 @@ rings of 6-8.  Those molecules are planar, so every fit is the rank-19 case; the
 
 The variants are taken alternately (off on off on ...) in one process after a warm-up round; a time is the host clock
 between two device synchronisations around the whole pass, and the figure kept is the median of ``--rounds`` (5).  One more
-pass runs with a HIP event pair around every ``tls_fit`` call (its row lookup and ``cartnet_adp_tls_fit``'s two
-launches): the entry point's own share.  The flag-off pass is the parent commit's flag-on pass of
+pass runs with a HIP event pair around every ``tls_fit`` call (``cartnet_adp_tls_fit``'s two launches; the lookups are
+per batch): the entry point's own share.  The flag-off pass is the parent commit's flag-on pass of
 ``profiles/exp_rigid_molecule.json``; without ``--rigid_molecule`` nothing of this runs.  There is no threshold: the tool
 reports.
 

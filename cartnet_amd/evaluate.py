@@ -16,7 +16,7 @@ import torch
 
 from .metrics import (adp_eval, batch_graph, bond_test, compute_3D_IoU, edge_row_ptr, get_similarity_index, molecule_test,
                       molecules, rotate_rows, split_rows, target_row_ptr, tls_fit as tls_fit_call, to_host)
-from .predict import TLS_KEYS, frame_stage, tls_entries
+from .predict import STATISTICS, TLS_KEYS, Analyses, frame_stage, tls_entries
 from .shard import random_rotations
 
 # the keys of the two pickles in the order the reference's loops create them (a Monte-Carlo round stores no temperature)
@@ -69,29 +69,23 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
     per crystal (the reference's test loader has batch size 1, loader/loader.py:121).  The crystals carry no refcode /
     original temperature: those two lists stay empty.  ``rotations`` = K > 1: the prediction that is evaluated against the
     truth is the mean over K frames (``predict.frame_stage``; one generator seeded with ``seed`` for the whole pass); the
-    pickle then also has ``rot_spread`` per crystal, the result ``rotations`` and ``rot_spread_max``.  ``rigid_bond`` =
-    ``(tol, threshold)``: ``metrics.bond_test`` on the prediction and on the truth of every batch; the pickle then also has
-    ``bond_delta_max`` and ``bond_delta_max_true`` per crystal (one value per row), the result ``rigid_bond_mean`` and
-    ``rigid_bond_mean_true`` (the mean ``|D|`` over the directed bonds of the pass, 0 without bonds): the truth's figure is
-    the baseline the prediction's is to be compared with.  ``rigid_molecule`` = ``(tol, threshold)``: the molecules of
-    every batch (``metrics.molecules``, found once) and ``metrics.molecule_test`` on the prediction and on the truth; the
-    pickle then also has ``mol``, ``mol_size`` and ``mol_status`` and, per test, ``mol_pairs`` / ``mol_delta_max`` /
-    ``mol_over`` and the same with the suffix ``_true`` (one value per row), the result ``molecules``,
-    ``molecules_tested``, ``rigid_molecule_pairs`` and ``rigid_molecule_mean`` / ``_max`` / ``_over`` and those three with
-    the suffix ``_true`` (over the directed pairs of the pass, 0 without pairs).  ``tls_fit`` = ``True`` (with
-    ``rigid_molecule`` only; otherwise ``ValueError``): ``metrics.tls_fit`` on the prediction and on the truth, on the same
-    molecules; the pickle then also has the per-row keys of ``predict.TLS_KEYS`` (``tls_u``, ``tls_resid``, ``tls_T``, ...)
-    and the same with the suffix ``_true``, the result ``tls_molecules``, ``tls_rank_deficient``, ``tls_nonphysical``,
-    ``tls_r`` (over all fitted rows of the pass) and ``tls_resid_max``, the last four also with the suffix ``_true``: the
-    truth's ``tls_r_true`` is the baseline the prediction's is to be compared with."""
-    if tls_fit and rigid_molecule is None:
-        raise ValueError("tls_fit fits the molecules of rigid_molecule: it needs that keyword")
+    pickle then also has ``rot_spread`` per crystal, the result ``rotations`` and ``rot_spread_max``.  The analyses
+    (``predict.Analyses``: a ``tls_fit`` without ``rigid_molecule`` is a ``ValueError``) run on the prediction and on the
+    truth of every batch, the truth's figures -- suffix ``_true`` -- being the baseline the prediction's are to be
+    compared with; the result's figures are those of ``predict.STATISTICS`` over the pass.  ``rigid_bond`` =
+    ``(tol, threshold)``: ``metrics.bond_test``; the pickle then also has ``bond_delta_max`` / ``_true`` (one value per
+    row), the result ``rigid_bond_mean`` / ``_true``.  ``rigid_molecule`` = ``(tol, threshold)``: the molecules of every
+    batch (``metrics.molecules``, found once) and ``metrics.molecule_test``; the pickle then also has ``MOLECULE_KEYS``,
+    the result ``molecules``, ``molecules_tested``, ``rigid_molecule_pairs`` and ``rigid_molecule_mean`` / ``_max`` /
+    ``_over`` / those three ``_true``.  ``tls_fit`` = ``True``: ``metrics.tls_fit`` on the same molecules; the pickle then
+    also has ``TLS_ROW_KEYS`` / ``_true``, the result ``tls_molecules`` and ``tls_rank_deficient``, ``tls_nonphysical``,
+    ``tls_r``, ``tls_resid_max`` / those four ``_true``."""
+    Analyses(rigid_bond=rigid_bond, rigid_molecule=rigid_molecule, tls_fit=tls_fit).checked()
     model.eval()
     out = {k: [] for k in INFERENCE_KEYS}
-    gen = None
+    gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     if rotations > 1:
         out["rot_spread"] = []
-        gen = torch.Generator(device=device).manual_seed(seed)
     bond_sums = None                                      # [2,4] fp64 on the device: crystal_stats summed, prediction / truth
     if rigid_bond is not None:
         out["bond_delta_max"], out["bond_delta_max_true"] = [], []
@@ -149,21 +143,22 @@ def inference(model, loader, device, output_path: str, rotations: int = 1, seed:
     if rotations > 1:
         spread = torch.cat(out["rot_spread"])
         result.update(rotations=rotations, rot_spread_max=float(spread.max()) if spread.numel() else 0.0)
+    def figures(key: str, sums: list, highs: list, once: tuple, twice: tuple) -> None:
+        """The figures of predict.STATISTICS[key] from the column sums and maxima of the prediction and of the truth
+        (0 where none is kept): those of ``once`` for the prediction, those of ``twice`` for both, the truth's as *_true."""
+        pred, true = (STATISTICS[key][1](s, hi) for s, hi in zip(sums, highs))
+        result.update({k: pred[k] for k in once})
+        result.update({k + suffix: f[k] for suffix, f in (("", pred), ("_true", true)) for k in twice})
     if rigid_bond is not None:
-        (n_p, s_p, _, _), (n_t, s_t, _, _) = bond_sums.tolist()
-        result.update(rigid_bond_mean=s_p / n_p if n_p else 0.0, rigid_bond_mean_true=s_t / n_t if n_t else 0.0)
+        figures("bond_stats", bond_sums.tolist(), [[0.0] * 4] * 2, (), ("rigid_bond_mean",))
     if rigid_molecule is not None:
-        counts, sums, highest = mol_counts.tolist(), mol_sums.tolist(), mol_max.tolist()
-        result.update(molecules=int(counts[0]), molecules_tested=int(counts[1]), rigid_molecule_pairs=int(sums[0][0]))
-        for suffix, (n_pairs, s, _, n_over), hi in zip(("", "_true"), sums, highest):
-            result.update({"rigid_molecule_mean" + suffix: s / n_pairs if n_pairs else 0.0,
-                           "rigid_molecule_max" + suffix: hi, "rigid_molecule_over" + suffix: int(n_over)})
+        counts = mol_counts.tolist()
+        figures("mol_stats", [counts + s for s in mol_sums.tolist()], [[0.0] * 7 + [hi, 0.0] for hi in mol_max.tolist()],
+                ("molecules", "molecules_tested", "rigid_molecule_pairs"),
+                ("rigid_molecule_mean", "rigid_molecule_max", "rigid_molecule_over"))
     if tls_fit:
-        sums, highest = tls_sums.tolist(), tls_max.tolist()
-        result.update(tls_molecules=int(sums[0][0]))
-        for suffix, (_, deficient, negative, r2, s2), hi in zip(("", "_true"), sums, highest):
-            result.update({"tls_rank_deficient" + suffix: int(deficient), "tls_nonphysical" + suffix: int(negative),
-                           "tls_r" + suffix: (r2 / s2) ** 0.5 if s2 > 0 else 0.0, "tls_resid_max" + suffix: hi})
+        figures("tls_stats", [s + [0.0] for s in tls_sums.tolist()], [[0.0] * 5 + [hi] for hi in tls_max.tolist()],
+                ("tls_molecules",), ("tls_rank_deficient", "tls_nonphysical", "tls_r", "tls_resid_max"))
     return result
 
 

@@ -4,32 +4,17 @@
 not) one forward, one ``adp_export`` (csrc/export_ops.hip: the predictions on the unit reciprocal axes -- the inverse of the
 transform the reference applied to the dataset's targets, dataset/extract_csd_data.py:115-123 -- with U_eq and the
 principal values / axes), the fractional coordinates, ONE device-to-host copy (``metrics.to_host``) and a split by row
-counts on the host.  ``write_cif`` writes one crystal of the result as a P1 CIF.  For crystals that came from CIF files
-(``cartnet_amd.symmetry.expand``) the same copy also brings one site-averaged ADP per atom of the asymmetric unit, and
-``write_cif_symmetric`` writes the crystal in the file's own setting.  With ``rigid_bond`` the copy also brings Hirshfeld's
-rigid-bond figures of the exported ADPs (``metrics.bond_test``, csrc/bond_ops.hip): a plausibility report that needs no truth.
-With ``riding_h`` it brings an isotropic U for every hydrogen, a multiple of its parent's exported U_eq
-(``metrics.riding_h``, csrc/riding_ops.hip), and both writers fill ``_atom_site_U_iso_or_equiv`` for every atom.
-With ``temperatures`` every batch is predicted at T temperatures by one forward over a replica batch, the result has one
-entry per crystal and temperature, and the copy also brings a least-squares line per row through the T exports
-(``metrics.temp_series``, csrc/series_ops.hip).
-With ``rigid_molecule`` the copy also brings the molecules of every crystal -- the components of its bond graph, found on
-the GPU, with every atom's unwrapped position -- and the rigid-body test of the exported ADPs over all pairs of atoms of a
-molecule (``metrics.molecules``, ``metrics.molecule_test``, csrc/molecule_ops.hip).
-With ``tls_fit`` on top of that it brings the TLS fit of every molecule of five or more atoms: the rigid-body tensors T, L
-and S that explain the molecule's exported ADPs best, the ADP that rigid body gives every atom and what is left over
-(``metrics.tls_fit``, csrc/tls_ops.hip).
-With ``aniso_h`` on top of ``riding_h`` it brings a full tensor for every hydrogen -- its parent's exported tensor, the change
-of the molecule's fitted rigid-body motion from the parent to the hydrogen where ``tls_fit`` gave one, and a nominal internal
-X-H motion (``metrics.aniso_h``, csrc/aniso_h_ops.hip) -- and both writers give such a hydrogen an anisotropic row.
-Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in memory),
-``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the forward in K
-frames that this pass and ``evaluate.inference`` share.
+counts on the host.  What else the copy brings -- for crystals from CIF files, in K frames, at T temperatures, and for
+the five analyses of ``Analyses`` -- is stated once, in ``GROUPS``: a row per group of keys with its documentation.
+``write_cif`` writes one crystal of the result as a P1 CIF, ``write_cif_symmetric`` one that came from a CIF file in the
+file's own setting.  Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in
+memory), ``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the
+forward in K frames that this pass and ``evaluate.inference`` share.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -37,22 +22,156 @@ from .metrics import (adp_export, aniso_h as aniso_h_call, batch_graph, bond_tes
                       check_temperatures, edge_row_ptr, frame_mean, molecule_test, molecules as find_molecules, riding_h as riding_h_call,
                       rotate_rows, split_rows, target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
 
-KEYS = ("name", "atoms", "frac", "z", "cell", "temp", "u_cart", "u_cif", "u_eq", "principal", "axes", "stats")
-SYM_KEYS = ("asym_labels", "asym_frac", "asym_z", "u_cif_asym", "spread", "symops")      # with a CifSymmetry only
-ROT_KEYS = ("rot_spread", "frames", "rot_stats")                                          # with rotations > 1 only
-BOND_KEYS = ("bond_count", "bond_delta_mean", "bond_delta_max", "bond_worst", "bond_over", "bond_ueq_ratio",
-             "bond_stats")                                                                # with rigid_bond only
-H_KEYS = ("u_iso", "h_parent", "h_count", "h_mult", "h_stats")                            # with riding_h only
-H_SYM_KEYS = ("u_iso_asym", "h_parent_asym")                                              # ... and a CifSymmetry
-MOL_KEYS = ("mol", "mol_size", "mol_status", "mol_pos", "mol_pairs", "mol_delta_mean", "mol_delta_max", "mol_worst",
-            "mol_over", "mol_stats")                                                      # with rigid_molecule only
-TLS_KEYS = ("tls_u", "tls_resid", "tls_T", "tls_L", "tls_S", "tls_origin", "tls_T_principal", "tls_L_principal",
-            "tls_rank", "tls_r", "tls_stats")                                            # with tls_fit only
-AH_KEYS = ("h_u_cart", "h_u_cif", "h_u_eq", "h_source", "h_aniso_stats")               # with aniso_h only
-AH_SYM_KEYS = ("h_u_cif_asym",)                                                           # ... and a CifSymmetry
-SERIES_KEYS = ("t_slope", "t_intercept", "t_ueq_slope", "t_ueq_intercept", "t_resid", "t_drops", "t_stats")
-# with two or more temperatures the result has one more key, "series": a dict of lists, one entry per input crystal, with
-# "name", "temps" and SERIES_KEYS
+
+class Analyses(NamedTuple):
+    """The analyses of a pass that run on the bond graph, as ``predict_adps`` and ``evaluate.inference`` take them by
+    keyword; ``None`` is off.  Each one's row of ``GROUPS`` says what it adds."""
+    rigid_bond: Optional[tuple] = None                    # (tol, threshold)
+    riding_h: Optional[tuple] = None                      # (tol, f, f_rot)
+    rigid_molecule: Optional[tuple] = None                # (tol, threshold)
+    tls_fit: Optional[bool] = None                        # True, with rigid_molecule only
+    aniso_h: Optional[tuple] = None                       # (stretch, bend), with riding_h only
+
+    def checked(self) -> "Analyses":
+        """Itself, or ``ValueError`` for an analysis without the one it builds on."""
+        if self.tls_fit and self.rigid_molecule is None:
+            raise ValueError("tls_fit fits the molecules of rigid_molecule: it needs that keyword")
+        if self.aniso_h is not None and self.riding_h is None:
+            raise ValueError("aniso_h builds on the parents of riding_h: it needs that keyword")
+        return self
+
+
+class Group(NamedTuple):
+    """One group of keys of a result.  ``present(analyses, sym, rotations, temperatures)``: whether a pass has it;
+    ``cuts``: its keys in order, each with how it is cut into the crystals' entries -- a tensor that travels to the host
+    as one slice of dim 0 per "crystal", or as the pieces of dim 0 that hold a crystal's atoms ("atom"), its non-hydrogen
+    rows ("row") or the non-hydrogen atoms of its asymmetric unit ("site"); ``None``: assembled on the host; ``doc``: what
+    the keys hold."""
+    present: Callable
+    cuts: Dict[str, Optional[str]]
+    doc: str
+
+
+# Every key of a result, stated once, in the key order of a result (it is in the pickle's bytes); "series" is last because
+# its keys live in result["series"], which has one entry per input crystal.
+GROUPS: Dict[str, Group] = {
+    "base": Group(lambda a, sym, K, T: True,
+        {"name": None, "atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "temp": None, "u_cart": "row",
+         "u_cif": "row", "u_eq": "row", "principal": "row", "axes": "row", "stats": "crystal"},
+        """``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms the rows belong to); ``frac`` [N,3] and ``z`` [N]
+        (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the shard has none); ``u_cart`` [n,3,3] (the
+        model's output); ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12); ``u_eq`` [n]; ``principal`` [n,3] ascending;
+        ``axes`` [n,3,3]; ``stats`` [3] fp64 (sum of u_eq, smallest principal value, rows with a non-positive one)."""),
+    "symmetry": Group(lambda a, sym, K, T: sym,
+        {"asym_labels": None, "asym_frac": None, "asym_z": None, "u_cif_asym": "site", "spread": "site", "symops": None},
+        """``sym``: the ``CifSymmetry`` of a shard expanded from CIF files.  ``asym_labels`` / ``asym_frac`` [a,3] /
+        ``asym_z`` [a] (the asymmetric unit as the file gives it), ``symops`` (strings, identity first), ``u_cif_asym``
+        [h,6] (one row per non-hydrogen atom of the asymmetric unit, the mean over its orbit,
+        ``symmetry.site_average``) and ``spread`` [h]."""),
+    "rotations": Group(lambda a, sym, K, T: K > 1,
+        {"rot_spread": "row", "frames": "crystal", "rot_stats": "crystal"},
+        """``rotations`` = K > 1: every batch is predicted in K frames by ONE forward of ``replicate(batch, K, R)``
+        with ``R = frames(B, K, gen, device)`` (one generator seeded with ``seed`` for the whole pass), the members are
+        brought back and averaged (``metrics.frame_mean``), and everything else derives from that mean: ``u_cart`` is
+        the mean.  ``rot_spread`` [n] (per row the largest deviation of a frame's prediction from the mean), ``frames``
+        [K,3,3] (the rotations used, the identity first) and ``rot_stats`` [2] fp64 (sum and maximum of
+        ``rot_spread``)."""),
+    "rigid_bond": Group(lambda a, sym, K, T: a.rigid_bond is not None,
+        {"bond_count": "row", "bond_delta_mean": "row", "bond_delta_max": "row", "bond_worst": "row", "bond_over": "row",
+         "bond_ueq_ratio": "row", "bond_stats": "crystal"},
+        """``rigid_bond`` = ``(tol, threshold)``: Hirshfeld's rigid-bond test, one ``metrics.bond_test``
+        (csrc/bond_ops.hip) per exported ``u_cart`` (with rotations the frame mean; with CIF input the rows of the
+        expanded cell, before site averaging): a plausibility report that needs no truth.  ``bond_count`` [n],
+        ``bond_delta_mean`` [n] (mean ``|D|`` over the atom's bonds, 0 without bonds), ``bond_delta_max`` [n],
+        ``bond_worst`` [n] (the partner of the worst bond as an atom index inside the crystal, -1 without bonds),
+        ``bond_over`` [n], ``bond_ueq_ratio`` [n] and ``bond_stats`` [4] fp64 (directed bonds, sum of ``|D|``, largest
+        ``|D|``, bonds over the threshold)."""),
+    "riding_h": Group(lambda a, sym, K, T: a.riding_h is not None,
+        {"u_iso": "atom", "h_parent": "atom", "h_count": "atom", "h_mult": "atom", "h_stats": "crystal"},
+        """``riding_h`` = ``(tol, f, f_rot)``: one ``metrics.riding_h`` (csrc/riding_ops.hip) per exported ``u_eq``
+        (with rotations the frame mean's); both CIF writers then fill ``_atom_site_U_iso_or_equiv`` for every atom.
+        ``u_iso`` [N] (every atom: a hydrogen's ``mult * u_eq[parent]``, NaN for an orphan; a non-hydrogen atom's own
+        ``u_eq``), ``h_parent`` [N] (an atom index inside the crystal, -1 where there is none), ``h_count`` [N]
+        (hydrogens riding on a non-hydrogen atom), ``h_mult`` [N] and ``h_stats`` [4] fp64 (hydrogens, orphans, sum of
+        the finite hydrogen ``u_iso``, hydrogens with a non-positive parent ``u_eq``)."""),
+    "riding_h_symmetry": Group(lambda a, sym, K, T: a.riding_h is not None and sym,
+        {"u_iso_asym": None, "h_parent_asym": None},
+        """``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``)."""),
+    "rigid_molecule": Group(lambda a, sym, K, T: a.rigid_molecule is not None,
+        {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "row", "mol_pairs": "row",
+         "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"},
+        """``rigid_molecule`` = ``(tol, threshold)``: per batch one ``metrics.molecules`` (the components of the bond
+        graph with every atom's unwrapped position; they do not depend on U, so they are found once for all T) and one
+        ``metrics.molecule_test`` (csrc/molecule_ops.hip) per exported ``u_cart``, as for ``rigid_bond`` and with the
+        stored ``cart_dir``: the rigid-body test over all pairs of atoms of a molecule.  ``mol`` [n] (the row's
+        molecule, numbered inside the crystal), ``mol_size`` [n], ``mol_status`` [n] (bit 1 periodic, bit 2 open),
+        ``mol_pos`` [n,3] fp32 (the atom's unwrapped position relative to its molecule's lowest atom; NaN where the
+        status is not 0), ``mol_pairs`` [n], ``mol_delta_mean`` [n], ``mol_delta_max`` [n], ``mol_worst`` [n] (an atom
+        index inside the crystal, -1 without pairs), ``mol_over`` [n] and ``mol_stats`` [9] fp64 (molecules, tested,
+        periodic, open, largest size; directed pairs, sum of ``|D|``, largest ``|D|``, pairs over the threshold)."""),
+    "tls_fit": Group(lambda a, sym, K, T: bool(a.tls_fit),
+        {"tls_u": "row", "tls_resid": "row", "tls_T": "row", "tls_L": "row", "tls_S": "row", "tls_origin": "row",
+         "tls_T_principal": "row", "tls_L_principal": "row", "tls_rank": "row", "tls_r": "row", "tls_stats": "crystal"},
+        """``tls_fit`` = ``True`` (with ``rigid_molecule`` only): one ``metrics.tls_fit`` (csrc/tls_ops.hip) beside
+        every ``molecule_test``: the rigid-body tensors T, L and S that explain the ADPs of a molecule of five or more
+        atoms best.  ``tls_u`` [n,3,3] (the ADP the fitted rigid body gives the atom), ``tls_resid`` [n] (``|Sym u_cart
+        - tls_u|_F``) and, repeated on every row of a molecule, ``tls_T`` / ``tls_L`` / ``tls_S`` [n,3,3] (A^2, rad^2,
+        rad A, about ``tls_origin``), ``tls_origin`` [n,3] (the centroid in the frame of ``mol_pos``),
+        ``tls_T_principal`` / ``tls_L_principal`` [n,3] ascending, ``tls_rank`` [n] (20: all parameters determined;
+        less: the minimum-norm representative; 0: not fitted; -1: no convergence) and ``tls_r`` [n] (the molecule's
+        ``sqrt(sum resid^2 / sum |Sym U|^2)``), and ``tls_stats`` [6] fp64 (fitted molecules, rank-deficient ones, ones
+        with a negative principal value, sum of ``resid^2``, sum of ``|Sym U|^2`` over the fitted rows, largest
+        ``resid``).  Rows of molecules that are not fitted (status not 0, fewer than five atoms) hold NaN, ``tls_resid``
+        / ``tls_rank`` / ``tls_r`` 0."""),
+    "aniso_h": Group(lambda a, sym, K, T: a.aniso_h is not None,
+        {"h_u_cart": "atom", "h_u_cif": "atom", "h_u_eq": "atom", "h_source": "atom", "h_aniso_stats": "crystal"},
+        """``aniso_h`` = ``(stretch, bend)`` (with ``riding_h`` only): one ``metrics.aniso_h`` (csrc/aniso_h_ops.hip)
+        wherever ``riding_h`` runs, with the TLS fit of the same ``u_cart`` when ``tls_fit`` is on (without it every
+        hydrogen with a parent has source 2), then one ``adp_export`` over atoms as rows; both CIF writers then give
+        such a hydrogen an anisotropic row.  Per ATOM: ``h_u_cart`` [N,3,3] (a non-hydrogen atom's own row; a hydrogen's
+        tensor: its parent's plus the change of the fitted rigid-body motion from the parent to the hydrogen plus
+        ``stretch`` along and ``bend`` across the X-H bond; NaN without one), ``h_u_cif`` [N,6], ``h_u_eq`` [N],
+        ``h_source`` [N] (0 none, 1 own row, 2 parent, 3 parent and TLS, 4 parent and a rank-deficient TLS) and
+        ``h_aniso_stats`` [4] fp64 (hydrogens with a tensor, those with source >= 3, the sum of their ``trace / 3``,
+        those not positive definite)."""),
+    "aniso_h_symmetry": Group(lambda a, sym, K, T: a.aniso_h is not None and sym,
+        {"h_u_cif_asym": None},
+        """``h_u_cif_asym`` [a,6] per atom of the asymmetric unit (``aniso_asym``: a hydrogen's is the listed image's,
+        not an orbit mean)."""),
+    "series": Group(lambda a, sym, K, T: T is not None and len(T) >= 2,
+        {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t_ueq_intercept": "row", "t_resid": "row",
+         "t_drops": "row", "t_stats": "crystal"},
+        """``temperatures`` = T >= 1 Kelvin values (strictly increasing, finite, > 0; otherwise ``ValueError``): every
+        batch is predicted at all of them by ONE forward of ``replicate_temperatures`` (with ``rotations`` = K that
+        forward holds ``T*K*B`` crystals, and the T temperatures share the batch's K frames), the model-side value of
+        ``T_t`` being ``standardised`` with the loader's ``temp_mean`` / ``temp_std``; the stored temperatures are not
+        read.  The result then has one entry per (crystal, temperature), crystal-major -- entry ``g*T + t`` -- with
+        ``temp`` = ``T_t`` as given and ``name`` = ``f"{name}_{T_t:g}K"``; every analysis runs once per temperature.
+        With T >= 2 it has one more key, ``series``: a dict of lists with one entry per input crystal, in the loader's
+        order -- ``name`` (unsuffixed), ``temps`` [T] fp32 and, from one ``metrics.temp_series`` (csrc/series_ops.hip)
+        per batch on the exported ``u_cif`` / ``u_eq`` (with rotations the frame means'), ``t_slope`` [n,6] (A^2/K) and
+        ``t_intercept`` [n,6] of ``u_cif``, ``t_ueq_slope`` [n], ``t_ueq_intercept`` [n], ``t_resid`` [n], ``t_drops``
+        [n] int32 and ``t_stats`` [4] fp64 (sum of ``t_ueq_slope``, rows whose U_eq slope is not > 0, rows with a drop,
+        largest ``t_resid``)."""),
+}
+(KEYS, SYM_KEYS, ROT_KEYS, BOND_KEYS, H_KEYS, H_SYM_KEYS, MOL_KEYS, TLS_KEYS, AH_KEYS, AH_SYM_KEYS,
+ SERIES_KEYS) = (tuple(g.cuts) for g in GROUPS.values())
+
+
+def _cuts(*names: str) -> Dict[str, str]:
+    return {k: c for name in names or GROUPS for k, c in GROUPS[name].cuts.items() if c is not None}
+
+
+# the cuts under the names they have always had (tests/test_cif_writers_golden.py holds SPLIT to these five); CUT: all
+SPLIT, CUT = _cuts("base", "symmetry", "rotations", "rigid_bond", "riding_h"), _cuts()
+SERIES_SPLIT, MOL_SPLIT, TLS_SPLIT, AH_SPLIT = _cuts("series"), _cuts("rigid_molecule"), _cuts("tls_fit"), _cuts("aniso_h")
+
+
+def result_keys(analyses: Analyses, sym: bool, rotations: int) -> tuple:
+    """The keys of a ``predict_adps`` result in its order (``sym``: whether the pass has a ``CifSymmetry``); ``series``,
+    which a pass at two or more temperatures adds at the end, is not among them."""
+    return tuple(k for g in GROUPS.values() if g.present(analyses, sym, rotations, None) for k in g.cuts)
+
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -123,15 +242,32 @@ def frame_stage(model, batch, row_ptr: torch.Tensor, rotations: int, gen, stats:
     ``metrics.frame_mean`` (``stats``: its per-crystal figures as well).  Returns ``(pred, R, FrameMean)``, the last two
     ``None`` for K = 1; ``batch`` comes back with its atomic numbers in ``x`` (a forward puts the features there: it
     replaces the tensor and writes into nothing, so no copy is taken)."""
-    if rotations == 1:
+    members, R = _forward(model, batch, rotations, gen)
+    pred, fm = _frame_mean(members, R, row_ptr, stats)
+    return pred, R, fm
+
+
+def _forward(model, batch, rotations: int, gen, temps: Optional[torch.Tensor] = None):
+    """ONE forward of ``batch`` in ``rotations`` = K frames and, with ``temps`` (``standardised``), at its T temperatures:
+    ``(members, R)``, the predictions of the ``T*K`` replicas (temperature-major, then frame) and the frames drawn from
+    ``gen``, ``None`` for K = 1.  Without ``temps`` and at K = 1 it is the plain forward of the batch as collated."""
+    R = frames(int(batch.num_graphs), rotations, gen, batch.x.device) if rotations > 1 else None
+    if temps is None and R is None:
         atoms = batch.x
-        pred, _ = model(batch)
+        members, _ = model(batch)
         batch.x = atoms
-        return pred, None, None
-    R = frames(int(batch.num_graphs), rotations, gen, batch.x.device)
-    members, _ = model(replicate(batch, rotations, R))                        # batch.x stays: the replica's is overwritten
+        return members, None
+    replica = replicate(batch, rotations, R) if temps is None else replicate_temperatures(batch, temps, rotations, R)
+    return model(replica)[0], R                                               # batch.x stays: the replica's is overwritten
+
+
+def _frame_mean(members: torch.Tensor, R: Optional[torch.Tensor], row_ptr: torch.Tensor, stats: bool):
+    """``(prediction, FrameMean)`` of one temperature's ``members`` in the frames ``R``: their ``metrics.frame_mean``, or
+    the members themselves and ``None`` without frames."""
+    if R is None:
+        return members, None
     fm = frame_mean(members, R, row_ptr, stats=stats)
-    return fm.mean, R, fm
+    return fm.mean, fm
 
 
 def parse_temperatures(spec: str) -> list:
@@ -307,29 +443,6 @@ def riding_asym(name: str, asym_z, z, h_parent, h_mult, parent_asym, u_eq_sites)
     return torch.where(heavy, own, of_parent).to(torch.float32), pa
 
 
-# How every key of the result that travels to the host as a tensor is cut into the crystals' entries: one slice of dim 0
-# per "crystal", or the pieces of dim 0 that hold a crystal's atoms ("atom"), its non-hydrogen rows ("row") or the
-# non-hydrogen atoms of its asymmetric unit ("site").  The other keys of the result are assembled on the host.
-SPLIT = {"atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "u_cart": "row", "u_cif": "row", "u_eq": "row",
-         "principal": "row", "axes": "row", "stats": "crystal",
-         "u_cif_asym": "site", "spread": "site",
-         "rot_spread": "row", "frames": "crystal", "rot_stats": "crystal",
-         "bond_count": "row", "bond_delta_mean": "row", "bond_delta_max": "row", "bond_worst": "row", "bond_over": "row",
-         "bond_ueq_ratio": "row", "bond_stats": "crystal",
-         "u_iso": "atom", "h_parent": "atom", "h_count": "atom", "h_mult": "atom", "h_stats": "crystal"}
-# The same for the keys of result["series"], which has one entry per input crystal: a table of its own, because SPLIT is
-# exactly the tensor keys of an entry (tests/test_cif_writers_golden.py holds it to that).
-SERIES_SPLIT = {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t_ueq_intercept": "row", "t_resid": "row",
-                "t_drops": "row", "t_stats": "crystal"}
-# ... and for MOL_KEYS: only "row" and "crystal" keys
-MOL_SPLIT = {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "row", "mol_pairs": "row",
-             "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"}
-# ... and for TLS_KEYS
-TLS_SPLIT = {**{k: "row" for k in TLS_KEYS}, "tls_stats": "crystal"}
-# ... and for AH_KEYS: per atom, not per row
-AH_SPLIT = {**{k: "atom" for k in AH_KEYS}, "h_aniso_stats": "crystal"}
-
-
 def _check_pass(loader, rotations: int):
     """What ``predict_adps`` requires of its arguments; returns the loader's shard."""
     if rotations < 1:
@@ -365,62 +478,76 @@ def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
             "frac": (batch.pos.unsqueeze(1) @ _inverse_cells(batch.cell)[batch.batch]).squeeze(1)}
 
 
-def _device_stage(model, batch, shard, sym, rotations: int, gen, rigid_bond, riding_h, rigid_molecule=None,
-                  tls_fit=None, aniso_h=None) -> dict:
-    """One batch (on the device) through the forward and the kernels that follow it.  Returns what travels to the host in
-    one ``to_host``: tensors under their key of ``SPLIT`` (``MOL_SPLIT``), and under names with a leading underscore what
+def _device_stage(model, batch, shard, sym, rotations: int, gen, analyses: Analyses, kelvin: Optional[list] = None,
+                  temps: Optional[torch.Tensor] = None) -> dict:
+    """One batch (on the device) through ONE forward (``_forward``; with the T temperatures ``kelvin``, ``temps`` are their
+    model-side values) and the kernels that follow it, those once per temperature on that temperature's rows.  Returns
+    what travels to the host in one ``to_host``: what does not depend on the prediction under its key of ``CUT``, the
+    keys of prediction t (the only one without temperatures) under ``"<key>@<t>"``, with T >= 2 the keys of
+    ``SERIES_KEYS`` (one ``temp_series`` call on the T exports), and under names with a leading underscore what
     ``_host_stage`` needs to cut and check them."""
+    T = 1 if kelvin is None else len(kelvin)
     row_ptr = target_row_ptr(batch)
     dev = _of_the_batch(batch, row_ptr)
-    if "temperature" in shard.t:
+    if kelvin is None and "temperature" in shard.t:
         dev["_temp"] = shard.t["temperature"][dev["_sel"]]                    # the collated one is standardised
-    pred, R, fm = frame_stage(model, batch, row_ptr, rotations, gen, stats=True)
-    if fm is not None:
-        dev.update(rot_spread=fm.spread, frames=R.transpose(0, 1), rot_stats=fm.crystal_spread)
-    graph, mo = _of_the_graph(batch, row_ptr, int(pred.shape[0]), rigid_bond, riding_h, rigid_molecule)
-    dev.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, graph, mo, rigid_molecule, tls_fit, aniso_h))
+    members, R = _forward(model, batch, rotations, gen, temps)
+    if R is not None:
+        dev["frames"] = R.transpose(0, 1)
+    rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
+    graph, mo = _of_the_graph(batch, row_ptr, rows // rotations, analyses)    # once for all T
+    per = []
+    for t in range(T):
+        pred, fm = _frame_mean(members[t * rows:(t + 1) * rows], R, row_ptr, stats=True)
+        d = {} if fm is None else {"rot_spread": fm.spread, "rot_stats": fm.crystal_spread}
+        d.update(_exported(pred, batch, row_ptr, sym, analyses, graph, mo))
+        per.append(d)
+        dev.update({f"{k}@{t}": v for k, v in d.items()})
+    if T >= 2:
+        ts = temp_series(torch.cat([d["u_cif"] for d in per]), torch.cat([d["u_eq"] for d in per]), kelvin, row_ptr)
+        dev.update(zip(SERIES_KEYS, ts))                                      # the fields of a TempSeries, in their order
     return dev
 
 
-def _of_the_graph(batch, row_ptr: torch.Tensor, rows: int, rigid_bond, riding_h, rigid_molecule):
-    """``(metrics.BatchGraph of the batch, its metrics.Molecules)``, each ``None`` unless a flag needs it: what the analyses
-    of ``_exported`` share and what does not depend on U, so checked, built and found once per batch (its atomic numbers in
-    ``x``), however many predictions of it follow."""
-    if rigid_bond is None and riding_h is None and rigid_molecule is None:
+def _of_the_graph(batch, row_ptr: torch.Tensor, rows: int, analyses: Analyses):
+    """``(metrics.BatchGraph of the batch, its metrics.Molecules)``, each ``None`` unless an analysis needs it: what the
+    analyses of ``_exported`` share and what does not depend on U, so checked, built and found once per batch (its atomic
+    numbers in ``x``), however many predictions of it follow."""
+    if analyses.rigid_bond is None and analyses.riding_h is None and analyses.rigid_molecule is None:
         return None, None
     graph = batch_graph(batch, rows, "predict_adps")
-    return graph, None if rigid_molecule is None else find_molecules(graph, row_ptr, rigid_molecule[0])
+    return graph, None if analyses.rigid_molecule is None else find_molecules(graph, row_ptr, analyses.rigid_molecule[0])
 
 
-def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond, riding_h, graph=None, mo=None,
-              rigid_molecule=None, tls_fit=None, aniso_h=None) -> dict:
-    """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch``: the export and, as asked for
-    and on ``graph`` and ``mo`` (``_of_the_graph``), the rigid-bond test, the rigid-body test (and the TLS fit) on the
-    molecules, the riding hydrogens (and their tensors, with the TLS fit if there is one) and the site average."""
+def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, analyses: Analyses, graph=None, mo=None) -> dict:
+    """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch``: the export and, as
+    ``analyses`` asks and on ``graph`` and ``mo`` (``_of_the_graph``), the rigid-bond test, the rigid-body test (and the
+    TLS fit) on the molecules, the riding hydrogens (and their tensors, with the TLS fit if there is one) and the site
+    average."""
     device = batch.x.device
     B = int(batch.num_graphs)
     sel = batch._meta[:B]
     ex = adp_export(pred, row_ptr, batch.cell, axes=True, stats=True, check=False)
     dev = dict(u_cart=pred, u_cif=ex.u_cif, u_eq=ex.u_eq, principal=ex.principal, axes=ex.axes,
                stats=ex.crystal_stats, _status=ex.status)
-    if rigid_bond is not None:
-        dev.update(bond_entries(bond_test(pred, graph, row_ptr, *rigid_bond), batch))
+    if analyses.rigid_bond is not None:
+        dev.update(bond_entries(bond_test(pred, graph, row_ptr, *analyses.rigid_bond), batch))
     tf = None
     if mo is not None:
-        dev.update(molecule_entries(mo, molecule_test(pred, graph, row_ptr, mo, rigid_molecule[1]), batch))
-        if tls_fit:
+        dev.update(molecule_entries(mo, molecule_test(pred, graph, row_ptr, mo, analyses.rigid_molecule[1]), batch))
+        if analyses.tls_fit:
             tf = tls_fit_call(pred, graph, row_ptr, mo)
             dev.update(tls_entries(tf))
-    if riding_h is not None:
-        rh = riding_h_call(ex.u_eq, graph, *riding_h)
+    if analyses.riding_h is not None:
+        rh = riding_h_call(ex.u_eq, graph, *analyses.riding_h)
         dev.update(riding_entries(rh, batch))
-        if aniso_h is not None:
-            ah = aniso_h_call(pred, graph, row_ptr, rh, mo if tf is not None else None, tf, *aniso_h)
+        if analyses.aniso_h is not None:
+            ah = aniso_h_call(pred, graph, row_ptr, rh, mo if tf is not None else None, tf, *analyses.aniso_h)
             dev.update(aniso_entries(ah, batch))
     if sym is not None:
         from .symmetry import site_average
         dev["u_cif_asym"], dev["spread"] = site_average(pred, row_ptr, batch._sel, sym)
-        if riding_h is not None:                                              # what riding_asym takes, per site and per atom
+        if analyses.riding_h is not None:                                     # what riding_asym takes, per site and per atom
             counts = torch.from_numpy(sym.site_count[batch._sel]).to(device)
             crystal = torch.repeat_interleave(torch.arange(B, device=device), counts,
                                               output_size=int(dev["u_cif_asym"].shape[0]))
@@ -429,86 +556,49 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, rigid_bond,
     return dev
 
 
-def _device_stage_series(model, batch, sym, rotations: int, gen, rigid_bond, riding_h, kelvin: list,
-                         temps: torch.Tensor, rigid_molecule=None, tls_fit=None, aniso_h=None) -> dict:
-    """One batch (on the device) at the T temperatures ``kelvin`` (``temps``: their model-side values, ``standardised``)
-    through ONE forward of ``replicate_temperatures`` and the kernels that follow it, those once per temperature on that
-    temperature's rows.  Returns what travels to the host in one ``to_host``: what does not depend on the temperature
-    under the names of ``_device_stage``, the keys of temperature t under ``"<key>@<t>"`` and, with T >= 2, the keys of
-    ``SERIES_KEYS`` (one ``temp_series`` call on the T exports)."""
-    B, T = int(batch.num_graphs), len(kelvin)
-    row_ptr = target_row_ptr(batch)
-    dev = _of_the_batch(batch, row_ptr)
-    R = frames(B, rotations, gen, batch.x.device) if rotations > 1 else None
-    members, _ = model(replicate_temperatures(batch, temps, rotations, R))    # batch.x stays: the replica's is overwritten
-    if R is not None:
-        dev["frames"] = R.transpose(0, 1)
-    rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
-    graph, mo = _of_the_graph(batch, row_ptr, rows // rotations, rigid_bond, riding_h, rigid_molecule)   # once for all T
-    per = []
+def _host_stage(out: Dict[str, List], series: Dict[str, List], host: dict, shard, sym, kelvin: Optional[list] = None) -> None:
+    """Appends the entries of one batch to ``out`` from the host copy of ``_device_stage``'s dict: one ``_entries`` per
+    prediction on its keys, the entries crystal-major (crystal g at temperature t is entry ``g*T + t`` of the batch), and
+    with T >= 2 the batch's crystals to ``series``."""
+    T = 1 if kelvin is None else len(kelvin)
+    shared = {k: v for k, v in host.items() if "@" not in k and k not in SERIES_SPLIT}
+    stage = [out] if T == 1 else [{k: [] for k in out} for _ in range(T)]
     for t in range(T):
-        pred, d = members[t * rows:(t + 1) * rows], {}
-        if R is not None:
-            fm = frame_mean(pred, R, row_ptr, stats=True)
-            pred = fm.mean
-            d.update(rot_spread=fm.spread, rot_stats=fm.crystal_spread)
-        d.update(_exported(pred, batch, row_ptr, sym, rigid_bond, riding_h, graph, mo, rigid_molecule, tls_fit, aniso_h))
-        per.append(d)
-        dev.update({f"{k}@{t}": v for k, v in d.items()})
-    if T >= 2:
-        ts = temp_series(torch.cat([d["u_cif"] for d in per]), torch.cat([d["u_eq"] for d in per]), kelvin, row_ptr)
-        dev.update(t_slope=ts.slope, t_intercept=ts.intercept, t_ueq_slope=ts.ueq_slope,
-                   t_ueq_intercept=ts.ueq_intercept, t_resid=ts.resid, t_drops=ts.drops, t_stats=ts.crystal_stats)
-    return dev
-
-
-def _host_stage_series(out: Dict[str, List], series: Dict[str, List], host: dict, shard, sym, kelvin: list) -> None:
-    """Appends the entries of one batch to ``out``, crystal-major (crystal g at temperature t is entry ``g*T + t`` of the
-    batch), and its crystals to ``series``, from the host copy of ``_device_stage_series``'s dict: one ``_host_stage`` per
-    temperature on that temperature's keys."""
-    T = len(kelvin)
-    shared = {k: v for k, v in host.items() if "@" not in k and k not in SERIES_KEYS}
-    B = int(shared["_sel"].shape[0])
-    per = []
-    for t, kt in enumerate(kelvin):
         mine = {k.rpartition("@")[0]: v for k, v in host.items() if k.endswith(f"@{t}")}
-        mine["_temp"] = torch.full((B,), kt, dtype=torch.float64)             # .tolist(): the Kelvin value as given
-        per.append({k: [] for k in out})
-        names, counts = _host_stage(per[t], {**shared, **mine}, shard, sym)
-    for g in range(B):
-        for t, kt in enumerate(kelvin):
-            for k in out:
-                out[k].append(f"{per[t][k][g]}_{kt:g}K" if k == "name" else per[t][k][g])
+        names, counts = _entries(stage[t], {**shared, **mine}, shard, sym, None if kelvin is None else kelvin[t])
     if T >= 2:
-        _split(series, {k: host[k] for k in SERIES_KEYS}, counts, SERIES_SPLIT)
+        for g in range(len(names)):
+            for per in stage:
+                for k in out:
+                    out[k].append(per[k][g])
+        _split(series, {k: host[k] for k in SERIES_KEYS}, counts)
         series["name"] += names
         series["temps"] += [torch.tensor(kelvin, dtype=torch.float32) for _ in names]
 
 
-def _split(out: Dict[str, List], host: dict, counts: dict, table: dict = SPLIT) -> None:
-    """Appends to ``out[k]`` the crystals' pieces of every host tensor ``host[k]``, cut as ``table[k]`` says."""
+def _split(out: Dict[str, List], host: dict, counts: dict) -> None:
+    """Appends to ``out[k]`` the crystals' pieces of every host tensor ``host[k]``, cut as ``CUT[k]`` says."""
     for k, t in host.items():
-        kind = table[k]
+        kind = CUT[k]
         out[k] += [c.clone() for c in t.unbind(0)] if kind == "crystal" else split_rows(t, counts[kind])
 
 
-def _host_stage(out: Dict[str, List], host: dict, shard, sym):
-    """Appends the crystals of one batch to ``out`` from the host copy of ``_device_stage``'s dict.  Returns the crystals'
-    names and their counts of rows, atoms and sites."""
+def _entries(out: Dict[str, List], host: dict, shard, sym, kelvin: Optional[float] = None):
+    """Appends the crystals of one batch to ``out`` from the host copy of one prediction of it; ``kelvin``: the
+    temperature it was predicted at, which then is its ``temp`` and the suffix of its ``name``, instead of the stored
+    one.  Returns the crystals' names (as stored) and their counts of rows, atoms and sites."""
     ids = host.pop("_sel").tolist()
     names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
     check_export_status(host.pop("_status"), names)
     rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
     counts = {"row": (rp[1:] - rp[:-1]).tolist(), "atom": (ap[1:] - ap[:-1]).tolist(),
               "site": [int(sym.site_count[i]) for i in ids] if sym is not None else None}
-    out["name"] += names
-    out["temp"] += host.pop("_temp").tolist() if "_temp" in host else [float("nan")] * len(ids)
+    stored = host.pop("_temp").tolist() if "_temp" in host else [float("nan")] * len(ids)
+    out["temp"] += stored if kelvin is None else [kelvin] * len(ids)          # the Kelvin value as given
+    out["name"] += names if kelvin is None else [f"{name}_{kelvin:g}K" for name in names]
     riding = "_ueq_asym" in host                                              # what riding_asym takes, per site and per atom
     ueq_sites = split_rows(host.pop("_ueq_asym"), counts["site"]) if riding else None
     parents = split_rows(host.pop("_parent_asym"), counts["atom"]) if riding else None
-    _split(out, {k: host.pop(k) for k in MOL_KEYS if k in host}, counts, MOL_SPLIT)
-    _split(out, {k: host.pop(k) for k in TLS_KEYS if k in host}, counts, TLS_SPLIT)
-    _split(out, {k: host.pop(k) for k in AH_KEYS if k in host}, counts, AH_SPLIT)
     _split(out, host, counts)
     if sym is not None:
         out["asym_labels"] += [sym.labels[i] for i in ids]
@@ -530,109 +620,32 @@ def _host_stage(out: Dict[str, List], host: dict, shard, sym):
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
                  temperatures=None, rigid_molecule=None, tls_fit=None, aniso_h=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
-    dict of lists with one entry per crystal, in the loader's order: ``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms
-    the rows belong to); ``frac`` [N,3] and ``z`` [N] (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the
-    shard has none); ``u_cart`` [n,3,3] (the model's output); ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12); ``u_eq`` [n];
-    ``principal`` [n,3] ascending; ``axes`` [n,3,3]; ``stats`` [3] fp64 (sum of u_eq, smallest principal value, rows with a
-    non-positive one).  A singular cell raises ``ValueError`` naming the crystal.  ``sym``: the ``CifSymmetry`` of a shard
-    expanded from CIF files; the result then also has, per crystal, ``asym_labels`` / ``asym_frac`` [a,3] / ``asym_z`` [a]
-    (the asymmetric unit as the file gives it), ``symops`` (strings, identity first), ``u_cif_asym`` [h,6] (one row per
-    non-hydrogen atom of the asymmetric unit, the mean over its orbit, ``symmetry.site_average``) and ``spread`` [h].
-    ``rotations`` = K > 1: every batch is predicted in K frames by ONE forward of ``replicate(batch, K, R)`` with
-    ``R = frames(B, K, gen, device)`` (one generator seeded with ``seed`` for the whole pass), the members are brought back
-    and averaged (``metrics.frame_mean``), and everything above derives from that mean: ``u_cart`` is the mean.  The result
-    then also has, per crystal, ``rot_spread`` [n] (per row the largest deviation of a frame's prediction from the mean),
-    ``frames`` [K,3,3] (the rotations used, the identity first) and ``rot_stats`` [2] fp64 (sum and maximum of
-    ``rot_spread``).  ``rotations`` = 1 is the pass as it always was.  ``rigid_bond`` = ``(tol, threshold)``: one
-    ``metrics.bond_test`` per batch on the ``u_cart`` that is exported (with rotations the frame mean; with CIF input the
-    rows of the expanded cell, before site averaging), travelling in the same copy.  The result then also has, per crystal,
-    ``bond_count`` [n], ``bond_delta_mean`` [n] (mean ``|D|`` over the atom's bonds, 0 without bonds), ``bond_delta_max``
-    [n], ``bond_worst`` [n] (the partner of the worst bond as an atom index inside the crystal, -1 without bonds),
-    ``bond_over`` [n], ``bond_ueq_ratio`` [n] and ``bond_stats`` [4] fp64 (directed bonds, sum of ``|D|``, largest ``|D|``,
-    bonds over the threshold).  ``None`` is the pass as it always was.  ``riding_h`` = ``(tol, f, f_rot)``: one
-    ``metrics.riding_h`` per batch on the ``u_eq`` that is exported (with rotations the frame mean's), travelling in the same
-    copy.  The result then also has, per crystal, ``u_iso`` [N] (every atom: a hydrogen's ``mult * u_eq[parent]``, NaN for
-    an orphan; a non-hydrogen atom's own ``u_eq``), ``h_parent`` [N] (an atom index inside the crystal, -1 where there is
-    none), ``h_count`` [N] (hydrogens riding on a non-hydrogen atom), ``h_mult`` [N] and ``h_stats`` [4] fp64 (hydrogens,
-    orphans, sum of the finite hydrogen ``u_iso``, hydrogens with a non-positive parent ``u_eq``); with ``sym`` also
-    ``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``).  ``None`` is the pass
-    as it always was.  ``temperatures`` = T >= 1 Kelvin values (strictly increasing, finite, > 0; otherwise ``ValueError``):
-    every batch is predicted at all of them by ONE forward of ``replicate_temperatures`` (with ``rotations`` = K that forward
-    holds ``T*K*B`` crystals, and the T temperatures share the batch's K frames), the model-side value of ``T_t`` being
-    ``standardised`` with the loader's ``temp_mean`` / ``temp_std``; the stored temperatures are not read.  The result then
-    has one entry per (crystal, temperature), crystal-major -- entry ``g*T + t`` -- each with the keys and shapes above,
-    ``temp`` = ``T_t`` as given and ``name`` = ``f"{name}_{T_t:g}K"``.  With T >= 2 it has one more key, ``series``: a dict
-    of lists with one entry per input crystal, in the loader's order -- ``name`` (unsuffixed), ``temps`` [T] fp32 and, from
-    one ``metrics.temp_series`` per batch on the exported ``u_cif`` / ``u_eq`` (with rotations the frame means'),
-    ``t_slope`` [n,6] (A^2/K) and ``t_intercept`` [n,6] of ``u_cif``, ``t_ueq_slope`` [n], ``t_ueq_intercept`` [n],
-    ``t_resid`` [n], ``t_drops`` [n] int32 and ``t_stats`` [4] fp64 (sum of ``t_ueq_slope``, rows whose U_eq slope is not
-    > 0, rows with a drop, largest ``t_resid``).  ``None`` is the pass as it always was.  ``rigid_molecule`` =
-    ``(tol, threshold)``: per batch one ``metrics.molecules`` (the components of the bond graph; they do not depend on U,
-    so with temperatures they are found once for all T) and one ``metrics.molecule_test`` per exported ``u_cart`` (with
-    rotations the frame mean, with the stored ``cart_dir``; with CIF input the rows of the expanded cell, before site
-    averaging), travelling in the same copy.  The result then also has, per crystal, ``mol`` [n] (the row's molecule,
-    numbered inside the crystal), ``mol_size`` [n], ``mol_status`` [n] (bit 1 periodic, bit 2 open), ``mol_pos`` [n,3] fp32
-    (the atom's unwrapped position relative to its molecule's lowest atom; NaN where the status is not 0), ``mol_pairs``
-    [n], ``mol_delta_mean`` [n], ``mol_delta_max`` [n], ``mol_worst`` [n] (an atom index inside the crystal, -1 without
-    pairs), ``mol_over`` [n] and ``mol_stats`` [9] fp64 (molecules, tested, periodic, open, largest size; directed pairs,
-    sum of ``|D|``, largest ``|D|``, pairs over the threshold).  ``None`` is the pass as it always was.  ``tls_fit`` = ``True``
-    (with ``rigid_molecule`` only; otherwise ``ValueError``): one ``metrics.tls_fit`` wherever ``molecule_test`` runs, on the
-    same ``u_cart`` and the same molecules, travelling in the same copy.  The result then also has, per crystal, ``tls_u``
-    [n,3,3] (the ADP the fitted rigid body gives the atom), ``tls_resid`` [n] (``|Sym u_cart - tls_u|_F``) and, repeated on
-    every row of a molecule, ``tls_T`` / ``tls_L`` / ``tls_S`` [n,3,3] (A^2, rad^2, rad A, about ``tls_origin``),
-    ``tls_origin`` [n,3] (the centroid in the frame of ``mol_pos``), ``tls_T_principal`` / ``tls_L_principal`` [n,3]
-    ascending, ``tls_rank`` [n] (20: all parameters determined; less: the minimum-norm representative; 0: not fitted;
-    -1: no convergence) and ``tls_r`` [n] (the molecule's ``sqrt(sum resid^2 / sum |Sym U|^2)``), and ``tls_stats`` [6] fp64
-    (fitted molecules, rank-deficient ones, ones with a negative principal value, sum of ``resid^2``, sum of
-    ``|Sym U|^2`` over the fitted rows, largest ``resid``).  Rows of molecules that are not fitted (status not 0, fewer
-    than five atoms) hold NaN, ``tls_resid`` / ``tls_rank`` / ``tls_r`` 0.  ``None`` is the pass as it always was.
-    ``aniso_h`` = ``(stretch, bend)`` (with ``riding_h`` only; otherwise ``ValueError``): one ``metrics.aniso_h`` wherever
-    ``riding_h`` runs -- on the frame mean with rotations, once per temperature, on the rows of the expanded cell with CIF
-    input -- with the TLS fit of the same ``u_cart`` when ``tls_fit`` is on (without it every hydrogen with a parent has
-    source 2), then one ``adp_export`` over atoms as rows, travelling in the same copy.  The result then also has, per
-    crystal and per ATOM, ``h_u_cart`` [N,3,3] (a non-hydrogen atom's own row; a hydrogen's tensor: its parent's plus the
-    change of the fitted rigid-body motion from the parent to the hydrogen plus ``stretch`` along and ``bend`` across the
-    X-H bond; NaN without one), ``h_u_cif`` [N,6], ``h_u_eq`` [N], ``h_source`` [N] (0 none, 1 own row, 2 parent, 3 parent
-    and TLS, 4 parent and a rank-deficient TLS) and ``h_aniso_stats`` [4] fp64 (hydrogens with a tensor, those with source
-    >= 3, the sum of their ``trace / 3``, those not positive definite); with ``sym`` also ``h_u_cif_asym`` [a,6] per atom
-    of the asymmetric unit (``aniso_asym``: a hydrogen's is the listed image's, not an orbit mean).  ``None`` is the pass
-    as it always was."""
+    dict of lists with one entry per crystal, in the loader's order, under the keys of ``GROUPS["base"]``; a singular cell
+    raises ``ValueError`` naming the crystal.  Every option adds what its row of ``GROUPS`` documents, all of it
+    travelling in the batch's one copy, with the keys in the order of ``result_keys``; ``None`` (``rotations`` = 1) is the
+    pass as it always was.  ``sym``: row ``symmetry``; ``rotations`` with ``seed``: ``rotations``; ``temperatures``:
+    ``series`` (one entry per crystal and temperature, and the key ``series``); ``rigid_bond``, ``riding_h``,
+    ``rigid_molecule``, ``tls_fit`` (``ValueError`` without ``rigid_molecule``) and ``aniso_h`` (``ValueError`` without
+    ``riding_h``): the rows of their names, for the two hydrogen options with ``sym`` also the rows ``*_symmetry``."""
     rotations = int(rotations)
-    if tls_fit and rigid_molecule is None:
-        raise ValueError("tls_fit fits the molecules of rigid_molecule: it needs that keyword")
-    if aniso_h is not None and riding_h is None:
-        raise ValueError("aniso_h builds on the parents of riding_h: it needs that keyword")
+    analyses = Analyses(rigid_bond, riding_h, rigid_molecule, tls_fit, aniso_h).checked()
     shard = _check_pass(loader, rotations)
     kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
     model.eval()
-    out: Dict[str, List] = {k: [] for k in KEYS + (SYM_KEYS if sym is not None else ())
-                            + (ROT_KEYS if rotations > 1 else ()) + (BOND_KEYS if rigid_bond is not None else ())
-                            + (H_KEYS if riding_h is not None else ())
-                            + (H_SYM_KEYS if riding_h is not None and sym is not None else ())
-                            + (MOL_KEYS if rigid_molecule is not None else ())
-                            + (TLS_KEYS if tls_fit else ())
-                            + (AH_KEYS if aniso_h is not None else ())
-                            + (AH_SYM_KEYS if aniso_h is not None and sym is not None else ())}
+    out: Dict[str, List] = {k: [] for k in result_keys(analyses, sym is not None, rotations)}
+    series: Dict[str, List] = {k: [] for k in ("name", "temps") + SERIES_KEYS}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
-    if kelvin is not None:
-        temps = standardised(kelvin, loader.temp_mean, loader.temp_std, device)
-        series: Dict[str, List] = {k: [] for k in ("name", "temps") + SERIES_KEYS}
+    temps = None if kelvin is None else standardised(kelvin, loader.temp_mean, loader.temp_std, device)
     with torch.no_grad():
         for batch in loader:
             if batch is None:
                 continue
             batch.to(device)
-            if kelvin is None:
-                _host_stage(out, to_host(_device_stage(model, batch, shard, sym, rotations, gen, rigid_bond, riding_h,
-                                                       rigid_molecule, tls_fit, aniso_h)), shard, sym)
-            else:
-                _host_stage_series(out, series, to_host(_device_stage_series(model, batch, sym, rotations, gen, rigid_bond,
-                                                                             riding_h, kelvin, temps, rigid_molecule,
-                                                                             tls_fit, aniso_h)),
-                                   shard, sym, kelvin)
+            dev = _device_stage(model, batch, shard, sym, rotations, gen, analyses, kelvin, temps)
+            _host_stage(out, series, to_host(dev), shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
-    if kelvin is not None and len(kelvin) >= 2:
+    if GROUPS["series"].present(analyses, sym is not None, rotations, kelvin):
         out["series"] = series
     return out
 
@@ -659,81 +672,74 @@ def load_input(path: str, device, temperature: Optional[float] = None):
     return DeviceShard(arrays, device, labeled=False, names=sym.names), sym, rejected
 
 
+def _ratio(total: float, count: int) -> float:
+    return total / count if count > 0 else 0.0
+
+
+# The figures of a whole pass from one kernel's fp64 per-crystal statistics, each formula once and in the order of the
+# result line (not the key order of a result): stats key -> (its width, ``figures(s, hi, rows)``), ``s`` the per-column
+# sums and ``hi`` the per-column maxima as Python floats, 0 for a pass without crystals.  ``pass_statistics`` takes them
+# from a result's stacked statistics, ``evaluate.inference`` from sums it accumulates on the device.
+STATISTICS = {
+    "t_stats": (4, lambda s, hi, rows: {                                      # rows: those of ONE temperature
+        "ueq_slope_mean": s[0] / max(rows, 1), "non_increasing_rows": int(s[1]), "rows_with_drops": int(s[2]),
+        "series_resid_max": hi[3]}),
+    "rot_stats": (2, lambda s, hi, rows: {"rot_spread_max": hi[1], "rot_spread_mean": s[0] / max(rows, 1)}),
+    "bond_stats": (4, lambda s, hi, rows=0: {                                 # over the directed bonds of the pass
+        "bonds": int(s[0]), "rigid_bond_mean": _ratio(s[1], int(s[0])), "rigid_bond_max": hi[2],
+        "rigid_bond_over": int(s[3])}),
+    "h_stats": (4, lambda s, hi, rows=0: {                                    # the mean is over the non-orphans
+        "hydrogens": int(s[0]), "h_orphans": int(s[1]), "h_uiso_mean": _ratio(s[2], int(s[0]) - int(s[1])),
+        "h_non_positive": int(s[3])}),
+    "h_aniso_stats": (4, lambda s, hi, rows=0: {
+        "h_aniso": int(s[0]), "h_aniso_tls": int(s[1]), "h_aniso_ueq_mean": _ratio(s[2], int(s[0])),
+        "h_aniso_non_positive": int(s[3])}),
+    "mol_stats": (9, lambda s, hi, rows=0: {                                  # over the entries: once per temperature
+        "molecules": int(s[0]), "molecules_tested": int(s[1]), "molecules_periodic": int(s[2]),
+        "molecules_open": int(s[3]), "molecule_atoms_max": int(hi[4]), "rigid_molecule_pairs": int(s[5]),
+        "rigid_molecule_mean": _ratio(s[6], int(s[5])), "rigid_molecule_max": hi[7], "rigid_molecule_over": int(s[8])}),
+    "tls_stats": (6, lambda s, hi, rows=0: {                                  # tls_r over all fitted rows of the pass
+        "tls_molecules": int(s[0]), "tls_rank_deficient": int(s[1]), "tls_nonphysical": int(s[2]),
+        "tls_r": math.sqrt(s[3] / s[4]) if s[4] > 0 else 0.0, "tls_resid_max": hi[5]}),
+}
+
+
+def _columns(stats: List[torch.Tensor], width: int):
+    """``(sums, maxima)`` per column of a list of [width] fp64 per-crystal statistics, each column reduced on its own."""
+    columns = (torch.stack(stats) if stats else torch.zeros(0, width, dtype=torch.float64)).unbind(1)
+    return [float(c.sum()) for c in columns], [float(c.max()) if stats else 0.0 for c in columns]
+
+
 def pass_statistics(out: Dict[str, List], output: Optional[str] = None, cif_dir: Optional[str] = None, rejected=None,
                     rotations: int = 1, temperatures: Optional[list] = None) -> dict:
     """The result line of a whole ``predict_adps`` pass from its result ``out`` (``rotations`` and ``temperatures`` as the
     pass was given them), summed from the kernels' fp64 per-crystal statistics: ``crystals``, ``rows``, ``u_eq_mean`` and
     ``non_positive_rows``, then ``output`` and ``cif_dir`` as given and the number of ``rejected`` crystals if there is
-    such a list (``load_input``); with ``temperatures`` ``entries`` and ``temperatures``, and from a ``series``
-    ``ueq_slope_mean``, ``non_increasing_rows``, ``rows_with_drops`` and ``series_resid_max``; with frames ``rotations``,
-    ``rot_spread_max`` and ``rot_spread_mean``; with the rigid-bond test ``bonds``, ``rigid_bond_mean`` / ``_max`` /
-    ``_over``; with the rigid-body test ``molecules``, ``molecules_tested`` / ``_periodic`` / ``_open``,
-    ``molecule_atoms_max`` and ``rigid_molecule_pairs`` / ``_mean`` / ``_max`` / ``_over`` (over the entries: with
-    temperatures every crystal counts once per temperature); with the TLS fit ``tls_molecules``, ``tls_rank_deficient``,
-    ``tls_nonphysical``, ``tls_r`` (over all fitted rows) and ``tls_resid_max``; with riding hydrogens ``hydrogens``, ``h_orphans``, ``h_uiso_mean`` (over the non-orphans) and
-    ``h_non_positive``; with anisotropic hydrogens ``h_aniso`` (hydrogens with a tensor), ``h_aniso_tls`` (those with a
-    libration term), ``h_aniso_ueq_mean`` (over ``h_aniso``) and ``h_aniso_non_positive``.  A pass without crystals gives
-    zeros."""
+    such a list (``load_input``); with ``temperatures`` ``entries`` and ``temperatures``; then, for every statistics key
+    of ``STATISTICS`` that the result (for ``t_stats`` its ``series``) has, that key's figures, with ``rotations`` in front
+    of the frames'.  A pass without crystals gives zeros."""
     n = len(out["name"])                                  # entries: one per crystal, or per crystal and temperature
     rows = sum(int(t.shape[0]) for t in out["u_eq"])
-
-    def stacked(key: str, width: int, of: dict = out) -> torch.Tensor:   # [n, width] fp64: one kernel's per-crystal figures
-        return torch.stack(of[key]) if of[key] else torch.zeros(0, width, dtype=torch.float64)
-    stats = stacked("stats", 3)
+    sums, _ = _columns(out["stats"], 3)
     res = {"crystals": n // len(temperatures) if temperatures else n, "rows": rows,
-           "u_eq_mean": float(stats[:, 0].sum()) / max(rows, 1), "non_positive_rows": int(stats[:, 2].sum()),
-           "output": output, "cif_dir": cif_dir}
+           "u_eq_mean": sums[0] / max(rows, 1), "non_positive_rows": int(sums[2]), "output": output, "cif_dir": cif_dir}
     if rejected is not None:
         res["rejected"] = len(rejected)
     if temperatures is not None:
         res.update(entries=n, temperatures=temperatures)
-    if "series" in out:                               # from the fp64 per-crystal stats of the lines; rows of ONE temperature
-        ts = stacked("t_stats", 4, out["series"])
-        res.update(ueq_slope_mean=float(ts[:, 0].sum()) / max(rows // len(temperatures), 1),
-                   non_increasing_rows=int(ts[:, 1].sum()), rows_with_drops=int(ts[:, 2].sum()),
-                   series_resid_max=float(ts[:, 3].max()) if len(ts) else 0.0)
-    if rotations > 1:                                 # per row, from the fp64 per-crystal (sum, maximum) of rot_spread
-        rot = stacked("rot_stats", 2)
-        res.update(rotations=rotations, rot_spread_max=float(rot[:, 1].max()) if n else 0.0,
-                   rot_spread_mean=float(rot[:, 0].sum()) / max(rows, 1))
-    if "bond_stats" in out:                           # over the directed bonds of the pass, from the fp64 per-crystal stats
-        bs = stacked("bond_stats", 4)
-        count = int(bs[:, 0].sum())
-        res.update(bonds=count, rigid_bond_mean=float(bs[:, 1].sum()) / count if count else 0.0,
-                   rigid_bond_max=float(bs[:, 2].max()) if n else 0.0, rigid_bond_over=int(bs[:, 3].sum()))
-    if "h_stats" in out:                              # from the fp64 per-crystal stats; the mean is over the non-orphans
-        hs = stacked("h_stats", 4)
-        hydrogens, orphans = int(hs[:, 0].sum()), int(hs[:, 1].sum())
-        res.update(hydrogens=hydrogens, h_orphans=orphans,
-                   h_uiso_mean=float(hs[:, 2].sum()) / (hydrogens - orphans) if hydrogens > orphans else 0.0,
-                   h_non_positive=int(hs[:, 3].sum()))
-    if "h_aniso_stats" in out:
-        ah = stacked("h_aniso_stats", 4)
-        count = int(ah[:, 0].sum())
-        res.update(h_aniso=count, h_aniso_tls=int(ah[:, 1].sum()),
-                   h_aniso_ueq_mean=float(ah[:, 2].sum()) / count if count else 0.0, h_aniso_non_positive=int(ah[:, 3].sum()))
-    if "mol_stats" in out:                            # the sums over the entries, from the fp64 per-crystal figures
-        ms = stacked("mol_stats", 9)
-        count = int(ms[:, 5].sum())
-        res.update(molecules=int(ms[:, 0].sum()), molecules_tested=int(ms[:, 1].sum()),
-                   molecules_periodic=int(ms[:, 2].sum()), molecules_open=int(ms[:, 3].sum()),
-                   molecule_atoms_max=int(ms[:, 4].max()) if n else 0, rigid_molecule_pairs=count,
-                   rigid_molecule_mean=float(ms[:, 6].sum()) / count if count else 0.0,
-                   rigid_molecule_max=float(ms[:, 7].max()) if n else 0.0, rigid_molecule_over=int(ms[:, 8].sum()))
-    if "tls_stats" in out:                            # the same; tls_r over all fitted rows of the pass
-        ts = stacked("tls_stats", 6)
-        r2, s2 = float(ts[:, 3].sum()), float(ts[:, 4].sum())
-        res.update(tls_molecules=int(ts[:, 0].sum()), tls_rank_deficient=int(ts[:, 1].sum()),
-                   tls_nonphysical=int(ts[:, 2].sum()), tls_r=math.sqrt(r2 / s2) if s2 > 0 else 0.0,
-                   tls_resid_max=float(ts[:, 5].max()) if n else 0.0)
+    for key, (width, figures) in STATISTICS.items():
+        of = out.get("series", {}) if key == "t_stats" else out
+        if key in of:
+            if key == "rot_stats":
+                res["rotations"] = rotations
+            res.update(figures(*_columns(of[key], width), rows // len(temperatures) if key == "t_stats" else rows))
     return res
 
 
 def entry(result: Dict[str, List], k: int) -> dict:
     """Crystal ``k`` of a ``predict_adps`` result: what ``write_cif`` (and, with the keys of a ``CifSymmetry``,
     ``write_cif_symmetric``) takes."""
-    return {key: result[key][k] for key in KEYS + SYM_KEYS + ROT_KEYS + BOND_KEYS + H_KEYS + H_SYM_KEYS + MOL_KEYS
-            + TLS_KEYS + AH_KEYS + AH_SYM_KEYS if key in result}
+    return {key: result[key][k] for g in GROUPS.values() for key in g.cuts if key in result}
 
 
 def cell_parameters(cell) -> tuple:

@@ -344,20 +344,22 @@ def check_predict_args(args) -> None:
         parse_temperatures(args.predict_temperatures)
 
 
-def rigid_molecule_option(args) -> dict:
-    """``--rigid_molecule`` (and ``--tls_fit`` on top of it) as the keywords of ``predict_adps`` /
-    ``evaluate.inference``; without a flag no keyword for it at all: the passes are called as they always were."""
-    if not args.rigid_molecule:
-        return {}
-    option = {"rigid_molecule": (args.bond_tolerance, args.rigid_molecule_threshold)}
-    if args.tls_fit:
-        option["tls_fit"] = True
-    return option
-
-
-def aniso_h_option(args) -> dict:
-    """``--aniso_h`` as the keyword of ``predict_adps``; without the flag no keyword at all."""
-    return {"aniso_h": (args.aniso_h_stretch, args.aniso_h_bend)} if args.aniso_h else {}
+def analysis_options(args, inference: bool = False) -> dict:
+    """The analysis flags as the keywords of ``predict_adps`` or, with ``inference``, of ``evaluate.inference`` (no
+    hydrogens there).  ``rigid_bond`` and ``riding_h`` are always among them, ``None`` without their flag; a later flag
+    that is not given contributes no keyword at all: the passes are called as they always were (``main`` has refused a
+    ``--tls_fit`` without ``--rigid_molecule``)."""
+    tol = args.bond_tolerance
+    options = {"rigid_bond": (tol, args.rigid_bond_threshold) if args.rigid_bond else None}
+    if not inference:
+        options["riding_h"] = (tol, args.riding_h_factor, args.riding_h_factor_rotating) if args.riding_h else None
+    if args.rigid_molecule:
+        options["rigid_molecule"] = (tol, args.rigid_molecule_threshold)
+        if args.tls_fit:
+            options["tls_fit"] = True
+    if args.aniso_h and not inference:
+        options["aniso_h"] = (args.aniso_h_stretch, args.aniso_h_bend)
+    return options
 
 
 def predict(model, args) -> dict:
@@ -374,10 +376,7 @@ def predict(model, args) -> dict:
     temps = parse_temperatures(args.predict_temperatures) if args.predict_temperatures is not None else None
     out = pr.predict_adps(
         model, ShardLoader(shard, cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
-        rotations=cfg.rotations, seed=cfg.seed, temperatures=temps,
-        rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None,
-        riding_h=(args.bond_tolerance, args.riding_h_factor, args.riding_h_factor_rotating) if args.riding_h else None,
-        **rigid_molecule_option(args), **aniso_h_option(args))
+        rotations=cfg.rotations, seed=cfg.seed, temperatures=temps, **analysis_options(args))
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     if args.predict_cif_dir:
@@ -424,10 +423,8 @@ def main(argv=None) -> dict:
         ck = torch.load(args.checkpoint_path, map_location=cfg.device)
         model.load_state_dict(ck["model_state"])
         if args.inference:
-            res = evaluate.inference(
-                model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations, seed=cfg.seed,
-                rigid_bond=(args.bond_tolerance, args.rigid_bond_threshold) if args.rigid_bond else None,
-                **rigid_molecule_option(args))
+            res = evaluate.inference(model, loaders[-1], cfg.device, args.inference_output, rotations=cfg.rotations,
+                                     seed=cfg.seed, **analysis_options(args, inference=True))
         else:
             res = evaluate.montecarlo(model, loaders[-1], cfg.device, args.inference_output,
                                       rounds=args.montecarlo_rounds, seed=cfg.seed)

@@ -193,8 +193,9 @@ def test_the_flag_is_refused_before_the_device_is_touched(monkeypatch):
         entry.main(["--predict", "--aniso_h", "--predict_input", "none.cnshard", "--checkpoint_path", "none.ckpt"])
     args = entry.build_parser().parse_args([])
     assert args.aniso_h is False and (args.aniso_h_stretch, args.aniso_h_bend) == (ANISO_H_STRETCH, ANISO_H_BEND) == (0.005, 0.020)
-    assert entry.aniso_h_option(args) == {}
+    assert entry.analysis_options(args) == {"rigid_bond": None, "riding_h": None}
     args = entry.build_parser().parse_args(["--aniso_h", "--aniso_h_stretch", "0.01", "--aniso_h_bend", "0.03"])
-    assert entry.aniso_h_option(args) == {"aniso_h": (0.01, 0.03)}
+    assert entry.analysis_options(args) == {"rigid_bond": None, "riding_h": None, "aniso_h": (0.01, 0.03)}
+    assert entry.analysis_options(args, inference=True) == {"rigid_bond": None}
     from cartnet_amd.config import set_cfg
     set_cfg()

@@ -18,7 +18,8 @@ def test_parser_defaults_and_old_defaults_stay():
     assert (d.rotations, d.eval_batch, d.predict, d.inference, d.predict_output) == (1, 1, False, False, "./predictions.pkl")
     a = p.parse_args(["--rigid_molecule", "--bond_tolerance", "0.25", "--rigid_molecule_threshold", "5e-4"])
     assert (a.rigid_molecule, a.bond_tolerance, a.rigid_molecule_threshold, a.rigid_bond_threshold) == (True, 0.25, 5e-4, 1e-3)
-    assert entry.rigid_molecule_option(d) == {} and entry.rigid_molecule_option(a) == {"rigid_molecule": (0.25, 5e-4)}
+    off = {"rigid_bond": None, "riding_h": None}                                         # always given; the later flags add a keyword or none
+    assert entry.analysis_options(d) == off and entry.analysis_options(a) == {**off, "rigid_molecule": (0.25, 5e-4)}
 
 
 def test_keys():

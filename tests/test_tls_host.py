@@ -193,6 +193,7 @@ def test_the_flag_alone_is_refused():
     with pytest.raises(SystemExit, match="--rigid_molecule"):
         entry.main(["--predict", "--tls_fit", "--predict_input", "none.cnshard", "--checkpoint_path", "none.ckpt"])
     args = entry.build_parser().parse_args(["--rigid_molecule", "--tls_fit"])
-    assert entry.rigid_molecule_option(args) == {"rigid_molecule": (0.4, 1e-3), "tls_fit": True}
-    assert "tls_fit" not in entry.rigid_molecule_option(entry.build_parser().parse_args(["--rigid_molecule"]))
+    assert entry.analysis_options(args, inference=True) == {"rigid_bond": None, "rigid_molecule": (0.4, 1e-3), "tls_fit": True}
+    assert entry.analysis_options(args) == {"rigid_bond": None, "riding_h": None, "rigid_molecule": (0.4, 1e-3), "tls_fit": True}
+    assert "tls_fit" not in entry.analysis_options(entry.build_parser().parse_args(["--rigid_molecule"]))
     assert entry.build_parser().parse_args([]).tls_fit is False

@@ -135,6 +135,43 @@ X-H motion.  Per atom ``i`` of a batch, ``u_h[i]`` [3,3] fp32 and ``source[i]`` 
 Using the parent's own tensor plus the CHANGE of the fitted motion keeps a hydrogen consistent with its parent even where
 the fit is poor; SHADE uses the fitted tensor at the hydrogen instead.  For exactly rigid rows (``U_p = U_TLS(r_p)``) the
 two coincide: ``u_h = U_TLS(r_p + v) + U_int``.
+
+The bond table (``metrics.bond_index`` and ``metrics.bond_table``, csrc/bond_table_ops.hip; ``bond_table_host`` below
+restates both in numpy): one entry per bond where the rules above give figures per atom -- Hirshfeld's ``D`` with its
+sign, the model-free bounds of Busing & Levy (Acta Cryst. 17 (1964) 142) on the thermally averaged bond length, and the
+length corrected for the libration of the fitted rigid body (Cruickshank, Acta Cryst. 9 (1956) 757; Schomaker &
+Trueblood 1968), the geometric product of a TLS analysis that THMA11 and PLATON print.
+
+  bonds       a directed edge ``e = (j -> i)`` is a bond exactly as for the rigid-bond test: ``is_bond`` and both ends with
+              an ADP row, every atom of the batch admissible as a source.
+  listed      the bonds with ``j < i`` (batch atom indices): a symmetric graph lists every bond once; a pair bonded
+              through two different images is two entries.  Entries come in target order and within a target in edge
+              order -- the graph's own order.
+  unlisted    the bond edges with ``j > i`` are counted per atom ``i`` and per crystal and never listed.  A graph capped
+              by ``--max_neighbours`` can hold a bond in one direction only: a crystal whose unlisted count differs from
+              its listed count has an asymmetric graph.
+  entry       ``a = j``, ``b = i``; ``dir = cart_dir[e]`` and ``length = cart_dist[e]`` as stored, ``d`` and ``l`` below.
+              All arithmetic is fp64 from the fp32 inputs, and every stored value is rounded once.
+  delta       ``d^T (Sym U_b - Sym U_a) d``, signed: the difference first, then ``_form`` (``bg_form`` of
+              csrc/bond_graph.h).  ``|delta|`` is the ``|D|`` the rigid-bond test folds for row ``b``.
+  bounds      ``w_x^2 = tr(U_x) - d^T Sym(U_x) d``, the mean-square displacement of atom ``x`` across the bond (the
+              trace summed 11 + 22 + 33).  ``lower = l + (sqrt(w_b^2) - sqrt(w_a^2))^2 / (2 l)`` and ``upper = l +
+              (sqrt(w_b^2) + sqrt(w_a^2))^2 / (2 l)``: fully correlated and fully anti-correlated motion across the bond.
+              A negative ``w^2`` (a row that is not positive definite) or a NaN row gives NaN in both, the square root's
+              own answer; such a bond is still listed, and counted.
+  libration   ``| r + 1/2 (tr(L) I - L) r |`` with ``r = l d``: the bond between the mean positions of two atoms of a
+              body that librates with ``L``.  ``L`` is ``params[atom_row[b], 6:12]`` (11 22 33 23 13 12) of the TLS fit AS
+              STORED in fp32; filled where ``rank[atom_row[b]] > 0``, NaN otherwise and without TLS results.  It does not
+              depend on ``S`` or on the origin.  A bond lies inside one molecule, so both ends share the fit.
+  tls_rank    ``rank[atom_row[b]]``, 0 without TLS results: below 20, ``L`` is the minimum-norm representative (a planar
+              or linear molecule), which a user may want to set aside as ``source`` 3 against 4 does for hydrogens.
+  crystal     from the values as stored, a bond belonging to the crystal of ``b``: listed, unlisted, the sum of
+              ``length``, the sum of ``|delta|``, the largest ``|delta|`` (a NaN is kept), the entries with a finite
+              ``libration``, the sum and the largest of ``libration - length`` over those (0 without one), and the
+              entries with a NaN bound.
+
+Not in the table: X-H bonds (a hydrogen has no ADP row), angles and torsions, and the riding-model correction, which
+needs a choice of which atom rides on which.
 """
 from __future__ import annotations
 
@@ -569,3 +606,80 @@ def aniso_hydrogens_host(u, z, edge_index, cart_dist, cart_dir, atom_row, parent
         tr = ((stored[a, 0, 0] + stored[a, 1, 1]) + stored[a, 2, 2]) / 3.0
         stats[g] = (len(a), (source[a] >= ANISO_H_TLS).sum(), tr.sum(), (~good[a]).sum())
     return {"u_h": u_h, "source": source, "crystal_stats": stats, "bond": bond, "lib": lib}
+
+
+def _form(w, x, y, z) -> np.ndarray:
+    """``v^T Sym(W) v`` for row-major ``w`` [n,9] and the components of ``v``, in the operation order of ``bg_form``
+    (csrc/bond_graph.h): the off-diagonal pairs enter as ``(w_ab + w_ba)``."""
+    return (w[:, 0] * x * x + w[:, 4] * y * y + w[:, 8] * z * z + (w[:, 1] + w[:, 3]) * x * y
+            + (w[:, 2] + w[:, 6]) * x * z + (w[:, 5] + w[:, 7]) * y * z)
+
+
+def bond_table_host(u, z, edge_index, cart_dist, cart_dir, atom_row, ptr=None, tol: float = BOND_TOLERANCE, params=None,
+                    rank=None) -> dict:
+    """The bond table of the module docstring in plain numpy, in the kernels' operation order: a dict with ``a``, ``b``
+    [nb] int64, ``dir`` [nb,3], ``length``, ``delta``, ``lower``, ``upper``, ``libration`` [nb] fp32, ``tls_rank`` [nb]
+    int32, ``counts`` and ``unlisted`` [N] int32 (per atom ``i``: its listed bonds, its bond edges with ``j > i``),
+    ``bond_ptr`` [B+1] int64 (the crystals' offsets into the table) and ``crystal_stats`` [B,9] fp64.  ``u`` [M,3,3] fp32;
+    ``z``, ``edge_index``, ``cart_dist``, ``cart_dir``, ``atom_row`` as for ``molecules_host``; ``ptr`` [B+1] (``None``:
+    one crystal); ``params`` [M,24] fp32 and ``rank`` [M] (``tls_fit_host``): both or neither."""
+    u = np.asarray(u, dtype=np.float32).reshape(-1, 9)
+    z = np.asarray(z, dtype=np.int64).reshape(-1)
+    src, tgt = (np.asarray(a, dtype=np.int64).reshape(-1) for a in np.asarray(edge_index).reshape(2, -1))
+    dist = np.asarray(cart_dist, dtype=np.float32).reshape(-1)
+    dirs = np.asarray(cart_dir, dtype=np.float32).reshape(-1, 3)
+    atom_row = np.asarray(atom_row, dtype=np.int64).reshape(-1)
+    N, M = len(z), len(u)
+    if (params is None) != (rank is None):
+        raise ValueError("params and rank come together or not at all")
+    ptr = np.asarray([0, N] if ptr is None else ptr, dtype=np.int64).reshape(-1)
+    B = len(ptr) - 1
+    inside = (src >= 0) & (src < N) & (tgt >= 0) & (tgt < N)
+    s, t = np.where(inside, src, 0), np.where(inside, tgt, 0)
+    has_row = (atom_row >= 0) & (atom_row < M)
+    bond = inside & has_row[s] & has_row[t] & is_bond(dist, z[t], z[s], tol, same_atom=s == t)
+    counts = np.bincount(t[bond & (s < t)], minlength=N).astype(np.int32)
+    unlisted = np.bincount(t[bond & (s > t)], minlength=N).astype(np.int32)
+    offset = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    e = np.nonzero(bond & (s < t))[0]
+    e = e[np.argsort(t[e], kind="stable")]                                    # target order, then edge order
+    a, b = s[e], t[e]
+    nb = len(e)
+    ub, ua = u[atom_row[b]].astype(np.float64), u[atom_row[a]].astype(np.float64)
+    x, y, zz = (dirs[e, k].astype(np.float64) for k in range(3))
+    l = dist[e].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        delta = _form(ub - ua, x, y, zz)
+        wb = np.sqrt(((ub[:, 0] + ub[:, 4]) + ub[:, 8]) - _form(ub, x, y, zz))
+        wa = np.sqrt(((ua[:, 0] + ua[:, 4]) + ua[:, 8]) - _form(ua, x, y, zz))
+        lo, hi = wb - wa, wb + wa
+        lower, upper = l + lo * lo / (2.0 * l), l + hi * hi / (2.0 * l)
+    libration = np.full(nb, np.nan)
+    tls_rank = np.zeros(nb, dtype=np.int32)
+    if params is not None:
+        p = np.asarray(params, dtype=np.float32).reshape(-1, 24).astype(np.float64)[atom_row[b]]
+        tls_rank = np.asarray(rank).reshape(-1)[atom_row[b]].astype(np.int32)
+        l11, l22, l33, l23, l13, l12 = (p[:, 6 + k] for k in range(6))
+        rx, ry, rz, tr = l * x, l * y, l * zz, (l11 + l22) + l33
+        with np.errstate(invalid="ignore", over="ignore"):
+            vx = rx + 0.5 * (tr * rx - ((l11 * rx + l12 * ry) + l13 * rz))
+            vy = ry + 0.5 * (tr * ry - ((l12 * rx + l22 * ry) + l23 * rz))
+            vz = rz + 0.5 * (tr * rz - ((l13 * rx + l23 * ry) + l33 * rz))
+            libration = np.where(tls_rank > 0, np.sqrt((vx * vx + vy * vy) + vz * vz), np.nan)
+    out = {"a": a, "b": b, "dir": dirs[e], "length": dist[e], "delta": delta.astype(np.float32),
+           "lower": lower.astype(np.float32), "upper": upper.astype(np.float32),
+           "libration": libration.astype(np.float32), "tls_rank": tls_rank, "counts": counts, "unlisted": unlisted,
+           "bond_ptr": offset[np.clip(ptr, 0, N)]}
+    stats = np.zeros((B, 9), dtype=np.float64)
+    for g in range(B):
+        sl = slice(out["bond_ptr"][g], out["bond_ptr"][g + 1])
+        ln, d, lib = (out[k][sl].astype(np.float64) for k in ("length", "delta", "libration"))
+        d = np.abs(d)
+        fin = np.isfinite(lib)
+        grow = (lib - ln)[fin]
+        nan_bound = np.isnan(out["lower"][sl]) | np.isnan(out["upper"][sl])
+        stats[g] = (len(ln), unlisted[ptr[g]:ptr[g + 1]].sum(), ln.sum(), d.sum(),
+                    (np.nan if np.isnan(d).any() else d.max()) if len(d) else 0.0, fin.sum(), grow.sum(),
+                    grow.max() if len(grow) else 0.0, nan_bound.sum())
+    out["crystal_stats"] = stats
+    return out

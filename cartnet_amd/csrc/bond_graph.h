@@ -1,11 +1,12 @@
-// The bond graph of a batch on the device: what bond_ops.hip, riding_ops.hip, molecule_ops.hip, tls_ops.hip and
-// aniso_h_ops.hip share, each rule written once.  The graph is the batch's radius graph (edges sorted by target atom, the
-// periodic images solved in cart_dist / cart_dir) with the two lookups metrics.batch_graph builds: atom_row [N] (an atom's
-// row in the model's output, -1 for a hydrogen) and seg_ptr [N+1] (atom i owns the edges [seg_ptr[i], seg_ptr[i+1])).
-// The rules are stated in cartnet_amd/bonds.py, which restates every kernel in numpy, bit for bit.
+// The bond graph of a batch on the device: what bond_ops.hip, bond_table_ops.hip, riding_ops.hip, molecule_ops.hip,
+// tls_ops.hip and aniso_h_ops.hip share, each rule written once.  The graph is the batch's radius graph (edges sorted by
+// target atom, the periodic images solved in cart_dist / cart_dir) with the two lookups metrics.batch_graph builds:
+// atom_row [N] (an atom's row in the model's output, -1 for a hydrogen) and seg_ptr [N+1] (atom i owns the edges
+// [seg_ptr[i], seg_ptr[i+1])).  The rules are stated in cartnet_amd/bonds.py, which restates every kernel in numpy, bit
+// for bit.
 //
 // Everything here is __device__ __forceinline__ and takes the compile flags of the file that includes it: aniso_h_ops.hip
-// is compiled with -ffp-contract=off, the other four are not, and each keeps the contraction it had.  bg_form is the only
+// is compiled with -ffp-contract=off, the others are not, and each keeps the contraction it had.  bg_form is the only
 // helper with products to contract; aniso_h_ops.hip does not call it.
 #pragma once
 #include "common.h"

@@ -1,6 +1,6 @@
 // The "one wave per crystal" reduction of the per-crystal figures (eval_ops.hip, export_ops.hip, frame_ops.hip,
-// series_ops.hip, and through bond_graph.h bond_ops.hip, riding_ops.hip, molecule_ops.hip, tls_ops.hip and
-// aniso_h_ops.hip): a workgroup of one wave owns crystal g, lane l takes rows l, l + 64, ... of the crystal in
+// series_ops.hip, and through bond_graph.h bond_ops.hip, bond_table_ops.hip, riding_ops.hip, molecule_ops.hip, tls_ops.hip
+// and aniso_h_ops.hip): a workgroup of one wave owns crystal g, lane l takes rows l, l + 64, ... of the crystal in
 // row order into fp64 accumulators, the 64 lane values are folded by a butterfly (o = 32, 16, ..., 1: the same pairs in the
 // same order on every run) and lane 0 stores.  No atomics, fixed order: two runs give the same bytes.  Every kernel keeps
 // its own per-row expression and its own store; what they share is the clamped row range and the folds.

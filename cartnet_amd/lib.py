@@ -381,6 +381,12 @@ PROTOTYPES = {
     "cartnet_adp_aniso_h": (C.c_int, [c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_i64p, C.c_void_p,
                                       c_f32p, c_i32p, C.c_double, C.c_double, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                       c_f32p, c_i32p, C.c_void_p, c_stream]),
+    "cartnet_bond_table_count": (C.c_int, [c_i64p, c_i64p, c_f32p, c_i64p, c_i64p, c_f32p, C.c_int32, C.c_float, C.c_int64,
+                                           C.c_int64, C.c_int64, c_i32p, c_i32p, c_stream]),
+    "cartnet_adp_bond_table": (C.c_int, [c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_f32p, C.c_int32,
+                                         C.c_float, c_i64p, c_i32p, c_f32p, c_i32p, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_int64, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                         c_f32p, c_i32p, C.c_void_p, c_stream]),
     "cartnet_adp_temp_series": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, c_i64p, C.c_int32, C.c_int64, c_f32p, c_f32p,
                                           c_f32p, c_i32p, C.c_void_p, c_stream]),
     "cartnet_collate": (C.c_int, [C.POINTER(Shard), c_i64p, c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int64, C.c_int64,

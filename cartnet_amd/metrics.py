@@ -298,7 +298,7 @@ def _batch_field(batch, *names):
 
 class BatchGraph(NamedTuple):
     """Everything the bond-graph analyses (``bond_test``, ``riding_h``, ``molecules``, ``molecule_test``, ``tls_fit``,
-    ``aniso_h``) take from a batch, checked once by ``batch_graph`` and good for every prediction of that batch: ``z`` [N]
+    ``aniso_h``, ``bond_index``, ``bond_table``) take from a batch, checked once by ``batch_graph`` and good for every prediction of that batch: ``z`` [N]
     int64; ``edge_index`` [2,E] sorted by target; ``cart_dist`` [E]; ``cart_dir`` [E,3] (``None`` if not asked for);
     ``mask`` = ``non_H_mask`` [N] (``None``: every atom has a row); ``M``, the rows; the two lookups of the kernels,
     ``atom_row`` [N] int64 (an atom's row, -1 outside the mask) and ``seg_ptr`` [N+1] int64 (atom i owns the edges
@@ -670,6 +670,116 @@ def aniso_h(u: torch.Tensor, batch, row_ptr: torch.Tensor, riding: RidingH, mole
             float(bend), B, N, M, E, u_h.data_ptr(), source.data_ptr(), stats.data_ptr(), _l.stream_ptr()),
             "cartnet_adp_aniso_h")
     return AnisoH(u_h, source, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The bond table (csrc/bond_table_ops.hip): one entry per bond where the analyses above give figures per atom -- D with
+# its sign, the Busing & Levy bounds on the bond length and the length corrected for the fitted libration.  Two calls,
+# because the bonds do not depend on U: counted once per batch, filled as often as there are predictions of it.  The
+# rule: bonds.py.
+
+class BondIndex(NamedTuple):
+    """What ``bond_index`` returns: ``counts`` [N] int32, per atom ``i`` the bonds ``j -> i`` with ``j < i``, which the
+    table lists; ``offsets`` [N+1] int64, their exclusive scan (atom i's entries start at ``offsets[i]``); ``bond_ptr``
+    [B+1] int64, the crystals' offsets into the table, on the device, and ``bond_ptr_host``, the same on the host (the one
+    copy ``bond_index`` makes: the table's length is ``bond_ptr_host[-1]``); ``unlisted`` [N] int32, per atom ``i`` its
+    bond edges with ``j > i``, which are counted and never listed; ``tol``, the tolerance the bonds were found with."""
+    counts: torch.Tensor
+    offsets: torch.Tensor
+    bond_ptr: torch.Tensor
+    bond_ptr_host: torch.Tensor
+    unlisted: torch.Tensor
+    tol: float
+
+
+class BondTable(NamedTuple):
+    """What ``bond_table`` returns, all on the device, per listed bond (``nb`` of them, in target order and within a target
+    in edge order): ``a`` and ``b`` [nb] int64, the batch's atom indices of the edge's source and target, ``a < b``;
+    ``dir`` [nb,3] and ``length`` [nb] fp32, the edge's ``cart_dir`` and ``cart_dist`` as stored; ``delta`` [nb] fp32,
+    ``d^T (Sym U_b - Sym U_a) d``, signed; ``lower`` and ``upper`` [nb] fp32, the Busing & Levy bounds on the thermally
+    averaged length (NaN where a tensor has a negative or NaN mean-square displacement across the bond); ``libration``
+    [nb] fp32, the length corrected for the libration ``L`` of the TLS fit of ``b``'s molecule (NaN without a fit) and
+    ``tls_rank`` [nb] int32, that fit's rank (0 without one); ``crystal_stats`` [B,9] fp64: listed bonds, unlisted ``j > i``
+    bond edges, sum of ``length``, sum of ``|delta|``, largest ``|delta|`` (keeps a NaN), bonds with a finite
+    ``libration``, sum and largest of ``libration - length`` over those, bonds with a NaN bound."""
+    a: torch.Tensor
+    b: torch.Tensor
+    dir: torch.Tensor
+    length: torch.Tensor
+    delta: torch.Tensor
+    lower: torch.Tensor
+    upper: torch.Tensor
+    libration: torch.Tensor
+    tls_rank: torch.Tensor
+    crystal_stats: torch.Tensor
+
+
+def bond_index(batch, row_ptr: torch.Tensor, tol: float = 0.4, rows: Optional[int] = None) -> BondIndex:
+    """Where the bonds of ``batch`` go in its bond table: one call of ``cartnet_bond_table_count``, a static-shape scan
+    (``torch.cumsum``) and ONE small device-to-host copy, the ``B + 1`` offsets of the crystals.  ``batch`` and ``rows``:
+    what ``batch_graph`` takes, or its ``BatchGraph``; ``row_ptr`` [B+1]: ``target_row_ptr``.  A bond is the rigid-bond
+    test's (``cartnet_amd.bonds``); it does not depend on U, so one index serves every prediction of the batch."""
+    g = batch_graph(batch, rows, "bond_index", need_dir=False)
+    z, N, ei, E, dist, M, dev = g.z, g.N, g.edge_index, g.E, g.cart_dist, g.M, g.z.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    if g.B != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {g.B}")
+    counts = torch.zeros(N, dtype=torch.int32, device=dev)
+    unlisted = torch.zeros(N, dtype=torch.int32, device=dev)
+    if N and M:                                  # else nothing is launched: no atom has a bond
+        with torch.cuda.device(dev):
+            _l.check(_l.load().cartnet_bond_table_count(
+                z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None, g.atom_row.data_ptr(),
+                g.seg_ptr.data_ptr(), g.radii.data_ptr(), int(g.radii.numel()), float(tol), N, M, E, counts.data_ptr(),
+                unlisted.data_ptr(), _l.stream_ptr()), "cartnet_bond_table_count")
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0, dtype=torch.int64)])
+    bond_ptr = offsets[g.atom_ptr.clamp(0, N)]
+    return BondIndex(counts, offsets, bond_ptr, bond_ptr.cpu(), unlisted, float(tol))
+
+
+def bond_table(u: torch.Tensor, batch, row_ptr: torch.Tensor, index: BondIndex, tls: Optional[TlsFit] = None) -> BondTable:
+    """The bond table of the ADPs ``u`` [M,3,3] on the bonds of ``batch``: one call of ``cartnet_adp_bond_table``.
+    ``batch``: what ``batch_graph`` takes, or its ``BatchGraph``; ``row_ptr`` [B+1]: ``target_row_ptr``; ``index``:
+    ``bond_index`` of the same batch.  ``tls``: a ``tls_fit`` of the same ``u``; with it a bond of a fitted molecule gets
+    its ``libration`` and ``tls_rank``, without it they are NaN and 0.  Nothing is read back."""
+    _check_fp32("u", u)
+    u, M, dev = u.detach().contiguous(), int(u.shape[0]), u.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    g = batch_graph(batch, M, "bond_table", "u", dev=dev)
+    if g.B != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {g.B}")
+    z, N, ei, E, dist, dirs = g.z, g.N, g.edge_index, g.E, g.cart_dist, g.cart_dir
+    offsets, unlisted, on_host = index.offsets, index.unlisted, index.bond_ptr_host
+    if not (tuple(offsets.shape) == (N + 1,) and offsets.dtype == torch.int64 and tuple(unlisted.shape) == (N,)
+            and unlisted.dtype == torch.int32 and offsets.device == dev and unlisted.device == dev
+            and tuple(on_host.shape) == (B + 1,) and on_host.device.type == "cpu"):
+        raise ValueError(f"index does not belong to this batch ({N} atoms, {B} crystals)")
+    params = rank = None
+    if tls is not None:
+        params, rank = tls.params, tls.rank
+        if not (tuple(params.shape) == (M, 24) and params.dtype == torch.float32 and tuple(rank.shape) == (M,)
+                and rank.dtype == torch.int32 and params.device == dev and rank.device == dev):
+            raise ValueError(f"tls does not belong to this u ({M} rows)")
+        params, rank = params.contiguous(), rank.contiguous()
+    nb = int(on_host[-1])
+    a, b = (torch.empty(nb, dtype=torch.int64, device=dev) for _ in range(2))
+    out_dir = torch.empty((nb, 3), dtype=torch.float32, device=dev)
+    length, delta, lower, upper, libration = (torch.empty(nb, dtype=torch.float32, device=dev) for _ in range(5))
+    tls_rank = torch.empty(nb, dtype=torch.int32, device=dev)
+    if M == 0 or N == 0:                         # the entry point launches nothing
+        return BondTable(a, b, out_dir, length, delta, lower, upper, libration, tls_rank,
+                         torch.zeros((B, 9), dtype=torch.float64, device=dev))
+    stats = torch.empty((B, 9), dtype=torch.float64, device=dev)
+    offsets, unlisted = offsets.contiguous(), unlisted.contiguous()
+    entries = (a, b, out_dir, length, delta, lower, upper, libration, tls_rank)
+    with torch.cuda.device(dev):
+        _l.check(_l.load().cartnet_adp_bond_table(
+            u.data_ptr(), z.data_ptr(), _l.ptr(ei) if E else None, _l.ptr(dist) if E else None, _l.ptr(dirs) if E else None,
+            g.atom_row.data_ptr(), g.seg_ptr.data_ptr(), g.atom_ptr.data_ptr(), g.radii.data_ptr(), int(g.radii.numel()),
+            float(index.tol), offsets.data_ptr(), unlisted.data_ptr(), _l.ptr(params) if M else None,
+            _l.ptr(rank) if M else None, B, N, M, E, nb, *(t.data_ptr() if nb else None for t in entries),
+            stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_bond_table")
+    return BondTable(*entries, stats)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

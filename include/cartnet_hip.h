@@ -633,6 +633,49 @@ int cartnet_adp_aniso_h(const float* u, const int64_t* z, const int64_t* edge_in
                         double* crystal_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * The bond table of one batch: one entry per bond instead of cartnet_adp_bond_test's per-atom aggregates, with
+ * Hirshfeld's D signed, the Busing & Levy (1964) bounds on the thermally averaged bond length and the length corrected
+ * for the libration of a fitted rigid body (Cruickshank 1956; Schomaker & Trueblood 1968).  The reference has no
+ * counterpart.  cartnet_amd/bonds.py states the rule, bond_table_host restates both calls.
+ *   z, edge_index, cart_dist, cart_dir, atom_row, seg_ptr, radii, n_radii, tol and the bond rule as for
+ *   cartnet_adp_bond_test; atom_ptr as for cartnet_adp_riding_h; params [M,24] fp32 and rank [M] int32:
+ *   cartnet_adp_tls_fit's, both or both NULL.
+ * A table's length is known only after the graph is read, so there are two calls with a scan between them:
+ *   cartnet_bond_table_count   per atom i: listed[i] [N] int32, the bond edges j -> i with j < i (a symmetric graph lists
+ *                              every bond once; a pair bonded through two images is two entries), and unlisted[i] [N]
+ *                              int32, those with j > i, which are counted and never listed (a capped graph can hold a bond
+ *                              in one direction only: the two counts of a crystal then differ).  Atoms without a row get
+ *                              0, 0.  It does not read U.
+ *   cartnet_adp_bond_table     offset [N+1] int64: the exclusive scan of listed, offset[N] = nb, the table's length.
+ *                              Atom i's entries take the slots offset[i] ... in edge order, so the table is in target
+ *                              order and within a target in edge order; a slot outside [0, nb) is never written.  Per
+ *                              entry, a = j and b = i (int64, atom indices of the batch), dir [nb,3] and length [nb] the
+ *                              edge's cart_dir and cart_dist bit for bit, and in fp64 from the fp32 inputs, rounded once:
+ *                                delta      d^T (Sym U_b - Sym U_a) d, signed, the difference taken first
+ *                                lower      l + (sqrt w_b^2 - sqrt w_a^2)^2 / (2 l),  w_x^2 = tr U_x - d^T Sym U_x d
+ *                                upper      l + (sqrt w_b^2 + sqrt w_a^2)^2 / (2 l);  both NaN for a negative or NaN w^2
+ *                                libration  |r + (tr(L) r - L r) / 2|, r = l d, L = params[atom_row[b], 6..11] (11 22 33
+ *                                           23 13 12) as stored, where rank[atom_row[b]] > 0; NaN otherwise
+ *                                tls_rank   rank[atom_row[b]] (int32), 0 without TLS results
+ * Per crystal (one wave each, from the values as stored):
+ *   crystal_stats [B,9] fp64 (or NULL) = (listed, unlisted, sum of length, sum of |delta|, largest |delta| -- it keeps a
+ *   NaN --, entries with a finite libration, the sum and the largest of libration - length over those (0 without one),
+ *   entries with a NaN bound).
+ * N == 0 (or B == 0 for the second call): returns 0 without a launch and writes nothing.  nb == 0 needs no u, no edge
+ * arrays and no per-entry outputs.  Edge ends and rows out of range are skipped, never dereferenced.  No atomics, no LDS,
+ * no workgroup waits for another: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_bond_table_count(const int64_t* z, const int64_t* edge_index, const float* cart_dist, const int64_t* atom_row,
+                             const int64_t* seg_ptr, const float* radii, int32_t n_radii, float tol, int64_t N, int64_t M,
+                             int64_t E, int32_t* listed, int32_t* unlisted, void* stream);
+int cartnet_adp_bond_table(const float* u, const int64_t* z, const int64_t* edge_index, const float* cart_dist,
+                           const float* cart_dir, const int64_t* atom_row, const int64_t* seg_ptr, const int64_t* atom_ptr,
+                           const float* radii, int32_t n_radii, float tol, const int64_t* offset, const int32_t* unlisted,
+                           const float* params, const int32_t* rank, int32_t B, int64_t N, int64_t M, int64_t E, int64_t nb,
+                           int64_t* a, int64_t* b, float* dir, float* length, float* delta, float* lower, float* upper,
+                           float* libration, int32_t* tls_rank, double* crystal_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * A least-squares line per row and component through the exported ADPs of one batch over T temperatures.  The reference
  * predicts every crystal at the one temperature it is stored with (main.py:21-60); the model reads the temperature, so
  * one batch replicated T times answers how the ellipsoids grow.

@@ -29,7 +29,9 @@ pass on the GPU and tests the ADPs for rigid-body motion over all pairs of atoms
 ``metrics.molecule_test``).  ``--tls_fit`` (with ``--rigid_molecule``) fits the rigid-body tensors T, L and S of
 Schomaker & Trueblood to the ADPs of every such molecule (``metrics.tls_fit``).  ``--aniso_h`` (with ``--riding_h``) gives
 every hydrogen a full tensor from its parent's, that rigid-body motion and a nominal internal X-H motion
-(``metrics.aniso_h``).  There is no CPU path: the model runs on an AMD GPU only.
+(``metrics.aniso_h``).  ``--bond_table`` lists the bonds of every crystal of a ``--predict`` pass with Hirshfeld's D, the
+Busing & Levy bounds on the bond length and, after a TLS fit, the libration-corrected length (``metrics.bond_table``).
+There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
 
@@ -190,6 +192,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "not a checked literature value: put in your own")
     p.add_argument("--aniso_h_bend", type=float, default=ANISO_H_BEND,
                    help="--aniso_h: the same across X-H, in both directions alike (A^2); nominal as well")
+    p.add_argument("--bond_table", action="store_true",
+                   help="--predict: list the bonds of every crystal (the edges of the radius graph within r_i + r_j + "
+                        "--bond_tolerance between non-hydrogen atoms, each once) with Hirshfeld's D per bond, signed, the "
+                        "Busing & Levy lower and upper bounds on the thermally averaged bond length and -- with "
+                        "--rigid_molecule --tls_fit -- the length corrected for the fitted libration (bonds_* in the "
+                        "pickle).  It needs no other analysis flag; refused without --predict.  The CIFs do not change")
     return p
 
 
@@ -359,6 +367,8 @@ def analysis_options(args, inference: bool = False) -> dict:
             options["tls_fit"] = True
     if args.aniso_h and not inference:
         options["aniso_h"] = (args.aniso_h_stretch, args.aniso_h_bend)
+    if args.bond_table and not inference:
+        options["bond_table"] = tol
     return options
 
 
@@ -394,6 +404,8 @@ def main(argv=None) -> dict:
         raise SystemExit("--aniso_h serves --predict only")
     if args.aniso_h and not args.riding_h:
         raise SystemExit("--aniso_h builds on the parents of --riding_h: give that flag as well")
+    if args.bond_table and not args.predict:
+        raise SystemExit("--bond_table serves --predict only")
     if args.predict or args.predict_temperatures is not None:
         check_predict_args(args)
     if args.rigid_molecule and not (args.predict or args.inference):

@@ -1,6 +1,6 @@
 """What the ``predict_adps`` benchmarks share (bench_predict.py, bench_predict_rotations.py, bench_bond_test.py,
-bench_riding_h.py, bench_rigid_molecule.py): the model and the shard, the timed pass, the alternating rounds, the event-stamping wrapper and the
-time-limited child process.  A tool states its variants and builds its JSON; everything else is here.
+bench_riding_h.py, bench_rigid_molecule.py, bench_bond_table.py): the model and the shard, the timed pass, the alternating
+rounds, the event-stamping wrapper and the time-limited child process.  A tool states its variants and builds its JSON; everything else is here.
 
 The model is CartNet D = 256, L = 4 (fresh weights, eval mode); the shard 512 synthetic crystals of 30-70 atoms, packed
 geometry-only without targets and graphed at radius 5 on the GPU -- the shard ``main.py --predict`` would hold.  A time is

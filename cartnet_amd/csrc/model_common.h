@@ -111,10 +111,19 @@ struct HostProfScope {
 #endif
 inline EventPool& event_pool() { thread_local EventPool p; return p; }      // one per thread, for both drivers
 
+// Test-only skew of one of the two streams (cartnet_debug_stream_skew, cartnet_hip.h): which = 0 off, 1 side, 2 main.
+// Off, its whole cost is one thread-local read per Streams operation; nothing is queued.
+struct StreamSkew { int which = 0, usec = 0; };
+inline StreamSkew& stream_skew() { thread_local StreamSkew s; return s; }
+
 // The two streams of one entry-point call: `main` is the caller's, `side` the optional second one (the same stream, and
 // every operation a no-op, when there is none).  Operations return 0, or 2 with the error text set.  The two mark_*
 // return nullptr both for "one stream: nothing to order" and for a failed record; a failure is remembered, and the next
 // fork / *_waits / join returns it -- a null event alone means "nothing was queued, nothing to wait for".
+// With the skew on and two streams, late() queues a bounded spin (cartnet_debug_spin) on the skewed stream wherever one
+// of its concurrent sections starts: in the constructor, after each of its waits, after each of its records that the other
+// stream waits for -- so whatever it runs next is late against the other stream.  A spin that cannot be queued counts as
+// a failed record.
 struct Streams {
   const char* who;      // the entry point, for the error text
   hipStream_t main, side;
@@ -124,17 +133,27 @@ struct Streams {
       : who(who_), main((hipStream_t)stream), side(aux_stream ? (hipStream_t)aux_stream : (hipStream_t)stream),
         dual(aux_stream != nullptr && aux_stream != stream), pool(&event_pool()) {
     pool->next = 0;
+    if (dual) late(side), late(main);
   }
   int fail(const char* what) { cartnet_set_error("%s: stream %s failed", who, what); return 2; }
+  void late(hipStream_t s) {      // only called when dual
+    const StreamSkew& k = stream_skew();
+    if (k.which == (s == side ? 1 : 2) && cartnet_debug_spin(k.usec, (void*)s) != 0) record_failed = true;
+  }
   hipEvent_t mark(hipStream_t s) {
     hipEvent_t e = pool->get();
-    if (e && hipEventRecord(e, s) == hipSuccess) return e;
+    if (e && hipEventRecord(e, s) == hipSuccess) {
+      late(s);
+      return e;
+    }
     record_failed = true;
     return nullptr;
   }
   int waits(hipStream_t s, hipEvent_t e, const char* what) {
     if (record_failed) return fail("event record");
-    return hipStreamWaitEvent(s, e, 0) == hipSuccess ? 0 : fail(what);
+    if (hipStreamWaitEvent(s, e, 0) != hipSuccess) return fail(what);
+    late(s);
+    return record_failed ? fail("skew spin") : 0;
   }
   // after(main) -> side waits
   int fork() {

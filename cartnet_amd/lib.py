@@ -427,6 +427,8 @@ PROTOTYPES = {
                                              C.c_int32, c_f32p, c_f32p, c_i32p, c_stream, c_stream]),
     "cartnet_icomformer_backward": (C.c_int, [C.POINTER(IcfModel), C.POINTER(BatchDesc), C.c_void_p, C.c_size_t, C.c_int32,
                                               c_f32p, c_f32p, C.POINTER(IcfParams), c_stream, c_stream]),
+    "cartnet_debug_spin": (C.c_int, [C.c_int32, c_stream]),
+    "cartnet_debug_stream_skew": (C.c_int, [C.c_int32, C.c_int32]),
 }
 
 

@@ -912,6 +912,19 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, gra
                                          float(grad_scale), _l.stream_ptr()), "cartnet_adam_step")
 
 
+# --------------------------------------------------------------------------------------------------- stream-order seam
+def debug_spin(usec: int, stream: Optional[torch.cuda.Stream] = None) -> None:
+    """Queue one bounded delay kernel of ``usec`` microseconds (0..5000) on ``stream`` (default: the current one)."""
+    _l.check(_l.load().cartnet_debug_spin(int(usec), _l.stream_ptr() if stream is None else stream.cuda_stream),
+             "cartnet_debug_spin")
+
+
+def debug_stream_skew(which: int, usec: int = 0) -> None:
+    """Test-only (include/cartnet_hip.h): make the side (1) or the main (2) stream of this thread's two-stream calls late by
+    ``usec`` microseconds at the start of each of its concurrent sections; 0 switches it off."""
+    _l.check(_l.load().cartnet_debug_stream_skew(int(which), int(usec)), "cartnet_debug_stream_skew")
+
+
 # --------------------------------------------------------------------------------------------------- iComformer pieces
 class SegmentLayout:
     """Minimal stand-in for GraphLayout where only (rowptr, N, E) matter: S segments of rows given by ``ptr``."""

@@ -13,7 +13,8 @@
  *     is a field of CartnetGemmArgs / CartnetModel.  What it does keep is per THREAD: the message behind
  *     cartnet_last_error(), and, inside cartnet_model_forward / _backward, a pool of hipEvent_t (created once per
  *     thread, disable-timing, reused by every call of that thread to order its two streams) -- so two host threads
- *     may drive two models concurrently, one thread must not interleave two calls.  The one process-global is the
+ *     may drive two models concurrently, one thread must not interleave two calls -- and the test-only stream skew of
+ *     cartnet_debug_stream_skew (off unless a test switches it on).  The one process-global is the
  *     opt-in launch timer (cartnet_profile_gemm*), off unless bench.py switches it on;
  *   - return value 0 = ok, non-zero = error; cartnet_last_error() returns a thread-local message.
  *   - shapes are validated on the host before launch (a bad shape returns an error, it never launches).
@@ -1447,6 +1448,23 @@ int cartnet_icomformer_backward(const CartnetIcfModel* model, const CartnetBatch
  * grad_scale multiplies g first (1/world_size after the RCCL gradient all-reduce). */
 int cartnet_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                       float beta1, float beta2, float eps, int32_t step, float grad_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Stream-order test seam (off by default; tests/test_gpu_stream_order.py).  The two-stream entry points above
+ * (cartnet_model_* and cartnet_icomformer_* with an aux_stream) sum in fixed orders without atomics, so a correct
+ * schedule writes the same bytes whatever the relative speed of the two streams.  These two calls make one stream late
+ * on purpose, by a bounded amount, so that a missing wait shows as different bytes.
+ * cartnet_debug_spin: queues ONE single-thread kernel on `stream` that polls the device wall clock until `usec`
+ *   microseconds have passed.  It also ends after a fixed number of loop iterations, so it cannot hang whatever the clock
+ *   does.  usec outside 0..5000 is refused (nothing is queued).
+ * cartnet_debug_stream_skew: per-THREAD setting.  which = 0: off; 1: the side (aux) stream is late; 2: the main stream
+ *   is late; usec as above.  While it is on, every dual-stream call of this thread queues a cartnet_debug_spin on the late
+ *   stream at the start of each of that stream's concurrent sections: once when the call begins, after every wait the
+ *   late stream performs on an event of the other one, and after every event recorded on the late stream that the other
+ *   one waits for.  With which = 0, or without an aux_stream, nothing is queued: the launch sequence is unchanged.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_debug_spin(int32_t usec, void* stream);
+int cartnet_debug_stream_skew(int32_t which, int32_t usec);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,38 @@ def test_weight_image_sizes_and_gemm_precision_validation_without_gpu():
     assert l.cartnet_gemm(ctypes.byref(args), None) != 0 and b"precision" in l.cartnet_last_error()
 
 
+def test_stream_skew_seam_validates_on_the_host_and_skew_restores_off(monkeypatch):
+    """cartnet_debug_spin / cartnet_debug_stream_skew (the stream-order test seam) refuse out-of-range arguments before any
+    HIP call; tests/stream_utils.py::skew switches the seam off and puts its patches back after an exception."""
+    from cartnet_amd import lib, model, ops
+    import stream_utils as su
+    l = lib.load()
+    for usec in (-1, 5001, 2 ** 31 - 1):
+        assert l.cartnet_debug_spin(usec, None) != 0 and b"0..5000" in l.cartnet_last_error()
+        assert l.cartnet_debug_stream_skew(1, usec) != 0 and b"0..5000" in l.cartnet_last_error()
+        with pytest.raises(lib.CartnetHipError, match="0..5000"):
+            ops.debug_stream_skew(1, usec)
+    for which in (-1, 3):
+        assert l.cartnet_debug_stream_skew(which, 100) != 0 and b"which" in l.cartnet_last_error()
+    for which, usec in ((1, 0), (2, 5000), (0, 0)):              # accepted; the last one leaves it off
+        assert l.cartnet_debug_stream_skew(which, usec) == 0
+    seen = []
+    real = ops.debug_stream_skew
+    monkeypatch.setattr(ops, "debug_stream_skew", lambda which, usec=0: (seen.append((which, usec)), real(which, usec))[1])
+    wait, bwd = torch.cuda.Stream.wait_stream, model._CartNetFunction.__dict__["backward"]
+    with pytest.raises(ZeroDivisionError):
+        with su.skew(su.SIDE, 250):
+            assert seen == [(su.SIDE, 250)] and torch.cuda.Stream.wait_stream is not wait
+            assert model._CartNetFunction.__dict__["backward"] is not bwd
+            1 / 0
+    assert seen[-1] == (su.OFF, 0) and su._ACTIVE["which"] == su.OFF
+    assert torch.cuda.Stream.wait_stream is wait and model._CartNetFunction.__dict__["backward"] is bwd
+    with pytest.raises(ValueError, match="0..5000"):
+        with su.skew(su.MAIN, 5001):
+            pass
+    assert seen[-1] == (su.OFF, 0)
+
+
 def test_product_model_fails_loudly_off_gpu():
     from cartnet_amd.model import CartNet
     from cartnet_amd.synthetic import make_batch

@@ -7,7 +7,9 @@ Two things live here (a helper module, not a conftest):
 * ``CASES``: launches as data (shapes, leading dimensions, views inside wider buffers, flags, precision, tile_policy)
   with the ``family`` the host-side plan (cartnet_gemm_plan) must give.  ``fake_args`` turns a case into a
   ``lib.GemmArgs`` of pointers that are never dereferenced (tests/test_gemm_plan_host.py, no GPU); ``make_tensors`` /
-  ``gemm_kwargs`` allocate the operands for a real launch (tests/test_gpu_gemm_families.py).
+  ``gemm_kwargs`` allocate the operands for a real launch (tests/test_gpu_gemm_families.py); every buffer a launch
+  indexes by its rows is allocated ``TAIL`` rows longer than the launch is told, with NaN behind the inputs and the
+  sentinel behind the outputs (``tail_kind``), so that a read or a write past the last row shows.
 
 Row counts are computed from tile counts: ``rows(t)`` is the smallest M with t row tiles of 128, so a case "at the
 threshold" has a last tile of one row and the case one row tile below it (``rows(t) - 1`` rows) a full last tile.
@@ -185,14 +187,54 @@ def width_of(family):
     return 128 if family == "f32nn128" else 256
 
 
+TAIL = 160                    # rows allocated behind the last row of every row-indexed buffer: more than one row tile
+
+
+def tail_kind(c, name):
+    """How a buffer of a case is indexed by the launch's rows (M, or K in the "tn" layout), and what lies behind its last
+    row: (axis, fill) or None.  Inputs get NaN -- a ragged last tile that reads past its rows, or a split-K slab past K,
+    shows in the product or in a column sum; tgt / src get 0, a valid row of the gathered matrices; outputs get SENTINEL,
+    which must still be there after the launch."""
+    if name in ("C", "P", "H") or (name[0] == "C" and name[1:].isdigit()):
+        return 0, SENTINEL
+    if name == "A" or (name == "B" and c.layout == "tn") or name == "gst_g" or (name[0] in "RD" and name[1:].isdigit()):
+        return 0, float("nan")
+    if name == "gst_env":
+        return 1, float("nan")
+    if name in ("tgt", "src"):
+        return 1, 0
+    return None
+
+
+class Tensors(dict):
+    """{buffer name: tensor of the case's shape}; ``full[name]`` is the allocation behind a row-indexed buffer, TAIL rows
+    longer, of which the entry is the view of the first rows (same leading dimension)."""
+
+    def __init__(self):
+        super().__init__()
+        self.full = {}
+
+
+def assert_tails(c, t):
+    """After a launch: every row behind the last still holds what make_tensors put there."""
+    assert t.full, "no buffer of the case has a tail"
+    for name, full in t.full.items():
+        axis, fill = tail_kind(c, name)
+        tail = full[t[name].shape[0]:] if axis == 0 else full[:, t[name].shape[1]:]
+        assert tail.numel() == TAIL * full.shape[1 - axis], name
+        ok = torch.isnan(tail) if fill != fill else tail == fill
+        assert bool(ok.all()), f"{name}: {int((~ok).sum())} cells behind the last row were overwritten"
+
+
 def make_tensors(c, device):
     """Real operands of a case on ``device``: different weights and biases per group (a kernel that reads the wrong
     group's shows), NaN in every cell a launch must write, SENTINEL in every padding column it must not, sorted tgt and
-    random src.  Returns {buffer name: tensor} (2-D; 1-row buffers are the vectors) -- leave it unchanged after the
-    launch except through the launch."""
+    random src.  Every buffer the launch indexes by its rows is allocated TAIL rows longer (``tail_kind``) and handed out
+    as the view of its first rows.  Returns a ``Tensors`` {buffer name: tensor} (2-D; 1-row buffers are the vectors) --
+    leave it unchanged after the launch except through the launch."""
     buf, view = _buffers(c)
     gen = torch.Generator().manual_seed(1000 + sum(map(ord, c.name)))
-    t = {}
+    t = Tensors()
     for name, (r, w, dt) in buf.items():
         if name in ("C", "P", "H") or name.startswith(("C", "colsum", "colsq")):
             x = torch.full((r, w), SENTINEL if name in ("C", "P", "H") else float("nan"), dtype=dt)
@@ -209,7 +251,14 @@ def make_tensors(c, device):
         else:
             scale = 0.1 if name.startswith("B") and c.layout != "tn" else 1.0
             x = torch.randn(r, w, generator=gen) * scale
-        t[name] = x.to(device)
+        kind = tail_kind(c, name)
+        if kind is None:
+            t[name] = x.to(device)
+            continue
+        axis, fill = kind
+        tail = torch.full((TAIL, w) if axis == 0 else (r, TAIL), fill, dtype=dt)
+        t.full[name] = torch.cat([x, tail], dim=axis).to(device)
+        t[name] = t.full[name][:r] if axis == 0 else t.full[name][:, :w]
     for field in ("C", "cpre", "a_act_out"):               # the cells the launch must write
         if field in view:
             for b, off, w in view[field]:

@@ -156,13 +156,19 @@ def step(model, sd, batch, decoy_batch, decoy_sd, mode="train", opt=None, after_
     torch.cuda.synchronize()
     if timer is not None:
         timer["ms"] = e0.elapsed_time(e1)
-    mode = "train" if mode == "dropped" else mode
+    return collect(model, pred, b, grads=mode in ("train", "dropped"))
+
+
+def collect(model, pred, b, grads=True):
+    """The results of one pass as clones (tests/test_gpu_poison_steps.py compares the same set): `pred`, `x_out` / `e_out`
+    where the model leaves them in the batch `b`, `grad.<name>` of every parameter that has one (`grads`), `buf.<name>` of
+    every BatchNorm running buffer."""
     out = {"pred": pred.detach().clone()}
     if torch.is_tensor(getattr(b, "x", None)) and b.x.is_floating_point():
         out["x_out"] = b.x.detach().clone()
     if torch.is_tensor(getattr(b, "edge_attr", None)):
         out["e_out"] = b.edge_attr.detach().clone()
-    if mode == "train":
+    if grads:
         for n, p in model.named_parameters():
             if p.grad is not None:
                 out["grad." + n] = p.grad.detach().clone()
@@ -172,8 +178,8 @@ def step(model, sd, batch, decoy_batch, decoy_sd, mode="train", opt=None, after_
     return out
 
 
-def assert_same(ref, got, what):
-    """Bitwise equality of two `step` results, tensor by tensor; the message names the tensors that differ."""
+def assert_same(ref, got, what, than="the one-stream step"):
+    """Bitwise equality of two `step` / `collect` results, tensor by tensor; the message names the tensors that differ."""
     assert ref.keys() == got.keys(), (what, sorted(set(ref) ^ set(got)))
     bad = [k for k in ref if not torch.equal(ref[k], got[k])]
-    assert not bad, f"{what}: {len(bad)} of {len(ref)} tensors differ from the one-stream step: {bad[:12]}"
+    assert not bad, f"{what}: {len(bad)} of {len(ref)} tensors differ from {than}: {bad[:12]}"

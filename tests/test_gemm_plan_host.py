@@ -55,6 +55,53 @@ def test_every_case_plans_to_its_family(lib, c):
     assert info.gate_stats == (1 if c.family in ("f32p", "f32nn128", "x3nn16") else 0)
 
 
+SMALL_CASES = [c for c in gc.CASES if c.M <= 300 and c.K <= 300]
+
+
+def test_tails_cover_every_row_indexed_buffer_of_every_case():
+    """gemm_cases.tail_kind names, for every case, exactly the buffers whose first dimension is the launch's M (K for the
+    tn layout's operands; splitk * M for the slabs) or, for the row vectors tgt / src / gst_env, whose length is."""
+    for c in gc.CASES:
+        buf, _ = gc._buffers(c)
+        rows_ = c.K if c.layout == "tn" else c.M
+        for name, (r, w, dt) in buf.items():
+            kind = gc.tail_kind(c, name)
+            if name in ("tgt", "src", "gst_env"):
+                assert kind is not None and kind[0] == 1 and (r, w) == (1, c.M), (c.name, name)
+            elif name.startswith(("bias", "Gi", "Gj", "colsum", "colsq", "img", "gst_mean", "gst_gamma", "gst_beta")) or \
+                    (name[0] == "B" and name != "B"):
+                assert kind is None, (c.name, name)
+            else:
+                want = c.splitk * c.M if name[0] == "C" and name != "C" else (rows_ if name in ("A", "B", "H") else c.M)
+                assert kind is not None and kind[0] == 0 and r == want, (c.name, name, r, want)
+                assert (kind[1] == gc.SENTINEL) == (name[0] in "CPH"), (c.name, name)
+
+
+@pytest.mark.parametrize("c", SMALL_CASES, ids=lambda c: c.name)
+def test_operands_are_views_of_longer_buffers_with_the_same_leading_dimension(c):
+    """make_tensors on the CPU: each row-indexed buffer is the first rows of an allocation TAIL rows longer, fake_args and
+    gemm_ref64 see the case's own M and K, and the fp64 statement is finite (no tail reaches it)."""
+    import torch
+    t = gc.make_tensors(c, "cpu")
+    buf, _ = gc._buffers(c)
+    assert len(SMALL_CASES) >= 40 and t.full
+    for name, full in t.full.items():
+        r, w, _ = buf[name]
+        axis, _ = gc.tail_kind(c, name)
+        assert tuple(t[name].shape) == (r, w) and t[name].data_ptr() == full.data_ptr()
+        assert tuple(full.shape) == ((r + gc.TAIL, w) if axis == 0 else (r, w + gc.TAIL))
+        assert t[name].stride(0) == full.stride(0)
+    gc.assert_tails(c, t)
+    for f in ("A", "B", "C"):
+        for v in gc.views(c, t, f):
+            assert v.shape[0] == buf[f if f in buf else f + "0"][0]
+    ref = gc.gemm_ref64(c, t)
+    assert all(bool(torch.isfinite(x).all()) for x in ref["C"])
+    t.full["C" if "C" in t.full else "C0"][-1, 0] = 0.0              # an overwritten tail cell is reported
+    with pytest.raises(AssertionError, match="behind the last row"):
+        gc.assert_tails(c, t)
+
+
 # the half-storage families: planned here from fake pointers, computed in tests/test_gpu_half_storage_kernels.py and the
 # half-storage block of tests/test_gpu_kernels.py (which assert the family of every launch)
 def _half(lib, layout, **flags):

@@ -9,7 +9,11 @@ Bounds are the ones the suite already applies to each kind of result (no new tol
   silu' / sigmoid factor (H_DACT of tests/test_gpu_kernels.py);
 * a_act_out: 1e-6; the fp64 column-sum partials: 1e-6 of the sums of the values the launch stored, row tile by row tile;
   the gate-statistics sums: 2e-6 (tests/test_gpu_kernels.py::test_gate_backward_sums_without_the_statistics_pass);
-* every padding column of an output view (ld > N) still holds its sentinel.
+* every padding column of an output view (ld > N) still holds its sentinel;
+* every row-indexed buffer has 160 rows behind its last (gemm_cases.TAIL): NaN behind the inputs (A, the tn layout's B,
+  resid, dact, the gate-statistics operands), index 0 behind tgt / src, the sentinel behind the outputs.  A ragged last
+  tile, a column-sum or gate-statistics epilogue or a split-K slab that takes in a row past M (or K) turns its figure
+  into NaN, which fails every bound; the output tails must still hold the sentinel.
 
 Per output tile (128 rows by the family's tile width) the worst error normalised by that tile's own max|ref| is printed
 and asserted too: with the whole-matrix constant where the worst figure recorded for the family is at most a quarter of
@@ -148,4 +152,6 @@ def test_case_reaches_its_family_and_matches_fp64(ops, c):
                 mask[off:off + v_.shape[1]] = False
             pad = t[name][:, mask.to(dev)]
             assert pad.numel() > 0 and bool((pad == gc.SENTINEL).all()), f"{name}: padding overwritten"
+    # the rows behind the last: outputs still hold the sentinel (the NaN behind the inputs is in no figure above)
+    gc.assert_tails(c, t)
     assert not bad, bad

@@ -170,8 +170,54 @@ Trueblood 1968), the geometric product of a TLS analysis that THMA11 and PLATON 
               ``libration``, the sum and the largest of ``libration - length`` over those (0 without one), and the
               entries with a NaN bound.
 
-Not in the table: X-H bonds (a hydrogen has no ADP row), angles and torsions, and the riding-model correction, which
-needs a choice of which atom rides on which.
+Not in the table: X-H bonds (a hydrogen has no ADP row) and the riding-model correction, which needs a choice of which
+atom rides on which.  Angles and torsions have tables of their own, below.
+
+The angle and torsion tables (``metrics.angle_index`` and ``metrics.angle_table``, csrc/angle_table_ops.hip;
+``angle_table_host`` below restates them in numpy): the valence angles and the torsions of the bond graph, each with the
+value the fitted libration gives, as THMA11 and PLATON print them beside the corrected distances.  Both are built from
+the edges of the radius graph alone (``cart_dir``, ``cart_dist``), never from ``pos``: cell faces and images need no
+special case.
+
+  adjacency   a directed edge ``e = (j -> i)`` is a bond exactly as for the bond table.  Atom ``i``'s adjacency is the
+              bond edges that name it as their target, in edge order, sources ``j < i`` and ``j > i`` alike; its degree
+              ``d_i`` is ``counts[i] + unlisted[i]`` of the bond table's index.
+  angles      for a centre ``i`` every pair ``k1 < k2`` of positions in its adjacency, ordered by ``k1`` then ``k2``:
+              ``d (d - 1) / 2`` entries, entry ``(k1, k2)`` in slot ``k1 (2 d - k1 - 1) / 2 + (k2 - k1 - 1)`` of the atom;
+              centres in atom order.  ``a = src[e1]``, ``b = i``, ``c = src[e2]``.  ``value = atan2(|p x q|, p . q)`` in
+              degrees with ``p, q = fp64(cart_dir[e1]), fp64(cart_dir[e2])`` as stored: both point into the centre, so the
+              angle is that of the outward vectors; ``atan2`` and not ``acos``, which loses half its digits at 180.  A
+              pair bonded through two images has two adjacency entries and therefore an angle, as it has two bonds.
+  torsions    the central bond is a listed bond of the bond table, edge ``e0 = (b -> c)`` with ``b < c``, in the bond
+              table's order.  The ``d`` side: the bond edges ``ed`` of ``c``'s adjacency other than ``e0``, in order.  The
+              ``a`` side: the bond edges ``ea`` of ``b``'s adjacency other than the reverse of ``e0``, in order.  The
+              entry is ``(a = src[ea], b, c, d = src[ed])`` in slot ``ia * n_d + id`` of the bond.  With ``b1 =
+              dir[ea]``, ``b2 = dir[e0]``, ``b3 = -dir[ed]`` (fp64 of the stored fp32), ``n1 = b1 x b2`` and ``n2 = b2 x
+              b3``: ``value = atan2(|b2| (b1 . n2), n1 . n2)`` in degrees, the IUPAC sign; an fp32 result of -180 is
+              stored as +180; NaN when ``n1 . n1 == 0`` or ``n2 . n2 == 0`` (a collinear end).  A three-membered ring
+              gives torsions with ``a == d``: they are listed, and a user who does not want them filters on the indices.
+  reverse     the reverse of ``e0``: among the bond edges ``e'`` of ``b``'s adjacency with ``src[e'] == c`` the one with
+              the smallest ``m = max_k |s_k|``, ``s_k = fp32(fp32(dist[e'] dir[e'][k]) + fp32(dist[e0] dir[e0][k]))`` --
+              fp32, two products and their sum -- and the maximum taken as ``m = |s_0|``, then ``|s_1|`` and ``|s_2|`` in
+              turn where they are greater (a NaN in ``s_0`` is never chosen).  Candidates in edge order with a strict
+              ``<``: a tie keeps the lowest edge.  Accepted only if ``m < MOLECULE_CLOSURE`` (0.5 A).  Without one --
+              a capped graph that holds the bond in one direction only -- nothing is excluded on the ``a`` side.
+  libration   filled only with TLS results and where ``rank[row] > 0``, the row being ``b``'s for an angle and ``c``'s
+              for a torsion (a fit is per molecule: the choice only fixes which copy is read).  Every vector ``v =
+              fp64(cart_dist) fp64(cart_dir)`` is replaced by ``v' = v + 1/2 (tr(L) v - L v)`` with ``L = params[row,
+              6:12]`` as stored and in the bond table's operation order, and the same two formulae run on the ``v'``
+              (``b3' = -v'(ed)``; -180 is stored as +180 here too).  A torsion that is NaN by the raw criterion is NaN.
+              Otherwise NaN; ``tls_rank`` is the row's rank, 0 without TLS results.
+  arithmetic  cross products as ``p_y q_z - p_z q_y`` (cyclic), dot products and squares as ``(x x' + y y') + z z'``,
+              all in fp64 without contraction; the degree factor is the fp64 constant 57.29577951308232; one rounding
+              to fp32 on store.
+  crystal     fp64, from the values as stored; an angle belongs to the crystal of ``b``, a torsion to that of ``c``.
+              ``angle_stats`` [5]: entries, sum of ``value``, entries with a finite ``libration``, sum and largest of
+              ``|libration - value|`` over those.  ``torsion_stats`` [5]: entries, entries with a NaN ``value``, entries
+              with a finite ``libration``, sum and largest of the circular ``|libration - value|`` (``min(x, 360 - x)``)
+              over those.
+
+Not in these tables: X-H geometry, non-bonded contacts, standard uncertainties, and the S / origin part of the correction.
 """
 from __future__ import annotations
 
@@ -682,4 +728,153 @@ def bond_table_host(u, z, edge_index, cart_dist, cart_dir, atom_row, ptr=None, t
                     (np.nan if np.isnan(d).any() else d.max()) if len(d) else 0.0, fin.sum(), grow.sum(),
                     grow.max() if len(grow) else 0.0, nan_bound.sum())
     out["crystal_stats"] = stats
+    return out
+
+
+ANGLE_DEGREES = 57.29577951308232   # 180 / pi as the kernels hold it (csrc/angle_table_ops.hip: AT_DEGREES)
+
+
+def _cross(p, q) -> np.ndarray:
+    return np.stack([p[..., 1] * q[..., 2] - p[..., 2] * q[..., 1], p[..., 2] * q[..., 0] - p[..., 0] * q[..., 2],
+                     p[..., 0] * q[..., 1] - p[..., 1] * q[..., 0]], axis=-1)
+
+
+def _dot(p, q) -> np.ndarray:
+    return (p[..., 0] * q[..., 0] + p[..., 1] * q[..., 1]) + p[..., 2] * q[..., 2]
+
+
+def _librated(v, p) -> np.ndarray:
+    """``v + 1/2 (tr(L) v - L v)`` for vectors ``v`` [n,3] and their rows' parameters ``p`` [n,24] (fp64), in the bond
+    table's operation order."""
+    l11, l22, l33, l23, l13, l12 = (p[:, 6 + k] for k in range(6))
+    rx, ry, rz, tr = v[:, 0], v[:, 1], v[:, 2], (l11 + l22) + l33
+    return np.stack([rx + 0.5 * (tr * rx - ((l11 * rx + l12 * ry) + l13 * rz)),
+                     ry + 0.5 * (tr * ry - ((l12 * rx + l22 * ry) + l23 * rz)),
+                     rz + 0.5 * (tr * rz - ((l13 * rx + l23 * ry) + l33 * rz))], axis=1)
+
+
+def _angle(p, q) -> np.ndarray:
+    c = _cross(p, q)
+    return (np.arctan2(np.sqrt(_dot(c, c)), _dot(p, q)) * ANGLE_DEGREES).astype(np.float32)
+
+
+def _torsion(b1, b2, b3):
+    """``(value fp32 with -180 stored as +180, defined)`` of the torsions of ``b1``, ``b2``, ``b3`` [n,3] fp64."""
+    n1, n2 = _cross(b1, b2), _cross(b2, b3)
+    defined = ~((_dot(n1, n1) == 0.0) | (_dot(n2, n2) == 0.0))
+    v = (np.arctan2(np.sqrt(_dot(b2, b2)) * _dot(b1, n2), _dot(n1, n2)) * ANGLE_DEGREES).astype(np.float32)
+    return np.where(v == np.float32(-180.0), np.float32(180.0), v), defined
+
+
+def reverse_edge(e0: int, candidates, cart_dist, cart_dir):
+    """``(edge or -1, m)``: the reverse of bond edge ``e0`` among ``candidates`` (edges in order) by the module
+    docstring's fp32 rule, and the smallest ``m`` seen (``inf`` without a candidate), accepted or not."""
+    best, at = np.float32(np.inf), -1
+    for e in candidates:
+        s = np.abs(cart_dist[e] * cart_dir[e] + cart_dist[e0] * cart_dir[e0])      # fp32: two products, one sum
+        m = s[0]
+        m = s[1] if s[1] > m else m
+        m = s[2] if s[2] > m else m
+        if m < best:
+            best, at = m, int(e)
+    return (at if best < np.float32(MOLECULE_CLOSURE) else -1), best
+
+
+def angle_table_host(z, edge_index, cart_dist, cart_dir, atom_row, ptr=None, tol: float = BOND_TOLERANCE, params=None,
+                     rank=None) -> dict:
+    """The angle and torsion tables of the module docstring in plain numpy, in the kernels' operation order: a dict with
+    ``degree`` [N] int64, ``nbr_ptr`` [N+1] int64 and ``adj`` (the bond edges, adjacency by adjacency); ``bond_edge``,
+    ``reverse`` and ``torsion_counts`` [nb] int64 per listed bond of the bond table (its edge, its reverse edge or -1, its
+    torsions) and ``reverse_m`` [nb] fp32 (the smallest closure value a candidate gave, ``inf`` without one);
+    ``angle_counts`` [N] int64; ``angle_ptr`` and ``torsion_ptr`` [B+1] int64, the crystals' offsets into the two tables;
+    ``angles``: a dict of ``a``, ``b``, ``c`` int64, ``value`` and ``libration`` fp32, ``tls_rank`` int32; ``torsions``:
+    the same with ``d``; ``angle_stats`` and ``torsion_stats`` [B,5] fp64.  ``z``, ``edge_index``, ``cart_dist``,
+    ``cart_dir``, ``atom_row`` and ``ptr`` as for ``molecules_host`` (an atom has a row where ``atom_row >= 0``);
+    ``params`` [M,24] fp32 and ``rank`` [M] (``tls_fit_host``): both or neither."""
+    z = np.asarray(z, dtype=np.int64).reshape(-1)
+    src, tgt = (np.asarray(a, dtype=np.int64).reshape(-1) for a in np.asarray(edge_index).reshape(2, -1))
+    dist = np.asarray(cart_dist, dtype=np.float32).reshape(-1)
+    dirs = np.asarray(cart_dir, dtype=np.float32).reshape(-1, 3)
+    atom_row = np.asarray(atom_row, dtype=np.int64).reshape(-1)
+    N = len(z)
+    if (params is None) != (rank is None):
+        raise ValueError("params and rank come together or not at all")
+    ptr = np.asarray([0, N] if ptr is None else ptr, dtype=np.int64).reshape(-1)
+    B = len(ptr) - 1
+    inside = (src >= 0) & (src < N) & (tgt >= 0) & (tgt < N)
+    s, t = np.where(inside, src, 0), np.where(inside, tgt, 0)
+    has_row = atom_row >= 0
+    bond = inside & has_row[s] & has_row[t] & is_bond(dist, z[t], z[s], tol, same_atom=s == t)
+    adj = np.nonzero(bond)[0]
+    adj = adj[np.argsort(t[adj], kind="stable")]                              # target order, then edge order
+    degree = np.bincount(t[adj], minlength=N).astype(np.int64)
+    nbr_ptr = np.concatenate([[0], np.cumsum(degree)])
+    bond_edge = adj[s[adj] < t[adj]]                                          # the bond table's rows
+    nb = len(bond_edge)
+    fit = params is not None
+    if fit:
+        par = np.asarray(params, dtype=np.float32).reshape(-1, 24).astype(np.float64)
+        rk = np.asarray(rank).reshape(-1).astype(np.int32)
+    d64, v64 = dirs.astype(np.float64), dist.astype(np.float64)[:, None] * dirs.astype(np.float64)
+
+    def finish(cols, vectors, row_atom, formula):
+        """The columns every table shares: ``tls_rank`` and ``libration`` of the entries whose edges are ``vectors`` (a
+        list of (edge array, sign)) and whose fit is read at ``row_atom``."""
+        n = len(row_atom)
+        cols["tls_rank"] = rk[atom_row[row_atom]] if fit else np.zeros(n, dtype=np.int32)
+        cols["libration"] = np.full(n, np.nan, dtype=np.float32)
+        on = cols["tls_rank"] > 0
+        if fit and on.any():
+            p = par[atom_row[row_atom[on]]]
+            with np.errstate(invalid="ignore", over="ignore"):
+                cols["libration"][on] = formula(*[sign * _librated(v64[e[on]], p) for e, sign in vectors], on)
+        return cols
+
+    # ---- angles: per centre the pairs k1 < k2 of its adjacency, k1 first
+    pairs = [(nbr_ptr[i] + k1, nbr_ptr[i] + k2) for i in range(N) for k1 in range(degree[i])
+             for k2 in range(k1 + 1, degree[i])]
+    k1, k2 = (np.asarray([p[c] for p in pairs], dtype=np.int64) for c in range(2))
+    e1, e2 = adj[k1], adj[k2]
+    angles = {"a": s[e1], "b": t[e1], "c": s[e2], "value": _angle(d64[e1], d64[e2])}
+    finish(angles, [(e1, 1.0), (e2, 1.0)], t[e1], lambda p, q, on: _angle(p, q))
+    angle_counts = degree * (degree - 1) // 2
+    angle_off = np.concatenate([[0], np.cumsum(angle_counts)])
+
+    # ---- torsions: per listed bond e0 = (b -> c) the edges into b without the reverse of e0, times those into c without e0
+    reverse, reverse_m = np.full(nb, -1, dtype=np.int64), np.full(nb, np.inf, dtype=np.float32)
+    counts = np.zeros(nb, dtype=np.int64)
+    ea, e0s, ed = [], [], []
+    for k, e0 in enumerate(bond_edge):
+        b, c = s[e0], t[e0]
+        into_b, into_c = adj[nbr_ptr[b]:nbr_ptr[b + 1]], adj[nbr_ptr[c]:nbr_ptr[c + 1]]
+        reverse[k], reverse_m[k] = reverse_edge(e0, into_b[s[into_b] == c], dist, dirs)
+        side_a, side_d = into_b[into_b != reverse[k]], into_c[into_c != e0]
+        counts[k] = len(side_a) * len(side_d)
+        for x in side_a:
+            for y in side_d:
+                ea.append(x), e0s.append(e0), ed.append(y)
+    ea, e0s, ed = (np.asarray(x, dtype=np.int64) for x in (ea, e0s, ed))
+    value, defined = _torsion(d64[ea], d64[e0s], -d64[ed])
+    torsions = {"a": s[ea], "b": s[e0s], "c": t[e0s], "d": s[ed],
+                "value": np.where(defined, value, np.float32(np.nan)).astype(np.float32)}
+    finish(torsions, [(ea, 1.0), (e0s, 1.0), (ed, -1.0)], t[e0s],
+           lambda b1, b2, b3, on: np.where(defined[on], _torsion(b1, b2, b3)[0], np.float32(np.nan)))
+    torsion_off = np.concatenate([[0], np.cumsum(counts)])
+    listed_off = np.concatenate([[0], np.cumsum(np.bincount(t[bond_edge], minlength=N))])
+
+    at = np.clip(ptr, 0, N)
+    out = {"degree": degree, "nbr_ptr": nbr_ptr, "adj": adj, "bond_edge": bond_edge, "reverse": reverse,
+           "reverse_m": reverse_m, "torsion_counts": counts, "angle_counts": angle_counts, "angle_ptr": angle_off[at],
+           "torsion_ptr": torsion_off[listed_off[at]], "angles": angles, "torsions": torsions}
+    a_stats, t_stats = np.zeros((B, 5), dtype=np.float64), np.zeros((B, 5), dtype=np.float64)
+    for g in range(B):
+        for stats, table, cut, circular in ((a_stats, angles, out["angle_ptr"], False),
+                                            (t_stats, torsions, out["torsion_ptr"], True)):
+            v, lib = (table[k][cut[g]:cut[g + 1]].astype(np.float64) for k in ("value", "libration"))
+            fin = np.isfinite(lib)
+            x = np.abs(lib - v)[fin]
+            if circular:
+                x = np.minimum(x, 360.0 - x)
+            stats[g] = (len(v), np.isnan(v).sum() if circular else v.sum(), fin.sum(), x.sum(), x.max() if len(x) else 0.0)
+    out["angle_stats"], out["torsion_stats"] = a_stats, t_stats
     return out

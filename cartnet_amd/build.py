@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcartnet_hip.so")
-SOURCES = ["abi.hip", "gemm.hip", "gemm_bn256.hip", "gemm_bn128.hip", "gemm_bn64.hip", "gemm_x3.hip", "gemm_x3s.hip", "gemm_f32.hip", "gemm_f32w128.hip", "gemm_f32ao.hip", "gemm_f32p.hip", "gemm_f32p2.hip", "gemm_f32p3.hip", "gemm_f32gate.hip", "gemm_x3ao.hip", "gemm_h.hip", "graph_ops.hip", "edge_ops.hip", "node_ops.hip", "optim.hip", "model.hip", "icomformer.hip", "stream_debug.hip", "comformer_ops.hip", "equi_ops.hip", "radius_graph.hip", "metrics.hip", "eval_ops.hip", "export_ops.hip", "frame_ops.hip", "bond_ops.hip", "bond_table_ops.hip", "riding_ops.hip", "molecule_ops.hip", "tls_ops.hip", "aniso_h_ops.hip", "series_ops.hip", "collate.hip", "shard_ops.hip", "lattice_ops.hip", "symmetry_ops.hip"]
+SOURCES = ["abi.hip", "gemm.hip", "gemm_bn256.hip", "gemm_bn128.hip", "gemm_bn64.hip", "gemm_x3.hip", "gemm_x3s.hip", "gemm_f32.hip", "gemm_f32w128.hip", "gemm_f32ao.hip", "gemm_f32p.hip", "gemm_f32p2.hip", "gemm_f32p3.hip", "gemm_f32gate.hip", "gemm_x3ao.hip", "gemm_h.hip", "graph_ops.hip", "edge_ops.hip", "node_ops.hip", "optim.hip", "model.hip", "icomformer.hip", "stream_debug.hip", "comformer_ops.hip", "equi_ops.hip", "radius_graph.hip", "metrics.hip", "eval_ops.hip", "export_ops.hip", "frame_ops.hip", "bond_ops.hip", "bond_table_ops.hip", "angle_table_ops.hip", "riding_ops.hip", "molecule_ops.hip", "tls_ops.hip", "aniso_h_ops.hip", "series_ops.hip", "collate.hip", "shard_ops.hip", "lattice_ops.hip", "symmetry_ops.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-source additions (the reason is at the top of the source file)
 # gemm_f32.hip: cn_gemm_f32tn_kernel declares 4 waves per SIMD to cap its registers at 128 (so that a main-stream GEMM
@@ -23,7 +23,8 @@ EXTRA_FLAGS = {"radius_graph.hip": ["-ffp-contract=off"], "lattice_ops.hip": ["-
                "gemm_f32p3.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "tls_ops.hip": ["-Rpass-analysis=kernel-resource-usage"],      # its scratch must be 0: DESIGN.md 2.12
                "aniso_h_ops.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],      # the same: DESIGN.md 2.13
-               "bond_table_ops.hip": ["-Rpass-analysis=kernel-resource-usage"]}      # no scratch, no LDS: DESIGN.md 2.16
+               "bond_table_ops.hip": ["-Rpass-analysis=kernel-resource-usage"],      # no scratch, no LDS: DESIGN.md 2.16
+               "angle_table_ops.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]}      # the same: DESIGN.md 2.17
 # Translation units whose kernels must not spill: gemm_f32p.hip counts its memory operations by hand -- a compiler reload of a
 # spilled VGPR drains that queue (s_waitcnt vmcnt(0) in the hot loop), and an SGPR restored by v_readlane right in front of an
 # inline-asm buffer instruction is read before it is written (the hazard recogniser does not look inside the string).

@@ -1,13 +1,13 @@
-// The bond graph of a batch on the device: what bond_ops.hip, bond_table_ops.hip, riding_ops.hip, molecule_ops.hip,
-// tls_ops.hip and aniso_h_ops.hip share, each rule written once.  The graph is the batch's radius graph (edges sorted by
-// target atom, the periodic images solved in cart_dist / cart_dir) with the two lookups metrics.batch_graph builds:
-// atom_row [N] (an atom's row in the model's output, -1 for a hydrogen) and seg_ptr [N+1] (atom i owns the edges
-// [seg_ptr[i], seg_ptr[i+1])).  The rules are stated in cartnet_amd/bonds.py, which restates every kernel in numpy, bit
-// for bit.
+// The bond graph of a batch on the device: what bond_ops.hip, bond_table_ops.hip, angle_table_ops.hip, riding_ops.hip,
+// molecule_ops.hip, tls_ops.hip and aniso_h_ops.hip share, each rule written once.  The graph is the batch's radius graph
+// (edges sorted by target atom, the periodic images solved in cart_dist / cart_dir) with the two lookups
+// metrics.batch_graph builds: atom_row [N] (an atom's row in the model's output, -1 for a hydrogen) and seg_ptr [N+1] (atom
+// i owns the edges [seg_ptr[i], seg_ptr[i+1])).  The rules are stated in cartnet_amd/bonds.py, which restates every kernel
+// in numpy, bit for bit.
 //
 // Everything here is __device__ __forceinline__ and takes the compile flags of the file that includes it: aniso_h_ops.hip
-// is compiled with -ffp-contract=off, the others are not, and each keeps the contraction it had.  bg_form is the only
-// helper with products to contract; aniso_h_ops.hip does not call it.
+// and angle_table_ops.hip are compiled with -ffp-contract=off, the others are not, and each keeps the contraction it had.
+// bg_form is the only helper with products to contract; neither of the two calls it.
 #pragma once
 #include "common.h"
 #include "crystal_reduce.h"
@@ -74,6 +74,12 @@ __device__ __forceinline__ bool bg_bond(const BondGraph& g, int64_t i, float ri,
 // ---- the ordered fold: the items a group found in one pass, folded in ITEM order whatever lane holds them, so a sum is
 // the sequential fp64 sum and a tie keeps the earlier item.  bg_walk calls step(l) with the wave lane l of every item of
 // the group at `base` whose lane raised `flag`, lowest lane first; step reads the item with __shfl(value, l).
+// the flags of the group at `base` alone, lane `sub` of the group in bit `sub`: a lane's rank among the raised flags is
+// the population count of the bits below its own (angle_table_ops.hip; bond_table_ops.hip keeps its own copy, bt_flags)
+__device__ __forceinline__ unsigned int bg_flags(bool flag, int base) {
+  return (unsigned int)((__ballot(flag) >> base) & ((1ull << BG_LANES) - 1));
+}
+
 template <typename Step>
 __device__ __forceinline__ void bg_walk(bool flag, int base, Step&& step) {
   unsigned int found = (unsigned int)((__ballot(flag) >> base) & ((1ull << BG_LANES) - 1));

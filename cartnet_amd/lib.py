@@ -387,6 +387,15 @@ PROTOTYPES = {
                                          C.c_float, c_i64p, c_i32p, c_f32p, c_i32p, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_int64, C.c_int64, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                          c_f32p, c_i32p, C.c_void_p, c_stream]),
+    "cartnet_bond_adjacency": (C.c_int, [c_i64p, c_i64p, c_f32p, c_i64p, c_i64p, c_f32p, C.c_int32, C.c_float, c_i64p,
+                                         c_i64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_i64p, c_i64p, c_stream]),
+    "cartnet_angle_table_count": (C.c_int, [c_i64p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_i64p, C.c_int64, C.c_int64,
+                                            C.c_int64, c_i64p, c_i64p, c_i64p, c_stream]),
+    "cartnet_adp_angle_table": (C.c_int, [c_i64p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p,
+                                          c_i64p, c_i64p, c_f32p, c_i32p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_int64, C.c_int64, C.c_int64, c_i64p, c_i64p, c_i64p, c_f32p, c_f32p, c_i32p,
+                                          c_i64p, c_i64p, c_i64p, c_i64p, c_f32p, c_f32p, c_i32p, C.c_void_p, C.c_void_p,
+                                          c_stream]),
     "cartnet_adp_temp_series": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, c_i64p, C.c_int32, C.c_int64, c_f32p, c_f32p,
                                           c_f32p, c_i32p, C.c_void_p, c_stream]),
     "cartnet_collate": (C.c_int, [C.POINTER(Shard), c_i64p, c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int64, C.c_int64,

@@ -298,7 +298,7 @@ def _batch_field(batch, *names):
 
 class BatchGraph(NamedTuple):
     """Everything the bond-graph analyses (``bond_test``, ``riding_h``, ``molecules``, ``molecule_test``, ``tls_fit``,
-    ``aniso_h``, ``bond_index``, ``bond_table``) take from a batch, checked once by ``batch_graph`` and good for every prediction of that batch: ``z`` [N]
+    ``aniso_h``, ``bond_index``, ``bond_table``, ``angle_index``, ``angle_table``) take from a batch, checked once by ``batch_graph`` and good for every prediction of that batch: ``z`` [N]
     int64; ``edge_index`` [2,E] sorted by target; ``cart_dist`` [E]; ``cart_dir`` [E,3] (``None`` if not asked for);
     ``mask`` = ``non_H_mask`` [N] (``None``: every atom has a row); ``M``, the rows; the two lookups of the kernels,
     ``atom_row`` [N] int64 (an atom's row, -1 outside the mask) and ``seg_ptr`` [N+1] int64 (atom i owns the edges
@@ -780,6 +780,162 @@ def bond_table(u: torch.Tensor, batch, row_ptr: torch.Tensor, index: BondIndex, 
             _l.ptr(rank) if M else None, B, N, M, E, nb, *(t.data_ptr() if nb else None for t in entries),
             stats.data_ptr(), _l.stream_ptr()), "cartnet_adp_bond_table")
     return BondTable(*entries, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The angle and torsion tables (csrc/angle_table_ops.hip): the valence angles and the torsions of the bond graph from the
+# edges alone, each with the value the fitted libration gives.  Two calls, as for the bond table: what is listed does not
+# depend on U, only the libration columns do (through the TLS fit).  The rule: bonds.py.
+
+class AngleIndex(NamedTuple):
+    """What ``angle_index`` returns, all on the device but the last: ``bonds``, the ``BondIndex`` it builds on (a degree
+    is its ``counts + unlisted``, a torsion's central bond a row of its table); ``nbr_ptr`` [N+1] int64, the exclusive scan
+    of the degrees; ``adj`` [E] int64, atom i's bond edges in edge order from ``adj[nbr_ptr[i]]`` on (what lies past
+    ``nbr_ptr[N]`` is not written); per listed bond ``bond_edge`` [nb] int64 (its edge), ``reverse`` [nb] int64 (the edge
+    that holds it in the other direction, -1 if the graph has none) and ``torsion_counts`` [nb] int64 with their
+    exclusive scan ``torsion_offsets`` [nb+1]; ``angle_counts`` [N] int64, ``d (d - 1) / 2`` per atom, with
+    ``angle_offsets`` [N+1]; ``angle_ptr`` and ``torsion_ptr`` [B+1] int64, the crystals' offsets into the two tables, and
+    ``table_ptr_host`` [2,B+1], both on the host (the one copy ``angle_index`` makes: the tables' lengths are
+    ``table_ptr_host[:, -1]``)."""
+    bonds: BondIndex
+    nbr_ptr: torch.Tensor
+    adj: torch.Tensor
+    bond_edge: torch.Tensor
+    reverse: torch.Tensor
+    torsion_counts: torch.Tensor
+    torsion_offsets: torch.Tensor
+    angle_counts: torch.Tensor
+    angle_offsets: torch.Tensor
+    angle_ptr: torch.Tensor
+    torsion_ptr: torch.Tensor
+    table_ptr_host: torch.Tensor
+
+
+class AngleTable(NamedTuple):
+    """What ``angle_table`` returns, all on the device.  Per valence angle a-b-c (centres in atom order, the pairs of a
+    centre's bond edges by the first, then the second): ``angle_a``, ``angle_b``, ``angle_c`` [na] int64, the batch's atom
+    indices; ``angle_value`` [na] fp32, degrees; ``angle_libration`` [na] fp32, the angle after the libration ``L`` of the
+    TLS fit of ``b``'s molecule (NaN without a fit) and ``angle_tls_rank`` [na] int32, that fit's rank (0 without one).
+    Per torsion a-b-c-d (the bond table's bonds b-c in its order, then the neighbours of ``b``, then those of ``c``):
+    ``torsion_a`` ... ``torsion_d`` [nt] int64; ``torsion_value`` [nt] fp32, degrees in (-180, 180] with the IUPAC sign,
+    NaN for a collinear end; ``torsion_libration`` and ``torsion_tls_rank`` as above, read at ``c``.  ``angle_stats``
+    [B,5] fp64: entries, sum of the values, entries with a finite libration, sum and largest of ``|libration - value|``
+    over those; ``torsion_stats`` [B,5] fp64: entries, NaN values, entries with a finite libration, sum and largest of the
+    circular ``|libration - value|`` over those."""
+    angle_a: torch.Tensor
+    angle_b: torch.Tensor
+    angle_c: torch.Tensor
+    angle_value: torch.Tensor
+    angle_libration: torch.Tensor
+    angle_tls_rank: torch.Tensor
+    torsion_a: torch.Tensor
+    torsion_b: torch.Tensor
+    torsion_c: torch.Tensor
+    torsion_d: torch.Tensor
+    torsion_value: torch.Tensor
+    torsion_libration: torch.Tensor
+    torsion_tls_rank: torch.Tensor
+    angle_stats: torch.Tensor
+    torsion_stats: torch.Tensor
+
+
+def _scan(counts: torch.Tensor) -> torch.Tensor:
+    """The exclusive scan of ``counts`` [n] with its total, [n+1] int64: a static-shape device op."""
+    return torch.cat([counts.new_zeros(1, dtype=torch.int64), torch.cumsum(counts, 0, dtype=torch.int64)])
+
+
+def _check_bond_index(bonds: BondIndex, N: int, B: int, dev) -> int:
+    """The length of the bond table of ``bonds`` after the check that it is the index of a batch of ``N`` atoms in ``B``
+    crystals on ``dev``."""
+    offsets, unlisted, counts, on_host = bonds.offsets, bonds.unlisted, bonds.counts, bonds.bond_ptr_host
+    if not (tuple(offsets.shape) == (N + 1,) and offsets.dtype == torch.int64 and offsets.device == dev
+            and all(tuple(t.shape) == (N,) and t.dtype == torch.int32 and t.device == dev for t in (unlisted, counts))
+            and tuple(bonds.bond_ptr.shape) == (B + 1,) and bonds.bond_ptr.device == dev
+            and tuple(on_host.shape) == (B + 1,) and on_host.device.type == "cpu"):
+        raise ValueError(f"index does not belong to this batch ({N} atoms, {B} crystals)")
+    return int(on_host[-1])
+
+
+def angle_index(batch, row_ptr: torch.Tensor, tol: float = 0.4, rows: Optional[int] = None,
+                bonds: Optional[BondIndex] = None) -> AngleIndex:
+    """Where the angles and the torsions of ``batch`` go in their tables: ``cartnet_bond_adjacency`` and
+    ``cartnet_angle_table_count``, static-shape scans around them and ONE small device-to-host copy, the two ``[B+1]``
+    offsets of the crystals together.  ``batch`` and ``rows``: what ``batch_graph`` takes, or its ``BatchGraph``;
+    ``row_ptr`` [B+1]: ``target_row_ptr``; ``bonds``: the ``bond_index`` of the same batch and tolerance if there is one
+    already (else it is built here, with its own copy).  Nothing depends on U, so one index serves every prediction of the batch."""
+    g = batch_graph(batch, rows, "angle_index")
+    N, ei, E, dist, dirs, M, dev = g.N, g.edge_index, g.E, g.cart_dist, g.cart_dir, g.M, g.z.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    if g.B != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {g.B}")
+    if bonds is None:
+        bonds = bond_index(g, row_ptr, tol)
+    elif bonds.tol != float(tol):
+        raise ValueError(f"bonds was built with the tolerance {bonds.tol}, not {float(tol)}")
+    nb = _check_bond_index(bonds, N, B, dev)
+    nbr_ptr = _scan(bonds.counts.to(torch.int64) + bonds.unlisted)
+    adj = torch.empty(E, dtype=torch.int64, device=dev)
+    bond_edge, reverse, torsion_counts = (torch.empty(nb, dtype=torch.int64, device=dev) for _ in range(3))
+    angle_counts = torch.zeros(N, dtype=torch.int64, device=dev)
+    if N and M and E:                            # else nothing is launched: no atom has a bond
+        offsets = bonds.offsets.contiguous()
+        with torch.cuda.device(dev):
+            _l.check(_l.load().cartnet_bond_adjacency(
+                g.z.data_ptr(), ei.data_ptr(), dist.data_ptr(), g.atom_row.data_ptr(), g.seg_ptr.data_ptr(),
+                g.radii.data_ptr(), int(g.radii.numel()), float(tol), nbr_ptr.data_ptr(), offsets.data_ptr(), N, M, E, nb,
+                adj.data_ptr(), _l.ptr(bond_edge) if nb else None, _l.stream_ptr()), "cartnet_bond_adjacency")
+            _l.check(_l.load().cartnet_angle_table_count(
+                ei.data_ptr(), dist.data_ptr(), dirs.data_ptr(), nbr_ptr.data_ptr(), offsets.data_ptr(), adj.data_ptr(),
+                _l.ptr(bond_edge) if nb else None, N, E, nb, angle_counts.data_ptr(), _l.ptr(reverse) if nb else None,
+                _l.ptr(torsion_counts) if nb else None, _l.stream_ptr()), "cartnet_angle_table_count")
+    angle_offsets, torsion_offsets = _scan(angle_counts), _scan(torsion_counts)
+    angle_ptr, torsion_ptr = angle_offsets[g.atom_ptr.clamp(0, N)], torsion_offsets[bonds.bond_ptr.clamp(0, nb)]
+    return AngleIndex(bonds, nbr_ptr, adj, bond_edge, reverse, torsion_counts, torsion_offsets, angle_counts, angle_offsets,
+                      angle_ptr, torsion_ptr, torch.stack([angle_ptr, torsion_ptr]).cpu())
+
+
+def angle_table(batch, row_ptr: torch.Tensor, index: AngleIndex, tls: Optional[TlsFit] = None) -> AngleTable:
+    """The angle and torsion tables of ``batch``: one call of ``cartnet_adp_angle_table``.  ``batch``: what
+    ``batch_graph`` takes, or its ``BatchGraph``; ``row_ptr`` [B+1]: ``target_row_ptr``; ``index``: ``angle_index`` of the
+    same batch.  ``tls``: a ``tls_fit`` of a prediction of the batch; with it an entry of a fitted molecule gets its
+    ``libration`` and ``tls_rank``, without it they are NaN and 0.  Nothing is read back."""
+    g = batch_graph(batch, None if tls is None else int(tls.rank.shape[0]), "angle_table", "tls")
+    N, ei, E, dist, dirs, M, dev = g.N, g.edge_index, g.E, g.cart_dist, g.cart_dir, g.M, g.z.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    if g.B != B:
+        raise ValueError(f"row_ptr names {B} crystals, batch.ptr {g.B}")
+    nb = _check_bond_index(index.bonds, N, B, dev)
+    on_host = index.table_ptr_host
+    lists = {"nbr_ptr": N + 1, "adj": E, "bond_edge": nb, "reverse": nb, "torsion_offsets": nb + 1, "angle_offsets": N + 1}
+    if not (all(tuple(getattr(index, k).shape) == (n,) and getattr(index, k).dtype == torch.int64
+                and getattr(index, k).device == dev for k, n in lists.items())
+            and tuple(on_host.shape) == (2, B + 1) and on_host.device.type == "cpu"):
+        raise ValueError(f"index does not belong to this batch ({N} atoms, {B} crystals)")
+    params = rank = None
+    if tls is not None:
+        params, rank = tls.params, tls.rank
+        if not (tuple(params.shape) == (M, 24) and params.dtype == torch.float32 and tuple(rank.shape) == (M,)
+                and rank.dtype == torch.int32 and params.device == dev and rank.device == dev):
+            raise ValueError(f"tls does not belong to this batch ({M} rows)")
+        params, rank = params.contiguous(), rank.contiguous()
+    na, nt = int(on_host[0, -1]), int(on_host[1, -1])
+    angles = tuple(torch.empty(na, dtype=d, device=dev) for d in (torch.int64,) * 3 + (torch.float32,) * 2 + (torch.int32,))
+    torsions = tuple(torch.empty(nt, dtype=d, device=dev) for d in (torch.int64,) * 4 + (torch.float32,) * 2 + (torch.int32,))
+    if M == 0 or N == 0:                         # the entry point launches nothing
+        return AngleTable(*angles, *torsions, *(torch.zeros((B, 5), dtype=torch.float64, device=dev) for _ in range(2)))
+    stats = tuple(torch.empty((B, 5), dtype=torch.float64, device=dev) for _ in range(2))
+    nbr_ptr, offsets, adj, bond_edge, reverse, angle_offsets, torsion_offsets = (t.contiguous() for t in (
+        index.nbr_ptr, index.bonds.offsets, index.adj, index.bond_edge, index.reverse, index.angle_offsets,
+        index.torsion_offsets))
+    with torch.cuda.device(dev):
+        _l.check(_l.load().cartnet_adp_angle_table(
+            _l.ptr(ei) if E else None, _l.ptr(dist) if E else None, _l.ptr(dirs) if E else None, g.atom_row.data_ptr(),
+            g.atom_ptr.data_ptr(), nbr_ptr.data_ptr(), offsets.data_ptr(), _l.ptr(adj) if E else None,
+            _l.ptr(bond_edge) if nb else None, _l.ptr(reverse) if nb else None, angle_offsets.data_ptr(),
+            torsion_offsets.data_ptr(), _l.ptr(params), _l.ptr(rank), B, N, M, E, nb, na, nt,
+            *(t.data_ptr() if na else None for t in angles), *(t.data_ptr() if nt else None for t in torsions),
+            stats[0].data_ptr(), stats[1].data_ptr(), _l.stream_ptr()), "cartnet_adp_angle_table")
+    return AngleTable(*angles, *torsions, *stats)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -5,8 +5,8 @@ not) one forward, one ``adp_export`` (csrc/export_ops.hip: the predictions on th
 transform the reference applied to the dataset's targets, dataset/extract_csd_data.py:115-123 -- with U_eq and the
 principal values / axes), the fractional coordinates, ONE device-to-host copy (``metrics.to_host``) and a split by row
 counts on the host.  What else the copy brings -- for crystals from CIF files, in K frames, at T temperatures, and for
-the five analyses of ``Analyses`` and the bond table -- is stated once, in ``GROUPS``: a row per group of keys with its
-documentation.  ``write_cif`` writes one crystal of the result as a P1 CIF, ``write_cif_symmetric`` one that came from a CIF file in the
+the five analyses of ``Analyses``, the bond table and the angle and torsion tables -- is stated once, in ``GROUPS``: a row
+per group of keys with its documentation.  ``write_cif`` writes one crystal of the result as a P1 CIF, ``write_cif_symmetric`` one that came from a CIF file in the
 file's own setting.  Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in
 memory), ``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the
 forward in K frames that this pass and ``evaluate.inference`` share.
@@ -18,10 +18,10 @@ from typing import Callable, Dict, List, NamedTuple, Optional
 
 import torch
 
-from .metrics import (adp_export, aniso_h as aniso_h_call, batch_graph, bond_index, bond_table as bond_table_call,
-                      bond_test, check_export_status, check_temperatures, edge_row_ptr, frame_mean, molecule_test,
-                      molecules as find_molecules, riding_h as riding_h_call, rotate_rows, split_rows, target_row_ptr,
-                      temp_series, tls_fit as tls_fit_call, to_host)
+from .metrics import (adp_export, angle_index, angle_table as angle_table_call, aniso_h as aniso_h_call, batch_graph,
+                      bond_index, bond_table as bond_table_call, bond_test, check_export_status, check_temperatures,
+                      edge_row_ptr, frame_mean, molecule_test, molecules as find_molecules, riding_h as riding_h_call,
+                      rotate_rows, split_rows, target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
 
 
 class Analyses(NamedTuple):
@@ -43,34 +43,37 @@ class Analyses(NamedTuple):
 
 
 class Group(NamedTuple):
-    """One group of keys of a result.  ``present(analyses, sym, rotations, temperatures, bond_table)``: whether a pass
-    has it (the last switch, ``None`` by default, is the one analysis that is no field of ``Analyses``);
+    """One group of keys of a result.  ``present(analyses, sym, rotations, temperatures, bond_table, angle_table)``:
+    whether a pass has it (the last two switches, ``None`` by default, are the analyses that are no field of ``Analyses``);
     ``cuts``: its keys in order, each with how it is cut into the crystals' entries -- a tensor that travels to the host
     as one slice of dim 0 per "crystal", or as the pieces of dim 0 that hold a crystal's atoms ("atom"), its non-hydrogen
-    rows ("row"), the non-hydrogen atoms of its asymmetric unit ("site") or its listed bonds ("bond", counted from the
-    batch's ``bond_ptr``); ``None``: assembled on the host; ``doc``: what the keys hold."""
+    rows ("row"), the non-hydrogen atoms of its asymmetric unit ("site"), its listed bonds ("bond", counted from the
+    batch's ``bond_ptr``), its angles ("angle") or its torsions ("torsion"; both counted from the batch's ``angle_ptr`` and
+    ``torsion_ptr``);
+    ``None``: assembled on the host; ``doc``: what the keys hold."""
     present: Callable
     cuts: Dict[str, Optional[str]]
     doc: str
 
 
-# Every key of a result, stated once, in the key order of a result (it is in the pickle's bytes); "series" is last because
-# its keys live in result["series"], which has one entry per input crystal.
+# Every key of a result, stated once, in the key order of a result (it is in the pickle's bytes).  The keys of "series"
+# live in result["series"], which has one entry per input crystal and is appended to a result last; the two rows after it
+# came later and follow ``bonds_*`` in a result.
 GROUPS: Dict[str, Group] = {
-    "base": Group(lambda a, sym, K, T, bt=None: True,
+    "base": Group(lambda a, sym, K, T, bt=None, at=None: True,
         {"name": None, "atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "temp": None, "u_cart": "row",
          "u_cif": "row", "u_eq": "row", "principal": "row", "axes": "row", "stats": "crystal"},
         """``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms the rows belong to); ``frac`` [N,3] and ``z`` [N]
         (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the shard has none); ``u_cart`` [n,3,3] (the
         model's output); ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12); ``u_eq`` [n]; ``principal`` [n,3] ascending;
         ``axes`` [n,3,3]; ``stats`` [3] fp64 (sum of u_eq, smallest principal value, rows with a non-positive one)."""),
-    "symmetry": Group(lambda a, sym, K, T, bt=None: sym,
+    "symmetry": Group(lambda a, sym, K, T, bt=None, at=None: sym,
         {"asym_labels": None, "asym_frac": None, "asym_z": None, "u_cif_asym": "site", "spread": "site", "symops": None},
         """``sym``: the ``CifSymmetry`` of a shard expanded from CIF files.  ``asym_labels`` / ``asym_frac`` [a,3] /
         ``asym_z`` [a] (the asymmetric unit as the file gives it), ``symops`` (strings, identity first), ``u_cif_asym``
         [h,6] (one row per non-hydrogen atom of the asymmetric unit, the mean over its orbit,
         ``symmetry.site_average``) and ``spread`` [h]."""),
-    "rotations": Group(lambda a, sym, K, T, bt=None: K > 1,
+    "rotations": Group(lambda a, sym, K, T, bt=None, at=None: K > 1,
         {"rot_spread": "row", "frames": "crystal", "rot_stats": "crystal"},
         """``rotations`` = K > 1: every batch is predicted in K frames by ONE forward of ``replicate(batch, K, R)``
         with ``R = frames(B, K, gen, device)`` (one generator seeded with ``seed`` for the whole pass), the members are
@@ -78,7 +81,7 @@ GROUPS: Dict[str, Group] = {
         the mean.  ``rot_spread`` [n] (per row the largest deviation of a frame's prediction from the mean), ``frames``
         [K,3,3] (the rotations used, the identity first) and ``rot_stats`` [2] fp64 (sum and maximum of
         ``rot_spread``)."""),
-    "rigid_bond": Group(lambda a, sym, K, T, bt=None: a.rigid_bond is not None,
+    "rigid_bond": Group(lambda a, sym, K, T, bt=None, at=None: a.rigid_bond is not None,
         {"bond_count": "row", "bond_delta_mean": "row", "bond_delta_max": "row", "bond_worst": "row", "bond_over": "row",
          "bond_ueq_ratio": "row", "bond_stats": "crystal"},
         """``rigid_bond`` = ``(tol, threshold)``: Hirshfeld's rigid-bond test, one ``metrics.bond_test``
@@ -88,7 +91,7 @@ GROUPS: Dict[str, Group] = {
         ``bond_worst`` [n] (the partner of the worst bond as an atom index inside the crystal, -1 without bonds),
         ``bond_over`` [n], ``bond_ueq_ratio`` [n] and ``bond_stats`` [4] fp64 (directed bonds, sum of ``|D|``, largest
         ``|D|``, bonds over the threshold)."""),
-    "riding_h": Group(lambda a, sym, K, T, bt=None: a.riding_h is not None,
+    "riding_h": Group(lambda a, sym, K, T, bt=None, at=None: a.riding_h is not None,
         {"u_iso": "atom", "h_parent": "atom", "h_count": "atom", "h_mult": "atom", "h_stats": "crystal"},
         """``riding_h`` = ``(tol, f, f_rot)``: one ``metrics.riding_h`` (csrc/riding_ops.hip) per exported ``u_eq``
         (with rotations the frame mean's); both CIF writers then fill ``_atom_site_U_iso_or_equiv`` for every atom.
@@ -96,10 +99,10 @@ GROUPS: Dict[str, Group] = {
         ``u_eq``), ``h_parent`` [N] (an atom index inside the crystal, -1 where there is none), ``h_count`` [N]
         (hydrogens riding on a non-hydrogen atom), ``h_mult`` [N] and ``h_stats`` [4] fp64 (hydrogens, orphans, sum of
         the finite hydrogen ``u_iso``, hydrogens with a non-positive parent ``u_eq``)."""),
-    "riding_h_symmetry": Group(lambda a, sym, K, T, bt=None: a.riding_h is not None and sym,
+    "riding_h_symmetry": Group(lambda a, sym, K, T, bt=None, at=None: a.riding_h is not None and sym,
         {"u_iso_asym": None, "h_parent_asym": None},
         """``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``)."""),
-    "rigid_molecule": Group(lambda a, sym, K, T, bt=None: a.rigid_molecule is not None,
+    "rigid_molecule": Group(lambda a, sym, K, T, bt=None, at=None: a.rigid_molecule is not None,
         {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "row", "mol_pairs": "row",
          "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"},
         """``rigid_molecule`` = ``(tol, threshold)``: per batch one ``metrics.molecules`` (the components of the bond
@@ -111,7 +114,7 @@ GROUPS: Dict[str, Group] = {
         status is not 0), ``mol_pairs`` [n], ``mol_delta_mean`` [n], ``mol_delta_max`` [n], ``mol_worst`` [n] (an atom
         index inside the crystal, -1 without pairs), ``mol_over`` [n] and ``mol_stats`` [9] fp64 (molecules, tested,
         periodic, open, largest size; directed pairs, sum of ``|D|``, largest ``|D|``, pairs over the threshold)."""),
-    "tls_fit": Group(lambda a, sym, K, T, bt=None: bool(a.tls_fit),
+    "tls_fit": Group(lambda a, sym, K, T, bt=None, at=None: bool(a.tls_fit),
         {"tls_u": "row", "tls_resid": "row", "tls_T": "row", "tls_L": "row", "tls_S": "row", "tls_origin": "row",
          "tls_T_principal": "row", "tls_L_principal": "row", "tls_rank": "row", "tls_r": "row", "tls_stats": "crystal"},
         """``tls_fit`` = ``True`` (with ``rigid_molecule`` only): one ``metrics.tls_fit`` (csrc/tls_ops.hip) beside
@@ -125,7 +128,7 @@ GROUPS: Dict[str, Group] = {
         with a negative principal value, sum of ``resid^2``, sum of ``|Sym U|^2`` over the fitted rows, largest
         ``resid``).  Rows of molecules that are not fitted (status not 0, fewer than five atoms) hold NaN, ``tls_resid``
         / ``tls_rank`` / ``tls_r`` 0."""),
-    "aniso_h": Group(lambda a, sym, K, T, bt=None: a.aniso_h is not None,
+    "aniso_h": Group(lambda a, sym, K, T, bt=None, at=None: a.aniso_h is not None,
         {"h_u_cart": "atom", "h_u_cif": "atom", "h_u_eq": "atom", "h_source": "atom", "h_aniso_stats": "crystal"},
         """``aniso_h`` = ``(stretch, bend)`` (with ``riding_h`` only): one ``metrics.aniso_h`` (csrc/aniso_h_ops.hip)
         wherever ``riding_h`` runs, with the TLS fit of the same ``u_cart`` when ``tls_fit`` is on (without it every
@@ -136,11 +139,11 @@ GROUPS: Dict[str, Group] = {
         ``h_source`` [N] (0 none, 1 own row, 2 parent, 3 parent and TLS, 4 parent and a rank-deficient TLS) and
         ``h_aniso_stats`` [4] fp64 (hydrogens with a tensor, those with source >= 3, the sum of their ``trace / 3``,
         those not positive definite)."""),
-    "aniso_h_symmetry": Group(lambda a, sym, K, T, bt=None: a.aniso_h is not None and sym,
+    "aniso_h_symmetry": Group(lambda a, sym, K, T, bt=None, at=None: a.aniso_h is not None and sym,
         {"h_u_cif_asym": None},
         """``h_u_cif_asym`` [a,6] per atom of the asymmetric unit (``aniso_asym``: a hydrogen's is the listed image's,
         not an orbit mean)."""),
-    "bond_table": Group(lambda a, sym, K, T, bt=None: bt is not None,
+    "bond_table": Group(lambda a, sym, K, T, bt=None, at=None: bt is not None,
         {"bonds_a": "bond", "bonds_b": "bond", "bonds_dir": "bond", "bonds_length": "bond", "bonds_delta": "bond",
          "bonds_lower": "bond", "bonds_upper": "bond", "bonds_libration": "bond", "bonds_tls_rank": "bond",
          "bonds_stats": "crystal"},
@@ -156,9 +159,9 @@ GROUPS: Dict[str, Group] = {
         libration ``L``; NaN without a fit), ``bonds_tls_rank`` [m] (that fit's rank, 0 without one) and ``bonds_stats``
         [9] fp64 (listed bonds, unlisted ``j > i`` bond edges -- a capped graph's differ --, sum of ``bonds_length``, sum
         of ``|D|``, largest ``|D|``, bonds with a libration, sum and largest of ``bonds_libration - bonds_length`` over
-        those, bonds with a NaN bound).  X-H bonds, angles, torsions and the riding-model correction are not here, and
-        no CIF writer reads these keys."""),
-    "series": Group(lambda a, sym, K, T, bt=None: T is not None and len(T) >= 2,
+        those, bonds with a NaN bound).  X-H bonds and the riding-model correction are not here (angles and torsions:
+        the rows ``angle_table`` and ``torsion_table``), and no CIF writer reads these keys."""),
+    "series": Group(lambda a, sym, K, T, bt=None, at=None: T is not None and len(T) >= 2,
         {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t_ueq_intercept": "row", "t_resid": "row",
          "t_drops": "row", "t_stats": "crystal"},
         """``temperatures`` = T >= 1 Kelvin values (strictly increasing, finite, > 0; otherwise ``ValueError``): every
@@ -173,9 +176,34 @@ GROUPS: Dict[str, Group] = {
         ``t_intercept`` [n,6] of ``u_cif``, ``t_ueq_slope`` [n], ``t_ueq_intercept`` [n], ``t_resid`` [n], ``t_drops``
         [n] int32 and ``t_stats`` [4] fp64 (sum of ``t_ueq_slope``, rows whose U_eq slope is not > 0, rows with a drop,
         largest ``t_resid``)."""),
+    "angle_table": Group(lambda a, sym, K, T, bt=None, at=None: at is not None,
+        {"angles_a": "angle", "angles_b": "angle", "angles_c": "angle", "angles_value": "angle",
+         "angles_libration": "angle", "angles_tls_rank": "angle", "angles_stats": "crystal"},
+        """``angle_table`` = the bond tolerance: per batch one ``metrics.angle_index`` (on the ``bond_index`` of
+        ``bond_table`` if that is on with the same tolerance; nothing in it depends on U, so it is built once for all T;
+        its two ``B + 1`` offsets travel in one further device-to-host copy of a batch) and one ``metrics.angle_table``
+        (csrc/angle_table_ops.hip) per exported ``u_cart``, wherever ``bond_table`` runs, with the TLS fit of the same
+        ``u_cart`` when ``tls_fit`` is on.  One entry per valence angle a-b-c of the bond graph, ``m`` of them: centres
+        ``b`` in atom order, the pairs of a centre's bond edges by the first, then the second.  ``angles_a`` /
+        ``angles_b`` / ``angles_c`` [m] (atom indices inside the crystal), ``angles_value`` [m] (degrees, from the stored
+        edge directions: cell faces and images need no special case), ``angles_libration`` [m] (the angle after the
+        fitted libration ``L`` of ``b``'s molecule; NaN without a fit), ``angles_tls_rank`` [m] (that fit's rank, 0
+        without one) and ``angles_stats`` [5] fp64 (angles, sum of ``angles_value``, angles with a libration, sum and
+        largest of ``|angles_libration - angles_value|`` over those).  No CIF writer reads these keys."""),
+    "torsion_table": Group(lambda a, sym, K, T, bt=None, at=None: at is not None,
+        {"torsions_a": "torsion", "torsions_b": "torsion", "torsions_c": "torsion", "torsions_d": "torsion",
+         "torsions_value": "torsion", "torsions_libration": "torsion", "torsions_tls_rank": "torsion",
+         "torsions_stats": "crystal"},
+        """With ``angle_table``, from the same two calls: one entry per torsion a-b-c-d, ``m`` of them, the central bonds
+        b-c in the bond table's order (``b < c``), then the neighbours of ``b``, then those of ``c``.  ``torsions_a`` ...
+        ``torsions_d`` [m] (atom indices inside the crystal; a three-membered ring gives entries with ``a == d``, which
+        a user filters on the indices), ``torsions_value`` [m] (degrees in (-180, 180], the IUPAC sign; NaN for a
+        collinear end), ``torsions_libration`` [m] and ``torsions_tls_rank`` [m] (as for the angles, read at ``c``) and
+        ``torsions_stats`` [5] fp64 (torsions, those with a NaN value, those with a libration, sum and largest of the
+        circular ``|torsions_libration - torsions_value|`` over those)."""),
 }
 (KEYS, SYM_KEYS, ROT_KEYS, BOND_KEYS, H_KEYS, H_SYM_KEYS, MOL_KEYS, TLS_KEYS, AH_KEYS, AH_SYM_KEYS, BT_KEYS,
- SERIES_KEYS) = (tuple(g.cuts) for g in GROUPS.values())
+ SERIES_KEYS, AT_KEYS, TT_KEYS) = (tuple(g.cuts) for g in GROUPS.values())
 
 
 def _cuts(*names: str) -> Dict[str, str]:
@@ -185,14 +213,16 @@ def _cuts(*names: str) -> Dict[str, str]:
 # the cuts under the names they have always had (tests/test_cif_writers_golden.py holds SPLIT to these five); CUT: all
 SPLIT, CUT = _cuts("base", "symmetry", "rotations", "rigid_bond", "riding_h"), _cuts()
 SERIES_SPLIT, MOL_SPLIT, TLS_SPLIT, AH_SPLIT = _cuts("series"), _cuts("rigid_molecule"), _cuts("tls_fit"), _cuts("aniso_h")
-BT_SPLIT = _cuts("bond_table")
+BT_SPLIT, AT_SPLIT, TT_SPLIT = _cuts("bond_table"), _cuts("angle_table"), _cuts("torsion_table")
 
 
-def result_keys(analyses: Analyses, sym: bool, rotations: int, bond_table: Optional[float] = None) -> tuple:
-    """The keys of a ``predict_adps`` result in its order (``sym``: whether the pass has a ``CifSymmetry``; ``bond_table``:
-    its tolerance, ``None`` without one); ``series``, which a pass at two or more temperatures adds at the end, is not
-    among them."""
-    return tuple(k for g in GROUPS.values() if g.present(analyses, sym, rotations, None, bond_table) for k in g.cuts)
+def result_keys(analyses: Analyses, sym: bool, rotations: int, bond_table: Optional[float] = None,
+                angle_table: Optional[float] = None) -> tuple:
+    """The keys of a ``predict_adps`` result in its order (``sym``: whether the pass has a ``CifSymmetry``; ``bond_table``
+    and ``angle_table``: their tolerances, ``None`` without one); ``series``, which a pass at two or more temperatures adds
+    at the end, is not among them."""
+    return tuple(k for g in GROUPS.values() if g.present(analyses, sym, rotations, None, bond_table, angle_table)
+                 for k in g.cuts)
 
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
@@ -400,6 +430,18 @@ def bond_table_entries(bt, batch) -> dict:
             "bonds_libration": bt.libration, "bonds_tls_rank": bt.tls_rank, "bonds_stats": bt.crystal_stats}
 
 
+def angle_table_entries(at, batch) -> dict:
+    """The keys of ``AT_KEYS`` and ``TT_KEYS`` from a ``metrics.AngleTable`` of ``batch``, on the device: the atom indices
+    brought inside their crystal as ``bond_table_entries`` does.  Static-shape device ops: nothing is read back."""
+    return {"angles_a": _in_crystal(at.angle_a, batch), "angles_b": _in_crystal(at.angle_b, batch),
+            "angles_c": _in_crystal(at.angle_c, batch), "angles_value": at.angle_value,
+            "angles_libration": at.angle_libration, "angles_tls_rank": at.angle_tls_rank, "angles_stats": at.angle_stats,
+            "torsions_a": _in_crystal(at.torsion_a, batch), "torsions_b": _in_crystal(at.torsion_b, batch),
+            "torsions_c": _in_crystal(at.torsion_c, batch), "torsions_d": _in_crystal(at.torsion_d, batch),
+            "torsions_value": at.torsion_value, "torsions_libration": at.torsion_libration,
+            "torsions_tls_rank": at.torsion_tls_rank, "torsions_stats": at.torsion_stats}
+
+
 _SYM6 = (0, 5, 4, 5, 1, 3, 4, 3, 2)               # a row-major symmetric 3x3 from its 11 22 33 23 13 12
 
 
@@ -510,7 +552,8 @@ def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
 
 
 def _device_stage(model, batch, shard, sym, rotations: int, gen, analyses: Analyses, kelvin: Optional[list] = None,
-                  temps: Optional[torch.Tensor] = None, bond_table: Optional[float] = None) -> dict:
+                  temps: Optional[torch.Tensor] = None, bond_table: Optional[float] = None,
+                  angle_table: Optional[float] = None) -> dict:
     """One batch (on the device) through ONE forward (``_forward``; with the T temperatures ``kelvin``, ``temps`` are their
     model-side values) and the kernels that follow it, those once per temperature on that temperature's rows.  Returns
     what travels to the host in one ``to_host``: what does not depend on the prediction under its key of ``CUT``, the
@@ -526,14 +569,16 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, analyses: Analy
     if R is not None:
         dev["frames"] = R.transpose(0, 1)
     rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
-    graph, mo, index = _of_the_graph(batch, row_ptr, rows // rotations, analyses, bond_table)   # once for all T
-    if index is not None:
+    graph, mo, index, angles = _of_the_graph(batch, row_ptr, rows // rotations, analyses, bond_table, angle_table)
+    if index is not None:                                                     # all four: once for all T
         dev["_bond_ptr"] = index.bond_ptr
+    if angles is not None:
+        dev["_angle_ptr"], dev["_torsion_ptr"] = angles.angle_ptr, angles.torsion_ptr
     per = []
     for t in range(T):
         pred, fm = _frame_mean(members[t * rows:(t + 1) * rows], R, row_ptr, stats=True)
         d = {} if fm is None else {"rot_spread": fm.spread, "rot_stats": fm.crystal_spread}
-        d.update(_exported(pred, batch, row_ptr, sym, analyses, graph, mo, index))
+        d.update(_exported(pred, batch, row_ptr, sym, analyses, graph, mo, index, angles))
         per.append(d)
         dev.update({f"{k}@{t}": v for k, v in d.items()})
     if T >= 2:
@@ -542,23 +587,29 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, analyses: Analy
     return dev
 
 
-def _of_the_graph(batch, row_ptr: torch.Tensor, rows: int, analyses: Analyses, bond_table: Optional[float] = None):
-    """``(metrics.BatchGraph of the batch, its metrics.Molecules, its metrics.BondIndex)``, each ``None`` unless an analysis
-    needs it: what the analyses of ``_exported`` share and what does not depend on U, so checked, built and found once per
-    batch (its atomic numbers in ``x``), however many predictions of it follow.  ``bond_table``: its tolerance."""
-    if analyses.rigid_bond is None and analyses.riding_h is None and analyses.rigid_molecule is None and bond_table is None:
-        return None, None, None
+def _of_the_graph(batch, row_ptr: torch.Tensor, rows: int, analyses: Analyses, bond_table: Optional[float] = None,
+                  angle_table: Optional[float] = None):
+    """``(metrics.BatchGraph of the batch, its metrics.Molecules, its metrics.BondIndex, its metrics.AngleIndex)``, each
+    ``None`` unless an analysis needs it: what the analyses of ``_exported`` share and what does not depend on U, so
+    checked, built and found once per batch (its atomic numbers in ``x``), however many predictions of it follow.
+    ``bond_table`` and ``angle_table``: their tolerances; at the same tolerance the angles build on the bond table's
+    index."""
+    if (analyses.rigid_bond is None and analyses.riding_h is None and analyses.rigid_molecule is None and bond_table is None
+            and angle_table is None):
+        return None, None, None, None
     graph = batch_graph(batch, rows, "predict_adps")
+    index = None if bond_table is None else bond_index(graph, row_ptr, bond_table)
     return (graph, None if analyses.rigid_molecule is None else find_molecules(graph, row_ptr, analyses.rigid_molecule[0]),
-            None if bond_table is None else bond_index(graph, row_ptr, bond_table))
+            index, None if angle_table is None else angle_index(
+                graph, row_ptr, angle_table, bonds=index if bond_table == angle_table else None))
 
 
 def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, analyses: Analyses, graph=None, mo=None,
-              index=None) -> dict:
+              index=None, angles=None) -> dict:
     """The kernels that follow the forward, on the prediction ``pred`` [M,3,3] of ``batch``: the export and, as
-    ``analyses`` asks and on ``graph``, ``mo`` and ``index`` (``_of_the_graph``), the rigid-bond test, the rigid-body test
-    (and the TLS fit) on the molecules, the riding hydrogens (and their tensors, with the TLS fit if there is one), the
-    bond table (with that fit as well) and the site average."""
+    ``analyses`` asks and on ``graph``, ``mo``, ``index`` and ``angles`` (``_of_the_graph``), the rigid-bond test, the
+    rigid-body test (and the TLS fit) on the molecules, the riding hydrogens (and their tensors, with the TLS fit if there
+    is one), the bond table and the angle and torsion tables (with that fit as well) and the site average."""
     device = batch.x.device
     B = int(batch.num_graphs)
     sel = batch._meta[:B]
@@ -581,6 +632,8 @@ def _exported(pred: torch.Tensor, batch, row_ptr: torch.Tensor, sym, analyses: A
             dev.update(aniso_entries(ah, batch))
     if index is not None:
         dev.update(bond_table_entries(bond_table_call(pred, graph, row_ptr, index, tf), batch))
+    if angles is not None:
+        dev.update(angle_table_entries(angle_table_call(graph, row_ptr, angles, tf), batch))
     if sym is not None:
         from .symmetry import site_average
         dev["u_cif_asym"], dev["spread"] = site_average(pred, row_ptr, batch._sel, sym)
@@ -623,15 +676,18 @@ def _split(out: Dict[str, List], host: dict, counts: dict) -> None:
 def _entries(out: Dict[str, List], host: dict, shard, sym, kelvin: Optional[float] = None):
     """Appends the crystals of one batch to ``out`` from the host copy of one prediction of it; ``kelvin``: the
     temperature it was predicted at, which then is its ``temp`` and the suffix of its ``name``, instead of the stored
-    one.  Returns the crystals' names (as stored) and their counts of rows, atoms, sites and listed bonds."""
+    one.  Returns the crystals' names (as stored) and their counts of rows, atoms, sites, listed bonds, angles and
+    torsions."""
     ids = host.pop("_sel").tolist()
     names = [shard.names[i] if shard.names is not None else f"crystal{i}" for i in ids]
     check_export_status(host.pop("_status"), names)
     rp, ap = host.pop("_row_ptr"), host.pop("_atom_ptr")
-    bp = host.pop("_bond_ptr", None)
+    bp, gp, tp = (host.pop(k, None) for k in ("_bond_ptr", "_angle_ptr", "_torsion_ptr"))
     counts = {"row": (rp[1:] - rp[:-1]).tolist(), "atom": (ap[1:] - ap[:-1]).tolist(),
               "site": [int(sym.site_count[i]) for i in ids] if sym is not None else None,
-              "bond": (bp[1:] - bp[:-1]).tolist() if bp is not None else None}
+              "bond": (bp[1:] - bp[:-1]).tolist() if bp is not None else None,
+              "angle": (gp[1:] - gp[:-1]).tolist() if gp is not None else None,
+              "torsion": (tp[1:] - tp[:-1]).tolist() if tp is not None else None}
     stored = host.pop("_temp").tolist() if "_temp" in host else [float("nan")] * len(ids)
     out["temp"] += stored if kelvin is None else [kelvin] * len(ids)          # the Kelvin value as given
     out["name"] += names if kelvin is None else [f"{name}_{kelvin:g}K" for name in names]
@@ -657,7 +713,8 @@ def _entries(out: Dict[str, List], host: dict, shard, sym, kelvin: Optional[floa
 
 
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
-                 temperatures=None, rigid_molecule=None, tls_fit=None, aniso_h=None, bond_table=None) -> Dict[str, List]:
+                 temperatures=None, rigid_molecule=None, tls_fit=None, aniso_h=None, bond_table=None,
+                 angle_table=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order, under the keys of ``GROUPS["base"]``; a singular cell
     raises ``ValueError`` naming the crystal.  Every option adds what its row of ``GROUPS`` documents, all of it
@@ -666,13 +723,14 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     ``series`` (one entry per crystal and temperature, and the key ``series``); ``rigid_bond``, ``riding_h``,
     ``rigid_molecule``, ``tls_fit`` (``ValueError`` without ``rigid_molecule``) and ``aniso_h`` (``ValueError`` without
     ``riding_h``): the rows of their names, for the two hydrogen options with ``sym`` also the rows ``*_symmetry``;
-    ``bond_table`` (the bond tolerance): the row of its name, the one analysis that is no field of ``Analyses``."""
+    ``bond_table`` and ``angle_table`` (the bond tolerance): the row ``bond_table`` and the rows ``angle_table`` and
+    ``torsion_table``, the analyses that are no field of ``Analyses``."""
     rotations = int(rotations)
     analyses = Analyses(rigid_bond, riding_h, rigid_molecule, tls_fit, aniso_h).checked()
     shard = _check_pass(loader, rotations)
     kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
     model.eval()
-    out: Dict[str, List] = {k: [] for k in result_keys(analyses, sym is not None, rotations, bond_table)}
+    out: Dict[str, List] = {k: [] for k in result_keys(analyses, sym is not None, rotations, bond_table, angle_table)}
     series: Dict[str, List] = {k: [] for k in ("name", "temps") + SERIES_KEYS}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     temps = None if kelvin is None else standardised(kelvin, loader.temp_mean, loader.temp_std, device)
@@ -681,7 +739,8 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
             if batch is None:
                 continue
             batch.to(device)
-            dev = _device_stage(model, batch, shard, sym, rotations, gen, analyses, kelvin, temps, bond_table)
+            dev = _device_stage(model, batch, shard, sym, rotations, gen, analyses, kelvin, temps, bond_table,
+                                angle_table)
             _host_stage(out, series, to_host(dev), shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()
@@ -745,6 +804,12 @@ STATISTICS = {
         "bonds_listed": int(s[0]), "bonds_unlisted": int(s[1]), "bond_length_mean": _ratio(s[2], int(s[0])),
         "bond_libration_bonds": int(s[5]), "bond_libration_mean": _ratio(s[6], int(s[5])), "bond_libration_max": hi[7],
         "bond_bounds_nan": int(s[8])}),
+    "angles_stats": (5, lambda s, hi, rows=0: {                               # the libration figures: |corrected - apparent|
+        "angles_listed": int(s[0]), "angle_mean": _ratio(s[1], int(s[0])), "angle_libration_angles": int(s[2]),
+        "angle_libration_mean": _ratio(s[3], int(s[2])), "angle_libration_max": hi[4]}),
+    "torsions_stats": (5, lambda s, hi, rows=0: {                             # ... on the circle
+        "torsions_listed": int(s[0]), "torsions_undefined": int(s[1]), "torsion_libration_torsions": int(s[2]),
+        "torsion_libration_mean": _ratio(s[3], int(s[2])), "torsion_libration_max": hi[4]}),
 }
 
 

@@ -677,6 +677,68 @@ int cartnet_adp_bond_table(const float* u, const int64_t* z, const int64_t* edge
                            float* libration, int32_t* tls_rank, double* crystal_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * The angle and torsion tables of one batch: the valence angles a-b-c and the torsions a-b-c-d of the bond graph, from
+ * the edges alone (cart_dir, cart_dist: never positions, so cell faces and images need no special case), each with the
+ * value the libration L of a fitted rigid body gives (v' = v + (tr(L) v - L v) / 2 on every bond vector v = l d).  The
+ * reference has no counterpart.  cartnet_amd/bonds.py states the rule, angle_table_host restates the three calls.
+ *   z, edge_index, cart_dist, cart_dir, atom_row, seg_ptr, radii, n_radii, tol and the bond rule as for
+ *   cartnet_adp_bond_test; atom_ptr as for cartnet_adp_riding_h; offset [N+1] int64 and nb as for cartnet_adp_bond_table;
+ *   nbr_ptr [N+1] int64: the exclusive scan of listed + unlisted of cartnet_bond_table_count, an atom's degree;
+ *   params [M,24] fp32 and rank [M] int32: cartnet_adp_tls_fit's, both or both NULL.
+ * Two nesting levels of variable length, so: lists, counts, a scan by the caller, fills.
+ *   cartnet_bond_adjacency     adj [E] int64: adj[nbr_ptr[i] + k] is the k-th bond edge of atom i's segment, sources
+ *                              below and above i alike, in edge order (entries from nbr_ptr[N] on are not written);
+ *                              bond_edge [nb] int64: bond_edge[offset[i] + k'] is the edge of i's k'-th listed bond, the
+ *                              edge of row offset[i] + k' of the bond table.
+ *   cartnet_angle_table_count  angle_count [N] int64: d (d - 1) / 2 for an atom of degree d.  Per listed bond e0 = (b -> c):
+ *                              reverse [nb] int64, among the bond edges e' of b's adjacency with source c the one with the
+ *                              smallest max_k |fp32(fp32(l' d'_k) + fp32(l0 d0_k))| (fp32, in this order; a tie: the
+ *                              lowest edge), accepted only below 0.5 A, else -1 (a capped graph can hold a bond in one
+ *                              direction only); torsion_count [nb] int64 = n_a n_d, n_d = d_c - 1, n_a = d_b less the
+ *                              reverse edge if there is one.
+ *   cartnet_adp_angle_table    angle_offset [N+1] and torsion_offset [nb+1] int64: the exclusive scans of the two counts;
+ *                              na and nt: the tables' lengths.  A slot outside its table is never written.
+ *                                angles    centre b = i in atom order, the pairs k1 < k2 of its adjacency by k1 then k2
+ *                                          in slot angle_offset[i] + k1 (2 d - k1 - 1) / 2 + (k2 - k1 - 1); a and c the
+ *                                          sources of the two edges; value = atan2(|p x q|, p . q) in degrees of the two
+ *                                          stored directions; libration the same of the two v', L of row atom_row[b].
+ *                                torsions  the listed bonds in the bond table's order, (ia, id) in slot
+ *                                          torsion_offset[bond] + ia n_d + id: ea the ia-th bond edge of b's adjacency
+ *                                          without the reverse edge, ed the id-th of c's without e0; a and d their
+ *                                          sources; with b1 = d(ea), b2 = d(e0), b3 = -d(ed), n1 = b1 x b2, n2 = b2 x b3:
+ *                                          value = atan2(|b2| b1 . n2, n1 . n2) in degrees (the IUPAC sign), an fp32
+ *                                          -180 stored as +180, NaN when n1 . n1 == 0 or n2 . n2 == 0; libration the
+ *                                          same of the v', L of row atom_row[c], NaN where value is.
+ *                                both      fp64 from the fp32 inputs, no contraction, rounded once on store; libration
+ *                                          is NaN and tls_rank 0 without params, else tls_rank is the row's rank and
+ *                                          libration is filled where it is > 0.
+ * Per crystal (one wave each, from the values as stored; an angle belongs to the crystal of b, a torsion to that of c):
+ *   angle_stats [B,5] fp64 = (entries, sum of value, entries with a finite libration, the sum and the largest of
+ *   |libration - value| over those); torsion_stats [B,5] fp64 = (entries, entries with a NaN value, entries with a finite
+ *   libration, the sum and the largest of min(x, 360 - x), x = |libration - value|, over those).  Both or both NULL.
+ * N == 0 (or B == 0 for the third call): returns 0 without a launch and writes nothing; so does the first call for E == 0.
+ * na == 0 / nt == 0 need no per-entry outputs.  Edges read from a list and atoms read from an edge are compared with E and
+ * N before they are dereferenced.  No atomics, no LDS, no workgroup waits for another: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_bond_adjacency(const int64_t* z, const int64_t* edge_index, const float* cart_dist, const int64_t* atom_row,
+                           const int64_t* seg_ptr, const float* radii, int32_t n_radii, float tol, const int64_t* nbr_ptr,
+                           const int64_t* offset, int64_t N, int64_t M, int64_t E, int64_t nb, int64_t* adj,
+                           int64_t* bond_edge, void* stream);
+int cartnet_angle_table_count(const int64_t* edge_index, const float* cart_dist, const float* cart_dir,
+                              const int64_t* nbr_ptr, const int64_t* offset, const int64_t* adj, const int64_t* bond_edge,
+                              int64_t N, int64_t E, int64_t nb, int64_t* angle_count, int64_t* reverse,
+                              int64_t* torsion_count, void* stream);
+int cartnet_adp_angle_table(const int64_t* edge_index, const float* cart_dist, const float* cart_dir,
+                            const int64_t* atom_row, const int64_t* atom_ptr, const int64_t* nbr_ptr, const int64_t* offset,
+                            const int64_t* adj, const int64_t* bond_edge, const int64_t* reverse,
+                            const int64_t* angle_offset, const int64_t* torsion_offset, const float* params,
+                            const int32_t* rank, int32_t B, int64_t N, int64_t M, int64_t E, int64_t nb, int64_t na,
+                            int64_t nt, int64_t* angle_a, int64_t* angle_b, int64_t* angle_c, float* angle_value,
+                            float* angle_libration, int32_t* angle_tls_rank, int64_t* torsion_a, int64_t* torsion_b,
+                            int64_t* torsion_c, int64_t* torsion_d, float* torsion_value, float* torsion_libration,
+                            int32_t* torsion_tls_rank, double* angle_stats, double* torsion_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * A least-squares line per row and component through the exported ADPs of one batch over T temperatures.  The reference
  * predicts every crystal at the one temperature it is stored with (main.py:21-60); the model reads the temperature, so
  * one batch replicated T times answers how the ellipsoids grow.

@@ -31,6 +31,8 @@ Schomaker & Trueblood to the ADPs of every such molecule (``metrics.tls_fit``). 
 every hydrogen a full tensor from its parent's, that rigid-body motion and a nominal internal X-H motion
 (``metrics.aniso_h``).  ``--bond_table`` lists the bonds of every crystal of a ``--predict`` pass with Hirshfeld's D, the
 Busing & Levy bounds on the bond length and, after a TLS fit, the libration-corrected length (``metrics.bond_table``).
+``--angle_table`` lists the valence angles and the torsions of the same bond graph, with their values after that
+libration (``metrics.angle_table``).
 There is no CPU path: the model runs on an AMD GPU only.
 """
 from __future__ import annotations
@@ -198,6 +200,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "Busing & Levy lower and upper bounds on the thermally averaged bond length and -- with "
                         "--rigid_molecule --tls_fit -- the length corrected for the fitted libration (bonds_* in the "
                         "pickle).  It needs no other analysis flag; refused without --predict.  The CIFs do not change")
+    p.add_argument("--angle_table", action="store_true",
+                   help="--predict: list the valence angles a-b-c and the torsions a-b-c-d of every crystal's bond graph "
+                        "(the bonds of --bond_table, found with --bond_tolerance), in degrees, from the edges of the "
+                        "radius graph, so through cell faces as well, and -- with --rigid_molecule --tls_fit -- their "
+                        "values after the fitted libration (angles_* and torsions_* in the pickle).  It needs no other "
+                        "analysis flag; refused without --predict.  The CIFs do not change")
     return p
 
 
@@ -369,6 +377,8 @@ def analysis_options(args, inference: bool = False) -> dict:
         options["aniso_h"] = (args.aniso_h_stretch, args.aniso_h_bend)
     if args.bond_table and not inference:
         options["bond_table"] = tol
+    if args.angle_table and not inference:
+        options["angle_table"] = tol
     return options
 
 
@@ -406,6 +416,8 @@ def main(argv=None) -> dict:
         raise SystemExit("--aniso_h builds on the parents of --riding_h: give that flag as well")
     if args.bond_table and not args.predict:
         raise SystemExit("--bond_table serves --predict only")
+    if args.angle_table and not args.predict:
+        raise SystemExit("--angle_table serves --predict only")
     if args.predict or args.predict_temperatures is not None:
         check_predict_args(args)
     if args.rigid_molecule and not (args.predict or args.inference):

@@ -8,7 +8,9 @@
 // output rows of one section (atoms, edges, targets, crystals) and finds the crystal a row belongs to by binary
 // search in the [B+1] output offsets.  The optional SO(3) augmentation (y <- R^T y R, cart_dir <- cart_dir R,
 // cell <- cell R) and the temperature standardisation are applied on the way through, so an augmented batch costs the
-// same single pass: HBM-bound, ~56 B read + ~60 B written per edge.
+// same single pass: HBM-bound, ~56 B read + ~60 B written per edge.  cartnet_collate_frame_view is the second view of a
+// batch: for a model that reads the crystals in another frame than the one they are stored in (iComformer's reduced cell,
+// dataset/datasetADP.py:75-80), the cart_dir rows and cells of that frame's shard and nothing else, 12 B + 12 B per edge.
 #include "common.h"
 
 namespace {
@@ -124,7 +126,51 @@ __global__ __launch_bounds__(256) void cn_collate_kernel(CartnetShard s, const i
   }
 }
 
+// The model's view of a batch that was collated from ANOTHER shard of the same crystals (the stored frame): only what the
+// frame changes, cart_dir rows and cells, gathered from this shard (the reduced frame) with cn_collate_kernel's blocks of
+// 256 rows and its segment search; plain copies, so the bits are those of cartnet_collate without rot.
+__global__ __launch_bounds__(256) void cn_collate_frame_view_kernel(CartnetShard s, const int64_t* __restrict__ sel,
+                                                                    const int64_t* __restrict__ edge_ptr, int B, int64_t E,
+                                                                    float* __restrict__ cart_dir, float* __restrict__ cell,
+                                                                    int nbE) {
+  int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (b < nbE) {                                                   // ---- edges
+    const int64_t e = (int64_t)b * 256 + tid;
+    if (e >= E) return;
+    const int g = find_segment(edge_ptr, B, e);
+    const int64_t q = s.edge_ptr[sel[g]] + (e - edge_ptr[g]);
+    cart_dir[e * 3] = s.cart_dir[q * 3];
+    cart_dir[e * 3 + 1] = s.cart_dir[q * 3 + 1];
+    cart_dir[e * 3 + 2] = s.cart_dir[q * 3 + 2];
+    return;
+  }
+  b -= nbE;
+  {                                                                // ---- crystals
+    const int g = b * 256 + tid;
+    if (g >= B) return;
+    const int64_t sg = sel[g];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cell[(size_t)g * 9 + k] = s.cell[sg * 9 + k];
+  }
+}
+
 }  // namespace
+
+extern "C" int cartnet_collate_frame_view(const CartnetShard* shard, const int64_t* sel, const int64_t* out_edge_ptr,
+                                          int32_t B, int64_t E, float* cart_dir_out, float* cell_out, void* stream) {
+  CN_CHECK(shard, "cartnet_collate_frame_view: null descriptor");
+  CN_CHECK(B >= 1 && E >= 0, "cartnet_collate_frame_view: bad sizes (B=%d)", B);
+  CN_CHECK(E < (1LL << 31) * 128, "cartnet_collate_frame_view: batch too large for one launch");
+  CN_CHECK(sel && out_edge_ptr, "cartnet_collate_frame_view: null selection / offsets");
+  CN_CHECK(shard->edge_ptr && shard->cell && cell_out, "cartnet_collate_frame_view: cell arrays missing");
+  CN_CHECK(E == 0 || (shard->cart_dir && cart_dir_out), "cartnet_collate_frame_view: edge arrays missing");
+  const int nbE = (int)((E + 255) / 256), nbG = (B + 255) / 256;
+  hipLaunchKernelGGL(cn_collate_frame_view_kernel, dim3(nbE + nbG), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     *shard, sel, out_edge_ptr, B, E, cart_dir_out, cell_out, nbE);
+  CN_LAUNCH_CHECK("cartnet_collate_frame_view");
+  return 0;
+}
 
 extern "C" int cartnet_collate(const CartnetShard* shard, const int64_t* sel, const int64_t* out_atom_ptr,
                                const int64_t* out_edge_ptr, const int64_t* out_y_ptr, int32_t B, int64_t N, int64_t E,

@@ -13,6 +13,10 @@
 //                                 cn_adp_export_kernel (export_ops.hip) does.
 //   cn_frame_mean_crystal_kernel  one wave per crystal: crystal_spread[g] = (sum, maximum) of the fp32 spread as stored
 //                                 (crystal_reduce.h; the maximum keeps a NaN).
+//   cn_stored_frame_kernel        cartnet_adp_stored_frame: the way back of a model that reads every crystal in ONE other frame
+//                                 (iComformer in the frame of its reduced cell, dataset/datasetADP.py:75-80): out = R_g P R_g^T
+//                                 by the same fm_member, one rotation per crystal shared by the T temperature slices of pred
+//                                 (blockIdx.y), one launch, no mean and no spread.
 //
 // No symmetrisation (the export does its own), the rotations are used as given.  No atomics, fixed order: two runs give the
 // same bytes.  Neither kernel uses scratch or LDS.
@@ -93,6 +97,36 @@ __global__ __launch_bounds__(SO_THREADS) void cn_frame_mean_kernel(const float* 
   }
 }
 
+// One row of cartnet_adp_stored_frame: out = R P R^T, the member of fm_member stored with one rounding.  With R the identity
+// out has pred's values exactly; a NaN in pred makes the row's results NaN and touches no other row.  Also compiled for the
+// host, as fm_frame_mean_row is.
+__host__ __device__ __forceinline__ void fm_stored_frame_row(const float* __restrict__ pred, const float* __restrict__ rot,
+                                                             float* __restrict__ out) {
+#pragma clang fp contract(off)
+  double u[9];
+  fm_member(pred, rot, u);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) out[q] = (float)u[q];
+}
+
+// blockIdx.y = the temperature slice: its M rows share row_ptr and the B rotations with every other slice.
+__global__ __launch_bounds__(SO_THREADS) void cn_stored_frame_kernel(const float* __restrict__ pred,
+                                                                     const float* __restrict__ rot,
+                                                                     const int64_t* __restrict__ ptr, int B, int64_t M,
+                                                                     float* __restrict__ out) {
+  const int64_t t0 = (int64_t)blockIdx.x * SO_TILE, i0 = t0 + (int64_t)threadIdx.x * SO_ITEMS;
+  if (i0 >= M) return;
+  const int64_t slice = (int64_t)blockIdx.y * M;
+  int g = so_walk_first(ptr, B, M, t0, i0);
+#pragma unroll 1
+  for (int k = 0; k < SO_ITEMS; ++k) {
+    const int64_t i = i0 + k;
+    if (i >= M) break;
+    g = so_walk_to(ptr, B, g, i);                                 // steps over empty crystals
+    fm_stored_frame_row(pred + (slice + i) * 9, rot + (size_t)g * 9, out + (slice + i) * 9);
+  }
+}
+
 __global__ __launch_bounds__(WAVE) void cn_frame_mean_crystal_kernel(const int64_t* __restrict__ ptr, int64_t M,
                                                                      const float* __restrict__ spread,
                                                                      double* __restrict__ stats) {
@@ -131,5 +165,19 @@ extern "C" int cartnet_adp_frame_mean(const float* pred, const float* rot, int32
     hipLaunchKernelGGL(cn_frame_mean_crystal_kernel, dim3(B), dim3(WAVE), 0, st, row_ptr, M, spread, crystal_spread);
     CN_LAUNCH_CHECK("cartnet_adp_frame_mean");
   }
+  return 0;
+}
+
+extern "C" int cartnet_adp_stored_frame(const float* pred, const float* rotation, const int64_t* row_ptr, int32_t B,
+                                        int64_t M, int32_t T, float* out, void* stream) {
+  CN_CHECK(T >= 1 && T <= 65535 && B >= 0 && M >= 0, "cartnet_adp_stored_frame: bad sizes (T=%d, B=%d, M=%lld)", T, B,
+           (long long)M);
+  CN_CHECK(M < (1LL << 31) * SO_TILE / 4, "cartnet_adp_stored_frame: too many rows for one launch");
+  if (M == 0 || B == 0) return 0;
+  CN_CHECK(pred && rotation && row_ptr && out, "cartnet_adp_stored_frame: null pointer");
+  CN_CHECK(out != pred, "cartnet_adp_stored_frame: out must not alias pred");
+  hipLaunchKernelGGL(cn_stored_frame_kernel, dim3((unsigned)((M + SO_TILE - 1) / SO_TILE), (unsigned)T), dim3(SO_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), pred, rotation, row_ptr, B, M, out);
+  CN_LAUNCH_CHECK("cartnet_adp_stored_frame");
   return 0;
 }

@@ -363,6 +363,7 @@ PROTOTYPES = {
                                      C.c_void_p, c_i32p, c_stream]),
     "cartnet_adp_frame_mean": (C.c_int, [c_f32p, c_f32p, C.c_int32, c_i64p, C.c_int32, C.c_int64, c_f32p, c_f32p,
                                          C.c_void_p, c_stream]),
+    "cartnet_adp_stored_frame": (C.c_int, [c_f32p, c_f32p, c_i64p, C.c_int32, C.c_int64, C.c_int32, c_f32p, c_stream]),
     "cartnet_adp_bond_test": (C.c_int, [c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_f32p, C.c_int32,
                                         C.c_float, C.c_double, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_i32p, c_f32p,
                                         c_f32p, c_i64p, c_i32p, c_f32p, C.c_void_p, c_stream]),
@@ -400,6 +401,8 @@ PROTOTYPES = {
                                           c_f32p, c_i32p, C.c_void_p, c_stream]),
     "cartnet_collate": (C.c_int, [C.POINTER(Shard), c_i64p, c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int64, C.c_int64,
                                   C.c_int64, c_f32p, C.c_float, C.c_float, C.POINTER(Collated), c_stream]),
+    "cartnet_collate_frame_view": (C.c_int, [C.POINTER(Shard), c_i64p, c_i64p, C.c_int32, C.c_int64, c_f32p, c_f32p,
+                                             c_stream]),
     "cartnet_shard_drop_h_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "cartnet_shard_drop_h_count": (C.c_int, [C.POINTER(Shard), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
                                              c_i64p, c_i64p, c_stream]),

@@ -253,6 +253,29 @@ def frame_mean(pred: torch.Tensor, rot: torch.Tensor, row_ptr: torch.Tensor, sta
     return FrameMean(mean, spread, cs)
 
 
+def stored_frame(pred: torch.Tensor, rotation: torch.Tensor, row_ptr: torch.Tensor, slices: int = 1) -> torch.Tensor:
+    """Predictions made in ONE other frame per crystal, back in the stored frame: one call of
+    ``cartnet_adp_stored_frame``.  ``pred`` [T*M,3,3] temperature-major, T = ``slices`` (1: one prediction of the batch's
+    M rows), as the model gives it for ``cart_dir @ R`` (``DeviceShard.frame_view``: the reduced cell of the iComformer
+    recipe); ``rotation`` [B,3,3] fp32, shared by the T slices; ``row_ptr`` [B+1] over ONE slice's rows.  Row i of crystal g comes
+    back as ``R_g P R_g^T`` (fp64 arithmetic, one rounding to fp32): bit for bit ``frame_mean(slice, rotation[None]).mean``;
+    with the identity it has ``pred``'s values."""
+    _check_fp32("pred", pred, shape="[T*M,3,3]")
+    dev = pred.device
+    row_ptr, B = _check_row_ptr(row_ptr, dev)
+    rotation = _check_rot(rotation, B, dev)
+    T = int(slices)
+    if T < 1 or int(pred.shape[0]) % T:
+        raise ValueError(f"pred holds {int(pred.shape[0])} rows: no multiple of the {T} slices")
+    pred, M = pred.detach().contiguous(), int(pred.shape[0]) // T
+    out = torch.empty((T * M, 3, 3), dtype=torch.float32, device=dev)
+    if M == 0:                                   # the entry point launches nothing
+        return out
+    _l.check(_l.load().cartnet_adp_stored_frame(pred.data_ptr(), rotation.data_ptr(), row_ptr.data_ptr(), B, M, T,
+                                                out.data_ptr(), _l.stream_ptr()), "cartnet_adp_stored_frame")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Rigid-bond test (csrc/bond_ops.hip): how well the displacement amplitudes of bonded atoms agree along their bond --
 # what a crystallographer checks first on a set of ADPs, and it needs no truth.  The bond rule and the radii: bonds.py.

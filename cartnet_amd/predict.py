@@ -9,7 +9,9 @@ the five analyses of ``Analyses``, the bond table and the angle and torsion tabl
 per group of keys with its documentation.  ``write_cif`` writes one crystal of the result as a P1 CIF, ``write_cif_symmetric`` one that came from a CIF file in the
 file's own setting.  Around the pass, for ``main.py --predict``: ``load_input`` (a shard file, or CIF files expanded in
 memory), ``parse_temperatures`` (the flag's SPEC) and ``pass_statistics`` (the result line).  ``frame_stage`` is the
-forward in K frames that this pass and ``evaluate.inference`` share.
+forward in K frames that this pass and ``evaluate.inference`` share.  A model that reads crystals in another frame than the
+stored one (iComformer: the reduced cell) gets it through ``model_frame``: only the forward sees that frame, its members
+come back through ``metrics.stored_frame``, and every key keeps its meaning and its frame (row ``model_frame``).
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import torch
 from .metrics import (adp_export, angle_index, angle_table as angle_table_call, aniso_h as aniso_h_call, batch_graph,
                       bond_index, bond_table as bond_table_call, bond_test, check_export_status, check_temperatures,
                       edge_row_ptr, frame_mean, molecule_test, molecules as find_molecules, riding_h as riding_h_call,
-                      rotate_rows, split_rows, target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
+                      rotate_rows, split_rows, stored_frame, target_row_ptr, temp_series, tls_fit as tls_fit_call, to_host)
 
 
 class Analyses(NamedTuple):
@@ -43,8 +45,9 @@ class Analyses(NamedTuple):
 
 
 class Group(NamedTuple):
-    """One group of keys of a result.  ``present(analyses, sym, rotations, temperatures, bond_table, angle_table)``:
-    whether a pass has it (the last two switches, ``None`` by default, are the analyses that are no field of ``Analyses``);
+    """One group of keys of a result.  ``present(analyses, sym, rotations, temperatures, bond_table, angle_table,
+    model_frame)``: whether a pass has it (``bond_table`` and ``angle_table``, ``None`` by default, are the analyses that
+    are no field of ``Analyses``; ``model_frame``, ``False`` by default: whether the model reads another frame);
     ``cuts``: its keys in order, each with how it is cut into the crystals' entries -- a tensor that travels to the host
     as one slice of dim 0 per "crystal", or as the pieces of dim 0 that hold a crystal's atoms ("atom"), its non-hydrogen
     rows ("row"), the non-hydrogen atoms of its asymmetric unit ("site"), its listed bonds ("bond", counted from the
@@ -60,20 +63,28 @@ class Group(NamedTuple):
 # live in result["series"], which has one entry per input crystal and is appended to a result last; the two rows after it
 # came later and follow ``bonds_*`` in a result.
 GROUPS: Dict[str, Group] = {
-    "base": Group(lambda a, sym, K, T, bt=None, at=None: True,
+    "base": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: True,
         {"name": None, "atoms": "row", "frac": "atom", "z": "atom", "cell": "crystal", "temp": None, "u_cart": "row",
          "u_cif": "row", "u_eq": "row", "principal": "row", "axes": "row", "stats": "crystal"},
         """``name``; ``atoms`` [n] (Z of the n non-hydrogen atoms the rows belong to); ``frac`` [N,3] and ``z`` [N]
         (all atoms); ``cell`` [3,3]; ``temp`` (Kelvin, as stored; NaN if the shard has none); ``u_cart`` [n,3,3] (the
         model's output); ``u_cif`` [n,6] (U11 U22 U33 U23 U13 U12); ``u_eq`` [n]; ``principal`` [n,3] ascending;
         ``axes`` [n,3,3]; ``stats`` [3] fp64 (sum of u_eq, smallest principal value, rows with a non-positive one)."""),
-    "symmetry": Group(lambda a, sym, K, T, bt=None, at=None: sym,
+    "model_frame": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: bool(mf),
+        {"cell_rotation": "crystal", "cell_reduced": "crystal"},
+        """``model_frame`` = the ``DeviceShard.with_optimized_cell()`` of the loader's shard (iComformer, whose recipe reads
+        a crystal in the frame of its reduced cell): the forward runs on ``model_frame.frame_view(batch)``, the members
+        come back once through ``metrics.stored_frame`` (``U = R P R^T``), and every other key keeps its meaning and its
+        frame -- the stored cell and the stored ``cart_dir`` serve the export, the analyses, the site average and the
+        writers.  ``cell_rotation`` [3,3] (R: the model read ``cart_dir @ R``) and ``cell_reduced`` [3,3] (the cell the
+        model read, rows = lattice vectors in the rotated frame).  ``rotations`` > 1 raises ``ValueError``."""),
+    "symmetry": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: sym,
         {"asym_labels": None, "asym_frac": None, "asym_z": None, "u_cif_asym": "site", "spread": "site", "symops": None},
         """``sym``: the ``CifSymmetry`` of a shard expanded from CIF files.  ``asym_labels`` / ``asym_frac`` [a,3] /
         ``asym_z`` [a] (the asymmetric unit as the file gives it), ``symops`` (strings, identity first), ``u_cif_asym``
         [h,6] (one row per non-hydrogen atom of the asymmetric unit, the mean over its orbit,
         ``symmetry.site_average``) and ``spread`` [h]."""),
-    "rotations": Group(lambda a, sym, K, T, bt=None, at=None: K > 1,
+    "rotations": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: K > 1,
         {"rot_spread": "row", "frames": "crystal", "rot_stats": "crystal"},
         """``rotations`` = K > 1: every batch is predicted in K frames by ONE forward of ``replicate(batch, K, R)``
         with ``R = frames(B, K, gen, device)`` (one generator seeded with ``seed`` for the whole pass), the members are
@@ -81,7 +92,7 @@ GROUPS: Dict[str, Group] = {
         the mean.  ``rot_spread`` [n] (per row the largest deviation of a frame's prediction from the mean), ``frames``
         [K,3,3] (the rotations used, the identity first) and ``rot_stats`` [2] fp64 (sum and maximum of
         ``rot_spread``)."""),
-    "rigid_bond": Group(lambda a, sym, K, T, bt=None, at=None: a.rigid_bond is not None,
+    "rigid_bond": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: a.rigid_bond is not None,
         {"bond_count": "row", "bond_delta_mean": "row", "bond_delta_max": "row", "bond_worst": "row", "bond_over": "row",
          "bond_ueq_ratio": "row", "bond_stats": "crystal"},
         """``rigid_bond`` = ``(tol, threshold)``: Hirshfeld's rigid-bond test, one ``metrics.bond_test``
@@ -91,7 +102,7 @@ GROUPS: Dict[str, Group] = {
         ``bond_worst`` [n] (the partner of the worst bond as an atom index inside the crystal, -1 without bonds),
         ``bond_over`` [n], ``bond_ueq_ratio`` [n] and ``bond_stats`` [4] fp64 (directed bonds, sum of ``|D|``, largest
         ``|D|``, bonds over the threshold)."""),
-    "riding_h": Group(lambda a, sym, K, T, bt=None, at=None: a.riding_h is not None,
+    "riding_h": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: a.riding_h is not None,
         {"u_iso": "atom", "h_parent": "atom", "h_count": "atom", "h_mult": "atom", "h_stats": "crystal"},
         """``riding_h`` = ``(tol, f, f_rot)``: one ``metrics.riding_h`` (csrc/riding_ops.hip) per exported ``u_eq``
         (with rotations the frame mean's); both CIF writers then fill ``_atom_site_U_iso_or_equiv`` for every atom.
@@ -99,10 +110,10 @@ GROUPS: Dict[str, Group] = {
         ``u_eq``), ``h_parent`` [N] (an atom index inside the crystal, -1 where there is none), ``h_count`` [N]
         (hydrogens riding on a non-hydrogen atom), ``h_mult`` [N] and ``h_stats`` [4] fp64 (hydrogens, orphans, sum of
         the finite hydrogen ``u_iso``, hydrogens with a non-positive parent ``u_eq``)."""),
-    "riding_h_symmetry": Group(lambda a, sym, K, T, bt=None, at=None: a.riding_h is not None and sym,
+    "riding_h_symmetry": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: a.riding_h is not None and sym,
         {"u_iso_asym": None, "h_parent_asym": None},
         """``u_iso_asym`` [a] and ``h_parent_asym`` [a] per atom of the asymmetric unit (``riding_asym``)."""),
-    "rigid_molecule": Group(lambda a, sym, K, T, bt=None, at=None: a.rigid_molecule is not None,
+    "rigid_molecule": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: a.rigid_molecule is not None,
         {"mol": "row", "mol_size": "row", "mol_status": "row", "mol_pos": "row", "mol_pairs": "row",
          "mol_delta_mean": "row", "mol_delta_max": "row", "mol_worst": "row", "mol_over": "row", "mol_stats": "crystal"},
         """``rigid_molecule`` = ``(tol, threshold)``: per batch one ``metrics.molecules`` (the components of the bond
@@ -114,7 +125,7 @@ GROUPS: Dict[str, Group] = {
         status is not 0), ``mol_pairs`` [n], ``mol_delta_mean`` [n], ``mol_delta_max`` [n], ``mol_worst`` [n] (an atom
         index inside the crystal, -1 without pairs), ``mol_over`` [n] and ``mol_stats`` [9] fp64 (molecules, tested,
         periodic, open, largest size; directed pairs, sum of ``|D|``, largest ``|D|``, pairs over the threshold)."""),
-    "tls_fit": Group(lambda a, sym, K, T, bt=None, at=None: bool(a.tls_fit),
+    "tls_fit": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: bool(a.tls_fit),
         {"tls_u": "row", "tls_resid": "row", "tls_T": "row", "tls_L": "row", "tls_S": "row", "tls_origin": "row",
          "tls_T_principal": "row", "tls_L_principal": "row", "tls_rank": "row", "tls_r": "row", "tls_stats": "crystal"},
         """``tls_fit`` = ``True`` (with ``rigid_molecule`` only): one ``metrics.tls_fit`` (csrc/tls_ops.hip) beside
@@ -128,7 +139,7 @@ GROUPS: Dict[str, Group] = {
         with a negative principal value, sum of ``resid^2``, sum of ``|Sym U|^2`` over the fitted rows, largest
         ``resid``).  Rows of molecules that are not fitted (status not 0, fewer than five atoms) hold NaN, ``tls_resid``
         / ``tls_rank`` / ``tls_r`` 0."""),
-    "aniso_h": Group(lambda a, sym, K, T, bt=None, at=None: a.aniso_h is not None,
+    "aniso_h": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: a.aniso_h is not None,
         {"h_u_cart": "atom", "h_u_cif": "atom", "h_u_eq": "atom", "h_source": "atom", "h_aniso_stats": "crystal"},
         """``aniso_h`` = ``(stretch, bend)`` (with ``riding_h`` only): one ``metrics.aniso_h`` (csrc/aniso_h_ops.hip)
         wherever ``riding_h`` runs, with the TLS fit of the same ``u_cart`` when ``tls_fit`` is on (without it every
@@ -139,11 +150,11 @@ GROUPS: Dict[str, Group] = {
         ``h_source`` [N] (0 none, 1 own row, 2 parent, 3 parent and TLS, 4 parent and a rank-deficient TLS) and
         ``h_aniso_stats`` [4] fp64 (hydrogens with a tensor, those with source >= 3, the sum of their ``trace / 3``,
         those not positive definite)."""),
-    "aniso_h_symmetry": Group(lambda a, sym, K, T, bt=None, at=None: a.aniso_h is not None and sym,
+    "aniso_h_symmetry": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: a.aniso_h is not None and sym,
         {"h_u_cif_asym": None},
         """``h_u_cif_asym`` [a,6] per atom of the asymmetric unit (``aniso_asym``: a hydrogen's is the listed image's,
         not an orbit mean)."""),
-    "bond_table": Group(lambda a, sym, K, T, bt=None, at=None: bt is not None,
+    "bond_table": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: bt is not None,
         {"bonds_a": "bond", "bonds_b": "bond", "bonds_dir": "bond", "bonds_length": "bond", "bonds_delta": "bond",
          "bonds_lower": "bond", "bonds_upper": "bond", "bonds_libration": "bond", "bonds_tls_rank": "bond",
          "bonds_stats": "crystal"},
@@ -161,7 +172,7 @@ GROUPS: Dict[str, Group] = {
         of ``|D|``, largest ``|D|``, bonds with a libration, sum and largest of ``bonds_libration - bonds_length`` over
         those, bonds with a NaN bound).  X-H bonds and the riding-model correction are not here (angles and torsions:
         the rows ``angle_table`` and ``torsion_table``), and no CIF writer reads these keys."""),
-    "series": Group(lambda a, sym, K, T, bt=None, at=None: T is not None and len(T) >= 2,
+    "series": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: T is not None and len(T) >= 2,
         {"t_slope": "row", "t_intercept": "row", "t_ueq_slope": "row", "t_ueq_intercept": "row", "t_resid": "row",
          "t_drops": "row", "t_stats": "crystal"},
         """``temperatures`` = T >= 1 Kelvin values (strictly increasing, finite, > 0; otherwise ``ValueError``): every
@@ -176,7 +187,7 @@ GROUPS: Dict[str, Group] = {
         ``t_intercept`` [n,6] of ``u_cif``, ``t_ueq_slope`` [n], ``t_ueq_intercept`` [n], ``t_resid`` [n], ``t_drops``
         [n] int32 and ``t_stats`` [4] fp64 (sum of ``t_ueq_slope``, rows whose U_eq slope is not > 0, rows with a drop,
         largest ``t_resid``)."""),
-    "angle_table": Group(lambda a, sym, K, T, bt=None, at=None: at is not None,
+    "angle_table": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: at is not None,
         {"angles_a": "angle", "angles_b": "angle", "angles_c": "angle", "angles_value": "angle",
          "angles_libration": "angle", "angles_tls_rank": "angle", "angles_stats": "crystal"},
         """``angle_table`` = the bond tolerance: per batch one ``metrics.angle_index`` (on the ``bond_index`` of
@@ -190,7 +201,7 @@ GROUPS: Dict[str, Group] = {
         fitted libration ``L`` of ``b``'s molecule; NaN without a fit), ``angles_tls_rank`` [m] (that fit's rank, 0
         without one) and ``angles_stats`` [5] fp64 (angles, sum of ``angles_value``, angles with a libration, sum and
         largest of ``|angles_libration - angles_value|`` over those).  No CIF writer reads these keys."""),
-    "torsion_table": Group(lambda a, sym, K, T, bt=None, at=None: at is not None,
+    "torsion_table": Group(lambda a, sym, K, T, bt=None, at=None, mf=False: at is not None,
         {"torsions_a": "torsion", "torsions_b": "torsion", "torsions_c": "torsion", "torsions_d": "torsion",
          "torsions_value": "torsion", "torsions_libration": "torsion", "torsions_tls_rank": "torsion",
          "torsions_stats": "crystal"},
@@ -202,7 +213,7 @@ GROUPS: Dict[str, Group] = {
         ``torsions_stats`` [5] fp64 (torsions, those with a NaN value, those with a libration, sum and largest of the
         circular ``|torsions_libration - torsions_value|`` over those)."""),
 }
-(KEYS, SYM_KEYS, ROT_KEYS, BOND_KEYS, H_KEYS, H_SYM_KEYS, MOL_KEYS, TLS_KEYS, AH_KEYS, AH_SYM_KEYS, BT_KEYS,
+(KEYS, MF_KEYS, SYM_KEYS, ROT_KEYS, BOND_KEYS, H_KEYS, H_SYM_KEYS, MOL_KEYS, TLS_KEYS, AH_KEYS, AH_SYM_KEYS, BT_KEYS,
  SERIES_KEYS, AT_KEYS, TT_KEYS) = (tuple(g.cuts) for g in GROUPS.values())
 
 
@@ -217,12 +228,12 @@ BT_SPLIT, AT_SPLIT, TT_SPLIT = _cuts("bond_table"), _cuts("angle_table"), _cuts(
 
 
 def result_keys(analyses: Analyses, sym: bool, rotations: int, bond_table: Optional[float] = None,
-                angle_table: Optional[float] = None) -> tuple:
+                angle_table: Optional[float] = None, model_frame: bool = False) -> tuple:
     """The keys of a ``predict_adps`` result in its order (``sym``: whether the pass has a ``CifSymmetry``; ``bond_table``
-    and ``angle_table``: their tolerances, ``None`` without one); ``series``, which a pass at two or more temperatures adds
-    at the end, is not among them."""
-    return tuple(k for g in GROUPS.values() if g.present(analyses, sym, rotations, None, bond_table, angle_table)
-                 for k in g.cuts)
+    and ``angle_table``: their tolerances, ``None`` without one; ``model_frame``: whether the pass has one); ``series``,
+    which a pass at two or more temperatures adds at the end, is not among them."""
+    return tuple(k for g in GROUPS.values()
+                 if g.present(analyses, sym, rotations, None, bond_table, angle_table, model_frame) for k in g.cuts)
 
 
 SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
@@ -553,9 +564,11 @@ def _of_the_batch(batch, row_ptr: torch.Tensor) -> dict:
 
 def _device_stage(model, batch, shard, sym, rotations: int, gen, analyses: Analyses, kelvin: Optional[list] = None,
                   temps: Optional[torch.Tensor] = None, bond_table: Optional[float] = None,
-                  angle_table: Optional[float] = None) -> dict:
+                  angle_table: Optional[float] = None, model_frame=None) -> dict:
     """One batch (on the device) through ONE forward (``_forward``; with the T temperatures ``kelvin``, ``temps`` are their
-    model-side values) and the kernels that follow it, those once per temperature on that temperature's rows.  Returns
+    model-side values) and the kernels that follow it, those once per temperature on that temperature's rows.  With
+    ``model_frame`` the forward -- and nothing else -- sees that shard's ``frame_view`` of the batch, and its members come
+    back to the stored frame through one ``stored_frame`` before anything reads them.  Returns
     what travels to the host in one ``to_host``: what does not depend on the prediction under its key of ``CUT``, the
     keys of prediction t (the only one without temperatures) under ``"<key>@<t>"``, with T >= 2 the keys of
     ``SERIES_KEYS`` (one ``temp_series`` call on the T exports), and under names with a leading underscore what
@@ -565,7 +578,13 @@ def _device_stage(model, batch, shard, sym, rotations: int, gen, analyses: Analy
     dev = _of_the_batch(batch, row_ptr)
     if kelvin is None and "temperature" in shard.t:
         dev["_temp"] = shard.t["temperature"][dev["_sel"]]                    # the collated one is standardised
-    members, R = _forward(model, batch, rotations, gen, temps)
+    if model_frame is None:
+        members, R = _forward(model, batch, rotations, gen, temps)
+    else:                                                                     # K = 1: predict_adps has refused more
+        view = model_frame.frame_view(batch)
+        members, R = _forward(model, view, 1, None, temps)
+        members = stored_frame(members, view.rotation, row_ptr, T)
+        dev["cell_rotation"], dev["cell_reduced"] = view.rotation, view.cell
     if R is not None:
         dev["frames"] = R.transpose(0, 1)
     rows = int(members.shape[0]) // T                                         # K*M: one temperature's slice
@@ -714,7 +733,7 @@ def _entries(out: Dict[str, List], host: dict, shard, sym, kelvin: Optional[floa
 
 def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int = 0, rigid_bond=None, riding_h=None,
                  temperatures=None, rigid_molecule=None, tls_fit=None, aniso_h=None, bond_table=None,
-                 angle_table=None) -> Dict[str, List]:
+                 angle_table=None, model_frame=None) -> Dict[str, List]:
     """Predicted ADPs of every crystal of ``loader`` (a ``ShardLoader``; a labeled shard's ``y`` is ignored).  Returns a
     dict of lists with one entry per crystal, in the loader's order, under the keys of ``GROUPS["base"]``; a singular cell
     raises ``ValueError`` naming the crystal.  Every option adds what its row of ``GROUPS`` documents, all of it
@@ -724,13 +743,28 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
     ``rigid_molecule``, ``tls_fit`` (``ValueError`` without ``rigid_molecule``) and ``aniso_h`` (``ValueError`` without
     ``riding_h``): the rows of their names, for the two hydrogen options with ``sym`` also the rows ``*_symmetry``;
     ``bond_table`` and ``angle_table`` (the bond tolerance): the row ``bond_table`` and the rows ``angle_table`` and
-    ``torsion_table``, the analyses that are no field of ``Analyses``."""
+    ``torsion_table``, the analyses that are no field of ``Analyses``.  ``model_frame`` (the loader's shard
+    ``.with_optimized_cell()``, for iComformer): the row ``model_frame``; it raises ``ValueError`` with ``rotations`` > 1,
+    because iComformer's features are invariant and ``replicate`` rotates ``cart_dir`` but not ``cell``: K frames would
+    feed it inconsistent inputs, and nothing would be averaged."""
     rotations = int(rotations)
     analyses = Analyses(rigid_bond, riding_h, rigid_molecule, tls_fit, aniso_h).checked()
     shard = _check_pass(loader, rotations)
+    if model_frame is not None:
+        if rotations > 1:
+            raise ValueError("predict_adps: model_frame serves one frame only (rotations = 1): the model's features are "
+                             "invariant, and the K frames rotate cart_dir but not cell, so they would feed it inconsistent "
+                             "inputs and nothing would be averaged")
+        import numpy as np
+        if (model_frame.num_graphs != shard.num_graphs or "rotation" not in model_frame.t
+                or not np.array_equal(model_frame.atom_ptr, shard.atom_ptr)
+                or not np.array_equal(model_frame.edge_ptr, shard.edge_ptr)):
+            raise ValueError("predict_adps: model_frame must be the with_optimized_cell() of the loader's shard (the same "
+                             "crystals with the same graph)")
     kelvin = None if temperatures is None else check_temperatures(temperatures, least=1, name="temperatures")
     model.eval()
-    out: Dict[str, List] = {k: [] for k in result_keys(analyses, sym is not None, rotations, bond_table, angle_table)}
+    out: Dict[str, List] = {k: [] for k in result_keys(analyses, sym is not None, rotations, bond_table, angle_table,
+                                                          model_frame is not None)}
     series: Dict[str, List] = {k: [] for k in ("name", "temps") + SERIES_KEYS}
     gen = torch.Generator(device=device).manual_seed(seed) if rotations > 1 else None
     temps = None if kelvin is None else standardised(kelvin, loader.temp_mean, loader.temp_std, device)
@@ -740,7 +774,7 @@ def predict_adps(model, loader, device, sym=None, rotations: int = 1, seed: int 
                 continue
             batch.to(device)
             dev = _device_stage(model, batch, shard, sym, rotations, gen, analyses, kelvin, temps, bond_table,
-                                angle_table)
+                                angle_table, model_frame)
             _host_stage(out, series, to_host(dev), shard, sym, kelvin)
     if hasattr(model, "flush_graph_checks"):
         model.flush_graph_checks()

@@ -356,21 +356,20 @@ class DeviceShard:
         ``cart_dir`` and, for per-atom 3x3 targets, ``y``; every other array is shared.  It also carries ``rotation``
         [G,9] fp32 (R per crystal) and ``basis`` [G,9] int8 (the signed integer coefficients of the three chosen vectors in
         the rows of the old cell).  Composes with ``without_hydrogens()`` in either order.  Raises ``ValueError`` naming
-        the first crystal whose cell is degenerate (no three independent vectors among the candidates)."""
+        the first crystal whose cell is degenerate (no three independent vectors among the candidates).  An unlabeled shard
+        has no ``y`` to rotate and gets the other four arrays: predictions made in this frame go back to the stored one as
+        ``R P R^T`` (``frame_view``, ``metrics.stored_frame``)."""
         self._need_graph("with_optimized_cell")
-        if not self._labeled:
-            raise ValueError("with_optimized_cell: not on an unlabeled shard (predictions in the frame of the reduced cell "
-                             "are not mapped back to the stored cell)")
         dev, t, G = self.device, self.t, self.num_graphs
         if "cell" not in t:
             raise ValueError("the shard carries no cell")
-        E, M = int(self.edge_ptr[-1]), int(self.y_ptr[-1])
+        E, M = int(self.edge_ptr[-1]), int(self.y_ptr[-1]) if self._labeled else 0     # unlabeled: no targets to rotate
         with torch.cuda.device(dev):
             new: Dict[str, torch.Tensor] = {"cell": torch.empty((G, 9), dtype=torch.float32, device=dev),
                                             "rotation": torch.empty((G, 9), dtype=torch.float32, device=dev),
                                             "basis": torch.empty((G, 9), dtype=torch.int8, device=dev),
                                             "cart_dir": torch.empty((E, 3), dtype=torch.float32, device=dev)}
-            if self.per_atom_target:
+            if self.per_atom_target and self._labeled:
                 new["y"] = torch.empty((M, 9), dtype=torch.float32, device=dev)
             status = torch.empty(G, dtype=torch.int32, device=dev)
             first_bad = torch.empty(1, dtype=torch.int64, device=dev)
@@ -447,7 +446,53 @@ class DeviceShard:
         b.num_graphs = B
         b._sel = sel_np                       # the crystals of the batch, on the host
         b._meta = meta_d                      # keeps the offsets alive until the kernel has run
+        b._offsets = meta[B:]                 # the three offset arrays on the host: frame_view compares counts with them
         return b
+
+    def frame_view(self, batch: Batch) -> Batch:
+        """The model's view of ``batch``, which another shard of the same crystals has collated (the stored frame), in this
+        shard's frame (``with_optimized_cell()`` of that shard: the reduced cell): a shallow copy of ``batch`` whose
+        ``cart_dir`` and ``cell`` are gathered from this shard by one launch (``cartnet_collate_frame_view``: bit for bit
+        those of ``self.collate(batch._sel)``) and which also carries ``rotation`` [B,3,3] (R per crystal: a prediction P
+        made on the view is ``R P R^T`` in the stored frame, ``metrics.stored_frame``).  Every other tensor is shared and
+        ``batch`` is not modified.  Raises ``ValueError`` unless this shard holds the batch's crystals, each with the atom
+        and edge count it has in the batch."""
+        self._need_graph("frame_view")
+        if "rotation" not in self.t or "cell" not in self.t:
+            raise ValueError("frame_view: this shard carries no rotation (it is no with_optimized_cell() shard)")
+        sel_np, offsets = getattr(batch, "_sel", None), getattr(batch, "_offsets", None)
+        if sel_np is None or offsets is None:
+            raise ValueError("frame_view: the batch was not collated from a resident shard")
+        B = int(sel_np.shape[0])
+        if B == 0:
+            raise ValueError("frame_view: the batch holds no crystal")
+        if B != int(batch.num_graphs) or int(sel_np.min()) < 0 or int(sel_np.max()) >= self.num_graphs:
+            raise ValueError("frame_view: the batch's crystals are not crystals of this shard")
+        meta = np.empty(2 * B + 1, dtype=np.int64)                 # [sel | edge offsets in THIS shard]
+        meta[:B] = sel_np
+        meta[B] = 0
+        np.cumsum(self.edge_ptr[sel_np + 1] - self.edge_ptr[sel_np], out=meta[B + 1:])
+        E = int(meta[2 * B])
+        atoms = self.atom_ptr[sel_np + 1] - self.atom_ptr[sel_np]
+        if (offsets.shape[0] != 3 * (B + 1) or not np.array_equal(np.diff(offsets[:B + 1]), atoms)
+                or not np.array_equal(offsets[B + 1:2 * B + 2], meta[B:])
+                or E != int(batch.edge_index.shape[1]) or int(atoms.sum()) != int(batch.batch.shape[0])):
+            raise ValueError("frame_view: a crystal of this shard has another atom or edge count than the batch's (the two "
+                             "shards must hold the same graph)")
+        dev = self.device
+        meta_d = torch.from_numpy(meta).pin_memory().to(dev, non_blocking=True)
+        view = batch.__class__()
+        view.__dict__.update(batch.__dict__)
+        view.cart_dir = torch.empty((E, 3), dtype=torch.float32, device=dev)
+        view.cell = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+        base = meta_d.data_ptr()
+        with torch.cuda.device(dev):
+            _l.check(self._lib.cartnet_collate_frame_view(_l.C.byref(self._desc), base, base + 8 * B, B, E,
+                                                          view.cart_dir.data_ptr(), view.cell.data_ptr(), _l.stream_ptr()),
+                     "cartnet_collate_frame_view")
+            view.rotation = self.t["rotation"][meta_d[:B]].view(B, 3, 3)
+        view._view_meta = meta_d              # keeps the offsets alive until the kernel has run
+        return view
 
 
 def random_rotations(n: int, gen: torch.Generator, device) -> torch.Tensor:

@@ -443,6 +443,23 @@ int cartnet_adp_frame_mean(const float* pred, const float* rot, int32_t K, const
                            float* mean, float* spread, double* crystal_spread, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Back to the stored frame from ONE other frame per crystal.  The reference's iComformer recipe reads every crystal in
+ * the frame of its reduced cell (dataset/datasetADP.py:75-80: cart_dir <- cart_dir R, y <- R^T y R, the convention of the
+ * Monte-Carlo step, main.py:95-97), so a prediction P made there is U = R P R^T in the frame the crystal is stored in:
+ *   pred [T*M,9] fp32, temperature-major: rows t*M ... (t+1)*M-1 are the batch's M rows at temperature t (T = 1: one
+ *   prediction); rotation [B,9] fp32, one row-major 3x3 per crystal (the `rotation` of
+ *   cartnet_shard_optimize_cell_select, gathered for the batch), shared by the T slices; row_ptr [B+1] int64 over ONE
+ *   slice's M rows, as for cartnet_adp_frame_mean (empty crystals are legal).
+ *   out [T*M,9]: out[t*M + i] = R_g P R_g^T in fp64 from the fp32 inputs with the operations of cartnet_adp_frame_mean's
+ *   member, stored as fp32 with one rounding: bit for bit the mean of that call with K = 1 per slice.  No
+ *   symmetrisation, R used as given; with the identity out has pred's values.  A NaN stays in its row.
+ * One launch for all T.  M == 0 or B == 0: returns 0 without a launch and writes nothing.  out must not alias pred.  No
+ * atomics: two runs give the same bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+int cartnet_adp_stored_frame(const float* pred, const float* rotation, const int64_t* row_ptr, int32_t B, int64_t M,
+                             int32_t T, float* out, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Hirshfeld's rigid-bond test on the ADPs of one batch: a plausibility figure that needs no truth.  The reference can
  * judge a prediction only against targets (main.py:47-49: IoU, MAE and similarity index per atom); for two covalently
  * bonded atoms the mean-square displacement amplitudes along the bond are nearly equal, whatever the truth is.
@@ -834,6 +851,18 @@ typedef struct CartnetCollated {
 int cartnet_collate(const CartnetShard* shard, const int64_t* sel, const int64_t* out_atom_ptr,
                     const int64_t* out_edge_ptr, const int64_t* out_y_ptr, int32_t B, int64_t N, int64_t E, int64_t M,
                     const float* rot, float temp_mean, float temp_std, const CartnetCollated* out, void* stream);
+
+/* cartnet_collate_frame_view: the model's view of a batch that was collated from ANOTHER shard of the same crystals.
+ * The iComformer recipe reads a crystal in the frame of its reduced cell (dataset/datasetADP.py:75-80) while everything
+ * that follows the forward of a prediction works in the frame the crystal is stored in (main.py:95-97 is the relation
+ * between the two).  For the crystals sel[0..B) of a batch already collated from the STORED shard this gathers, from
+ * `shard` = the reduced-frame shard with the same graph, only what the frame changes: cart_dir_out [E,3] and cell_out
+ * [B,9] -- about 12 B read and 12 B written per edge against the ~56 B + ~60 B of a second cartnet_collate.  out_edge_ptr
+ * [B+1]: the exclusive prefix sums of the selected crystals' edge counts IN `shard` (E = its last entry); the caller
+ * checks that they are the batch's.  Plain copies: the two outputs have the bits cartnet_collate gives them without
+ * rot.  One launch, the 256-row blocks and the segment search of cartnet_collate; no atomics, no LDS, fixed order. */
+int cartnet_collate_frame_view(const CartnetShard* shard, const int64_t* sel, const int64_t* out_edge_ptr, int32_t B,
+                               int64_t E, float* cart_dir_out, float* cell_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
  * The hydrogen-free copy of a whole shard (reference: dataset/datasetADP.py:49-72, DatasetADP.get with

@@ -138,6 +138,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "entry and one CIF per crystal and temperature (NAME_150K), and with two or more temperatures a "
                         "least-squares line per atom through them (series).  Not with --disable_temp, and with --predict "
                         "only")
+    p.add_argument("--model_frame", type=str, default="stored", choices=["stored", "reduced_cell"],
+                   help="--predict: the frame the model reads every crystal in.  stored (default): the cell and cart_dir as "
+                        "the input stores them, as CartNet and eComformer are trained.  reduced_cell: --model icomformer "
+                        "only, and required for it -- the forward runs in the frame of each crystal's canonical reduced "
+                        "cell, as iComformer is trained (graph capped at --max_neighbours), and the predictions are "
+                        "brought back (U = R P R^T), so that every key of the pickle, the analyses and the CIFs stay in "
+                        "the stored cell; the pickle gains cell_rotation and cell_reduced.  Not with --rotations K > 1")
     p.add_argument("--predict_output", type=str, default="./predictions.pkl")
     p.add_argument("--predict_cif_dir", type=str, default=None, help="--predict: also write one CIF per crystal here (a shard's crystals in P1, a CIF's in its own setting)")
     p.add_argument("--rotations", type=int, default=1,
@@ -268,10 +275,11 @@ def graph_request(cfg, shard_graph: Optional[dict], has_graph: bool) -> Optional
     return want
 
 
-def shard_recipe(shards: list):
+def shard_recipe(shards: list, cell: bool = True):
     """The reference's dataset recipe on resident shards, in the reference's order -- graph (graph_request), hydrogen
-    removal (dataset/datasetADP.py:49-72), canonical cell (:75-80).  Returns the new shards and the (mean, std) of the
-    temperature standardisation of :17-18,43-45, which the collation kernel applies (the files hold Kelvin)."""
+    removal (dataset/datasetADP.py:49-72), canonical cell (:75-80; not with ``cell=False``: ``predict`` keeps the stored
+    frame and derives the model's from it).  Returns the new shards and the (mean, std) of the temperature
+    standardisation of :17-18,43-45, which the collation kernel applies (the files hold Kelvin)."""
     from cartnet_amd.synthetic import TEMP_MEAN, TEMP_STD
     adp = cfg.dataset.name == "ADP"
     shards = list(shards)
@@ -279,17 +287,17 @@ def shard_recipe(shards: list):
         req = graph_request(cfg, s.graph, s.has_graph)
         if req is not None:
             shards[i] = s.with_radius_graph(*req)
-    return hydrogen_and_cell_steps(shards), ((TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0))
+    return hydrogen_and_cell_steps(shards, cell), ((TEMP_MEAN, TEMP_STD) if adp and cfg.standarize_temp else (0.0, 1.0))
 
 
-def hydrogen_and_cell_steps(shards: list) -> list:
+def hydrogen_and_cell_steps(shards: list, cell: bool = True) -> list:
     """The steps of the recipe that follow the graph, on resident shards: hydrogen removal under ``--disable_H``
-    (loader/loader.py:29-32: DatasetADP(hydrogens=cfg.use_H), whatever the model), then the canonical lattice frame of
-    iComformer on ADP (loader/loader.py:24-32: DatasetADP(optimize_cell=True))."""
+    (loader/loader.py:29-32: DatasetADP(hydrogens=cfg.use_H), whatever the model), then -- unless ``cell`` is False -- the
+    canonical lattice frame of iComformer on ADP (loader/loader.py:24-32: DatasetADP(optimize_cell=True))."""
     adp = cfg.dataset.name == "ADP"
     if adp and not cfg.use_H:
         shards = [s.without_hydrogens() for s in shards]
-    if adp and cfg.model == "icomformer":
+    if cell and adp and cfg.model == "icomformer":
         shards = [s.with_optimized_cell() for s in shards]
     return shards
 
@@ -347,10 +355,17 @@ def check_predict_args(args) -> None:
         raise SystemExit("--predict: weights not provided (--checkpoint_path)")
     if args.predict_input is None:
         raise SystemExit("--predict: no input shard (--predict_input FILE.cnshard)")
-    if cfg.model == "icomformer":
-        raise SystemExit("--predict does not serve --model icomformer: its recipe reads crystals in the frame of the "
-                         "reduced cell, and mapping U back to the stored cell is not implemented (use CartNet or "
-                         "ecomformer)")
+    if cfg.model == "icomformer" and args.model_frame != "reduced_cell":
+        raise SystemExit("--predict does not serve --model icomformer in the stored frame: its recipe reads crystals in the "
+                         "frame of the reduced cell.  Give --model_frame reduced_cell: the forward then runs there and U is "
+                         "mapped back to the stored cell")
+    if cfg.model != "icomformer" and args.model_frame != "stored":
+        raise SystemExit(f"--model_frame {args.model_frame} serves --model icomformer only: {cfg.model} is trained in the "
+                         "stored frame")
+    if cfg.model == "icomformer" and cfg.rotations > 1:
+        raise SystemExit("--predict --model icomformer serves one frame only (--rotations 1): its features are invariant, "
+                         "and the K frames rotate cart_dir but not the cell, so they would feed it inconsistent inputs and "
+                         "nothing would be averaged")
     if args.riding_h and not cfg.use_H:
         raise SystemExit("--riding_h with --disable_H: the hydrogens are gone, so there is nothing to ride")
     if args.predict_temperatures is not None:
@@ -387,16 +402,21 @@ def predict(model, args) -> dict:
     batches of ``--eval_batch``; the pickle of ``cartnet_amd.predict.predict_adps`` and, if asked for, one CIF per
     crystal.  CIF input (a file or a directory): the crystals the reference's filters accept are expanded to their unit
     cells on the GPU and take the same path; the pickle and the CIFs then carry one site-averaged ADP per atom of the
-    asymmetric unit, and the result counts the ``rejected`` crystals (names and reasons go to stderr)."""
+    asymmetric unit, and the result counts the ``rejected`` crystals (names and reasons go to stderr).
+    ``--model icomformer --model_frame reduced_cell``: the recipe stops before the canonical cell, so the loader's shard -- graphed with
+    ``--max_neighbours``, as iComformer is trained -- stays in the stored frame for the export, the analyses and the
+    writers; its ``with_optimized_cell()`` is the ``model_frame`` of the pass, the frame only the forward sees, and the
+    result says ``"model_frame": "reduced_cell"``."""
     import pickle
     from cartnet_amd import predict as pr
     from cartnet_amd.shard import ShardLoader
     source, sym, rejected = pr.load_input(args.predict_input, cfg.device, args.predict_temperature)
-    (shard,), (mean, std) = shard_recipe([source])
+    (shard,), (mean, std) = shard_recipe([source], cell=False)
+    frame = {"model_frame": shard.with_optimized_cell()} if cfg.model == "icomformer" else {}
     temps = parse_temperatures(args.predict_temperatures) if args.predict_temperatures is not None else None
     out = pr.predict_adps(
         model, ShardLoader(shard, cfg.eval_batch, temp_mean=mean, temp_std=std), cfg.device, sym=sym,
-        rotations=cfg.rotations, seed=cfg.seed, temperatures=temps, **analysis_options(args))
+        rotations=cfg.rotations, seed=cfg.seed, temperatures=temps, **analysis_options(args), **frame)
     with open(args.predict_output, "wb") as f:
         pickle.dump(out, f)
     if args.predict_cif_dir:
@@ -404,7 +424,10 @@ def predict(model, args) -> dict:
         for k, name in enumerate(out["name"]):            # entries: one per crystal, or per crystal and temperature
             (pr.write_cif if sym is None else pr.write_cif_symmetric)(
                 os.path.join(args.predict_cif_dir, f"{name}.cif"), pr.entry(out, k))
-    return pr.pass_statistics(out, args.predict_output, args.predict_cif_dir, rejected, cfg.rotations, temps)
+    res = pr.pass_statistics(out, args.predict_output, args.predict_cif_dir, rejected, cfg.rotations, temps)
+    if frame:
+        res["model_frame"] = "reduced_cell"
+    return res
 
 
 def main(argv=None) -> dict:
@@ -418,6 +441,8 @@ def main(argv=None) -> dict:
         raise SystemExit("--bond_table serves --predict only")
     if args.angle_table and not args.predict:
         raise SystemExit("--angle_table serves --predict only")
+    if args.model_frame != "stored" and not args.predict:
+        raise SystemExit("--model_frame serves --predict only")
     if args.predict or args.predict_temperatures is not None:
         check_predict_args(args)
     if args.rigid_molecule and not (args.predict or args.inference):
